@@ -8,12 +8,23 @@
 A "step" = fwd + bwd + gradient SUM all-reduce (RCCL) + per-variable clip + TF-Adam on one synthetic batch
 already resident in HBM (the reference's `Examples/sec`, train.py:450-451).  Workload = BASELINE configs[1]:
 NetVladV1 K=256 hidden=512, rgb+audio 1152-d, 300 frames, bs 80 per GPU (weak scaling: cfg-4 at 8 GPUs).
-Rank 0 prints ONE JSON line.  Extra objects: `roofline` for the residual-aggregation kernel (K2, video
-stream) timed with HIP events on the launch stream inside the timed region, and `cpu_baseline` = the CPU
-oracle (fp32 torch restatement, oracle/) timed on this box's host cores on a bounded sample (N=1 only).
+Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, a fixed number of spin-up and warm-up steps, the K timed
+steps, the outputs (``--dump-outputs DIR``) and the line.  ``--full`` adds everything else, as before:
+`other_configs` (cfg3 and cfg5 timed in child processes), `roofline` for the residual-aggregation kernel (K2,
+video stream) timed with HIP events on the launch stream inside the timed region, `assign_gemm`, `clip_adam`,
+`gradient_state`, `dispatches_per_step`, `cpu_baseline` = the CPU oracle (fp32 torch restatement, oracle/) timed
+on the host cores on a bounded sample with the `parity` check against it (N=1 only), and with N > 1 the
+`collectives` trace and the `replicas` check.
+
+``--dump-outputs DIR`` writes what the last timed step handed its caller as float32 .npy files (see
+dump_outputs); with the same arguments every run starts from the same seeded weights and batches and runs the
+same steps, so two builds can be compared output for output.
 """
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -64,6 +75,8 @@ WORKLOADS = {
                               "per product with fp32 accumulation; batch statistics, norms, projection, gating, MoE, gradients and the "
                               "optimiser in fp32"),
 }
+# ms per step measured on one MI355X at the final code of round 6 (README): converts --spinup-seconds into a fixed step count
+SPINUP_STEP_MS = {"cfg2": 6.7, "cfg3": 8.5, "cfg5": 5.3}
 
 
 def set_flags(wl):
@@ -237,7 +250,7 @@ def run_all(argv):
 
 
 def other_configs(args):
-    """Default run only (cfg2 on one GPU): BASELINE configs[2] (cfg3) and configs[4] at its per-GPU share (cfg5) timed by this same script
+    """``--full`` run of cfg2 on one GPU: BASELINE configs[2] (cfg3) and configs[4] at its per-GPU share (cfg5) timed by this same script
     in FRESH child processes BEFORE this process touches the GPU, their headline figures embedded in the cfg-2 line as ``other_configs`` --
     so that the driver's one command puts all three single-GPU configurations under its clock.  Each child: the same steps / warm-up,
     rotating batches, no CPU baseline (that is this line's ``cpu_baseline``), at most ``limit`` seconds."""
@@ -247,7 +260,7 @@ def other_configs(args):
     for cfg in ("cfg3", "cfg5"):
         cmd = [sys.executable, os.path.abspath(__file__), "--config", cfg, "--gpus", "1", "--steps", str(args.steps), "--warmup",
                str(args.warmup), "--spinup-seconds", str(min(args.spinup_seconds, 2.0)), "--batches", str(args.batches),
-               "--no-cpu-baseline", "--no-other-configs"] + (["--single-batch"] if args.single_batch else [])
+               "--full", "--no-cpu-baseline", "--no-other-configs"] + (["--single-batch"] if args.single_batch else [])
         t0 = time.perf_counter()
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=limit)
@@ -296,6 +309,36 @@ def count_dispatches(step):
     except Exception as ex:                          # the count is a diagnostic, never a reason to fail the bench
         sys.stderr.write(f"[bench.py] dispatch count unavailable: {type(ex).__name__}: {ex}\n")
         return None
+
+
+def dump_outputs(path, out, trainer, per_variable=16384, seed=0):
+    """``--dump-outputs``: what the last timed step handed its caller, as float32 .npy files in ``path``:
+      predictions.npy  [batch, vocab]  the step's predictions (rank 0's shard)
+      loss.npy         []              its label loss
+      variables.npy    [n]             the model's variables after the step's update, every variable of the store in name order:
+                                       all entries of one with at most ``per_variable`` of them, else ``per_variable`` entries at
+                                       positions drawn (with replacement, sorted) from a CPU generator seeded with ``seed`` afresh
+                                       for each variable -- the same positions in every run and every build.
+    A few MB in all at the benched configurations."""
+    import numpy as np
+    if trainer.sharded is not None:
+        trainer.sharded.wait_parameters()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "predictions.npy"), out["predictions"].detach().float().cpu().numpy())
+    np.save(os.path.join(path, "loss.npy"), out["loss"].detach().float().cpu().numpy())
+    g = torch.Generator()
+    parts = []
+    for name in sorted(trainer.store.vars):
+        v = trainer.store.vars[name].detach()
+        if not v.is_floating_point():
+            continue
+        flat = v.reshape(-1)
+        if flat.numel() > per_variable:
+            g.manual_seed(seed)
+            idx = torch.randint(0, flat.numel(), (per_variable,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.float().cpu())
+    np.save(os.path.join(path, "variables.npy"), torch.cat(parts).numpy())
 
 
 def replica_check(trainer, world, group=None):
@@ -366,13 +409,20 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=20)   # a cold box needs ~0.2 s of load before clocks and caches settle
     ap.add_argument("--spinup-seconds", type=float, default=3.0,
-                    help="untimed steps before the W warm-up steps until this much wall time has passed: a box that has "
-                         "been idle needs a few seconds of load before its clocks settle (measured: 7.1-7.6k clips/s in the "
+                    help="untimed steps before the W warm-up steps, about this much wall time of them at the workload's measured "
+                         "step time (SPINUP_STEP_MS; a fixed count, so that a run's steps depend on its arguments alone): a GPU that "
+                         "has been idle needs a few seconds of load before its clocks settle (measured: 7.1-7.6k clips/s in the "
                          "first second, 8.4-8.7k afterwards)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: other_configs, roofline and kernel figures, gradient state, dispatch count, "
+                         "cpu_baseline + parity, and with N > 1 the collective trace and the replica check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (predictions, loss, a fixed sample of the updated "
+                         "variables) as float32 .npy files under DIR (rank 0)")
     ap.add_argument("--batches", type=int, default=8, help="distinct resident synthetic batches rotated through every step (seeds rank * N + i)")
     ap.add_argument("--single-batch", action="store_true", help="one batch for every step (the behaviour of rounds 1-4), for an A/B")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default run (cfg2, one GPU): do not time cfg3 and cfg5 in child processes first (see other_configs)")
+                    help="--full run (cfg2, one GPU): do not time cfg3 and cfg5 in child processes first (see other_configs)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=25.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-dispatch-count", action="store_true",
@@ -399,7 +449,7 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     others = None
     profiled = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
-    if (args.config == "cfg2" and world == 1 and args.gpus == 1 and not args.no_other_configs and not profiled
+    if (args.full and args.config == "cfg2" and world == 1 and args.gpus == 1 and not args.no_other_configs and not profiled
             and not any(k.startswith("LPM_") for k in os.environ)):
         others = other_configs(args)                 # child processes, before this one initialises the GPU
     if not torch.cuda.is_available():
@@ -473,16 +523,9 @@ def main():
             next_step()
         torch.cuda.synchronize()
         dog.tick("spin-up steps")
-        t_spin = time.perf_counter()
-        for _ in range(3):
-            next_step()
-        torch.cuda.synchronize()
-        per = (time.perf_counter() - t_spin) / 3
-        n_spin = torch.tensor([max(0, int(args.spinup_seconds / max(per, 1e-4)))], device=device, dtype=torch.int64)
-        if world > 1:
-            dist.broadcast(n_spin, src=0)
-        spin = 5 + int(n_spin.item())
-        for i in range(spin - 5):
+        # a count fixed by the arguments (not by a clock): the timed steps then start from the same state in every run
+        spin = 2 + math.ceil(1000.0 * args.spinup_seconds / SPINUP_STEP_MS[args.config])
+        for i in range(spin - 2):
             next_step()
             if i % 32 == 0:
                 torch.cuda.synchronize()
@@ -491,51 +534,59 @@ def main():
     dog.tick("warm-up steps")
     for _ in range(args.warmup):
         next_step()
-    ops.KERNEL_TIMELINE = []
     from learnablepoolingmethods_amd import _capi
     lib = _capi.load()
-    lib._lpm_kernel_timing_enable(1)       # K1 / K2 launches carry their own start/stop HIP events (kernel duration proper)
-    if world > 1:
-        from learnablepoolingmethods_amd import train as _train
-        _train.TRACE.on = True             # three compute-stream events per collective: the overlap evidence printed below
+    if args.full:
+        ops.KERNEL_TIMELINE = []
+        lib._lpm_kernel_timing_enable(1)   # K1 / K2 launches carry their own start/stop HIP events (kernel duration proper)
+        if world > 1:
+            from learnablepoolingmethods_amd import train as _train
+            _train.TRACE.on = True         # three compute-stream events per collective: the overlap evidence printed below
     barrier("barrier before the timed steps")
     t0 = time.perf_counter()
     for _ in range(args.steps):
         out = next_step()
     barrier("barrier after the timed steps")
     elapsed = time.perf_counter() - t0
-    # the state the timed steps ran in: how much of the last timed step's gradient is exactly zero (a saturated, frozen model shows up
-    # here).  hidden1_weights' slice is left out on the routes that never write its gradient (factored / sharded update).
-    ga = trainer.arena
-    g0 = ga.offsets_host[1] if (trainer.factored is not None or trainer.sharded is not None) else 0
-    gsl = ga.grad[g0:]
-    grad_state = {"zero_fraction": round(float((gsl == 0).float().mean()), 6) if gsl.numel() else None,
-                  "max_abs": float(f"{float(gsl.abs().max()):.3e}") if gsl.numel() else None, "entries": int(gsl.numel()),
-                  "of": "the gradient arena after the last timed step" + (" without hidden1_weights (its gradient is never written on this route)" if g0 else "")}
-    timeline, ops.KERNEL_TIMELINE = ops.KERNEL_TIMELINE, None
-    lib._lpm_kernel_timing_enable(0)
-    dispatches = count_dispatches(next_step) if (world == 1 and not args.no_dispatch_count) else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, trainer)
+    grad_state, timeline, dispatches = None, [], None
+    k1_ms = k2_ms = at_ms = fin_ms = []
+    if args.full:
+        # the state the timed steps ran in: how much of the last timed step's gradient is exactly zero (a saturated, frozen model shows
+        # up here).  hidden1_weights' slice is left out on the routes that never write its gradient (factored / sharded update).
+        ga = trainer.arena
+        g0 = ga.offsets_host[1] if (trainer.factored is not None or trainer.sharded is not None) else 0
+        gsl = ga.grad[g0:]
+        grad_state = {"zero_fraction": round(float((gsl == 0).float().mean()), 6) if gsl.numel() else None,
+                      "max_abs": float(f"{float(gsl.abs().max()):.3e}") if gsl.numel() else None, "entries": int(gsl.numel()),
+                      "of": "the gradient arena after the last timed step" + (" without hidden1_weights (its gradient is never written on this "
+                                                                              "route)" if g0 else "")}
+        timeline, ops.KERNEL_TIMELINE = ops.KERNEL_TIMELINE, None
+        lib._lpm_kernel_timing_enable(0)
+        dispatches = count_dispatches(next_step) if (world == 1 and not args.no_dispatch_count) else None
 
-    def kernel_ms(tag):
-        import ctypes
-        buf = (ctypes.c_float * 4096)()
-        n = lib._lpm_kernel_timing_read(tag, buf, 4096)
-        return [float(buf[i]) for i in range(n)]
-    k1_ms, k2_ms = kernel_ms(1), kernel_ms(2)
-    at_ms, fin_ms = kernel_ms(3), kernel_ms(4)
+        def kernel_ms(tag):
+            import ctypes
+            buf = (ctypes.c_float * 4096)()
+            n = lib._lpm_kernel_timing_read(tag, buf, 4096)
+            return [float(buf[i]) for i in range(n)]
+        k1_ms, k2_ms = kernel_ms(1), kernel_ms(2)
+        at_ms, fin_ms = kernel_ms(3), kernel_ms(4)
     replicas = None
     collectives = None
     if world > 1:
-        _train.TRACE.on = False
-        collectives = _train.TRACE.summary()   # rank 0's view: window = compute between a collective's launch and its wait, exposed = the stall
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        # after the timed region: do all towers hold the same parameters?  (data-parallel replicas apply identical updates -- on the
-        # sharded route each rank updates its 1/N of hidden1_weights and the all-gather hands everyone the rest: a rank that missed a
-        # collective or read the variable before its gather landed shows up here, on the first real multi-GPU run as well)
-        dog.tick("replica consistency check (all_gather of parameter checksums)")
-        replicas = replica_check(trainer, world)
+        if args.full:
+            _train.TRACE.on = False
+            collectives = _train.TRACE.summary()   # rank 0's view: window = compute between a collective's launch and its wait, exposed = the stall
+            # after the timed region: do all towers hold the same parameters?  (data-parallel replicas apply identical updates -- on the
+            # sharded route each rank updates its 1/N of hidden1_weights and the all-gather hands everyone the rest: a rank that missed a
+            # collective or read the variable before its gather landed shows up here, on the first real multi-GPU run as well)
+            dog.tick("replica consistency check (all_gather of parameter checksums)")
+            replicas = replica_check(trainer, world)
     loss = float(out["loss"])
 
     if rank == 0:
@@ -620,8 +671,10 @@ def main():
                 "warmup": args.warmup, "spinup_steps": spin, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak",
                 "vs_baseline": None, "dtype": wl["dtype"], "data": "synthetic", "dtype_detail": wl["dtype_detail"],
                 "config": {"workload": wl["workload"], "global_batch": global_batch, "seq_len": MAX_FRAMES, "parallelism": f"dp{world}"},
-                "final_loss": round(loss, 4), "gradient_state": grad_state,
+                "final_loss": round(loss, 4),
                 "batches": {"distinct": NB, "seeds": f"rank * {NB} + i, i < {NB}", "rotation": "spin-up, warm-up and timed steps take them in turn; all resident in HBM"}}
+        if grad_state is not None:
+            line["gradient_state"] = grad_state
         # launches per step: counted live, on one more step AFTER the timed region (single GPU: the extra steps hold collectives otherwise)
         if world == 1 and dispatches is not None:
             line["dispatches_per_step"] = dispatches
@@ -681,7 +734,7 @@ def main():
                                  "frac": round(byts / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
             if k5f:
                 line["clip_adam"]["factored_avg_ms"] = round(sum(t for _, t in k5f) / len(k5f), 4)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"], first = cpu_baseline(args.cpu_baseline_seconds, wl)
             line["parity"] = parity_check(first, device, wl)
         print(json.dumps(line), flush=True)

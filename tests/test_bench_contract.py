@@ -149,3 +149,48 @@ def test_bench_self_launch_on_this_box_names_its_phase():
         return
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 4 and "self-launch: device count" in r.stderr and "Traceback" not in r.stderr, r.stderr[-2000:]
+
+
+def test_bench_dump_outputs_writes_float32_arrays_and_fixed_samples(tmp_path):
+    """--dump-outputs: predictions, loss and a sample of the variables as float32 .npy; the sampled positions do not depend on the run."""
+    import importlib
+    import types
+
+    import numpy as np
+    import torch
+    bench = importlib.import_module("bench")
+    g = torch.Generator().manual_seed(3)
+    store = types.SimpleNamespace(vars={"tower/b": torch.randn(7, generator=g), "tower/a": torch.randn(300, 200, generator=g),
+                                        "global_step": torch.zeros((), dtype=torch.int64)})
+    trainer = types.SimpleNamespace(store=store, sharded=None)
+    out = {"predictions": torch.rand(4, 9, generator=g, dtype=torch.float64), "loss": torch.tensor(0.5)}
+    for d in ("one", "two"):
+        bench.dump_outputs(str(tmp_path / d), out, trainer, per_variable=1000)
+    for name in ("predictions", "loss", "variables"):
+        a, b = np.load(tmp_path / "one" / f"{name}.npy"), np.load(tmp_path / "two" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b), name
+    v = np.load(tmp_path / "one" / "variables.npy")
+    assert v.shape == (1000 + 7,)                          # tower/a sampled, tower/b whole, the integer counter left out
+    assert np.isin(v[:1000], store.vars["tower/a"].numpy().reshape(-1)).all()
+    assert np.array_equal(v[1000:], store.vars["tower/b"].numpy())
+    assert np.load(tmp_path / "one" / "predictions.npy").shape == (4, 9)
+
+
+def test_bench_plain_run_starts_no_other_configurations(monkeypatch):
+    """A plain run times the headline alone: the child processes of other_configs belong to --full."""
+    import importlib
+    import sys
+
+    import torch
+    bench = importlib.import_module("bench")
+
+    def boom(*a, **k):
+        raise AssertionError("a plain run started the other configurations")
+    monkeypatch.setattr(bench, "other_configs", boom)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    try:
+        bench.main()
+        raise AssertionError("main() must stop where it finds no GPU")
+    except SystemExit as e:
+        assert "needs an MI355X" in str(e.code)

@@ -190,7 +190,7 @@ def test_bench_self_launch_two_ranks(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--spinup-seconds", "0",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     two = torch.cuda.device_count() >= 2
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     if not two:
@@ -220,7 +220,7 @@ def test_bench_eight_ranks_share_the_gpu_over_gloo(config, global_batch):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", LPM_SHARE_GPU="1")
     env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", config, "--gpus", "8", "--steps", "2", "--warmup", "1",
-           "--spinup-seconds", "0", "--no-cpu-baseline"]
+           "--spinup-seconds", "0", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=800)
     if r.returncode != 0 and os.environ.get("LPM_TEST_KEEP_STDERR"):
         open(os.path.join(os.environ["LPM_TEST_KEEP_STDERR"], f"eight_ranks_{config}.err"), "w").write(r.stderr)
