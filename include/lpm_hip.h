@@ -127,6 +127,30 @@ int lpm_frame_apply_tiles2(const float* raw, const int32_t* num_frames, int B, i
                            const float* scale, const float* shift, float* y, void* xt_video, void* xr_video, int Dv,
                            void* xt_audio, void* xr_audio, int Da, lpm_stream_t stream);
 int lpm_frame_stats_nblk(int B, int S);   /* rows of `partial` lpm_frame_stats writes (for lpm_bn_fold) */
+/* Eval mode from the reader's quantised frames: the apply forms above with the dequantisation and the per-frame L2 normalisation of
+ * lpm_dequantize_l2_normalize folded in, for the S SAMPLED frames only.  lpm_frame_inv_norm_q8 writes inv_norm [B*S] fp32, the inverse
+ * L2 norm of the dequantised frame behind every sampled row (0: a frame at or past num_frames, zero after the reader's padding; F <= 2048);
+ * each *_q8 apply form then reads q [B, max_frames, F] uint8 (4-byte aligned) and inv_norm in place of `raw` and writes exactly what its
+ * fp32 form writes when `raw` is lpm_dequantize_l2_normalize's output for the same q, num_frames and quantisation range -- bit for bit.
+ * scale / shift are the folded eval-mode affine (no statistics pass). */
+int lpm_frame_inv_norm_q8(const unsigned char* q, const int32_t* num_frames, int B, int max_frames, int F, int S,
+                          float max_quantized_value, float min_quantized_value, float* inv_norm, lpm_stream_t stream);
+int lpm_frame_apply_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
+                       const int32_t* num_frames, int B, int max_frames, int F, int S, const float* scale, const float* shift, float* y,
+                       lpm_stream_t stream);
+int lpm_frame_apply_tiles_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
+                             const int32_t* num_frames, int B, int max_frames, int F, int S, const float* scale, const float* shift, float* y,
+                             void* xt_video, int Dv, void* xt_audio, int Da, lpm_stream_t stream);
+int lpm_frame_apply_tiles_split_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
+                                   const int32_t* num_frames, int B, int max_frames, int F, int S, const float* scale, const float* shift,
+                                   float* y_video, float* y_audio, void* xt_video, int Dv, void* xt_audio, int Da, lpm_stream_t stream);
+int lpm_frame_apply_tiles2_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
+                              const int32_t* num_frames, int B, int max_frames, int F, int S, const float* scale, const float* shift, float* y,
+                              void* xt_video, void* xr_video, int Dv, void* xt_audio, void* xr_audio, int Da, lpm_stream_t stream);
+int lpm_frame_apply_tiles_bf16_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
+                                  const int32_t* num_frames, int B, int max_frames, int F, int S, const float* scale, const float* shift,
+                                  float* y, void* xt_video, void* xr_video, int Dv, void* xt_audio, void* xr_audio, int Da,
+                                  lpm_stream_t stream);
 /* backward of input_bn's affine parameters only (the frames are data, never a trainable tensor, so no
  * gradient w.r.t. raw is produced): dgamma = sum dy*xhat, dbeta = sum dy over the gathered rows.
  * dy [B*S, F] with row stride lddy; mean/var = the batch statistics lpm_bn_fold returned.
@@ -879,6 +903,11 @@ int lpm_factored_clip_adam_copy_dx(const void* xt, const void* dyt, const float*
  * a counter-based hash of (seed, i) -- one store stream instead of torch's bernoulli_ (round 6).  n bytes, a multiple of 16; 16-byte aligned.
  * The same (seed, n, keep_prob) gives the same mask.  The consumers are lpm_layer_norm_act_mask_image_fwd[_fmt] / lpm_layer_norm_act_mask_bwd[_fmt]. */
 int lpm_dropout_keep_mask(void* mask, int64_t n, float keep_prob, uint64_t seed, lpm_stream_t stream);
+
+/* Row top-k (export_model.py's top 20 classes per video): p fp32 [B, V] -> index int32 [B, k] and value fp32 [B, k], the order of
+ * torch.sort(p, dim=1, descending=True, stable=True)[:, :k] -- ties by ascending index, NaN above +inf, -0 equal to +0; value holds the
+ * entries themselves.  1 <= k <= 64, k <= V <= 65536; one workgroup per row. */
+int lpm_topk_rows(const float* p, int B, int V, int k, int32_t* index, float* value, lpm_stream_t stream);
 
 #ifdef __cplusplus
 }

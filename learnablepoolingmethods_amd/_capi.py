@@ -50,6 +50,12 @@ SIGNATURES = {
     "lpm_frame_stats_nblk": (_i, [_i, _i]),
     "lpm_frame_bn_bwd": (_i, [_f, _l, _f, _f, _i, _i, _i, _i, _f, _f, _fl, _f, _f, _f, _s, _f]),
     "lpm_frame_bn_bwd_split": (_i, [_f, _l, _f, _l, _i, _f, _f, _i, _i, _i, _i, _f, _f, _fl, _f, _f, _f, _s, _f]),
+    "lpm_frame_inv_norm_q8": (_i, [_f, _f, _i, _i, _i, _i, _fl, _fl, _f, _f]),
+    "lpm_frame_apply_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _f, _f]),
+    "lpm_frame_apply_tiles_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _f, _f, _i, _f, _i, _f]),
+    "lpm_frame_apply_tiles_split_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _i, _f]),
+    "lpm_frame_apply_tiles2_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _f, _i, _f]),
+    "lpm_frame_apply_tiles_bf16_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _f, _i, _f]),
     "lpm_bn_fold": (_i, [_f, _i, _i, _l, _f, _f, _fl, _fl, _f, _f, _f, _f, _f, _f, _f]),
     "lpm_assign_gemm_nblk": (_i, [_i]),
     "lpm_assign_gemm_fwd": (_i, [_f, _l, _f, _i, _i, _i, _i, _f, _f, _f]),
@@ -179,6 +185,7 @@ SIGNATURES = {
     "lpm_factored_clip_adam": (_i, [_f, _f, _i, _i, _i, _f, _f, _f, _fl, _fl, _fl, _fl, _fl, _l, _f, _s, _f]),
     "lpm_multi_tensor_clip_adam": (_i, [_f, _f, _f, _f, _f, _i, _l, _fl, _fl, _fl, _fl, _fl, _l, _f, _f]),
     "lpm_dropout_keep_mask": (_i, [_f, _l, _fl, C.c_uint64, _f]),
+    "lpm_topk_rows": (_i, [_f, _i, _i, _i, _f, _f, _f]),
     "lpm_multi_tensor_clip_adam_l2": (_i, [_f, _f, _f, _f, _f, _f, _i, _l, _fl, _fl, _fl, _fl, _fl, _l, _f, _f]),
     "lpm_weight_pack": (_i, [_f, _i, _f]),
     "lpm_sum_splits": (_i, [_f, _i, _i, _i, _f, _f, _f, _i, _f]),          # (jobs: a HOST array of WeightPackJob)

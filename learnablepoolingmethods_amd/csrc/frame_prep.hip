@@ -6,6 +6,9 @@
 // statistics of the gathered rows (per-block partials -> lpm_bn_fold), a second pass gathers again
 // and writes the normalised rows that K1 and K2 consume.  Both are pure HBM streams (float4,
 // row-contiguous 4.6 KB reads).
+// Eval mode from the reader's quantised frames (the *_q8 entry points): the apply kernels read the uint8 frames of the sampled
+// rows and one inverse L2 norm per sampled row (lpm_frame_inv_norm_q8), and produce bit for bit what they produce from
+// lpm_dequantize_l2_normalize's fp32 frames -- without writing (and re-reading) the fp32 frames of all max_frames.
 #include "lpm_common.h"
 
 namespace lpm {
@@ -17,6 +20,53 @@ __device__ __forceinline__ int sample_index(int j, float step, int nf) {
     const float v = __fmul_rn((float)j, step);
     return (int)__fmul_rn(fminf(v, 1.0f), (float)nf);
 }
+
+// One wave's share of a quantised frame row (lane owns the uchar4 columns lane + 64 i, F <= 2048): the dequantised values
+// (utils.Dequantize: u * range/255 + range/512 + min) into v, and the row's inverse L2 norm rsqrt(max(sum x^2, 1e-12)).
+// dequantize_l2_normalize_kernel and frame_inv_norm_q8_kernel both use it: one summation order, one rounding.
+__device__ __forceinline__ float dequant_row_inv_norm(const uchar4* __restrict__ src, int lane, int F4, float scalar, float bias,
+                                                      float4 (&v)[8]) {
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int c = lane + 64 * i;
+        v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (c < F4) {
+            const uchar4 u = src[c];
+            v[i] = make_float4(fmaf((float)u.x, scalar, bias), fmaf((float)u.y, scalar, bias), fmaf((float)u.z, scalar, bias),
+                               fmaf((float)u.w, scalar, bias));
+        }
+        ss += v[i].x * v[i].x + v[i].y * v[i].y + v[i].z * v[i].z + v[i].w * v[i].w;
+    }
+    ss = wave_sum(ss);
+    return rsqrtf(fmaxf(ss, 1e-12f));
+}
+
+// Where the apply kernels read the sampled frames.  FrameSrc<float>: the fp32 batch [B, max_frames, F].  FrameSrc<unsigned char>:
+// the reader's uint8 batch plus one inverse norm per SAMPLED row (lpm_frame_inv_norm_q8; 0 marks a frame at or past num_frames,
+// which the reader pads with zeros) -- each value is dequantised and rounded to fp32 times the inverse norm, exactly the value
+// lpm_dequantize_l2_normalize stores, before the kernel's own arithmetic.  load4: four consecutive features at element offset off
+// of sampled row `row` (= b S + j).
+template <typename T>
+struct FrameSrc;
+template <>
+struct FrameSrc<float> {
+    const float* __restrict__ raw;
+    __device__ __forceinline__ float4 load4(int64_t off, int64_t) const { return *reinterpret_cast<const float4*>(raw + off); }
+};
+template <>
+struct FrameSrc<unsigned char> {
+    const unsigned char* __restrict__ raw;
+    const float* __restrict__ inv;
+    float scalar, bias;
+    __device__ __forceinline__ float4 load4(int64_t off, int64_t row) const {
+        const float s = inv[row];
+        if (s == 0.f) return make_float4(0.f, 0.f, 0.f, 0.f);
+        const uchar4 u = *reinterpret_cast<const uchar4*>(raw + off);
+        return make_float4(__fmul_rn(fmaf((float)u.x, scalar, bias), s), __fmul_rn(fmaf((float)u.y, scalar, bias), s),
+                           __fmul_rn(fmaf((float)u.z, scalar, bias), s), __fmul_rn(fmaf((float)u.w, scalar, bias), s));
+    }
+};
 
 __global__ __launch_bounds__(256) void frame_stats_kernel(const float* __restrict__ raw,
                                                           const int32_t* __restrict__ num_frames, int B,
@@ -49,8 +99,8 @@ __global__ __launch_bounds__(256) void frame_stats_kernel(const float* __restric
     }
 }
 
-__global__ __launch_bounds__(256) void frame_apply_kernel(const float* __restrict__ raw,
-                                                          const int32_t* __restrict__ num_frames, int B,
+template <typename Src>
+__global__ __launch_bounds__(256) void frame_apply_kernel(Src raw, const int32_t* __restrict__ num_frames, int B,
                                                           int max_frames, int F, int S, float step,
                                                           const float* __restrict__ scale,
                                                           const float* __restrict__ shift, float* __restrict__ y) {
@@ -61,7 +111,7 @@ __global__ __launch_bounds__(256) void frame_apply_kernel(const float* __restric
         const int b = r / S, j = r % S;
         int idx = sample_index(j, step, num_frames[b]);
         idx = max(0, min(idx, max_frames - 1));
-        float4 v = *reinterpret_cast<const float4*>(raw + ((int64_t)b * max_frames + idx) * F + c);
+        float4 v = raw.load4(((int64_t)b * max_frames + idx) * F + c, r);
         if (scale) {
             const float4 sc = *reinterpret_cast<const float4*>(scale + c);
             const float4 sh = *reinterpret_cast<const float4*>(shift + c);
@@ -81,8 +131,8 @@ __device__ __forceinline__ unsigned fp_bf16_rne(float v) {
     u += 0x7fffu + ((u >> 16) & 1u);
     return u >> 16;
 }
-__global__ __launch_bounds__(256) void frame_apply_tiles_kernel(const float* __restrict__ raw,
-                                                                const int32_t* __restrict__ num_frames, int B,
+template <typename Src>
+__global__ __launch_bounds__(256) void frame_apply_tiles_kernel(Src raw, const int32_t* __restrict__ num_frames, int B,
                                                                 int max_frames, int F, int S, float step,
                                                                 const float* __restrict__ scale,
                                                                 const float* __restrict__ shift, float* __restrict__ y,
@@ -111,7 +161,7 @@ __global__ __launch_bounds__(256) void frame_apply_tiles_kernel(const float* __r
             if (j < S) {
                 int idx = sample_index(j, step, nf);
                 idx = max(0, min(idx, max_frames - 1));
-                f = *reinterpret_cast<const float4*>(raw + ((int64_t)b * max_frames + idx) * F + c);
+                f = raw.load4(((int64_t)b * max_frames + idx) * F + c, (int64_t)b * S + j);
                 f.x = fmaf(f.x, sc.x, sh.x); f.y = fmaf(f.y, sc.y, sh.y);
                 f.z = fmaf(f.z, sc.z, sh.z); f.w = fmaf(f.w, sc.w, sh.w);
                 const int64_t row = (int64_t)b * S + j;
@@ -207,27 +257,36 @@ __global__ __launch_bounds__(256) void dequantize_l2_normalize_kernel(const unsi
             for (int c = lane; c < F4; c += 64) dst[c] = make_float4(0.f, 0.f, 0.f, 0.f);
             continue;
         }
-        const uchar4* src = reinterpret_cast<const uchar4*>(q + r * F);
         float4 v[8];
-        float ss = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int c = lane + 64 * i;
-            v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (c < F4) {
-                const uchar4 u = src[c];
-                v[i] = make_float4(fmaf((float)u.x, scalar, bias), fmaf((float)u.y, scalar, bias), fmaf((float)u.z, scalar, bias),
-                                   fmaf((float)u.w, scalar, bias));
-            }
-            ss += v[i].x * v[i].x + v[i].y * v[i].y + v[i].z * v[i].z + v[i].w * v[i].w;
-        }
-        ss = wave_sum(ss);
-        const float inv = rsqrtf(fmaxf(ss, 1e-12f));
+        const float inv = dequant_row_inv_norm(reinterpret_cast<const uchar4*>(q + r * F), lane, F4, scalar, bias, v);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int c = lane + 64 * i;
             if (c < F4) dst[c] = make_float4(v[i].x * inv, v[i].y * inv, v[i].z * inv, v[i].w * inv);
         }
+    }
+}
+
+// The inverse L2 norm of the dequantised frame behind every SAMPLED row r = b S + j (the frame idx = sample_index(j) of clip b), for
+// the FrameSrc<unsigned char> apply kernels: 1 byte read per feature of the S sampled frames, 4 bytes written per row.  A frame at
+// or past num_frames[b] -- zero after the reader's padding -- gets 0.  Same wave split and order as dequantize_l2_normalize_kernel.
+__global__ __launch_bounds__(256) void frame_inv_norm_q8_kernel(const unsigned char* __restrict__ q, const int32_t* __restrict__ num_frames,
+                                                                int B, int max_frames, int F, int S, float step, float scalar, float bias,
+                                                                float* __restrict__ inv) {
+    const int lane = threadIdx.x & 63;
+    const int F4 = F >> 2;
+    const int64_t rows = (int64_t)B * S;
+    for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4) {
+        const int b = (int)(r / S), j = (int)(r % S);
+        const int nf = num_frames[b];
+        int idx = sample_index(j, step, nf);
+        idx = max(0, min(idx, max_frames - 1));
+        float s = 0.f;
+        if (idx < nf) {                                   // wave-uniform
+            float4 v[8];
+            s = dequant_row_inv_norm(reinterpret_cast<const uchar4*>(q + ((int64_t)b * max_frames + idx) * F), lane, F4, scalar, bias, v);
+        }
+        if (lane == 0) inv[r] = s;
     }
 }
 
@@ -265,8 +324,8 @@ __global__ __launch_bounds__(256) void l2_normalize_rows_kernel(const float* __r
 // PL = 2 (fp32 storage, lpm_frame_apply_tiles2): the same pass writes the SPLIT-bf16 forms -- frame tiles with ceil(S / 16) steps per
 // clip (the layout of lpm_split_frames) and row tiles with 2 ceil(S / 64) tiles per clip (the layout of lpm_split_rows_tiles), hi and
 // lo planes -- so that K1 needs no tile-split pass of its own over the fp32 matrix.
-template <int PL>
-__global__ __launch_bounds__(256) void frame_apply_tiles_bf16_kernel(const float* __restrict__ raw, const int32_t* __restrict__ num_frames,
+template <int PL, typename Src>
+__global__ __launch_bounds__(256) void frame_apply_tiles_bf16_kernel(Src raw, const int32_t* __restrict__ num_frames,
                                                                      int B, int max_frames, int F, int S, float step,
                                                                      const float* __restrict__ scale, const float* __restrict__ shift,
                                                                      float* __restrict__ y, uint4* __restrict__ xtv, uint4* __restrict__ xrv,
@@ -293,9 +352,9 @@ __global__ __launch_bounds__(256) void frame_apply_tiles_bf16_kernel(const float
             if (j < S) {
                 int idx = sample_index(j, step, nf);
                 idx = max(0, min(idx, max_frames - 1));
-                const float* src = raw + ((int64_t)b * max_frames + idx) * F + c;
-                f0 = *reinterpret_cast<const float4*>(src);
-                f1 = *reinterpret_cast<const float4*>(src + 4);
+                const int64_t src = ((int64_t)b * max_frames + idx) * F + c, row = (int64_t)b * S + j;
+                f0 = raw.load4(src, row);
+                f1 = raw.load4(src + 4, row);
                 f0.x = fmaf(f0.x, sc[0], sh[0]); f0.y = fmaf(f0.y, sc[1], sh[1]); f0.z = fmaf(f0.z, sc[2], sh[2]); f0.w = fmaf(f0.w, sc[3], sh[3]);
                 f1.x = fmaf(f1.x, sc[4], sh[4]); f1.y = fmaf(f1.y, sc[5], sh[5]); f1.z = fmaf(f1.z, sc[6], sh[6]); f1.w = fmaf(f1.w, sc[7], sh[7]);
                 if (y) {
@@ -357,6 +416,86 @@ extern "C" int lpm_frame_stats_nblk(int B, int S) { return fp_nblk(B, S); }
     LPM_REQUIRE(B > 0 && max_frames > 0 && F > 0 && S > 0, LPM_ERR_BADARG, name ": bad sizes");                      \
     LPM_REQUIRE(F % 4 == 0, LPM_ERR_UNSUPPORTED_SHAPE, name ": need F %% 4 == 0 (F=%d)", F)
 
+// The quantised forms (*_q8): q [B, max_frames, F] uint8 (4-byte aligned), inv_norm [B S] from lpm_frame_inv_norm_q8 with the same
+// num_frames / S / quantisation range.
+#define LPM_FRAME_Q8_CHECK(name)                                                                                                     \
+    LPM_REQUIRE(q && inv_norm && num_frames, LPM_ERR_BADARG, name ": null pointer");                                                 \
+    LPM_REQUIRE(max_quantized_value > min_quantized_value, LPM_ERR_BADARG, name ": empty quantisation range");                       \
+    LPM_REQUIRE(B > 0 && max_frames > 0 && F > 0 && S > 0, LPM_ERR_BADARG, name ": bad sizes");                                       \
+    LPM_REQUIRE(F % 4 == 0 && ((uintptr_t)q & 3) == 0, LPM_ERR_UNSUPPORTED_SHAPE, name ": need F %% 4 == 0, aligned input (F=%d)", F)
+
+namespace {
+
+using lpm::FrameSrc;
+
+// utils.Dequantize's affine, computed as lpm_dequantize_l2_normalize computes it
+FrameSrc<unsigned char> q8_src(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value) {
+    const float range = max_quantized_value - min_quantized_value;
+    return FrameSrc<unsigned char>{q, inv_norm, range / 255.0f, range / 512.0f + min_quantized_value};
+}
+
+template <typename Src>
+int launch_frame_apply(Src raw, const int32_t* num_frames, int B, int max_frames, int F, int S, const float* scale, const float* shift,
+                       float* y, hipStream_t stream, const char* name) {
+    using namespace lpm;
+    LPM_REQUIRE(y && ((scale == nullptr) == (shift == nullptr)), LPM_ERR_BADARG, "%s: bad pointers", name);
+    const float step = 1.0f / (float)S;
+    const int64_t total = (int64_t)B * S * (F / 4);
+    const int64_t want = (total + 255) / 256;
+    hipLaunchKernelGGL(frame_apply_kernel<Src>, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, stream, raw, num_frames, B,
+                       max_frames, F, S, step, scale, shift, y);
+    return check_launch(name);
+}
+
+// y2 == NULL: one [B S, F] matrix y (lpm_frame_apply_tiles); else y [B S, Dv] and y2 [B S, Da] (lpm_frame_apply_tiles_split)
+template <typename Src>
+int launch_frame_apply_tiles(Src raw, const int32_t* num_frames, int B, int max_frames, int F, int S, const float* scale,
+                             const float* shift, float* y, float* y2, void* xt_video, int Dv, void* xt_audio, int Da, hipStream_t stream,
+                             const char* name) {
+    using namespace lpm;
+    if (y2 == nullptr) {
+        LPM_REQUIRE(y && ((scale == nullptr) == (shift == nullptr)), LPM_ERR_BADARG, "%s: bad pointers", name);
+        LPM_REQUIRE(Dv > 0 && Da >= 0 && Dv + Da == F && Dv % 32 == 0 && Da % 32 == 0, LPM_ERR_UNSUPPORTED_SHAPE,
+                    "%s: need Dv + Da == F, both multiples of 32 (F=%d Dv=%d Da=%d)", name, F, Dv, Da);
+    } else {
+        LPM_REQUIRE(y && ((scale == nullptr) == (shift == nullptr)), LPM_ERR_BADARG, "%s: bad pointers", name);
+        LPM_REQUIRE(Dv > 0 && Da > 0 && Dv + Da == F && Dv % 32 == 0 && Da % 32 == 0 && (((uintptr_t)y | (uintptr_t)y2) & 15) == 0,
+                    LPM_ERR_UNSUPPORTED_SHAPE, "%s: need Dv + Da == F, both multiples of 32, aligned outputs (F=%d Dv=%d Da=%d)", name, F,
+                    Dv, Da);
+    }
+    const float step = 1.0f / (float)S;
+    const int64_t total = (int64_t)B * ((S + 15) / 16) * 2 * (F / 4);
+    const int64_t want = (total + 255) / 256;
+    hipLaunchKernelGGL(frame_apply_tiles_kernel<Src>, dim3((unsigned)(want < 8192 ? want : 8192)), dim3(256), 0, stream, raw, num_frames,
+                       B, max_frames, F, S, step, scale, shift, y, (uint4*)xt_video, Dv, (uint4*)xt_audio, Da, y2);
+    return check_launch(name);
+}
+
+// PL = 1: lpm_frame_apply_tiles_bf16 (y optional, row tiles required); PL = 2: lpm_frame_apply_tiles2 (y required, row tiles optional)
+template <int PL, typename Src>
+int launch_frame_apply_tiles_bf16(Src raw, const int32_t* num_frames, int B, int max_frames, int F, int S, const float* scale,
+                                  const float* shift, float* y, void* xt_video, void* xr_video, int Dv, void* xt_audio, void* xr_audio,
+                                  int Da, hipStream_t stream, const char* name) {
+    using namespace lpm;
+    if (PL == 1)
+        LPM_REQUIRE(xt_video && xr_video && ((scale == nullptr) == (shift == nullptr)) && ((xt_audio == nullptr) == (xr_audio == nullptr)),
+                    LPM_ERR_BADARG, "%s: bad pointers", name);
+    else
+        LPM_REQUIRE(y && xt_video && ((scale == nullptr) == (shift == nullptr)) && (Da == 0 || xt_audio), LPM_ERR_BADARG,
+                    "%s: bad pointers", name);
+    LPM_REQUIRE(Dv > 0 && Da >= 0 && Dv + Da == F && Dv % 32 == 0 && Da % 32 == 0, LPM_ERR_UNSUPPORTED_SHAPE,
+                "%s: need Dv + Da == F, both multiples of 32 (F=%d Dv=%d Da=%d)", name, F, Dv, Da);
+    const float step = 1.0f / (float)S;
+    const int64_t total = (int64_t)B * 4 * ((S + 63) / 64) * 2 * (F / 8);
+    const int64_t want = (total + 255) / 256;
+    hipLaunchKernelGGL((frame_apply_tiles_bf16_kernel<PL, Src>), dim3((unsigned)(want < 16384 ? want : 16384)), dim3(256), 0, stream, raw,
+                       num_frames, B, max_frames, F, S, step, scale, shift, y, (uint4*)xt_video, (uint4*)xr_video, Dv, (uint4*)xt_audio,
+                       (uint4*)xr_audio, Da);
+    return check_launch(name);
+}
+
+}  // namespace
+
 extern "C" int lpm_frame_stats(const float* raw, const int32_t* num_frames, int B, int max_frames, int F, int S,
                                float* partial, lpm_stream_t stream) {
     using namespace lpm;
@@ -370,48 +509,25 @@ extern "C" int lpm_frame_stats(const float* raw, const int32_t* num_frames, int 
 
 extern "C" int lpm_frame_apply(const float* raw, const int32_t* num_frames, int B, int max_frames, int F, int S,
                                const float* scale, const float* shift, float* y, lpm_stream_t stream) {
-    using namespace lpm;
     LPM_FRAME_CHECK("lpm_frame_apply");
-    LPM_REQUIRE(y && ((scale == nullptr) == (shift == nullptr)), LPM_ERR_BADARG, "lpm_frame_apply: bad pointers");
-    const float step = 1.0f / (float)S;
-    const int64_t total = (int64_t)B * S * (F / 4);
-    const int64_t want = (total + 255) / 256;
-    hipLaunchKernelGGL(frame_apply_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, (hipStream_t)stream, raw,
-                       num_frames, B, max_frames, F, S, step, scale, shift, y);
-    return check_launch("lpm_frame_apply");
+    return launch_frame_apply(FrameSrc<float>{raw}, num_frames, B, max_frames, F, S, scale, shift, y, (hipStream_t)stream, "lpm_frame_apply");
 }
 
 extern "C" int lpm_frame_apply_tiles(const float* raw, const int32_t* num_frames, int B, int max_frames, int F, int S,
                                      const float* scale, const float* shift, float* y, void* xt_video, int Dv,
                                      void* xt_audio, int Da, lpm_stream_t stream) {
-    using namespace lpm;
     LPM_FRAME_CHECK("lpm_frame_apply_tiles");
-    LPM_REQUIRE(y && ((scale == nullptr) == (shift == nullptr)), LPM_ERR_BADARG, "lpm_frame_apply_tiles: bad pointers");
-    LPM_REQUIRE(Dv > 0 && Da >= 0 && Dv + Da == F && Dv % 32 == 0 && Da % 32 == 0, LPM_ERR_UNSUPPORTED_SHAPE,
-                "lpm_frame_apply_tiles: need Dv + Da == F, both multiples of 32 (F=%d Dv=%d Da=%d)", F, Dv, Da);
-    const float step = 1.0f / (float)S;
-    const int64_t total = (int64_t)B * ((S + 15) / 16) * 2 * (F / 4);
-    const int64_t want = (total + 255) / 256;
-    hipLaunchKernelGGL(frame_apply_tiles_kernel, dim3((unsigned)(want < 8192 ? want : 8192)), dim3(256), 0, (hipStream_t)stream, raw,
-                       num_frames, B, max_frames, F, S, step, scale, shift, y, (uint4*)xt_video, Dv, (uint4*)xt_audio, Da, (float*)nullptr);
-    return check_launch("lpm_frame_apply_tiles");
+    return launch_frame_apply_tiles(FrameSrc<float>{raw}, num_frames, B, max_frames, F, S, scale, shift, y, nullptr, xt_video, Dv, xt_audio,
+                                    Da, (hipStream_t)stream, "lpm_frame_apply_tiles");
 }
 // ... with the two column blocks as two contiguous matrices y_video [B S, Dv] and y_audio [B S, Da] (round 6: NetVladV2)
 extern "C" int lpm_frame_apply_tiles_split(const float* raw, const int32_t* num_frames, int B, int max_frames, int F, int S,
                                            const float* scale, const float* shift, float* y_video, float* y_audio, void* xt_video, int Dv,
                                            void* xt_audio, int Da, lpm_stream_t stream) {
-    using namespace lpm;
     LPM_FRAME_CHECK("lpm_frame_apply_tiles_split");
-    LPM_REQUIRE(y_video && y_audio && ((scale == nullptr) == (shift == nullptr)), LPM_ERR_BADARG, "lpm_frame_apply_tiles_split: bad pointers");
-    LPM_REQUIRE(Dv > 0 && Da > 0 && Dv + Da == F && Dv % 32 == 0 && Da % 32 == 0 && (((uintptr_t)y_video | (uintptr_t)y_audio) & 15) == 0,
-                LPM_ERR_UNSUPPORTED_SHAPE, "lpm_frame_apply_tiles_split: need Dv + Da == F, both multiples of 32, aligned outputs (F=%d Dv=%d Da=%d)",
-                F, Dv, Da);
-    const float step = 1.0f / (float)S;
-    const int64_t total = (int64_t)B * ((S + 15) / 16) * 2 * (F / 4);
-    const int64_t want = (total + 255) / 256;
-    hipLaunchKernelGGL(frame_apply_tiles_kernel, dim3((unsigned)(want < 8192 ? want : 8192)), dim3(256), 0, (hipStream_t)stream, raw,
-                       num_frames, B, max_frames, F, S, step, scale, shift, y_video, (uint4*)xt_video, Dv, (uint4*)xt_audio, Da, y_audio);
-    return check_launch("lpm_frame_apply_tiles_split");
+    LPM_REQUIRE(y_video && y_audio, LPM_ERR_BADARG, "lpm_frame_apply_tiles_split: bad pointers");
+    return launch_frame_apply_tiles(FrameSrc<float>{raw}, num_frames, B, max_frames, F, S, scale, shift, y_video, y_audio, xt_video, Dv,
+                                    xt_audio, Da, (hipStream_t)stream, "lpm_frame_apply_tiles_split");
 }
 
 // bf16 storage: see frame_apply_tiles_bf16_kernel.  y may be NULL (then the fp32 frames are not written at all); the tile buffers
@@ -420,19 +536,9 @@ extern "C" size_t lpm_frame_tiles_bf16_bytes(int B, int S, int D) { return (size
 extern "C" int lpm_frame_apply_tiles_bf16(const float* raw, const int32_t* num_frames, int B, int max_frames, int F, int S,
                                           const float* scale, const float* shift, float* y, void* xt_video, void* xr_video, int Dv,
                                           void* xt_audio, void* xr_audio, int Da, lpm_stream_t stream) {
-    using namespace lpm;
     LPM_FRAME_CHECK("lpm_frame_apply_tiles_bf16");
-    LPM_REQUIRE(xt_video && xr_video && ((scale == nullptr) == (shift == nullptr)) && ((xt_audio == nullptr) == (xr_audio == nullptr)),
-                LPM_ERR_BADARG, "lpm_frame_apply_tiles_bf16: bad pointers");
-    LPM_REQUIRE(Dv > 0 && Da >= 0 && Dv + Da == F && Dv % 32 == 0 && Da % 32 == 0, LPM_ERR_UNSUPPORTED_SHAPE,
-                "lpm_frame_apply_tiles_bf16: need Dv + Da == F, both multiples of 32 (F=%d Dv=%d Da=%d)", F, Dv, Da);
-    const float step = 1.0f / (float)S;
-    const int64_t total = (int64_t)B * 4 * ((S + 63) / 64) * 2 * (F / 8);
-    const int64_t want = (total + 255) / 256;
-    hipLaunchKernelGGL(frame_apply_tiles_bf16_kernel<1>, dim3((unsigned)(want < 16384 ? want : 16384)), dim3(256), 0, (hipStream_t)stream,
-                       raw, num_frames, B, max_frames, F, S, step, scale, shift, y, (uint4*)xt_video, (uint4*)xr_video, Dv,
-                       (uint4*)xt_audio, (uint4*)xr_audio, Da);
-    return check_launch("lpm_frame_apply_tiles_bf16");
+    return launch_frame_apply_tiles_bf16<1>(FrameSrc<float>{raw}, num_frames, B, max_frames, F, S, scale, shift, y, xt_video, xr_video, Dv,
+                                            xt_audio, xr_audio, Da, (hipStream_t)stream, "lpm_frame_apply_tiles_bf16");
 }
 
 // fp32 storage: a2 + a3 -> y (fp32 [B*S, F]) AND the split-bf16 frame tiles (lpm_xt_bytes each: K2's operand) AND row tiles
@@ -440,19 +546,69 @@ extern "C" int lpm_frame_apply_tiles_bf16(const float* raw, const int32_t* num_f
 extern "C" int lpm_frame_apply_tiles2(const float* raw, const int32_t* num_frames, int B, int max_frames, int F, int S,
                                       const float* scale, const float* shift, float* y, void* xt_video, void* xr_video, int Dv,
                                       void* xt_audio, void* xr_audio, int Da, lpm_stream_t stream) {
-    using namespace lpm;
     LPM_FRAME_CHECK("lpm_frame_apply_tiles2");
-    LPM_REQUIRE(y && xt_video && ((scale == nullptr) == (shift == nullptr)) && (Da == 0 || xt_audio), LPM_ERR_BADARG,
-                "lpm_frame_apply_tiles2: bad pointers");
-    LPM_REQUIRE(Dv > 0 && Da >= 0 && Dv + Da == F && Dv % 32 == 0 && Da % 32 == 0, LPM_ERR_UNSUPPORTED_SHAPE,
-                "lpm_frame_apply_tiles2: need Dv + Da == F, both multiples of 32 (F=%d Dv=%d Da=%d)", F, Dv, Da);
-    const float step = 1.0f / (float)S;
-    const int64_t total = (int64_t)B * 4 * ((S + 63) / 64) * 2 * (F / 8);
-    const int64_t want = (total + 255) / 256;
-    hipLaunchKernelGGL(frame_apply_tiles_bf16_kernel<2>, dim3((unsigned)(want < 16384 ? want : 16384)), dim3(256), 0, (hipStream_t)stream,
-                       raw, num_frames, B, max_frames, F, S, step, scale, shift, y, (uint4*)xt_video, (uint4*)xr_video, Dv,
-                       (uint4*)xt_audio, (uint4*)xr_audio, Da);
-    return check_launch("lpm_frame_apply_tiles2");
+    return launch_frame_apply_tiles_bf16<2>(FrameSrc<float>{raw}, num_frames, B, max_frames, F, S, scale, shift, y, xt_video, xr_video, Dv,
+                                            xt_audio, xr_audio, Da, (hipStream_t)stream, "lpm_frame_apply_tiles2");
+}
+
+// ---- eval mode from the reader's quantised frames -----------------------------------------------------------------------------
+extern "C" int lpm_frame_inv_norm_q8(const unsigned char* q, const int32_t* num_frames, int B, int max_frames, int F, int S,
+                                     float max_quantized_value, float min_quantized_value, float* inv_norm, lpm_stream_t stream) {
+    using namespace lpm;
+    LPM_FRAME_Q8_CHECK("lpm_frame_inv_norm_q8");
+    LPM_REQUIRE(F <= 2048, LPM_ERR_UNSUPPORTED_SHAPE, "lpm_frame_inv_norm_q8: need F <= 2048 (F=%d)", F);
+    const FrameSrc<unsigned char> src = q8_src(q, inv_norm, max_quantized_value, min_quantized_value);
+    const int64_t rows = (int64_t)B * S, want = (rows + 3) / 4;
+    hipLaunchKernelGGL(frame_inv_norm_q8_kernel, dim3((unsigned)(want < 16384 ? want : 16384)), dim3(256), 0, (hipStream_t)stream, q,
+                       num_frames, B, max_frames, F, S, 1.0f / (float)S, src.scalar, src.bias, inv_norm);
+    return check_launch("lpm_frame_inv_norm_q8");
+}
+
+extern "C" int lpm_frame_apply_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
+                                  const int32_t* num_frames, int B, int max_frames, int F, int S, const float* scale, const float* shift,
+                                  float* y, lpm_stream_t stream) {
+    LPM_FRAME_Q8_CHECK("lpm_frame_apply_q8");
+    return launch_frame_apply(q8_src(q, inv_norm, max_quantized_value, min_quantized_value), num_frames, B, max_frames, F, S, scale, shift,
+                              y, (hipStream_t)stream, "lpm_frame_apply_q8");
+}
+
+extern "C" int lpm_frame_apply_tiles_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value,
+                                        float min_quantized_value, const int32_t* num_frames, int B, int max_frames, int F, int S,
+                                        const float* scale, const float* shift, float* y, void* xt_video, int Dv, void* xt_audio, int Da,
+                                        lpm_stream_t stream) {
+    LPM_FRAME_Q8_CHECK("lpm_frame_apply_tiles_q8");
+    return launch_frame_apply_tiles(q8_src(q, inv_norm, max_quantized_value, min_quantized_value), num_frames, B, max_frames, F, S, scale,
+                                    shift, y, nullptr, xt_video, Dv, xt_audio, Da, (hipStream_t)stream, "lpm_frame_apply_tiles_q8");
+}
+
+extern "C" int lpm_frame_apply_tiles_split_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value,
+                                              float min_quantized_value, const int32_t* num_frames, int B, int max_frames, int F, int S,
+                                              const float* scale, const float* shift, float* y_video, float* y_audio, void* xt_video,
+                                              int Dv, void* xt_audio, int Da, lpm_stream_t stream) {
+    LPM_FRAME_Q8_CHECK("lpm_frame_apply_tiles_split_q8");
+    LPM_REQUIRE(y_video && y_audio, LPM_ERR_BADARG, "lpm_frame_apply_tiles_split_q8: bad pointers");
+    return launch_frame_apply_tiles(q8_src(q, inv_norm, max_quantized_value, min_quantized_value), num_frames, B, max_frames, F, S, scale,
+                                    shift, y_video, y_audio, xt_video, Dv, xt_audio, Da, (hipStream_t)stream, "lpm_frame_apply_tiles_split_q8");
+}
+
+extern "C" int lpm_frame_apply_tiles_bf16_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value,
+                                             float min_quantized_value, const int32_t* num_frames, int B, int max_frames, int F, int S,
+                                             const float* scale, const float* shift, float* y, void* xt_video, void* xr_video, int Dv,
+                                             void* xt_audio, void* xr_audio, int Da, lpm_stream_t stream) {
+    LPM_FRAME_Q8_CHECK("lpm_frame_apply_tiles_bf16_q8");
+    return launch_frame_apply_tiles_bf16<1>(q8_src(q, inv_norm, max_quantized_value, min_quantized_value), num_frames, B, max_frames, F, S,
+                                            scale, shift, y, xt_video, xr_video, Dv, xt_audio, xr_audio, Da, (hipStream_t)stream,
+                                            "lpm_frame_apply_tiles_bf16_q8");
+}
+
+extern "C" int lpm_frame_apply_tiles2_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value,
+                                         float min_quantized_value, const int32_t* num_frames, int B, int max_frames, int F, int S,
+                                         const float* scale, const float* shift, float* y, void* xt_video, void* xr_video, int Dv,
+                                         void* xt_audio, void* xr_audio, int Da, lpm_stream_t stream) {
+    LPM_FRAME_Q8_CHECK("lpm_frame_apply_tiles2_q8");
+    return launch_frame_apply_tiles_bf16<2>(q8_src(q, inv_norm, max_quantized_value, min_quantized_value), num_frames, B, max_frames, F, S,
+                                            scale, shift, y, xt_video, xr_video, Dv, xt_audio, xr_audio, Da, (hipStream_t)stream,
+                                            "lpm_frame_apply_tiles2_q8");
 }
 
 extern "C" int lpm_frame_bn_bwd(const float* dy, int64_t lddy, const float* raw, const int32_t* num_frames, int B,

@@ -336,7 +336,7 @@ class NetVladV2(models.BaseModel):
         max_frames, feature_size = iterations, model_input.shape[2]
         has_audio = feature_size > 1024
         split = None
-        if (has_audio and add_batch_norm and vs.default_store().summaries is None and ops.frame_sample_bn_split_ok(model_input, 1024)):
+        if (has_audio and add_batch_norm and vs.default_store().summaries is None and ops.frame_sample_bn_split_ok(model_input, 1024, is_training)):
             # the two streams' blocks of the sampled, batch-normalised frames as two contiguous matrices straight from the frame-prep
             # kernel (ops.frame_sample_bn_split): same values, same variables; no column slices, copies or gradient concatenation
             bn = layers.bn_variables("input_bn", feature_size, model_input.device)

@@ -34,3 +34,26 @@ def write_predictions(out_file, trainer, batches: Iterable, top_k: int = 20) -> 
             out_file.write(line)
         n += len(ids)
     return n
+
+
+def format_top_k_lines(video_ids: Sequence, class_indexes, scores) -> Iterator[str]:
+    """The lines of format_lines from an already selected top k (export_model.py's ``class_indexes`` / ``predictions``)."""
+    classes, scores = torch.as_tensor(class_indexes).cpu().tolist(), torch.as_tensor(scores).cpu().tolist()
+    for vid, cs, ss in zip(video_ids, classes, scores):
+        if isinstance(vid, bytes):
+            vid = vid.decode("utf-8")
+        yield vid + "," + " ".join("%i %g" % (c, s) for c, s in zip(cs, ss)) + "\n"
+
+
+def write_top_k(out_file, predictor, batches: Iterable, top_k: int = 20) -> int:
+    """write_predictions' CSV, byte for byte, from a predictor.Predictor: the top k of every video selected on the GPU
+    (Predictor.top_k, lpm_topk_rows) instead of a sort of all classes.  Returns the number of videos written."""
+    k = min(int(top_k), predictor.vocab_size)
+    out_file.write(CSV_HEADER)
+    n = 0
+    for ids, frames, _, num_frames in batches:
+        classes, scores = predictor.top_k(frames, num_frames, k)
+        for line in format_top_k_lines(ids, classes, scores):
+            out_file.write(line)
+        n += len(ids)
+    return n

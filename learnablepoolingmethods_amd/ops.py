@@ -252,15 +252,50 @@ def dequantize_l2_normalize(q, num_frames, max_quantized_value=2.0, min_quantize
 # ----------------------------------------------------------------------------------------------
 # a2 + a3: SampleUniformFrames + input_bn
 # ----------------------------------------------------------------------------------------------
+# The reader's quantisation range (readers.py: max_quantized_value=2, min_quantized_value=-2): uint8 frames reaching the frame-prep
+# ops are dequantised with it, as Trainer._normalize_input's dequantize_l2_normalize does.
+QUANT_MAX, QUANT_MIN = 2.0, -2.0
+
+
+def _check_q8_eval(raw, is_training, what):
+    """uint8 frames are the reader's quantised batch: accepted in eval mode only (the training path needs fp32 frames)."""
+    if raw.dtype == torch.uint8 and is_training:
+        raise LpmError(f"{what}: uint8 (quantised) frames are accepted in eval mode only (is_training=False); training needs the "
+                       "dequantised, L2-normalised fp32 frames (ops.dequantize_l2_normalize)")
+
+
+def _frame_inputs(lib, raw, num_frames, S, what):
+    """-> (raw, nf, inv): fp32 frames as they are (inv None), or uint8 frames with the inverse L2 norms of their S sampled rows per clip
+    (lpm_frame_inv_norm_q8) for the *_q8 apply forms."""
+    nf = num_frames.to(device=raw.device, dtype=torch.int32).contiguous()
+    if raw.dtype != torch.uint8:
+        return _f32(raw, what).contiguous(), nf, None
+    raw = raw.contiguous()
+    if raw.dim() != 3:
+        raise LpmError(f"{what} must be [batch, max_frames, feature]")
+    B, MF, F = raw.shape
+    inv = _empty((B * S,), raw)
+    lib.check(lib._lpm_frame_inv_norm_q8(ptr(raw), ptr(nf), B, MF, F, S, QUANT_MAX, QUANT_MIN, ptr(inv), stream_ptr()),
+              "lpm_frame_inv_norm_q8")
+    return raw, nf, inv
+
+
+def _frame_apply_call(lib, name, raw, inv, *args):
+    """lpm_<name>(raw, *args), or its quantised form lpm_<name>_q8(q, inv_norm, range, *args) when inv is given."""
+    if inv is None:
+        lib.check(getattr(lib, "_lpm_" + name)(ptr(raw), *args), "lpm_" + name)
+    else:
+        lib.check(getattr(lib, "_lpm_" + name + "_q8")(ptr(raw), ptr(inv), QUANT_MAX, QUANT_MIN, *args), "lpm_" + name + "_q8")
+
+
 class _FrameSampleBN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, raw, num_frames, gamma, beta, moving_mean, moving_var, S, is_training, use_bn, storage="f32", materialize=True):
         lib = _capi.load()
-        raw = _f32(raw, "model_input").contiguous()
+        raw, nf, inv = _frame_inputs(lib, raw, num_frames, S, "model_input")
         if raw.dim() != 3:
             raise LpmError("model_input must be [batch, max_frames, feature]")
         B, MF, F = raw.shape
-        nf = num_frames.to(device=raw.device, dtype=torch.int32).contiguous()
         y = _empty((B * S, F), raw)
         mean = var = None
         if use_bn:
@@ -284,9 +319,8 @@ class _FrameSampleBN(torch.autograd.Function):
             nb = lambda d: torch.empty(lib._lpm_frame_tiles_bf16_bytes(B, S, d) // 4, dtype=torch.int32, device=raw.device)
             xtv, xrv = nb(Dv), nb(Dv)
             xta, xra = (nb(Da), nb(Da)) if Da else (None, None)
-            lib.check(lib._lpm_frame_apply_tiles_bf16(ptr(raw), ptr(nf), B, MF, F, S, ptr(scale), ptr(shift), ptr(y) if materialize else None,
-                                                      ptr(xtv), ptr(xrv), Dv, ptr(xta), ptr(xra), Da, stream_ptr()),
-                      "lpm_frame_apply_tiles_bf16")
+            _frame_apply_call(lib, "frame_apply_tiles_bf16", raw, inv, ptr(nf), B, MF, F, S, ptr(scale), ptr(shift),
+                              ptr(y) if materialize else None, ptr(xtv), ptr(xrv), Dv, ptr(xta), ptr(xra), Da, stream_ptr())
             _XT_CACHE.clear()
             _XT_CACHE.update(base=weakref.ref(y), F=F, Dv=Dv, S=S, B=B, video=xtv, audio=xta, video_rows=xrv, audio_rows=xra,
                              storage="bf16", unmaterialised=None if materialize else y.untyped_storage().data_ptr())
@@ -299,18 +333,18 @@ class _FrameSampleBN(torch.autograd.Function):
                 # K1's row-tile operand leaves with the same pass (no lpm_split_rows_tiles over the fp32 matrix afterwards)
                 xrv = torch.empty(lib._lpm_row_tiles_bytes(B, S, Dv) // 4, dtype=torch.int32, device=raw.device)
                 xra = torch.empty(lib._lpm_row_tiles_bytes(B, S, Da) // 4, dtype=torch.int32, device=raw.device) if Da else None
-                lib.check(lib._lpm_frame_apply_tiles2(ptr(raw), ptr(nf), B, MF, F, S, ptr(scale), ptr(shift), ptr(y), ptr(xtv), ptr(xrv),
-                                                      Dv, ptr(xta), ptr(xra), Da, stream_ptr()), "lpm_frame_apply_tiles2")
+                _frame_apply_call(lib, "frame_apply_tiles2", raw, inv, ptr(nf), B, MF, F, S, ptr(scale), ptr(shift), ptr(y), ptr(xtv),
+                                  ptr(xrv), Dv, ptr(xta), ptr(xra), Da, stream_ptr())
             else:
-                lib.check(lib._lpm_frame_apply_tiles(ptr(raw), ptr(nf), B, MF, F, S, ptr(scale), ptr(shift), ptr(y), ptr(xtv), Dv,
-                                                     ptr(xta), Da, stream_ptr()), "lpm_frame_apply_tiles")
+                _frame_apply_call(lib, "frame_apply_tiles", raw, inv, ptr(nf), B, MF, F, S, ptr(scale), ptr(shift), ptr(y), ptr(xtv), Dv,
+                                  ptr(xta), Da, stream_ptr())
             _XT_CACHE.clear()
             _XT_CACHE.update(base=weakref.ref(y), F=F, Dv=Dv, S=S, B=B, video=xtv, audio=xta, video_rows=xrv, audio_rows=xra)
         else:
-            lib.check(lib._lpm_frame_apply(ptr(raw), ptr(nf), B, MF, F, S, ptr(scale), ptr(shift), ptr(y), stream_ptr()),
-                      "lpm_frame_apply")
+            _frame_apply_call(lib, "frame_apply", raw, inv, ptr(nf), B, MF, F, S, ptr(scale), ptr(shift), ptr(y), stream_ptr())
         ctx.use_bn, ctx.is_training, ctx.S = use_bn, is_training, S
-        if use_bn:
+        ctx.q8 = inv is not None
+        if use_bn and not ctx.q8:
             if is_training:
                 ctx.save_for_backward(raw, nf, mean, var)
             else:
@@ -321,6 +355,8 @@ class _FrameSampleBN(torch.autograd.Function):
     def backward(ctx, dy):
         if not ctx.use_bn:
             return (None,) * 11
+        if ctx.q8:
+            raise LpmError("frame_sample_bn: no gradient through the eval-mode path of uint8 frames")
         lib = _capi.load()
         raw, nf, mean, var = ctx.saved_tensors
         B, MF, F = raw.shape
@@ -331,6 +367,28 @@ class _FrameSampleBN(torch.autograd.Function):
         lib.check(lib._lpm_frame_bn_bwd(ptr(dy), dy.stride(0), ptr(raw), ptr(nf), B, MF, F, ctx.S, ptr(mean), ptr(var),
                                         BN_EPS, ptr(dgamma), ptr(dbeta), ptr(ws), wsb, stream_ptr()), "lpm_frame_bn_bwd")
         return None, None, dgamma, dbeta, None, None, None, None, None, None, None
+
+
+TOPK_MAX_K = 64          # lpm_topk_rows' limits
+TOPK_MAX_V = 65536
+
+
+def topk_rows(p, k):
+    """-> (index int32 [B, k], value fp32 [B, k]): the k largest entries of every row of p [B, V] in the order of
+    torch.sort(p, dim=1, descending=True, stable=True)[:, :k] (lpm_topk_rows)."""
+    if p.dtype != torch.float32 or p.dim() != 2:
+        raise LpmError("topk_rows: expected a float32 [batch, classes] tensor")
+    B, V = p.shape
+    k = int(k)
+    if not (1 <= k <= TOPK_MAX_K and k <= V <= TOPK_MAX_V):
+        raise LpmError(f"topk_rows: need 1 <= k <= {TOPK_MAX_K} and k <= classes <= {TOPK_MAX_V} (k={k}, classes={V})")
+    lib = _capi.load()
+    p = p.contiguous()
+    index = torch.empty((B, k), dtype=torch.int32, device=p.device)
+    value = torch.empty((B, k), dtype=torch.float32, device=p.device)
+    if B:
+        lib.check(lib._lpm_topk_rows(ptr(p), B, V, k, ptr(index), ptr(value), stream_ptr()), "lpm_topk_rows")
+    return index, value
 
 
 # ----------------------------------------------------------------------------------------------
@@ -449,7 +507,10 @@ def frame_sample_bn(raw, num_frames, S, gamma=None, beta=None, moving_mean=None,
     """[B, max_frames, F] -> [B*S, F]: uniform frame sampling (model_utils.py:101-122) fused with
     input_bn (frame_level_models.py:2265-2271).  The frames are data: no gradient flows to ``raw``.
     storage="bf16" (BASELINE cfg-5): the result is written as plain bf16 operand tiles for ops.netvlad(storage="bf16"); the fp32
-    matrix that is returned is filled in only with ``materialize`` (otherwise it is a handle nobody may read)."""
+    matrix that is returned is filled in only with ``materialize`` (otherwise it is a handle nobody may read).
+    ``raw`` may be the reader's uint8 batch (quantised, un-normalised) when ``is_training`` is False: the dequantisation and the per-frame
+    L2 normalisation of Trainer._normalize_input happen inside the frame pass, for the sampled frames only -- the same values bit for bit."""
+    _check_q8_eval(raw, is_training, "frame_sample_bn")
     use_bn = gamma is not None
     return _FrameSampleBN.apply(raw, num_frames, gamma, beta, moving_mean, moving_var, int(S), bool(is_training), use_bn, storage,
                                 bool(materialize))
@@ -464,10 +525,9 @@ class _FrameSampleBNSplit(torch.autograd.Function):
     @staticmethod
     def forward(ctx, raw, num_frames, gamma, beta, moving_mean, moving_var, S, is_training, Dv):
         lib = _capi.load()
-        raw = _f32(raw, "model_input").contiguous()
+        raw, nf, inv = _frame_inputs(lib, raw, num_frames, S, "model_input")
         B, MF, F = raw.shape
         Da = F - Dv
-        nf = num_frames.to(device=raw.device, dtype=torch.int32).contiguous()
         if is_training:
             nblk = lib._lpm_frame_stats_nblk(B, S)
             partial = _empty((nblk, 2, F), raw)
@@ -480,17 +540,19 @@ class _FrameSampleBNSplit(torch.autograd.Function):
         yv, ya = _empty((B * S, Dv), raw), _empty((B * S, Da), raw)
         xtv = torch.empty(lib._lpm_xt_bytes(B, S, Dv) // 4, dtype=torch.int32, device=raw.device)
         xta = torch.empty(lib._lpm_xt_bytes(B, S, Da) // 4, dtype=torch.int32, device=raw.device)
-        lib.check(lib._lpm_frame_apply_tiles_split(ptr(raw), ptr(nf), B, MF, F, S, ptr(scale), ptr(shift), ptr(yv), ptr(ya), ptr(xtv), Dv,
-                                                   ptr(xta), Da, stream_ptr()), "lpm_frame_apply_tiles_split")
+        _frame_apply_call(lib, "frame_apply_tiles_split", raw, inv, ptr(nf), B, MF, F, S, ptr(scale), ptr(shift), ptr(yv), ptr(ya), ptr(xtv),
+                          Dv, ptr(xta), Da, stream_ptr())
         _XT_CACHE.clear()
         _XT_CACHE.update(split=True, F=F, Dv=Dv, S=S, B=B, video=xtv, audio=xta, video_t=yv, audio_t=ya,
                          video_ver=yv._version, audio_ver=ya._version)
-        ctx.S, ctx.Dv = S, Dv
+        ctx.S, ctx.Dv, ctx.q8 = S, Dv, inv is not None
         ctx.save_for_backward(raw, nf, mean, var)
         return yv, ya
 
     @staticmethod
     def backward(ctx, dv, da):
+        if ctx.q8:
+            raise LpmError("frame_sample_bn_split: no gradient through the eval-mode path of uint8 frames")
         lib = _capi.load()
         raw, nf, mean, var = ctx.saved_tensors
         B, MF, F = raw.shape
@@ -509,14 +571,18 @@ class _FrameSampleBNSplit(torch.autograd.Function):
 FRAME_SPLIT = os.environ.get("LPM_FRAME_SPLIT", "1") != "0"      # "0": NetVladV2 slices one [B S, F] matrix (A/B)
 
 
-def frame_sample_bn_split_ok(raw, Dv):
-    return bool(FRAME_SPLIT and raw.is_cuda and raw.dim() == 3 and raw.dtype == torch.float32 and VLAD_PRECISION == "bf16x3"
+def frame_sample_bn_split_ok(raw, Dv, is_training=True):
+    """uint8 frames (the reader's quantised batch) qualify in eval mode only."""
+    dtype_ok = raw.dtype == torch.float32 or (raw.dtype == torch.uint8 and not is_training)
+    return bool(FRAME_SPLIT and raw.is_cuda and raw.dim() == 3 and dtype_ok and VLAD_PRECISION == "bf16x3"
                 and 0 < Dv < raw.shape[2] and Dv % 32 == 0 and (raw.shape[2] - Dv) % 32 == 0)
 
 
 def frame_sample_bn_split(raw, num_frames, S, gamma, beta, moving_mean, moving_var, is_training, Dv):
     """-> (rgb [B*S, Dv], audio [B*S, F - Dv]): uniform frame sampling + input_bn (model_utils.py:101-122, frame_level_models.py:2265-2271)
-    with the two streams' blocks as separate contiguous matrices; gamma / beta receive ONE gradient each."""
+    with the two streams' blocks as separate contiguous matrices; gamma / beta receive ONE gradient each.  uint8 ``raw``: as in
+    frame_sample_bn, eval mode only."""
+    _check_q8_eval(raw, is_training, "frame_sample_bn_split")
     return _FrameSampleBNSplit.apply(raw, num_frames, gamma, beta, moving_mean, moving_var, int(S), bool(is_training), int(Dv))
 
 

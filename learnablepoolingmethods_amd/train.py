@@ -455,6 +455,19 @@ class BucketGather:
         return {n for b in self.gathered for n in self.bucket_names[b]}
 
 
+def normalize_input(raw, num_frames=None):
+    """The model input of train.py:262-264: L2-normalised frames (the quantised reader output dequantised and zero-padded first)."""
+    if raw.dtype == torch.uint8:          # quantised reader output: dequantise + pad + normalise in one pass
+        if raw.is_cuda:
+            return ops.dequantize_l2_normalize(raw, num_frames)
+        t = torch.arange(raw.shape[1], device=raw.device).view(1, -1, 1)
+        x = torch.where(t < num_frames.view(-1, 1, 1), utils.Dequantize(raw.float()), torch.zeros((), device=raw.device))
+        return layers.l2_normalize(x, 2)
+    if raw.is_cuda and raw.shape[-1] % 4 == 0 and raw.shape[-1] <= 2048 and not raw.requires_grad:
+        return ops.l2_normalize_rows(raw)
+    return layers.l2_normalize(raw, 2)
+
+
 class Trainer:
     """Owns the variable store, the arenas and the optimiser state; ``step`` is one ``sess.run(train_op)``."""
 
@@ -518,15 +531,7 @@ class Trainer:
         return result, reg_losses
 
     def _normalize_input(self, raw, num_frames=None):
-        if raw.dtype == torch.uint8:          # quantised reader output: dequantise + pad + normalise in one pass
-            if raw.is_cuda:
-                return ops.dequantize_l2_normalize(raw, num_frames)
-            t = torch.arange(raw.shape[1], device=raw.device).view(1, -1, 1)
-            x = torch.where(t < num_frames.view(-1, 1, 1), utils.Dequantize(raw.float()), torch.zeros((), device=raw.device))
-            return layers.l2_normalize(x, 2)
-        if raw.is_cuda and raw.shape[-1] % 4 == 0 and raw.shape[-1] <= 2048 and not raw.requires_grad:
-            return ops.l2_normalize_rows(raw)
-        return layers.l2_normalize(raw, 2)
+        return normalize_input(raw, num_frames)
 
     def build(self, model_input_raw, num_frames, labels):
         """Create every variable (a throw-away forward: moving statistics are restored afterwards),
