@@ -909,6 +909,15 @@ int lpm_dropout_keep_mask(void* mask, int64_t n, float keep_prob, uint64_t seed,
  * entries themselves.  1 <= k <= 64, k <= V <= 65536; one workgroup per row. */
 int lpm_topk_rows(const float* p, int B, int V, int k, int32_t* index, float* value, lpm_stream_t stream);
 
+/* Per-row evaluation metrics (eval_util.EvaluationMetrics.accumulate's per-video terms): p fp32 [B, V], labels uint8 [B, V] (0 / 1) ->
+ * hit1 uint8 [B] (the label at the arg-max; ties: lowest index), num_labels int32 [B] (n, the positives of the row), hits_at_n int32 [B]
+ * (positives with p > 0 among the first n entries of torch.sort(p, descending=True, stable=True)), loss_row fp64 [B] (optional, null
+ * skips it: sum over the row of -[y logf(p + 1e-5) + (1 - y) logf(1 - p + 1e-5)], terms in fp32, summed in fp64 in a fixed order), and
+ * top_index int32 / top_value fp32 / top_label uint8 [B, k], bit-identical to lpm_topk_rows and the labels at its indexes.
+ * 1 <= k <= 64, k <= V <= 65536; one workgroup per row, cost independent of n and k. */
+int lpm_eval_rows(const float* p, const unsigned char* labels, int B, int V, int k, unsigned char* hit1, int32_t* num_labels,
+                  int32_t* hits_at_n, double* loss_row, int32_t* top_index, float* top_value, unsigned char* top_label, lpm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,7 @@ SIGNATURES = {
     "lpm_multi_tensor_clip_adam": (_i, [_f, _f, _f, _f, _f, _i, _l, _fl, _fl, _fl, _fl, _fl, _l, _f, _f]),
     "lpm_dropout_keep_mask": (_i, [_f, _l, _fl, C.c_uint64, _f]),
     "lpm_topk_rows": (_i, [_f, _i, _i, _i, _f, _f, _f]),
+    "lpm_eval_rows": (_i, [_f, _f, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f]),
     "lpm_multi_tensor_clip_adam_l2": (_i, [_f, _f, _f, _f, _f, _f, _i, _l, _fl, _fl, _fl, _fl, _fl, _l, _f, _f]),
     "lpm_weight_pack": (_i, [_f, _i, _f]),
     "lpm_sum_splits": (_i, [_f, _i, _i, _i, _f, _f, _f, _i, _f]),          # (jobs: a HOST array of WeightPackJob)

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import weakref
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -389,6 +389,63 @@ def topk_rows(p, k):
     if B:
         lib.check(lib._lpm_topk_rows(ptr(p), B, V, k, ptr(index), ptr(value), stream_ptr()), "lpm_topk_rows")
     return index, value
+
+
+class EvalRows(NamedTuple):
+    """ops.eval_rows' per-row outputs ([B] each, top_* [B, k])."""
+    hit1: torch.Tensor          # uint8: the label at the arg-max (ties: lowest index)
+    num_labels: torch.Tensor    # int32: n, the positives of the row
+    hits_at_n: torch.Tensor     # int32: positives with p > 0 among the row's first n entries of the stable descending sort
+    loss_row: Optional[torch.Tensor]   # fp64: the row's cross-entropy sum (None without with_loss)
+    top_index: torch.Tensor     # int32 [B, k]: as topk_rows
+    top_value: torch.Tensor     # fp32 [B, k]: as topk_rows
+    top_label: torch.Tensor     # uint8 [B, k]: the labels at top_index
+
+
+def _eval_rows_out(B, k, with_loss, dev) -> EvalRows:
+    return EvalRows(hit1=torch.empty(B, dtype=torch.uint8, device=dev), num_labels=torch.empty(B, dtype=torch.int32, device=dev),
+                    hits_at_n=torch.empty(B, dtype=torch.int32, device=dev),
+                    loss_row=torch.empty(B, dtype=torch.float64, device=dev) if with_loss else None,
+                    top_index=torch.empty((B, k), dtype=torch.int32, device=dev),
+                    top_value=torch.empty((B, k), dtype=torch.float32, device=dev), top_label=torch.empty((B, k), dtype=torch.uint8, device=dev))
+
+
+def eval_rows(p, labels, k, with_loss=True, out: Optional[EvalRows] = None) -> EvalRows:
+    """Per-row evaluation metrics of predictions p fp32 [B, V] against 0 / 1 labels [B, V] (bool or uint8) in one HIP pass
+    (lpm_eval_rows): the terms of eval_util's Hit@1 and PERR, the k best entries exactly as topk_rows selects them, and (with_loss) the
+    row sums of losses.py's CrossEntropyLoss taken from the predictions, -[y log(p + 1e-5) + (1 - y) log(1 - p + 1e-5)] with fp32 terms
+    and an fp64 sum.  That is the loss eval.py reports for a model without a "loss" output; it is not the fused head's
+    cancellation-free loss that Trainer.step reports.  ``out``: an EvalRows of contiguous tensors to write into (rows of a caller's
+    buffers; its loss_row decides with_loss).  Arguments are checked before any launch."""
+    if not isinstance(p, torch.Tensor) or p.dtype != torch.float32 or p.dim() != 2:
+        raise LpmError("eval_rows: expected float32 predictions [batch, classes]")
+    if not isinstance(labels, torch.Tensor) or labels.dtype not in (torch.uint8, torch.bool) or labels.shape != p.shape:
+        raise LpmError(f"eval_rows: expected bool or uint8 labels of the predictions' shape {tuple(p.shape)}")
+    B, V = p.shape
+    k = int(k)
+    if not (1 <= k <= TOPK_MAX_K and k <= V <= TOPK_MAX_V):
+        raise LpmError(f"eval_rows: need 1 <= k <= {TOPK_MAX_K} and k <= classes <= {TOPK_MAX_V} (k={k}, classes={V})")
+    if not (p.is_cuda and labels.is_cuda and p.device == labels.device):
+        raise LpmError("eval_rows: predictions and labels must be on the same GPU device (eval_util.EvaluationMetrics computes the "
+                       "metrics of CPU tensors)")
+    if out is None:
+        out = _eval_rows_out(B, k, with_loss, p.device)
+    else:
+        like = _eval_rows_out(0, k, out.loss_row is not None, "meta")
+        for name, t, ref in zip(EvalRows._fields, out, like):
+            if (t is None) != (ref is None) or (t is not None and (t.dtype != ref.dtype or t.device != p.device or not t.is_contiguous()
+                                                                   or tuple(t.shape) != (B,) + tuple(ref.shape[1:]))):
+                raise LpmError(f"eval_rows: out.{name} must be a contiguous {ref.dtype if ref is not None else None} tensor of "
+                               f"{(B,) + tuple(ref.shape[1:]) if ref is not None else ''} on {p.device}")
+    lib = _capi.load()
+    p = p.contiguous()
+    y = labels.contiguous()
+    if y.dtype == torch.bool:
+        y = y.view(torch.uint8)
+    if B:
+        lib.check(lib._lpm_eval_rows(ptr(p), ptr(y), B, V, k, ptr(out.hit1), ptr(out.num_labels), ptr(out.hits_at_n), ptr(out.loss_row),
+                                     ptr(out.top_index), ptr(out.top_value), ptr(out.top_label), stream_ptr()), "lpm_eval_rows")
+    return out
 
 
 # ----------------------------------------------------------------------------------------------
