@@ -39,7 +39,9 @@ enum {
     LPM_ERR_BADARG = -1,
     LPM_ERR_UNSUPPORTED_SHAPE = -2,
     LPM_ERR_WORKSPACE = -3,
-    LPM_ERR_LAUNCH = -4
+    LPM_ERR_LAUNCH = -4,
+    LPM_ERR_IO = -5,  /* TFRecord framing: a CRC mismatch */
+    LPM_ERR_DATA = -6 /* a malformed tf.train.SequenceExample */
 };
 
 /* flags of lpm_vlad_aggregate_{fwd,bwd} */
@@ -917,6 +919,40 @@ int lpm_topk_rows(const float* p, int B, int V, int k, int32_t* index, float* va
  * 1 <= k <= 64, k <= V <= 65536; one workgroup per row, cost independent of n and k. */
 int lpm_eval_rows(const float* p, const unsigned char* labels, int B, int V, int k, unsigned char* hit1, int32_t* num_labels,
                   int32_t* hits_at_n, double* loss_row, int32_t* top_index, float* top_value, unsigned char* top_label, lpm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The frame reader's device path (readers.YT8MFrameFeatureReader.device_batches): the two host entry points below look at the header
+ * bytes of a buffer of TFRecord records and never at a frame's payload; the records go to the GPU as they are and the two kernels put
+ * the frames and the labels in place.  The host entry points need no device and take no stream.
+ *
+ * Framing (u64 length, masked CRC-32C of the length, payload, masked CRC-32C of the payload): walks whole records from the start of
+ * buf [nbytes] and writes each payload's offset / length (at most max_records), their number and the bytes they take, framing included
+ * (*consumed).  It stops, without an error, at max_records or where the rest does not hold a whole record, so a caller reading a file in
+ * pieces carries buf + *consumed over.  verify_crc != 0 checks both CRCs: LPM_ERR_IO names record record_base + i, and *num_records counts
+ * the records before it.
+ *
+ * Locating: walks each record as a tf.train.SequenceExample with the semantics of readers.parse_sequence_example /
+ * prepare_serialized_examples and writes per clip: num_frames [n] (capped at max_frames); frame_offset [n, num_features, max_frames],
+ * the byte offset from buf of each frame's payload (-1 at and beyond num_frames); the labels in [0, num_classes) as a CSR list,
+ * label_start [n + 1] into label_index [label_capacity], *labels_needed their number (LPM_ERR_WORKSPACE when label_capacity is too small);
+ * the video id's offset / length (0 / 0 without one).  LPM_ERR_DATA: a malformed example, a frame whose payload is not feature_sizes[f]
+ * bytes, or features whose frame counts differ; *failed_record is its index and the error text names record_base + index. */
+int lpm_tfrecord_frame(const void* buf, int64_t nbytes, int verify_crc, int max_records, int64_t record_base, int64_t* rec_offset,
+                       int64_t* rec_length, int* num_records, int64_t* consumed);
+int lpm_yt8m_locate(const void* buf, int64_t nbytes, const int64_t* rec_offset, const int64_t* rec_length, int num_records,
+                    int64_t record_base, const char* const* feature_names, const int* feature_sizes, int num_features, int max_frames,
+                    int num_classes, int32_t* num_frames, int64_t* frame_offset, int32_t* label_start, int32_t* label_index,
+                    int64_t label_capacity, int64_t* labels_needed, int64_t* id_offset, int32_t* id_length, int* failed_record);
+/* buf [nbytes] in DEVICE memory (an allocation of `capacity` >= nbytes rounded up to 16 bytes, 16-byte aligned) + frame_offset and
+ * num_frames as above (device) -> out uint8 [B, max_frames, sum(feature_sizes)] (16-byte aligned): frame t of feature f of clip b in row t,
+ * columns of f; rows at and beyond num_frames[b] zero.  One launch; aligned 16-byte loads, bytes shifted into place in registers, 16-byte
+ * stores.  feature_sizes (a HOST array): positive multiples of 4, else LPM_ERR_UNSUPPORTED_SHAPE.  An offset whose frame does not lie
+ * inside [0, nbytes) gives zeros, never a read outside the allocation. */
+int lpm_gather_frames(const void* buf, int64_t nbytes, int64_t capacity, const int64_t* frame_offset, const int32_t* num_frames, int B,
+                      int max_frames, const int* feature_sizes, int num_features, void* out, lpm_stream_t stream);
+/* CSR label lists (device; duplicates and empty lists are legal) -> out uint8 0 / 1 [B, num_classes], zeros included. */
+int lpm_labels_dense(const int32_t* label_start, const int32_t* label_index, int num_labels, int B, int num_classes, void* out,
+                     lpm_stream_t stream);
 
 #ifdef __cplusplus
 }

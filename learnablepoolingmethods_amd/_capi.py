@@ -187,6 +187,10 @@ SIGNATURES = {
     "lpm_dropout_keep_mask": (_i, [_f, _l, _fl, C.c_uint64, _f]),
     "lpm_topk_rows": (_i, [_f, _i, _i, _i, _f, _f, _f]),
     "lpm_eval_rows": (_i, [_f, _f, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f]),
+    "lpm_tfrecord_frame": (_i, [_f, _l, _i, _i, _l, _f, _f, _f, _f]),               # (host entry points: _f = any caller-owned buffer)
+    "lpm_yt8m_locate": (_i, [_f, _l, _f, _f, _i, _l, _f, _f, _i, _i, _i, _f, _f, _f, _f, _l, _f, _f, _f, _f]),
+    "lpm_gather_frames": (_i, [_f, _l, _l, _f, _f, _i, _i, _f, _i, _f, _f]),
+    "lpm_labels_dense": (_i, [_f, _f, _i, _i, _i, _f, _f]),
     "lpm_multi_tensor_clip_adam_l2": (_i, [_f, _f, _f, _f, _f, _f, _i, _l, _fl, _fl, _fl, _fl, _fl, _l, _f, _f]),
     "lpm_weight_pack": (_i, [_f, _i, _f]),
     "lpm_sum_splits": (_i, [_f, _i, _i, _i, _f, _f, _f, _i, _f]),          # (jobs: a HOST array of WeightPackJob)
@@ -210,6 +214,9 @@ SIGNATURES = {
     "lpm_bn_rows_act_image_fwd_fmt": (_i, [_f, _f, _i, _i, _i, _f, _f, _fl, _fl, _i, _f, _f, _f, _f, _f, _f, _s, _f, _f]),
     "lpm_bn_act_bwd_image_fmt": (_i, [_f, _f, _f, _i, _f, _f, _f, _fl, _i, _i, _f, _f, _f, _f, _f, _s, _f, _f]),
 }
+LPM_ERR_WORKSPACE = -3
+LPM_ERR_IO = -5                  # lpm_tfrecord_frame: a CRC mismatch
+LPM_ERR_DATA = -6                # lpm_yt8m_locate: a malformed example
 LPM_OPERAND_BF16X3 = 0
 LPM_OPERAND_FP16X2 = 1
 LPM_OPERAND_FP16X3 = 2

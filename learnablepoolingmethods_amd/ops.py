@@ -448,6 +448,51 @@ def eval_rows(p, labels, k, with_loss=True, out: Optional[EvalRows] = None) -> E
     return out
 
 
+GATHER_MAX_FEATURES = 8      # lpm_gather_frames' limit
+
+
+def gather_frames(raw, nbytes, frame_offset, num_frames, feature_sizes, max_frames):
+    """The reader's frame gather (lpm_gather_frames): ``raw``, a uint8 CUDA buffer whose first ``nbytes`` bytes are TFRecord records as
+    they lie in the file (its length must cover nbytes rounded up to 16), ``frame_offset`` int64 [B, len(feature_sizes), max_frames]
+    (byte offsets of the frame payloads, readers.locate_records) and ``num_frames`` int32 [B] -> uint8 [B, max_frames,
+    sum(feature_sizes)], zero at and beyond num_frames.  Feature sizes must be multiples of 4 (LpmError otherwise; no fallback)."""
+    sizes = [int(s) for s in feature_sizes]
+    for name, t, dt in (("raw", raw, torch.uint8), ("frame_offset", frame_offset, torch.int64), ("num_frames", num_frames, torch.int32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise LpmError(f"gather_frames: {name} must be a contiguous {dt} tensor on the GPU (there is no CPU fallback)")
+    B, T = int(num_frames.numel()), int(max_frames)
+    if raw.dim() != 1 or tuple(frame_offset.shape) != (B, len(sizes), T) or num_frames.dim() != 1:
+        raise LpmError(f"gather_frames: expected raw [bytes], frame_offset [{B}, {len(sizes)}, {T}], num_frames [{B}]")
+    if not (frame_offset.device == raw.device == num_frames.device):
+        raise LpmError("gather_frames: all tensors must be on the same device")
+    nbytes = int(nbytes)
+    lib = _capi.load()
+    out = torch.empty((B, T, sum(sizes)), dtype=torch.uint8, device=raw.device)
+    if B:
+        arr = (C.c_int * len(sizes))(*sizes)
+        lib.check(lib._lpm_gather_frames(ptr(raw), nbytes, raw.numel(), ptr(frame_offset), ptr(num_frames), B, T,
+                                         C.cast(arr, C.c_void_p), len(sizes), ptr(out), stream_ptr()), "lpm_gather_frames")
+    return out
+
+
+def labels_dense(label_start, label_index, num_classes):
+    """CSR label lists (``label_start`` int32 [B + 1] into ``label_index`` int32 [n]; duplicates and empty lists are legal) -> the dense
+    bool [B, num_classes] matrix (lpm_labels_dense)."""
+    for name, t in (("label_start", label_start), ("label_index", label_index)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_cuda or t.dim() != 1 or not t.is_contiguous():
+            raise LpmError(f"labels_dense: {name} must be a contiguous int32 vector on the GPU (there is no CPU fallback)")
+    if label_start.device != label_index.device or label_start.numel() < 1 or int(num_classes) < 1:
+        raise LpmError("labels_dense: need label_start [B + 1] and label_index on one device, num_classes >= 1")
+    B, V = label_start.numel() - 1, int(num_classes)
+    lib = _capi.load()
+    out = torch.empty((B, V), dtype=torch.uint8, device=label_start.device)
+    if B:
+        n = int(label_index.numel())
+        lib.check(lib._lpm_labels_dense(ptr(label_start), ptr(label_index) if n else None, n, B, V, ptr(out), stream_ptr()),
+                  "lpm_labels_dense")
+    return out.view(torch.bool)
+
+
 # ----------------------------------------------------------------------------------------------
 # second HIP stream for the audio branch
 # ----------------------------------------------------------------------------------------------

@@ -8,17 +8,28 @@ Unlike the reference, the reader hands the frames on QUANTISED (uint8, 1 byte pe
 HIP kernel on the device (``ops.dequantize_l2_normalize``), so the host->device copy and the first HBM read carry 4x fewer
 bytes.  ``dequantize=True`` reproduces the reference's float32 ``[max_frames, sum(feature_sizes)]`` matrix on the host.
 
+Two routes lead through the reader.  ``batches()`` is the pure-Python one, and the yardstick.  ``device_batches()`` yields the same
+batches as tensors on the GPU: a thread reads the records into pinned memory, the native indexer (``frame_records`` /
+``locate_records``: lpm_tfrecord_frame, lpm_yt8m_locate) looks at their header bytes only, the record bytes go to the device as they
+are and ``ops.gather_frames`` / ``ops.labels_dense`` put frames and labels in place.
+
 There are no TFRecord fixtures in the reference; ``write_tfrecord`` / ``make_sequence_example`` produce files in the same
 format for the round-trip tests and for synthetic data."""
 from __future__ import annotations
 
+import ctypes as C
+import os
+import queue
 import struct
-from typing import Dict, Iterable, Iterator, List, Sequence, Tuple
+import threading
+import time
+from concurrent.futures import ThreadPoolExecutor
+from typing import Dict, Iterable, Iterator, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from . import utils
+from . import _capi, utils
 
 # ---- CRC-32C (Castagnoli), table driven, and the TFRecord mask ---------------------------------------------------------
 _CRC_TABLE = None
@@ -202,6 +213,117 @@ def make_sequence_example(video_id: str, labels: Sequence[int], features: Dict[s
     return _enc_ld(1, ctx) + _enc_ld(2, fl)
 
 
+# ---- the native indexer (liblpm_hip.so, host code: no GPU needed; ctypes releases the GIL during the calls) --------------------------
+class RecordIndex(NamedTuple):
+    """locate_records' per-clip tables (numpy; offsets are bytes from the start of the buffer the records lie in)."""
+    num_frames: np.ndarray      # int32 [n], capped at max_frames
+    frame_offset: np.ndarray    # int64 [n, features, max_frames], -1 at and beyond num_frames
+    label_start: np.ndarray     # int32 [n + 1]: clip i's labels are label_index[label_start[i]:label_start[i + 1]]
+    label_index: np.ndarray     # int32 [>= label_start[n]]: the labels in [0, num_classes), file order, duplicates kept
+    id_offset: np.ndarray       # int64 [n]
+    id_length: np.ndarray       # int32 [n] (0 without an id)
+
+
+def _as_bytes_array(buf) -> np.ndarray:
+    a = buf if isinstance(buf, np.ndarray) else np.frombuffer(buf, dtype=np.uint8)
+    if a.dtype != np.uint8 or a.ndim != 1 or not a.flags.c_contiguous:
+        raise ValueError("expected a contiguous one-dimensional uint8 buffer")
+    return a
+
+
+def _vp(a: Optional[np.ndarray]):
+    return None if a is None or a.size == 0 else C.c_void_p(a.ctypes.data)
+
+
+def _raise_native(lib, status: int, what: str, prefix: str = ""):
+    """LPM_ERR_IO -> IOError, LPM_ERR_DATA -> ValueError (the types read_tfrecord / prepare_serialized_examples raise)."""
+    text = lib.last_error()
+    if prefix:                                              # the caller names file and record itself: "<entry point>: record i: why" -> why
+        text = prefix + text.split(": ", 2)[-1]
+    if status == _capi.LPM_ERR_IO:
+        raise IOError(text)
+    if status == _capi.LPM_ERR_DATA:
+        raise ValueError(text)
+    raise _capi.LpmError(f"{what} failed with status {status}: {text}")
+
+
+def frame_records(buf, verify_crc: bool = False, max_records: Optional[int] = None, record_base: int = 0):
+    """TFRecord framing of a byte buffer (lpm_tfrecord_frame) -> (payload offsets int64 [n], payload lengths int64 [n], bytes consumed).
+    Only whole records count: a caller reading a file in pieces carries ``buf[consumed:]`` over.  ``verify_crc`` checks both masked
+    CRC-32Cs of every record (IOError, naming record ``record_base + i``)."""
+    a = _as_bytes_array(buf)
+    lib = _capi.load()
+    offs, lens, consumed = [], [], 0
+    nrec, used = C.c_int(0), C.c_int64(0)
+    while max_records is None or len(offs) < max_records:
+        chunk = 1024 if max_records is None else min(1024, max_records - len(offs))
+        o, ln = np.empty(chunk, np.int64), np.empty(chunk, np.int64)
+        rest = a[consumed:]
+        st = lib._lpm_tfrecord_frame(_vp(rest), rest.size, int(bool(verify_crc)), chunk, record_base + len(offs), _vp(o), _vp(ln),
+                                     C.byref(nrec), C.byref(used))
+        if st != 0:
+            _raise_native(lib, st, "lpm_tfrecord_frame")
+        offs.extend((o[:nrec.value] + consumed).tolist())
+        lens.extend(ln[:nrec.value].tolist())
+        consumed += used.value
+        if nrec.value < chunk:
+            break
+    return np.asarray(offs, np.int64), np.asarray(lens, np.int64), consumed
+
+
+def frame_file(path: str, verify_crc: bool = False):
+    """A whole TFRecord file -> (its bytes uint8 [size], payload offsets, payload lengths); IOError, naming the record, for a CRC
+    mismatch and for a file that ends inside a record (read_tfrecord's errors)."""
+    buf = np.fromfile(path, dtype=np.uint8)
+    lib = _capi.load()
+    try:
+        offs, lens, consumed = frame_records(buf, verify_crc=verify_crc)
+    except IOError as e:
+        raise IOError(f"{path}: {lib.last_error()}") from e
+    if consumed != buf.size:
+        raise IOError(f"{path}: record {len(offs)}: truncated record")
+    return buf, offs, lens
+
+
+def _locate_into(lib, a, rec_offset, rec_length, names_arr, sizes_arr, num_features, max_frames, num_classes, record_base, idx: RecordIndex):
+    """One lpm_yt8m_locate call into caller-owned arrays -> (status, labels needed, failed record)."""
+    needed, failed = C.c_int64(0), C.c_int(-1)
+    st = lib._lpm_yt8m_locate(_vp(a), a.size, _vp(rec_offset), _vp(rec_length), len(rec_offset), record_base, C.cast(names_arr, C.c_void_p),
+                              C.cast(sizes_arr, C.c_void_p), num_features, max_frames, num_classes, _vp(idx.num_frames),
+                              _vp(idx.frame_offset), _vp(idx.label_start), _vp(idx.label_index), idx.label_index.size, C.byref(needed),
+                              _vp(idx.id_offset), _vp(idx.id_length), C.byref(failed))
+    return st, needed.value, failed.value
+
+
+def _feature_arrays(feature_names, feature_sizes):
+    names = (C.c_char_p * len(feature_names))(*[str(n).encode("utf-8") for n in feature_names])
+    sizes = (C.c_int * len(feature_sizes))(*[int(s) for s in feature_sizes])
+    return names, sizes
+
+
+def locate_records(buf, rec_offset, rec_length, feature_names=("rgb", "audio"), feature_sizes=(1024, 128), max_frames=300,
+                   num_classes=3862, record_base: int = 0) -> RecordIndex:
+    """Where the frames, labels and ids of the tf.train.SequenceExample records of ``buf`` lie (lpm_yt8m_locate): the header bytes are
+    walked with parse_sequence_example's semantics, the frame payloads are never touched.  ValueError for what
+    prepare_serialized_examples refuses (and for a frame whose payload is not its feature's size), naming the record."""
+    a = _as_bytes_array(buf)
+    ro, rl = np.ascontiguousarray(rec_offset, np.int64), np.ascontiguousarray(rec_length, np.int64)
+    n, nf = len(ro), len(feature_names)
+    names, sizes = _feature_arrays(feature_names, feature_sizes)
+    lib = _capi.load()
+    cap = 8 * n + 16
+    while True:
+        idx = RecordIndex(np.zeros(n, np.int32), np.full((n, nf, max_frames), -1, np.int64), np.zeros(n + 1, np.int32), np.zeros(cap, np.int32),
+                          np.zeros(n, np.int64), np.zeros(n, np.int32))
+        st, needed, _ = _locate_into(lib, a, ro, rl, names, sizes, nf, int(max_frames), int(num_classes), record_base, idx)
+        if st == _capi.LPM_ERR_WORKSPACE and needed > cap:
+            cap = needed
+            continue
+        if st != 0:
+            _raise_native(lib, st, "lpm_yt8m_locate")
+        return idx
+
+
 # ---- the reader ---------------------------------------------------------------------------------------------------------
 class BaseReader(object):
     """readers.py:59-66."""
@@ -267,3 +389,323 @@ class YT8MFrameFeatureReader(BaseReader):
                     yield flush()
         if ids and not drop_remainder:
             yield flush()
+
+    def device_batches(self, files: Sequence[str], batch_size: int, device="cuda", drop_remainder: bool = False, verify_crc: bool = False,
+                       prefetch: int = 2, reader_threads: int = 1, stats: Optional[dict] = None):
+        """What ``batches()`` yields, as tensors on the GPU: (ids, frames uint8 cuda [B, max_frames, F], labels bool cuda [B, V],
+        num_frames int32 cuda [B]), bit for bit.  A background thread reads the records of one batch back to back into a pinned host
+        slot, runs the native indexer over their header bytes, copies slot and tables to the device on a side stream and launches
+        ``ops.gather_frames`` / ``ops.labels_dense`` there; the consumer's current stream waits for that batch's event.  The tensors belong
+        to the consumer.  ``prefetch``: finished batches that may wait for the consumer (the ring has prefetch + reader_threads pinned slots).
+        ``reader_threads``: threads that read whole batches into their slots (1: the thread that walks the record headers itself).  ``stats``: a dict that receives the host
+        seconds spent reading and indexing, bytes, batches, and (``stats["time_gather"] = True``) device events before the copies, between copies and kernels and after them.
+        Errors (IOError: framing, CRC, truncation; ValueError: a malformed example) are raised at the batch they belong to; closing the
+        generator stops and joins the thread.  Needs a GPU: there is no CPU fallback (use ``batches()``)."""
+        dev = torch.device(device)
+        if dev.type != "cuda" or not torch.cuda.is_available():
+            raise _capi.LpmError("device_batches needs an MI355X (cuda/hip device); batches() is the host route")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if any(int(s) <= 0 or int(s) % 4 for s in self.feature_sizes) or len(self.feature_sizes) > 8:
+            raise _capi.LpmError(f"device_batches: at most 8 features whose sizes are positive multiples of 4 (got {self.feature_sizes})")
+        if int(batch_size) < 1 or int(prefetch) < 1 or int(reader_threads) < 1:
+            raise ValueError("device_batches: batch_size, prefetch and reader_threads must be at least 1")
+        _capi.load()
+        pipe = _DevicePipeline(self, list(files), int(batch_size), dev, bool(drop_remainder), bool(verify_crc), int(prefetch),
+                               int(reader_threads), stats)
+        try:
+            while True:
+                item = pipe.get()
+                if item is None:
+                    return
+                if isinstance(item, BaseException):
+                    raise item
+                ids, frames, labels, nf, done = item
+                cur = torch.cuda.current_stream(dev)
+                cur.wait_event(done)
+                for t in (frames, labels, nf):                  # allocated on the side stream, used (and freed) on the consumer's
+                    t.record_stream(cur)
+                yield ids, frames, labels, nf
+        finally:
+            pipe.close()
+
+
+class _Slot:
+    """One pinned host slot of the ring: the records of one batch back to back (framing included), and the tables that go to the device
+    with them.  ``copied`` is recorded after the copies out of the slot; the slot is not refilled before it has completed."""
+
+    def __init__(self, nbytes: int):
+        self.copied: Optional[torch.cuda.Event] = None
+        self.free = threading.Event()                           # set while the read thread may take the slot
+        self.free.set()
+        self._alloc(nbytes)
+        self.meta = torch.empty(1 << 16, dtype=torch.uint8, pin_memory=True)
+
+    def _alloc(self, nbytes: int):
+        self.t = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+        self.np = self.t.numpy()
+        self.mv = memoryview(self.np)
+
+    def reserve(self, nbytes: int):
+        """Room for nbytes (the slot is empty: nothing is kept)."""
+        if nbytes > self.t.numel():
+            self._alloc(max(nbytes, 2 * self.t.numel()))
+
+    def reserve_meta(self, nbytes: int):
+        if nbytes > self.meta.numel():
+            self.meta = torch.empty(max(nbytes, 2 * self.meta.numel()), dtype=torch.uint8, pin_memory=True)
+
+
+def _pread_exact(fd: int, mv, offset: int) -> int:
+    """Fills mv from the file at ``offset``; returns the bytes read (short only at the end of the file)."""
+    n = 0
+    while n < len(mv):
+        r = os.preadv(fd, [mv[n:]], offset + n)
+        if r == 0:
+            break
+        n += r
+    return n
+
+
+class _DevicePipeline:
+    """The two threads behind YT8MFrameFeatureReader.device_batches: one reads the records of batch k + 1 into a
+    pinned slot while the other indexes batch k, enqueues its copies and kernels and hands it to the consumer."""
+
+    def __init__(self, reader, files, batch_size, dev, drop_remainder, verify_crc, prefetch, reader_threads, stats):
+        self.reader, self.files, self.B, self.dev = reader, files, batch_size, dev
+        self.drop_remainder, self.verify_crc, self.nthreads = drop_remainder, verify_crc, reader_threads
+        self.stats = stats if stats is not None else {}
+        self.lock = threading.Lock()
+        for k in ("walk_s", "read_s", "index_s", "issue_s", "bytes", "batches", "clips"):
+            self.stats.setdefault(k, 0)
+        self.time_gather = bool(self.stats.get("time_gather"))
+        if self.time_gather:
+            self.stats.setdefault("gather_events", [])
+        self.nslots = prefetch + reader_threads
+        self.slots: List[_Slot] = []
+        self.mid = queue.Queue()                               # read thread -> index thread: (slot, bytes, records) | None | exception
+        self.out = queue.Queue(maxsize=prefetch)               # index thread -> consumer: batches | None | exception
+        self.stop = threading.Event()
+        self.threads = [threading.Thread(target=self._run_read, name="lpm-device-batches-read", daemon=True),
+                        threading.Thread(target=self._run_index, name="lpm-device-batches-index", daemon=True)]
+        for t in self.threads:
+            t.start()
+
+    # ---- consumer side ------------------------------------------------------------------------------------------------------------
+    def get(self):
+        return self.out.get()
+
+    def close(self):
+        self.stop.set()
+        while any(t.is_alive() for t in self.threads):
+            try:
+                self.out.get_nowait()                          # a producer blocked on a full queue sees the stop flag within its timeout
+            except queue.Empty:
+                pass
+            for t in self.threads:
+                t.join(timeout=0.02)
+        while True:                                            # drop what is left (device tensors of batches nobody asked for)
+            try:
+                self.out.get_nowait()
+            except queue.Empty:
+                break
+        for s in self.slots:                                   # nothing may still read a slot when its pinned memory goes
+            if s.copied is not None:
+                s.copied.synchronize()
+
+    # ---- producer side: one thread reads records into the slots, one indexes them and drives the device ---------------------------------
+    def _put(self, item) -> bool:
+        while not self.stop.is_set():
+            try:
+                self.out.put(item, timeout=0.05)
+                return True
+            except queue.Full:
+                continue
+        return False
+
+    def _run_read(self):
+        pool = ThreadPoolExecutor(max_workers=self.nthreads, thread_name_prefix="lpm-record-read") if self.nthreads > 1 else None
+        try:
+            torch.cuda.set_device(self.dev)                     # (pinned allocations)
+            self._fill(pool)
+            self.mid.put(None)
+        except BaseException as e:                              # handed on in order: raised in the consumer after the batches before it
+            self.mid.put(e)
+        finally:
+            if pool is not None:
+                pool.shutdown(wait=True)
+
+    def _run_index(self):
+        try:
+            torch.cuda.set_device(self.dev)
+            self.side = torch.cuda.Stream(device=self.dev)
+            while not self.stop.is_set():
+                try:
+                    item = self.mid.get(timeout=0.05)
+                except queue.Empty:
+                    continue
+                if item is None or isinstance(item, BaseException):
+                    self._put(item)
+                    return
+                job, slot, nbytes, src = item
+                try:
+                    if job is not None:
+                        job.result()                            # the read of this batch (a reader thread's IOError surfaces here, in order)
+                    ok = self._emit(slot, nbytes, src)
+                finally:
+                    slot.free.set()
+                if not ok:
+                    return
+        except BaseException as e:
+            self._put(e)
+            self.stop.set()                                     # the read thread has nobody to read for any more
+
+    def _acquire(self, k: int, nbytes: int) -> Optional[_Slot]:
+        """Slot k % nslots, once the index thread is done with it and the copy out of it has completed; None when stopping."""
+        if len(self.slots) < self.nslots:
+            self.slots.append(_Slot(nbytes if not self.slots else self.slots[0].t.numel()))
+        slot = self.slots[k % self.nslots]
+        while not slot.free.wait(timeout=0.05):
+            if self.stop.is_set():
+                return None
+        if slot.copied is not None:
+            slot.copied.synchronize()
+            slot.copied = None
+        slot.free.clear()
+        return slot
+
+    def _fill(self, pool):
+        """Walks the record headers of the files (12 bytes each: the payload is not read here), cuts the stream into batches and has every
+        batch read into its slot: one positioned read per run of records that lie back to back in one file, which is the layout of
+        the slot as well."""
+        k = 0                                                   # batch counter: slot k % nslots
+        segs, src, total = [], [], 0                            # runs [path, file offset, bytes]; (path, index in its file) per record
+        head = bytearray(12)
+        hv = memoryview(head)
+        for path in self.files:
+            with open(path, "rb", buffering=0) as f:
+                fd = f.fileno()
+                size, fpos, idx = os.fstat(fd).st_size, 0, 0
+                while not self.stop.is_set():
+                    t0 = time.perf_counter()
+                    got = _pread_exact(fd, hv, fpos)
+                    if got == 0:
+                        break
+                    if got < 12:
+                        raise IOError(f"{path}: record {idx}: truncated record header")
+                    (length,) = struct.unpack_from("<Q", head)
+                    if length + 4 > size - fpos - 12:           # (also a corrupt length: nothing that large is read or allocated)
+                        raise IOError(f"{path}: record {idx}: truncated record")
+                    n = 16 + length
+                    if segs and segs[-1][0] == path and segs[-1][1] + segs[-1][2] == fpos:
+                        segs[-1][2] += n
+                    else:
+                        segs.append([path, fpos, n])
+                    src.append((path, idx))
+                    total += n
+                    fpos += n
+                    idx += 1
+                    self.stats["walk_s"] += time.perf_counter() - t0
+                    if len(src) == self.B:
+                        if not self._submit(pool, k, segs, src, total):
+                            return
+                        k += 1
+                        segs, src, total = [], [], 0
+            if self.stop.is_set():
+                return
+        if src and not self.drop_remainder:
+            self._submit(pool, k, segs, src, total)
+
+    def _submit(self, pool, k, segs, src, total) -> bool:
+        slot = self._acquire(k, total + total // 4)
+        if slot is None:
+            return False
+        slot.reserve(total)
+        if pool is None:
+            self._read_job(slot, segs)
+            self.mid.put((None, slot, total, src))
+        else:
+            self.mid.put((pool.submit(self._read_job, slot, segs), slot, total, src))
+        return True
+
+    def _read_job(self, slot: _Slot, segs):
+        t0 = time.perf_counter()
+        pos = 0
+        for path, off, n in segs:
+            fd = os.open(path, os.O_RDONLY)
+            try:
+                got = _pread_exact(fd, slot.mv[pos:pos + n], off)
+            finally:
+                os.close(fd)
+            if got < n:
+                raise IOError(f"{path}: truncated record (the file ends before offset {off + n})")
+            pos += n
+        with self.lock:
+            self.stats["read_s"] += time.perf_counter() - t0
+
+    def _emit(self, slot: _Slot, nbytes: int, src) -> bool:
+        """Index the slot's records, send slot and tables to the device, gather; False when the consumer has gone."""
+        from . import ops
+        r, lib = self.reader, _capi.load()
+        n, nfeat, T = len(src), len(r.feature_names), r.max_frames
+        t0 = time.perf_counter()
+        buf = slot.np[:nbytes]
+        ro, rl = np.empty(n, np.int64), np.empty(n, np.int64)
+        nrec, used = C.c_int(0), C.c_int64(0)
+        st = lib._lpm_tfrecord_frame(_vp(buf), nbytes, int(self.verify_crc), n, 0, _vp(ro), _vp(rl), C.byref(nrec), C.byref(used))
+        if st != 0:
+            path, idx = src[min(nrec.value, n - 1)]
+            _raise_native(lib, st, "lpm_tfrecord_frame", f"{path}: record {idx}: ")
+        if nrec.value != n or used.value != nbytes:
+            raise IOError(f"{src[0][0]}: the slot's framing does not match the records read ({nrec.value} of {n})")
+        names, sizes = _feature_arrays(r.feature_names, r.feature_sizes)
+        id_off, id_len = np.empty(n, np.int64), np.empty(n, np.int32)
+        n_off = 8 * n * nfeat * T                               # the tables, in one pinned block: offsets | label_start | num_frames | labels
+        n_fixed = n_off + 4 * (n + 1) + 4 * n
+        slot.reserve_meta(n_fixed + 4 * (8 * n + 64))
+        while True:
+            m = slot.meta.numpy()
+            idx = RecordIndex(m[n_off + 4 * (n + 1):n_fixed].view(np.int32), m[:n_off].view(np.int64),
+                              m[n_off:n_off + 4 * (n + 1)].view(np.int32), m[n_fixed:(m.size // 4) * 4].view(np.int32), id_off, id_len)
+            st, needed, failed = _locate_into(lib, buf, ro, rl, names, sizes, nfeat, T, r.num_classes, 0, idx)
+            if st == _capi.LPM_ERR_WORKSPACE and n_fixed + 4 * needed > slot.meta.numel():
+                slot.reserve_meta(n_fixed + 4 * needed)
+                continue
+            if st != 0:
+                path, i = src[max(failed, 0)]
+                _raise_native(lib, st, "lpm_yt8m_locate", f"{path}: record {i}: ")
+            break
+        nlab = int(idx.label_start[n])
+        ids = [bytes(buf[o:o + ln]).decode("utf-8") for o, ln in zip(id_off.tolist(), id_len.tolist())]
+        t1 = time.perf_counter()
+        with torch.cuda.stream(self.side):
+            ev = None
+            if self.time_gather:                                # (before the copies, between copies and kernels, after the kernels)
+                ev = tuple(torch.cuda.Event(enable_timing=True) for _ in range(3))
+                ev[0].record(self.side)
+            raw = torch.empty(((nbytes + 15) // 16) * 16 + 16, dtype=torch.uint8, device=self.dev)
+            raw[:nbytes].copy_(slot.t[:nbytes], non_blocking=True)
+            n_meta = n_fixed + 4 * nlab
+            meta = torch.empty(n_meta, dtype=torch.uint8, device=self.dev)
+            meta.copy_(slot.meta[:n_meta], non_blocking=True)
+            slot.copied = torch.cuda.Event()
+            slot.copied.record(self.side)
+            nf = meta[n_off + 4 * (n + 1):n_fixed].view(torch.int32).clone()      # (its own storage: it goes to the consumer)
+            if ev is not None:
+                ev[1].record(self.side)
+            frames = ops.gather_frames(raw, nbytes, meta[:n_off].view(torch.int64).view(n, nfeat, T), nf, r.feature_sizes, T)
+            labels = ops.labels_dense(meta[n_off:n_off + 4 * (n + 1)].view(torch.int32), meta[n_fixed:n_meta].view(torch.int32),
+                                      r.num_classes)
+            if ev is not None:
+                ev[2].record(self.side)
+                self.stats["gather_events"].append(ev)
+            done = torch.cuda.Event()
+            done.record(self.side)
+        t2 = time.perf_counter()
+        st_ = self.stats
+        st_["index_s"] += t1 - t0
+        st_["issue_s"] += t2 - t1
+        st_["bytes"] += nbytes
+        st_["batches"] += 1
+        st_["clips"] += n
+        return self._put((ids, frames, labels, nf, done))
