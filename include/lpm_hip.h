@@ -153,6 +153,20 @@ int lpm_frame_apply_tiles_bf16_q8(const unsigned char* q, const float* inv_norm,
                                   const int32_t* num_frames, int B, int max_frames, int F, int S, const float* scale, const float* shift,
                                   float* y, void* xt_video, void* xr_video, int Dv, void* xt_audio, void* xr_audio, int Da,
                                   lpm_stream_t stream);
+/* Training mode from the reader's quantised frames: lpm_frame_stats, lpm_frame_bn_bwd and lpm_frame_bn_bwd_split reading q and inv_norm
+ * (lpm_frame_inv_norm_q8) in place of `raw`.  Every frame value is formed as the *_q8 apply forms form it, and every column sums the
+ * rows of its 32-row block in the fp32 forms' order, so `partial`, dgamma and dbeta are bit for bit those of the fp32 forms on
+ * lpm_dequantize_l2_normalize's output.  The gradients and the workspace must be 16-byte aligned, row strides and Dv multiples of 4. */
+int lpm_frame_stats_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
+                       const int32_t* num_frames, int B, int max_frames, int F, int S, float* partial, lpm_stream_t stream);
+int lpm_frame_bn_bwd_q8(const float* dy, int64_t lddy, const unsigned char* q, const float* inv_norm, float max_quantized_value,
+                        float min_quantized_value, const int32_t* num_frames, int B, int max_frames, int F, int S, const float* mean,
+                        const float* var, float eps, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
+                        lpm_stream_t stream);
+int lpm_frame_bn_bwd_split_q8(const float* dy_video, int64_t ldv, const float* dy_audio, int64_t lda, int Dv, const unsigned char* q,
+                              const float* inv_norm, float max_quantized_value, float min_quantized_value, const int32_t* num_frames,
+                              int B, int max_frames, int F, int S, const float* mean, const float* var, float eps, float* dgamma,
+                              float* dbeta, void* workspace, size_t workspace_bytes, lpm_stream_t stream);
 /* backward of input_bn's affine parameters only (the frames are data, never a trainable tensor, so no
  * gradient w.r.t. raw is produced): dgamma = sum dy*xhat, dbeta = sum dy over the gathered rows.
  * dy [B*S, F] with row stride lddy; mean/var = the batch statistics lpm_bn_fold returned.

@@ -50,6 +50,9 @@ SIGNATURES = {
     "lpm_frame_stats_nblk": (_i, [_i, _i]),
     "lpm_frame_bn_bwd": (_i, [_f, _l, _f, _f, _i, _i, _i, _i, _f, _f, _fl, _f, _f, _f, _s, _f]),
     "lpm_frame_bn_bwd_split": (_i, [_f, _l, _f, _l, _i, _f, _f, _i, _i, _i, _i, _f, _f, _fl, _f, _f, _f, _s, _f]),
+    "lpm_frame_stats_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f]),
+    "lpm_frame_bn_bwd_q8": (_i, [_f, _l, _f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _fl, _f, _f, _f, _s, _f]),
+    "lpm_frame_bn_bwd_split_q8": (_i, [_f, _l, _f, _l, _i, _f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _fl, _f, _f, _f, _s, _f]),
     "lpm_frame_inv_norm_q8": (_i, [_f, _f, _i, _i, _i, _i, _fl, _fl, _f, _f]),
     "lpm_frame_apply_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _f, _f]),
     "lpm_frame_apply_tiles_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _f, _f, _i, _f, _i, _f]),

@@ -9,6 +9,10 @@
 // Eval mode from the reader's quantised frames (the *_q8 entry points): the apply kernels read the uint8 frames of the sampled
 // rows and one inverse L2 norm per sampled row (lpm_frame_inv_norm_q8), and produce bit for bit what they produce from
 // lpm_dequantize_l2_normalize's fp32 frames -- without writing (and re-reading) the fp32 frames of all max_frames.
+// Training mode from the quantised frames (lpm_frame_stats_q8, lpm_frame_bn_bwd*_q8): the statistics and the dgamma / dbeta partial
+// kernels are templated on the same source.  A thread of the uint8 form owns FOUR adjacent columns (one uchar4 load per row; a byte
+// load per lane would use a quarter of each 64-byte request) with one accumulator pair per column, so every column still sums the rows
+// of its 32-row block in order, s += v, q = fma(v, v, q) -- the partials are bit for bit those of the fp32 form on the fp32 frames.
 #include "lpm_common.h"
 
 namespace lpm {
@@ -53,6 +57,9 @@ template <>
 struct FrameSrc<float> {
     const float* __restrict__ raw;
     __device__ __forceinline__ float4 load4(int64_t off, int64_t) const { return *reinterpret_cast<const float4*>(raw + off); }
+    // the column-partial kernels: W adjacent columns per thread
+    static constexpr int W = 1;
+    __device__ __forceinline__ void loadw(int64_t off, int64_t, float (&v)[1]) const { v[0] = raw[off]; }
 };
 template <>
 struct FrameSrc<unsigned char> {
@@ -66,12 +73,39 @@ struct FrameSrc<unsigned char> {
         return make_float4(__fmul_rn(fmaf((float)u.x, scalar, bias), s), __fmul_rn(fmaf((float)u.y, scalar, bias), s),
                            __fmul_rn(fmaf((float)u.z, scalar, bias), s), __fmul_rn(fmaf((float)u.w, scalar, bias), s));
     }
+    static constexpr int W = 4;
+    __device__ __forceinline__ void loadw(int64_t off, int64_t row, float (&v)[4]) const {
+        const float4 f = load4(off, row);
+        v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
+    }
 };
 
-__global__ __launch_bounds__(256) void frame_stats_kernel(const float* __restrict__ raw,
-                                                          const int32_t* __restrict__ num_frames, int B,
+// W consecutive floats at p (W = 4: p 16-byte aligned)
+template <int W>
+__device__ __forceinline__ void loadw_f32(const float* __restrict__ p, float (&v)[W]) {
+    if constexpr (W == 4) {
+        const float4 f = *reinterpret_cast<const float4*>(p);
+        v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < W; ++k) v[k] = p[k];
+    }
+}
+template <int W>
+__device__ __forceinline__ void storew_f32(float* __restrict__ p, const float (&v)[W]) {
+    if constexpr (W == 4) {
+        *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < W; ++k) p[k] = v[k];
+    }
+}
+
+template <typename Src>
+__global__ __launch_bounds__(256) void frame_stats_kernel(Src raw, const int32_t* __restrict__ num_frames, int B,
                                                           int max_frames, int F, int S, float step,
                                                           float* __restrict__ partial) {
+    constexpr int W = Src::W;
     const int r0 = blockIdx.x * FP_ROWS;
     const int rows = B * S;
     const int r1 = min(rows, r0 + FP_ROWS);
@@ -86,16 +120,22 @@ __global__ __launch_bounds__(256) void frame_stats_kernel(const float* __restric
         }
     }
     __syncthreads();
-    for (int c = threadIdx.x; c < F; c += 256) {
-        float s = 0.f, q = 0.f;
+    for (int c = threadIdx.x * W; c < F; c += 256 * W) {
+        float s[W], q[W];
+#pragma unroll
+        for (int k = 0; k < W; ++k) s[k] = q[k] = 0.f;
         for (int r = 0; r < r1 - r0; ++r) {
-            const float v = raw[base[r] + c];
-            s += v;
-            q = fmaf(v, v, q);
+            float v[W];
+            raw.loadw(base[r] + c, r0 + r, v);
+#pragma unroll
+            for (int k = 0; k < W; ++k) {
+                s[k] += v[k];
+                q[k] = fmaf(v[k], v[k], q[k]);
+            }
         }
         float* p = partial + (int64_t)blockIdx.x * 2 * F;
-        p[c] = s;
-        p[F + c] = q;
+        storew_f32<W>(p + c, s);
+        storew_f32<W>(p + F + c, q);
     }
 }
 
@@ -192,13 +232,14 @@ __global__ __launch_bounds__(256) void frame_apply_tiles_kernel(Src raw, const i
 }
 
 // column partials of (sum dy, sum dy * x) over the gathered rows, for dgamma/dbeta of input_bn
-__global__ __launch_bounds__(256) void frame_bn_bwd_partial_kernel(const float* __restrict__ dy, int64_t lddy,
-                                                                   const float* __restrict__ raw,
+template <typename Src>
+__global__ __launch_bounds__(256) void frame_bn_bwd_partial_kernel(const float* __restrict__ dy, int64_t lddy, Src raw,
                                                                    const int32_t* __restrict__ num_frames, int B,
                                                                    int max_frames, int F, int S, float step,
                                                                    float* __restrict__ partial, const float* __restrict__ dy2,
                                                                    int64_t lddy2, int Dv) {
     // dy2 != null: the gradient arrives as two matrices, columns [0, Dv) in dy and [Dv, F) in dy2 (lpm_frame_apply_tiles_split's outputs)
+    constexpr int W = Src::W;       // W = 4: Dv, both row strides and both pointers are multiples of four floats (checked by the host)
     const int r0 = blockIdx.x * FP_ROWS;
     const int rows = B * S;
     const int r1 = min(rows, r0 + FP_ROWS);
@@ -213,16 +254,23 @@ __global__ __launch_bounds__(256) void frame_bn_bwd_partial_kernel(const float* 
         }
     }
     __syncthreads();
-    for (int c = threadIdx.x; c < F; c += 256) {
-        float s = 0.f, q = 0.f;
+    for (int c = threadIdx.x * W; c < F; c += 256 * W) {
+        float s[W], q[W];
+#pragma unroll
+        for (int k = 0; k < W; ++k) s[k] = q[k] = 0.f;
         for (int r = 0; r < r1 - r0; ++r) {
-            const float g = (dy2 && c >= Dv) ? dy2[(int64_t)(r0 + r) * lddy2 + (c - Dv)] : dy[(int64_t)(r0 + r) * lddy + c];
-            s += g;
-            q = fmaf(g, raw[base[r] + c], q);
+            float g[W], x[W];
+            loadw_f32<W>((dy2 && c >= Dv) ? dy2 + (int64_t)(r0 + r) * lddy2 + (c - Dv) : dy + (int64_t)(r0 + r) * lddy + c, g);
+            raw.loadw(base[r] + c, r0 + r, x);
+#pragma unroll
+            for (int k = 0; k < W; ++k) {
+                s[k] += g[k];
+                q[k] = fmaf(g[k], x[k], q[k]);
+            }
         }
         float* p = partial + (int64_t)blockIdx.x * 2 * F;
-        p[c] = s;
-        p[F + c] = q;
+        storew_f32<W>(p + c, s);
+        storew_f32<W>(p + F + c, q);
     }
 }
 
@@ -494,17 +542,49 @@ int launch_frame_apply_tiles_bf16(Src raw, const int32_t* num_frames, int B, int
     return check_launch(name);
 }
 
+template <typename Src>
+int launch_frame_stats(Src raw, const int32_t* num_frames, int B, int max_frames, int F, int S, float* partial, hipStream_t stream,
+                       const char* name) {
+    using namespace lpm;
+    LPM_REQUIRE(partial, LPM_ERR_BADARG, "%s: null workspace", name);
+    LPM_REQUIRE(Src::W == 1 || ((uintptr_t)partial & 15) == 0, LPM_ERR_UNSUPPORTED_SHAPE, "%s: need a 16-byte aligned workspace", name);
+    const float step = 1.0f / (float)S;
+    hipLaunchKernelGGL(frame_stats_kernel<Src>, dim3(fp_nblk(B, S)), dim3(256), 0, stream, raw, num_frames, B, max_frames, F, S, step,
+                       partial);
+    return check_launch(name);
+}
+
+// dy2 == NULL: one gradient matrix dy [B S, F] (lpm_frame_bn_bwd); else dy [B S, Dv] and dy2 [B S, F - Dv] (lpm_frame_bn_bwd_split)
+template <typename Src>
+int launch_frame_bn_bwd(const float* dy, int64_t lddy, const float* dy2, int64_t lddy2, int Dv, Src raw, const int32_t* num_frames, int B,
+                        int max_frames, int F, int S, const float* mean, const float* var, float eps, float* dgamma, float* dbeta,
+                        void* workspace, size_t workspace_bytes, hipStream_t stream, const char* name) {
+    using namespace lpm;
+    if (dy2 == nullptr)
+        LPM_REQUIRE(dy && mean && var && dgamma && dbeta && workspace && lddy >= F, LPM_ERR_BADARG, "%s: bad pointers", name);
+    else
+        LPM_REQUIRE(dy && mean && var && dgamma && dbeta && workspace && Dv > 0 && Dv < F && lddy >= Dv && lddy2 >= F - Dv, LPM_ERR_BADARG,
+                    "%s: bad pointers / strides", name);
+    LPM_REQUIRE(workspace_bytes >= lpm_frame_stats_workspace_bytes(B, S, F), LPM_ERR_WORKSPACE, "%s: workspace too small", name);
+    if (Src::W == 4)        // float4 reads of the gradient, float4 writes of the partials
+        LPM_REQUIRE((((uintptr_t)dy | (uintptr_t)dy2 | (uintptr_t)workspace) & 15) == 0 && lddy % 4 == 0 &&
+                        (dy2 == nullptr || (lddy2 % 4 == 0 && Dv % 4 == 0)),
+                    LPM_ERR_UNSUPPORTED_SHAPE, "%s: need 16-byte aligned gradients and workspace, row strides and Dv multiples of 4", name);
+    const float step = 1.0f / (float)S;
+    const int nblk = fp_nblk(B, S);
+    hipLaunchKernelGGL(frame_bn_bwd_partial_kernel<Src>, dim3(nblk), dim3(256), 0, stream, dy, lddy, raw, num_frames, B, max_frames, F, S,
+                       step, (float*)workspace, dy2, lddy2, dy2 ? Dv : F);
+    hipLaunchKernelGGL(frame_bn_bwd_reduce_kernel, dim3((F + 15) / 16), dim3(1024), 0, stream, (const float*)workspace, nblk, F, mean, var,
+                       eps, dgamma, dbeta);
+    return check_launch(name);
+}
+
 }  // namespace
 
 extern "C" int lpm_frame_stats(const float* raw, const int32_t* num_frames, int B, int max_frames, int F, int S,
                                float* partial, lpm_stream_t stream) {
-    using namespace lpm;
     LPM_FRAME_CHECK("lpm_frame_stats");
-    LPM_REQUIRE(partial, LPM_ERR_BADARG, "lpm_frame_stats: null workspace");
-    const float step = 1.0f / (float)S;
-    hipLaunchKernelGGL(frame_stats_kernel, dim3(fp_nblk(B, S)), dim3(256), 0, (hipStream_t)stream, raw, num_frames, B,
-                       max_frames, F, S, step, partial);
-    return check_launch("lpm_frame_stats");
+    return launch_frame_stats(FrameSrc<float>{raw}, num_frames, B, max_frames, F, S, partial, (hipStream_t)stream, "lpm_frame_stats");
 }
 
 extern "C" int lpm_frame_apply(const float* raw, const int32_t* num_frames, int B, int max_frames, int F, int S,
@@ -615,36 +695,49 @@ extern "C" int lpm_frame_bn_bwd(const float* dy, int64_t lddy, const float* raw,
                                 int max_frames, int F, int S, const float* mean, const float* var, float eps,
                                 float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
                                 lpm_stream_t stream) {
-    using namespace lpm;
     LPM_FRAME_CHECK("lpm_frame_bn_bwd");
-    LPM_REQUIRE(dy && mean && var && dgamma && dbeta && workspace && lddy >= F, LPM_ERR_BADARG, "lpm_frame_bn_bwd: bad pointers");
-    LPM_REQUIRE(workspace_bytes >= lpm_frame_stats_workspace_bytes(B, S, F), LPM_ERR_WORKSPACE, "lpm_frame_bn_bwd: workspace too small");
-    const float step = 1.0f / (float)S;
-    const int nblk = fp_nblk(B, S);
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(frame_bn_bwd_partial_kernel, dim3(nblk), dim3(256), 0, s, dy, lddy, raw, num_frames, B, max_frames, F, S,
-                       step, (float*)workspace, (const float*)nullptr, (int64_t)0, F);
-    hipLaunchKernelGGL(frame_bn_bwd_reduce_kernel, dim3((F + 15) / 16), dim3(1024), 0, s, (const float*)workspace, nblk, F, mean,
-                       var, eps, dgamma, dbeta);
-    return check_launch("lpm_frame_bn_bwd");
+    return launch_frame_bn_bwd(dy, lddy, nullptr, 0, F, FrameSrc<float>{raw}, num_frames, B, max_frames, F, S, mean, var, eps, dgamma, dbeta,
+                               workspace, workspace_bytes, (hipStream_t)stream, "lpm_frame_bn_bwd");
 }
 // ... with the gradient as two matrices: dy_video [B S, Dv] (row stride ldv) and dy_audio [B S, F - Dv] (row stride lda)
 extern "C" int lpm_frame_bn_bwd_split(const float* dy_video, int64_t ldv, const float* dy_audio, int64_t lda, int Dv, const float* raw,
                                       const int32_t* num_frames, int B, int max_frames, int F, int S, const float* mean, const float* var,
                                       float eps, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, lpm_stream_t stream) {
-    using namespace lpm;
     LPM_FRAME_CHECK("lpm_frame_bn_bwd_split");
-    LPM_REQUIRE(dy_video && dy_audio && mean && var && dgamma && dbeta && workspace && Dv > 0 && Dv < F && ldv >= Dv && lda >= F - Dv,
-                LPM_ERR_BADARG, "lpm_frame_bn_bwd_split: bad pointers / strides");
-    LPM_REQUIRE(workspace_bytes >= lpm_frame_stats_workspace_bytes(B, S, F), LPM_ERR_WORKSPACE, "lpm_frame_bn_bwd_split: workspace too small");
-    const float step = 1.0f / (float)S;
-    const int nblk = fp_nblk(B, S);
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(frame_bn_bwd_partial_kernel, dim3(nblk), dim3(256), 0, s, dy_video, ldv, raw, num_frames, B, max_frames, F, S,
-                       step, (float*)workspace, dy_audio, lda, Dv);
-    hipLaunchKernelGGL(frame_bn_bwd_reduce_kernel, dim3((F + 15) / 16), dim3(1024), 0, s, (const float*)workspace, nblk, F, mean,
-                       var, eps, dgamma, dbeta);
-    return check_launch("lpm_frame_bn_bwd_split");
+    LPM_REQUIRE(dy_audio, LPM_ERR_BADARG, "lpm_frame_bn_bwd_split: bad pointers / strides");
+    return launch_frame_bn_bwd(dy_video, ldv, dy_audio, lda, Dv, FrameSrc<float>{raw}, num_frames, B, max_frames, F, S, mean, var, eps, dgamma,
+                               dbeta, workspace, workspace_bytes, (hipStream_t)stream, "lpm_frame_bn_bwd_split");
+}
+
+// ---- training mode from the reader's quantised frames: the batch statistics and the dgamma / dbeta partials, bit for bit those of the
+// fp32 forms on lpm_dequantize_l2_normalize's frames (inv_norm from lpm_frame_inv_norm_q8; gradients and workspace 16-byte aligned) ----
+extern "C" int lpm_frame_stats_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
+                                  const int32_t* num_frames, int B, int max_frames, int F, int S, float* partial, lpm_stream_t stream) {
+    LPM_FRAME_Q8_CHECK("lpm_frame_stats_q8");
+    return launch_frame_stats(q8_src(q, inv_norm, max_quantized_value, min_quantized_value), num_frames, B, max_frames, F, S, partial,
+                              (hipStream_t)stream, "lpm_frame_stats_q8");
+}
+
+extern "C" int lpm_frame_bn_bwd_q8(const float* dy, int64_t lddy, const unsigned char* q, const float* inv_norm, float max_quantized_value,
+                                   float min_quantized_value, const int32_t* num_frames, int B, int max_frames, int F, int S,
+                                   const float* mean, const float* var, float eps, float* dgamma, float* dbeta, void* workspace,
+                                   size_t workspace_bytes, lpm_stream_t stream) {
+    LPM_FRAME_Q8_CHECK("lpm_frame_bn_bwd_q8");
+    return launch_frame_bn_bwd(dy, lddy, nullptr, 0, F, q8_src(q, inv_norm, max_quantized_value, min_quantized_value), num_frames, B,
+                               max_frames, F, S, mean, var, eps, dgamma, dbeta, workspace, workspace_bytes, (hipStream_t)stream,
+                               "lpm_frame_bn_bwd_q8");
+}
+
+extern "C" int lpm_frame_bn_bwd_split_q8(const float* dy_video, int64_t ldv, const float* dy_audio, int64_t lda, int Dv,
+                                         const unsigned char* q, const float* inv_norm, float max_quantized_value,
+                                         float min_quantized_value, const int32_t* num_frames, int B, int max_frames, int F, int S,
+                                         const float* mean, const float* var, float eps, float* dgamma, float* dbeta, void* workspace,
+                                         size_t workspace_bytes, lpm_stream_t stream) {
+    LPM_FRAME_Q8_CHECK("lpm_frame_bn_bwd_split_q8");
+    LPM_REQUIRE(dy_audio, LPM_ERR_BADARG, "lpm_frame_bn_bwd_split_q8: bad pointers / strides");
+    return launch_frame_bn_bwd(dy_video, ldv, dy_audio, lda, Dv, q8_src(q, inv_norm, max_quantized_value, min_quantized_value), num_frames, B,
+                               max_frames, F, S, mean, var, eps, dgamma, dbeta, workspace, workspace_bytes, (hipStream_t)stream,
+                               "lpm_frame_bn_bwd_split_q8");
 }
 
 extern "C" int lpm_l2_normalize_rows(const float* x, int64_t rows, int F, float* y, lpm_stream_t stream) {

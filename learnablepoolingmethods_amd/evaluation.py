@@ -73,6 +73,26 @@ def _per_class_ap(cls, pred, lab, class_pos):
     return torch.where(class_pos > 0, ap / class_pos.clamp_min(1.0), torch.zeros_like(ap))
 
 
+def batch_metrics(predictions, labels, top_k: int = 20) -> torch.Tensor:
+    """-> fp64 [3] on the predictions' device: Hit@1, PERR and GAP of ONE batch (eval_util.calculate_hit_at_one,
+    calculate_precision_at_equal_recall_rate, calculate_gap(top_k)) -- what train.py:461-465 computes for its log line.  On the GPU:
+    one lpm_eval_rows pass (ops.eval_rows, no loss) and the average precision of the pooled top-k entries, all on the device with no
+    host sync (the caller copies the three numbers when it wants them).  CPU tensors go through eval_util."""
+    p = torch.as_tensor(predictions)
+    y = torch.as_tensor(labels).to(p.device)
+    if not p.is_cuda:
+        return torch.tensor([eval_util.calculate_hit_at_one(p, y), eval_util.calculate_precision_at_equal_recall_rate(p, y),
+                             eval_util.calculate_gap(p, y, top_k)], dtype=torch.float64)
+    if y.dtype not in (torch.bool, torch.uint8):
+        y = y != 0
+    f64 = torch.float64
+    r = ops.eval_rows(p.to(torch.float32), y, min(int(top_k), p.shape[1]), with_loss=False)
+    n = r.num_labels.to(f64)
+    perr = torch.where(n > 0, r.hits_at_n.to(f64) / n.clamp_min(1.0), torch.zeros_like(n)).mean()
+    gap = _average_precision(r.top_value.reshape(-1).to(f64), r.top_label.reshape(-1).to(f64), n.sum())
+    return torch.stack([r.hit1.to(f64).mean(), perr, gap])
+
+
 class DeviceEvaluationMetrics:
     """eval_util.EvaluationMetrics on the GPU: accumulate(predictions, labels, loss=None), get(), clear()."""
 

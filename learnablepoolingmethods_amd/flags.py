@@ -119,3 +119,8 @@ FLAGS.define("library_gemm_selection", True, "build extension: the fp32 library 
              "TunableOp with tuning OFF: a recorded shape takes its recorded solution, any other shape the library's default).  The MoE-4 head of "
              "BASELINE configs[4] is 159 + 87 us forward on the default choices and 47 + 39 us on the recorded ones; the file is ignored (with a "
              "warning from PyTorch) where its ROCm / hipBLASLt / rocBLAS / device validators do not match")
+FLAGS.define("train_quantised_frames", True, "build extension: Trainer.build / step / calibrate_operand_scales hand the reader's uint8 frames on "
+             "the GPU straight to the frame-prep kernels of NetVladV1 / NetVladV2 (lpm_frame_inv_norm_q8, lpm_frame_stats_q8, the *_q8 apply "
+             "forms, lpm_frame_bn_bwd*_q8) instead of first writing the dequantised, L2-normalised fp32 frames of all max_frames "
+             "(ops.dequantize_l2_normalize) -- the same results bit for bit.  False: the fp32 detour (A/B).  fp32 input, the CPU and other "
+             "models are not affected")

@@ -138,12 +138,14 @@ class _GammaWatch:
                           "switched off, the input gradient is formed explicitly from now on")
 
 
-def _sample_and_normalise(model_input, num_frames, iterations, add_batch_norm, is_training, storage="f32"):
-    """SampleUniformFrames + reshape + input_bn (frame_level_models.py:2248-2271), one fused kernel pair."""
+def _sample_and_normalise(model_input, num_frames, iterations, add_batch_norm, is_training, storage="f32", quantised_training=False):
+    """SampleUniformFrames + reshape + input_bn (frame_level_models.py:2248-2271), one fused kernel pair.  quantised_training: uint8
+    frames (the reader's batch) are accepted in training mode too (ops.frame_sample_bn)."""
     bn = layers.bn_variables("input_bn", model_input.shape[2], model_input.device) if add_batch_norm else (None,) * 4
     # bf16 storage: the fp32 matrix itself is only filled in when summaries are being collected (nothing else reads it)
     return ops.frame_sample_bn(model_input, num_frames.reshape(-1), iterations, *bn, is_training=is_training, storage=storage,
-                               materialize=storage == "f32" or vs.default_store().summaries is not None)
+                               materialize=storage == "f32" or vs.default_store().summaries is not None,
+                               quantised_training=quantised_training)
 
 
 class NetVladV1(models.BaseModel):
@@ -152,7 +154,7 @@ class NetVladV1(models.BaseModel):
 
     def create_model(self, model_input, vocab_size, num_frames, iterations=None, add_batch_norm=None,
                      sample_random_frames=None, cluster_size=None, hidden_size=None, is_training=True, encoder=None,
-                     **unused_params):
+                     quantised_training=False, **unused_params):
         iterations = iterations or FLAGS.iterations
         add_batch_norm = add_batch_norm or FLAGS.netvlad_add_batch_norm
         cluster_size = cluster_size or FLAGS.netvlad_cluster_size
@@ -187,7 +189,7 @@ class NetVladV1(models.BaseModel):
                               "back to fp32 storage (explicit input-gradient path)")
             storage = "f32"
 
-        reshaped_input = _sample_and_normalise(model_input, num_frames, iterations, add_batch_norm, is_training, storage)
+        reshaped_input = _sample_and_normalise(model_input, num_frames, iterations, add_batch_norm, is_training, storage, quantised_training)
         if storage == "f32" or vs.default_store().summaries is not None:
             vs.summary("input_bn", reshaped_input)
 
@@ -325,7 +327,7 @@ class NetVladV2(models.BaseModel):
 
     def create_model(self, model_input, vocab_size, num_frames, iterations=None, add_batch_norm=None,
                      sample_random_frames=None, cluster_size=None, hidden_size=None, is_training=True,
-                     dropout_masks=None, dropout_rate=None, **unused_params):
+                     dropout_masks=None, dropout_rate=None, quantised_training=False, **unused_params):
         iterations = iterations or FLAGS.iterations
         add_batch_norm = add_batch_norm or FLAGS.netvlad_add_batch_norm
         cluster_size = cluster_size or FLAGS.netvlad_cluster_size
@@ -336,14 +338,15 @@ class NetVladV2(models.BaseModel):
         max_frames, feature_size = iterations, model_input.shape[2]
         has_audio = feature_size > 1024
         split = None
-        if (has_audio and add_batch_norm and vs.default_store().summaries is None and ops.frame_sample_bn_split_ok(model_input, 1024, is_training)):
+        if (has_audio and add_batch_norm and vs.default_store().summaries is None and ops.frame_sample_bn_split_ok(model_input, 1024, is_training, quantised_training)):
             # the two streams' blocks of the sampled, batch-normalised frames as two contiguous matrices straight from the frame-prep
             # kernel (ops.frame_sample_bn_split): same values, same variables; no column slices, copies or gradient concatenation
             bn = layers.bn_variables("input_bn", feature_size, model_input.device)
-            split = ops.frame_sample_bn_split(model_input, num_frames.reshape(-1), iterations, *bn, is_training, 1024)
+            split = ops.frame_sample_bn_split(model_input, num_frames.reshape(-1), iterations, *bn, is_training, 1024, quantised_training)
             reshaped_input = None
         else:
-            reshaped_input = _sample_and_normalise(model_input, num_frames, iterations, add_batch_norm, is_training)
+            reshaped_input = _sample_and_normalise(model_input, num_frames, iterations, add_batch_norm, is_training,
+                                                   quantised_training=quantised_training)
             vs.summary("input_bn", reshaped_input)
 
         video_NetVLAD = video_pooling_modules.NetVladAttenCluster(1024, max_frames, cluster_size, add_batch_norm,

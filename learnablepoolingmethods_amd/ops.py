@@ -257,9 +257,10 @@ def dequantize_l2_normalize(q, num_frames, max_quantized_value=2.0, min_quantize
 QUANT_MAX, QUANT_MIN = 2.0, -2.0
 
 
-def _check_q8_eval(raw, is_training, what):
-    """uint8 frames are the reader's quantised batch: accepted in eval mode only (the training path needs fp32 frames)."""
-    if raw.dtype == torch.uint8 and is_training:
+def _check_q8_eval(raw, is_training, what, quantised_training=False):
+    """uint8 frames are the reader's quantised batch: accepted in eval mode, and in training mode only when the caller asks for the
+    quantised training path (``quantised_training``: the statistics and gradient kernels read the uint8 frames, on the GPU)."""
+    if raw.dtype == torch.uint8 and is_training and not (quantised_training and raw.is_cuda):
         raise LpmError(f"{what}: uint8 (quantised) frames are accepted in eval mode only (is_training=False); training needs the "
                        "dequantised, L2-normalised fp32 frames (ops.dequantize_l2_normalize)")
 
@@ -278,6 +279,14 @@ def _frame_inputs(lib, raw, num_frames, S, what):
     lib.check(lib._lpm_frame_inv_norm_q8(ptr(raw), ptr(nf), B, MF, F, S, QUANT_MAX, QUANT_MIN, ptr(inv), stream_ptr()),
               "lpm_frame_inv_norm_q8")
     return raw, nf, inv
+
+
+def _frame_stats_call(lib, raw, inv, *args):
+    """lpm_frame_stats(raw, *args), or lpm_frame_stats_q8(q, inv_norm, range, *args) when inv is given: the same partials bit for bit."""
+    if inv is None:
+        lib.check(lib._lpm_frame_stats(ptr(raw), *args), "lpm_frame_stats")
+    else:
+        lib.check(lib._lpm_frame_stats_q8(ptr(raw), ptr(inv), QUANT_MAX, QUANT_MIN, *args), "lpm_frame_stats_q8")
 
 
 def _frame_apply_call(lib, name, raw, inv, *args):
@@ -302,7 +311,7 @@ class _FrameSampleBN(torch.autograd.Function):
             if is_training:
                 nblk = lib._lpm_frame_stats_nblk(B, S)
                 partial = _empty((nblk, 2, F), raw)
-                lib.check(lib._lpm_frame_stats(ptr(raw), ptr(nf), B, MF, F, S, ptr(partial), stream_ptr()), "lpm_frame_stats")
+                _frame_stats_call(lib, raw, inv, ptr(nf), B, MF, F, S, ptr(partial), stream_ptr())
                 mean, var, scale, shift = bn_fold(partial, nblk, F, B * S, gamma, beta, moving_mean, moving_var)
             else:
                 scale, shift = folded_eval_affine(gamma, beta, moving_mean, moving_var)
@@ -344,7 +353,10 @@ class _FrameSampleBN(torch.autograd.Function):
             _frame_apply_call(lib, "frame_apply", raw, inv, ptr(nf), B, MF, F, S, ptr(scale), ptr(shift), ptr(y), stream_ptr())
         ctx.use_bn, ctx.is_training, ctx.S = use_bn, is_training, S
         ctx.q8 = inv is not None
-        if use_bn and not ctx.q8:
+        if use_bn and ctx.q8:
+            if is_training:       # quantised training: the uint8 frames and their inverse norms stand in for the fp32 frames
+                ctx.save_for_backward(raw, nf, inv, mean, var)
+        elif use_bn:
             if is_training:
                 ctx.save_for_backward(raw, nf, mean, var)
             else:
@@ -355,17 +367,25 @@ class _FrameSampleBN(torch.autograd.Function):
     def backward(ctx, dy):
         if not ctx.use_bn:
             return (None,) * 11
-        if ctx.q8:
+        if ctx.q8 and not ctx.is_training:
             raise LpmError("frame_sample_bn: no gradient through the eval-mode path of uint8 frames")
         lib = _capi.load()
-        raw, nf, mean, var = ctx.saved_tensors
+        if ctx.q8:
+            raw, nf, inv, mean, var = ctx.saved_tensors
+        else:
+            raw, nf, mean, var = ctx.saved_tensors
         B, MF, F = raw.shape
         dy = _rows(dy.contiguous(), "dy")
-        dgamma, dbeta = _empty((F,), raw), _empty((F,), raw)
+        dgamma, dbeta = _empty((F,), dy), _empty((F,), dy)
         wsb = lib._lpm_frame_stats_workspace_bytes(B, ctx.S, F)
         ws = torch.empty(wsb // 4, dtype=torch.float32, device=raw.device)
-        lib.check(lib._lpm_frame_bn_bwd(ptr(dy), dy.stride(0), ptr(raw), ptr(nf), B, MF, F, ctx.S, ptr(mean), ptr(var),
-                                        BN_EPS, ptr(dgamma), ptr(dbeta), ptr(ws), wsb, stream_ptr()), "lpm_frame_bn_bwd")
+        if ctx.q8:
+            lib.check(lib._lpm_frame_bn_bwd_q8(ptr(dy), dy.stride(0), ptr(raw), ptr(inv), QUANT_MAX, QUANT_MIN, ptr(nf), B, MF, F, ctx.S,
+                                               ptr(mean), ptr(var), BN_EPS, ptr(dgamma), ptr(dbeta), ptr(ws), wsb, stream_ptr()),
+                      "lpm_frame_bn_bwd_q8")
+        else:
+            lib.check(lib._lpm_frame_bn_bwd(ptr(dy), dy.stride(0), ptr(raw), ptr(nf), B, MF, F, ctx.S, ptr(mean), ptr(var),
+                                            BN_EPS, ptr(dgamma), ptr(dbeta), ptr(ws), wsb, stream_ptr()), "lpm_frame_bn_bwd")
         return None, None, dgamma, dbeta, None, None, None, None, None, None, None
 
 
@@ -605,14 +625,17 @@ def _dx_slot_view(slot_ref, D):
 
 
 def frame_sample_bn(raw, num_frames, S, gamma=None, beta=None, moving_mean=None, moving_var=None, is_training=True, storage="f32",
-                    materialize=True):
+                    materialize=True, quantised_training=False):
     """[B, max_frames, F] -> [B*S, F]: uniform frame sampling (model_utils.py:101-122) fused with
     input_bn (frame_level_models.py:2265-2271).  The frames are data: no gradient flows to ``raw``.
     storage="bf16" (BASELINE cfg-5): the result is written as plain bf16 operand tiles for ops.netvlad(storage="bf16"); the fp32
     matrix that is returned is filled in only with ``materialize`` (otherwise it is a handle nobody may read).
     ``raw`` may be the reader's uint8 batch (quantised, un-normalised) when ``is_training`` is False: the dequantisation and the per-frame
-    L2 normalisation of Trainer._normalize_input happen inside the frame pass, for the sampled frames only -- the same values bit for bit."""
-    _check_q8_eval(raw, is_training, "frame_sample_bn")
+    L2 normalisation of Trainer._normalize_input happen inside the frame pass, for the sampled frames only -- the same values bit for bit.
+    ``quantised_training``: uint8 frames on the GPU are accepted in training mode too -- the batch statistics (lpm_frame_stats_q8) and
+    the gamma / beta gradients (lpm_frame_bn_bwd_q8) read the uint8 frames, autograd keeps (q, num_frames, inverse norms, mean, var)
+    instead of fp32 frames, and every result equals the fp32 path's on ops.dequantize_l2_normalize(raw, num_frames) bit for bit."""
+    _check_q8_eval(raw, is_training, "frame_sample_bn", quantised_training)
     use_bn = gamma is not None
     return _FrameSampleBN.apply(raw, num_frames, gamma, beta, moving_mean, moving_var, int(S), bool(is_training), use_bn, storage,
                                 bool(materialize))
@@ -633,7 +656,7 @@ class _FrameSampleBNSplit(torch.autograd.Function):
         if is_training:
             nblk = lib._lpm_frame_stats_nblk(B, S)
             partial = _empty((nblk, 2, F), raw)
-            lib.check(lib._lpm_frame_stats(ptr(raw), ptr(nf), B, MF, F, S, ptr(partial), stream_ptr()), "lpm_frame_stats")
+            _frame_stats_call(lib, raw, inv, ptr(nf), B, MF, F, S, ptr(partial), stream_ptr())
             mean, var, scale, shift = bn_fold(partial, nblk, F, B * S, gamma, beta, moving_mean, moving_var)
         else:
             scale, shift = folded_eval_affine(gamma, beta, moving_mean, moving_var)
@@ -647,24 +670,35 @@ class _FrameSampleBNSplit(torch.autograd.Function):
         _XT_CACHE.clear()
         _XT_CACHE.update(split=True, F=F, Dv=Dv, S=S, B=B, video=xtv, audio=xta, video_t=yv, audio_t=ya,
                          video_ver=yv._version, audio_ver=ya._version)
-        ctx.S, ctx.Dv, ctx.q8 = S, Dv, inv is not None
-        ctx.save_for_backward(raw, nf, mean, var)
+        ctx.S, ctx.Dv, ctx.q8, ctx.is_training = S, Dv, inv is not None, is_training
+        if ctx.q8 and is_training:
+            ctx.save_for_backward(raw, nf, inv, mean, var)
+        else:
+            ctx.save_for_backward(raw, nf, mean, var)
         return yv, ya
 
     @staticmethod
     def backward(ctx, dv, da):
-        if ctx.q8:
+        if ctx.q8 and not ctx.is_training:
             raise LpmError("frame_sample_bn_split: no gradient through the eval-mode path of uint8 frames")
         lib = _capi.load()
-        raw, nf, mean, var = ctx.saved_tensors
+        if ctx.q8:
+            raw, nf, inv, mean, var = ctx.saved_tensors
+        else:
+            raw, nf, mean, var = ctx.saved_tensors
         B, MF, F = raw.shape
         Dv = ctx.Dv
         M = B * ctx.S
         dv = _rows(dv.contiguous(), "dy") if dv is not None else torch.zeros((M, Dv), dtype=torch.float32, device=raw.device)
         da = _rows(da.contiguous(), "dy") if da is not None else torch.zeros((M, F - Dv), dtype=torch.float32, device=raw.device)
-        dgamma, dbeta = _empty((F,), raw), _empty((F,), raw)
+        dgamma, dbeta = _empty((F,), dv), _empty((F,), dv)
         wsb = lib._lpm_frame_stats_workspace_bytes(B, ctx.S, F)
         ws = torch.empty(wsb // 4, dtype=torch.float32, device=raw.device)
+        if ctx.q8:
+            lib.check(lib._lpm_frame_bn_bwd_split_q8(ptr(dv), dv.stride(0), ptr(da), da.stride(0), Dv, ptr(raw), ptr(inv), QUANT_MAX, QUANT_MIN,
+                                                     ptr(nf), B, MF, F, ctx.S, ptr(mean), ptr(var), BN_EPS, ptr(dgamma), ptr(dbeta), ptr(ws), wsb,
+                                                     stream_ptr()), "lpm_frame_bn_bwd_split_q8")
+            return None, None, dgamma, dbeta, None, None, None, None, None
         lib.check(lib._lpm_frame_bn_bwd_split(ptr(dv), dv.stride(0), ptr(da), da.stride(0), Dv, ptr(raw), ptr(nf), B, MF, F, ctx.S, ptr(mean),
                                               ptr(var), BN_EPS, ptr(dgamma), ptr(dbeta), ptr(ws), wsb, stream_ptr()), "lpm_frame_bn_bwd_split")
         return None, None, dgamma, dbeta, None, None, None, None, None
@@ -673,18 +707,18 @@ class _FrameSampleBNSplit(torch.autograd.Function):
 FRAME_SPLIT = os.environ.get("LPM_FRAME_SPLIT", "1") != "0"      # "0": NetVladV2 slices one [B S, F] matrix (A/B)
 
 
-def frame_sample_bn_split_ok(raw, Dv, is_training=True):
-    """uint8 frames (the reader's quantised batch) qualify in eval mode only."""
-    dtype_ok = raw.dtype == torch.float32 or (raw.dtype == torch.uint8 and not is_training)
+def frame_sample_bn_split_ok(raw, Dv, is_training=True, quantised_training=False):
+    """uint8 frames (the reader's quantised batch) qualify in eval mode, and in training mode with ``quantised_training``."""
+    dtype_ok = raw.dtype == torch.float32 or (raw.dtype == torch.uint8 and (not is_training or quantised_training))
     return bool(FRAME_SPLIT and raw.is_cuda and raw.dim() == 3 and dtype_ok and VLAD_PRECISION == "bf16x3"
                 and 0 < Dv < raw.shape[2] and Dv % 32 == 0 and (raw.shape[2] - Dv) % 32 == 0)
 
 
-def frame_sample_bn_split(raw, num_frames, S, gamma, beta, moving_mean, moving_var, is_training, Dv):
+def frame_sample_bn_split(raw, num_frames, S, gamma, beta, moving_mean, moving_var, is_training, Dv, quantised_training=False):
     """-> (rgb [B*S, Dv], audio [B*S, F - Dv]): uniform frame sampling + input_bn (model_utils.py:101-122, frame_level_models.py:2265-2271)
     with the two streams' blocks as separate contiguous matrices; gamma / beta receive ONE gradient each.  uint8 ``raw``: as in
-    frame_sample_bn, eval mode only."""
-    _check_q8_eval(raw, is_training, "frame_sample_bn_split")
+    frame_sample_bn, eval mode only unless ``quantised_training``."""
+    _check_q8_eval(raw, is_training, "frame_sample_bn_split", quantised_training)
     return _FrameSampleBNSplit.apply(raw, num_frames, gamma, beta, moving_mean, moving_var, int(S), bool(is_training), int(Dv))
 
 

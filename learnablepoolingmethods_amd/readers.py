@@ -429,6 +429,138 @@ class YT8MFrameFeatureReader(BaseReader):
         finally:
             pipe.close()
 
+    def training_batches(self, files: Sequence[str], batch_size: int, device="cuda", num_epochs: Optional[int] = None, seed: int = 0,
+                         shuffle_files: bool = True, capacity: Optional[int] = None, min_after_dequeue: Optional[int] = None,
+                         **device_batches_kwargs):
+        """The training input order (reference: train.py:172-184, ``string_input_producer(shuffle=True)`` feeding
+        ``shuffle_batch_join(capacity=5*batch, min_after_dequeue=batch, allow_smaller_final_batch=True)``): yields what
+        ``device_batches`` (on a CPU device: ``batches``) yields, with the clips shuffled through a ``ShufflePool`` on ``device``.
+        The file list is permuted once at the start of every epoch (``shuffle_files``) with the pool's generator; epochs follow each
+        other without draining the pool, as the reference's filename queue feeds its readers; ``num_epochs=None`` runs until the
+        consumer stops.  Every batch has ``batch_size`` clips except the last one of a finite run.
+
+        The same parameters and guarantees as the reference's queues -- NOT the same random stream: the order comes from
+        ``numpy.random.Generator(PCG64(seed))`` and is reproducible for a seed, a file list and a batch size, on either device.
+        Closing the generator closes the underlying ``device_batches`` generator (its threads are joined)."""
+        files = list(files)
+        dev = torch.device(device)
+        rng = np.random.Generator(np.random.PCG64(seed))
+
+        def source():
+            epoch = 0
+            while num_epochs is None or epoch < num_epochs:
+                order = [files[i] for i in rng.permutation(len(files))] if shuffle_files else files
+                if dev.type == "cuda":
+                    yield from self.device_batches(order, batch_size, device=dev, **device_batches_kwargs)
+                else:
+                    yield from self.batches(order, batch_size, **device_batches_kwargs)
+                epoch += 1
+                if not files:
+                    return
+        src = source()
+        try:
+            yield from ShufflePool(src, batch_size, capacity=capacity, min_after_dequeue=min_after_dequeue, rng=rng)
+        finally:
+            src.close()
+
+
+class ShufflePool:
+    """``tf.train.shuffle_batch_join``'s policy over any iterator of (ids, frames, labels, num_frames) batches whose tensors live on
+    one device (``batches()`` output on the CPU, ``device_batches()`` output on the GPU).
+
+    The pool holds up to ``capacity`` clips in tensors preallocated on the input's device when the first batch arrives (the ids stay on
+    the host).  Before each dequeue it pulls input batches while a whole one (the largest seen so far) still fits.  A dequeue draws
+    ``batch_size`` distinct clips uniformly from the pool with a host generator (``numpy.random.Generator(PCG64(seed))``) and needs
+    ``min_after_dequeue`` clips to stay behind until the input is exhausted; then the pool drains and the last batch may be smaller.
+    Clips leave through ``index_select`` and arrive in the holes through ``index_copy_`` on the consumer's current stream; every count
+    is known on the host from ``len(ids)``, so nothing waits for the device.  The yielded tensors are fresh and belong to the consumer.
+    The same guarantees as the reference's queue, not its random stream."""
+
+    def __init__(self, batches, batch_size: int, capacity: Optional[int] = None, min_after_dequeue: Optional[int] = None, seed: int = 0,
+                 rng: Optional[np.random.Generator] = None):
+        self.batch_size = int(batch_size)
+        self.capacity = 5 * self.batch_size if capacity is None else int(capacity)
+        self.min_after_dequeue = self.batch_size if min_after_dequeue is None else int(min_after_dequeue)
+        if self.batch_size < 1 or self.min_after_dequeue < 0 or self.capacity < self.batch_size + self.min_after_dequeue:
+            raise ValueError("ShufflePool: need batch_size >= 1, min_after_dequeue >= 0 and capacity >= batch_size + min_after_dequeue")
+        self.rng = np.random.Generator(np.random.PCG64(seed)) if rng is None else rng
+        self._it = iter(batches)
+        self._exhausted = False
+        self._pool = None                                   # (frames, labels, num_frames), each [capacity, ...]
+        self._ids: List[object] = [None] * self.capacity
+        self._filled = np.zeros(0, dtype=np.int64)          # slots that hold a clip
+        self._free = list(range(self.capacity - 1, -1, -1))  # slots that do not (a stack: slot 0 first)
+        self._in_batch = 0                                  # clips of the largest input batch seen
+
+    def __len__(self):
+        return len(self._filled)
+
+    def _index(self, slots, dev):
+        idx = torch.from_numpy(np.ascontiguousarray(slots, dtype=np.int64))
+        if dev.type != "cuda":
+            return idx
+        pinned = torch.empty(idx.shape, dtype=torch.int64, pin_memory=True)      # (caching host allocator: reused only after the copy)
+        pinned.copy_(idx)
+        return pinned.to(dev, non_blocking=True)
+
+    def _pull(self) -> bool:
+        try:
+            ids, frames, labels, nf = next(self._it)
+        except StopIteration:
+            self._exhausted = True
+            return False
+        n = len(ids)
+        if n == 0:
+            return True
+        if not (frames.shape[0] == labels.shape[0] == nf.shape[0] == n):
+            raise ValueError("ShufflePool: a batch's tensors and ids disagree on the number of clips")
+        if self._pool is None:
+            self._pool = tuple(torch.empty((self.capacity,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device) for t in (frames, labels, nf))
+        if n > len(self._free):
+            raise ValueError(f"ShufflePool: an input batch of {n} clips does not fit (capacity {self.capacity}, "
+                             f"{len(self._filled)} clips held)")
+        self._in_batch = max(self._in_batch, n)
+        slots = np.array([self._free.pop() for _ in range(n)], dtype=np.int64)
+        idx = self._index(slots, self._pool[0].device)
+        for dst, t in zip(self._pool, (frames, labels, nf)):
+            if t.device != dst.device or t.dtype != dst.dtype or t.shape[1:] != dst.shape[1:]:
+                raise ValueError("ShufflePool: every batch must have the first one's device, dtypes and clip shapes")
+            dst.index_copy_(0, idx, t)
+        for s_, i in zip(slots, ids):
+            self._ids[s_] = i
+        self._filled = np.concatenate([self._filled, slots])
+        return True
+
+    def _dequeue(self, n: int):
+        pos = self.rng.choice(len(self._filled), size=n, replace=False)
+        slots = self._filled[pos]
+        keep = np.ones(len(self._filled), dtype=bool)
+        keep[pos] = False
+        self._filled = self._filled[keep]
+        idx = self._index(slots, self._pool[0].device)
+        frames, labels, nf = (t.index_select(0, idx) for t in self._pool)
+        ids = [self._ids[s_] for s_ in slots]
+        for s_ in slots[::-1]:
+            self._ids[s_] = None
+            self._free.append(int(s_))
+        return ids, frames, labels, nf
+
+    def __iter__(self):
+        while True:
+            # room for a whole input batch (the first one: unknown size, the pool is empty): pull
+            while not self._exhausted and len(self._free) >= max(self._in_batch, 1):
+                self._pull()
+            held = len(self._filled)
+            if not self._exhausted:
+                if held - self.batch_size < self.min_after_dequeue:
+                    raise ValueError(f"ShufflePool: capacity {self.capacity} cannot hold batch_size + min_after_dequeue = "
+                                     f"{self.batch_size + self.min_after_dequeue} clips next to a free input batch of {self._in_batch}")
+                yield self._dequeue(self.batch_size)
+            elif held:
+                yield self._dequeue(min(self.batch_size, held))
+            else:
+                return
+
 
 class _Slot:
     """One pinned host slot of the ring: the records of one batch back to back (framing included), and the tables that go to the device

@@ -533,17 +533,31 @@ class Trainer:
     def _normalize_input(self, raw, num_frames=None):
         return normalize_input(raw, num_frames)
 
+    def _quantised_frames(self, raw) -> bool:
+        """FLAGS.train_quantised_frames: the reader's uint8 batch on the GPU goes to the model as it is (the frame-prep kernels
+        dequantise and normalise the sampled frames where they read them) -- for the models whose frame op takes it, at a feature size
+        the q8 kernels accept (lpm_frame_inv_norm_q8)."""
+        from .predictor import FUSED_Q8_MODELS
+        return bool(FLAGS.train_quantised_frames and raw.dtype == torch.uint8 and raw.is_cuda and raw.dim() == 3
+                    and type(self.model).__name__ in FUSED_Q8_MODELS and raw.shape[2] % 4 == 0 and raw.shape[2] <= 2048)
+
+    def _model_input(self, raw, num_frames, kw):
+        """-> (model input, model keywords): train.py:262-264's normalised fp32 frames, or the uint8 batch itself (_quantised_frames)."""
+        if self._quantised_frames(raw):
+            return raw, {**kw, "quantised_training": True}
+        return self._normalize_input(raw, num_frames), kw
+
     def build(self, model_input_raw, num_frames, labels):
         """Create every variable (a throw-away forward: moving statistics are restored afterwards),
         then move the trainable ones into the flat arenas and set up the gradient buckets."""
         if self.arena is not None:
             return
         with torch.no_grad():
-            x = self._normalize_input(model_input_raw.to(self.device), num_frames.to(self.device))
+            x, kw = self._model_input(model_input_raw.to(self.device), num_frames.to(self.device), {})
             # undo the moving-average side effects of the dry run: statistics that existed before it (e.g. loaded after a
             # predict()) get their values back, the ones it created start at their initial values
             before = {n: v.clone() for n, v in self.store.vars.items() if not self.store.trainable[n]}
-            self._forward(x, num_frames, labels)
+            self._forward(x, num_frames, labels, **kw)
             self._l2_regs = []
             for n, v in self.store.vars.items():
                 if n in before:
@@ -667,7 +681,7 @@ class Trainer:
         self.arena.zero_grad()
         if self.bucket_gather is not None:
             self.bucket_gather.arm()
-        model_input = self._normalize_input(model_input_raw, num_frames)                        # train.py:262-264
+        model_input, kw = self._model_input(model_input_raw, num_frames, kw)                    # train.py:262-264
         if self.operand_scales is not None:
             self.operand_scales.begin_step()       # harvest the maxima measured so far, decide this step's operand format
             ops._ACTIVE_SCALES = self.operand_scales
@@ -814,7 +828,7 @@ class Trainer:
         self.build(model_input_raw, num_frames, labels)
         before = {n: v.clone() for n, v in self.store.vars.items() if not self.store.trainable[n]}
         self.arena.zero_grad()
-        model_input = self._normalize_input(model_input_raw, num_frames)
+        model_input, kw = self._model_input(model_input_raw, num_frames, kw)
         self._early = None                       # (no optimiser work inside this backward)
         was = sc.enabled
         sc.enabled = False                       # this pass runs in split-bf16 whatever is known so far
