@@ -968,6 +968,30 @@ int lpm_gather_frames(const void* buf, int64_t nbytes, int64_t capacity, const i
 int lpm_labels_dense(const int32_t* label_start, const int32_t* label_index, int num_labels, int B, int num_classes, void* out,
                      lpm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Histograms for the TensorBoard writer (summaries.py), with the semantics of tensorflow::histogram::Histogram::Add.
+ *
+ * Segments: x fp32 [x_len] (device, 4-byte aligned), seg_start / seg_len int64 [num_segments] (DEVICE arrays of element offsets and
+ * lengths; any offset, not only 16-byte aligned ones; every length >= 1 and every segment inside [0, x_len) -- a segment that is not
+ * counts nothing), limits fp64 [num_limits] ascending (device; its last entry should be >= FLT_MAX: a value beyond it is counted in the
+ * last bucket) ->
+ *   counts    int64 [num_segments, num_limits]: finite elements by bucket = index of the first limit strictly greater than (double)v
+ *             (std::upper_bound; -0.0 as 0.0), exact at every limit for any ascending table
+ *   stats     fp64 [num_segments, 5]: min, max, num, sum, sum_squares of the finite elements (DBL_MAX, -DBL_MAX, 0, 0, 0 without any);
+ *             sums of (double)v and (double)v * (double)v over per-workgroup partials in a fixed order: bit-identical from run to run
+ *   nonfinite int64 [num_segments]: NaN and +-Inf elements, which enter nothing else
+ * max_seg_len (host): the longest segment, 1 <= max_seg_len <= x_len < 2^40 -- it sizes the grid and the workspace only (a longer segment
+ * is still counted in full).  workspace: 16-byte aligned, lpm_histogram_segments_workspace_bytes(num_segments, max_seg_len) bytes.
+ * num_segments <= 65535, num_limits <= 2048.  Integer atomics for the counts, none for the sums.
+ *
+ * Quantised frames: q uint8 [B, max_frames, F] (device, 4-byte aligned, F % 4 == 0), num_frames int32 [B] -> counts int64 [257]:
+ * entries 0..255 the byte values over frames t < num_frames[b], entry 256 the number of elements of the frames at and beyond it. */
+size_t lpm_histogram_segments_workspace_bytes(int num_segments, int64_t max_seg_len);
+int lpm_histogram_segments(const float* x, int64_t x_len, const int64_t* seg_start, const int64_t* seg_len, int num_segments,
+                           int64_t max_seg_len, const double* limits, int num_limits, int64_t* counts, double* stats, int64_t* nonfinite,
+                           void* workspace, size_t workspace_bytes, lpm_stream_t stream);
+int lpm_histogram_frames_q8(const void* q, const int32_t* num_frames, int B, int max_frames, int F, int64_t* counts, lpm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

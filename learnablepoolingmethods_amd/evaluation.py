@@ -188,12 +188,13 @@ class DeviceEvaluationMetrics:
         return {"avg_hit_at_one": out[0], "avg_perr": out[1], "avg_loss": out[2], "aps": out[4:], "gap": out[3], "num_examples": N}
 
 
-def evaluate(model, batches, top_k: int = 20, metrics=None) -> Dict[str, object]:
+def evaluate(model, batches, top_k: int = 20, metrics=None, summary_writer=None, global_step=None) -> Dict[str, object]:
     """eval.py's evaluation_loop for anything with ``.predict(frames, num_frames)`` and ``.vocab_size`` (a Predictor or a Trainer) over
     (ids, frames, labels, num_frames) batches (readers.YT8MFrameFeatureReader.batches; uint8 frames go into predict as they are).
     Predictions on a GPU go into DeviceEvaluationMetrics, CPU predictions into eval_util.EvaluationMetrics with cross_entropy_rows as
     the loss.  ``metrics`` (cleared first) replaces the default.  -> get()'s dict plus map (the mean of aps), num_examples and
-    examples_per_second."""
+    examples_per_second.  With ``summary_writer`` (summaries.SummaryWriter) AND ``global_step`` the epoch's Epoch/Eval_Avg_Hit@1,
+    Epoch/Eval_Avg_Perr, Epoch/Eval_Avg_Loss, Epoch/Eval_MAP and Epoch/Eval_GAP are written at that step (utils.py:123-137)."""
     t0 = time.perf_counter()
     if metrics is not None:
         metrics.clear()
@@ -215,6 +216,10 @@ def evaluate(model, batches, top_k: int = 20, metrics=None) -> Dict[str, object]
     info["map"] = float(np.mean(info["aps"]))
     info["num_examples"] = metrics.num_examples
     info["examples_per_second"] = metrics.num_examples / seconds if seconds > 0 else float("inf")
+    if summary_writer is not None and global_step is not None:
+        summary_writer.add_scalars({"Epoch/Eval_Avg_Hit@1": info["avg_hit_at_one"], "Epoch/Eval_Avg_Perr": info["avg_perr"],
+                                    "Epoch/Eval_Avg_Loss": info["avg_loss"], "Epoch/Eval_MAP": info["map"],
+                                    "Epoch/Eval_GAP": info["gap"]}, int(global_step))
     return info
 
 

@@ -468,6 +468,100 @@ def eval_rows(p, labels, k, with_loss=True, out: Optional[EvalRows] = None) -> E
     return out
 
 
+HISTOGRAM_MAX_LIMITS = 2048        # lpm_histogram_segments' limits
+HISTOGRAM_MAX_SEGMENTS = 65535
+_DEFAULT_LIMITS = {}               # device -> summaries.default_bucket_limits() as an fp64 tensor there
+
+
+class Histogram(NamedTuple):
+    """ops.histogram_segments' outputs, one row per segment (device tensors)."""
+    counts: torch.Tensor        # int64 [n, L]: finite elements by bucket (the first limit strictly greater than the value)
+    stats: torch.Tensor         # fp64 [n, 5]: min, max, num, sum, sum_squares of the finite elements
+    nonfinite: torch.Tensor     # int64 [n]: NaN and +-Inf elements (counted nowhere else)
+
+
+def _host_int64(v, what):
+    if isinstance(v, torch.Tensor):
+        v = v.detach().cpu()       # (a device tensor is read back here: pass host values to stay asynchronous)
+    t = torch.as_tensor(v)
+    if t.dim() != 1 or t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise LpmError(f"histogram_segments: {what} must be a one-dimensional integer sequence")
+    return t.to(torch.int64)
+
+
+def histogram_segments(x, seg_start=None, seg_len=None, limits=None) -> Histogram:
+    """TensorFlow's histogram (tensorflow::histogram::Histogram::Add) of segments of an fp32 GPU tensor in one pass over it
+    (lpm_histogram_segments): segment i is the ``seg_len[i]`` elements of ``x.reshape(-1)`` from element ``seg_start[i]`` on (host
+    sequences; any offsets, gaps between segments are not read into any count); without segments the whole tensor is one.  ``limits``:
+    ascending fp64 bucket limits (a host sequence, at most 2048, the last at least FLT_MAX), default summaries.default_bucket_limits().
+    Non-finite elements are counted in ``nonfinite`` only.  Arguments are checked before any launch."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+        raise LpmError("histogram_segments: expected a float32 tensor")
+    if not x.is_cuda:
+        raise LpmError("histogram_segments: needs a tensor on an MI355X (cuda/hip device); got a CPU tensor.  summaries.SummaryWriter."
+                       "add_histogram takes the numpy route for CPU tensors")
+    n_x = x.numel()
+    if (seg_start is None) != (seg_len is None):
+        raise LpmError("histogram_segments: seg_start and seg_len come together")
+    if seg_start is None:
+        start, length = torch.zeros(1, dtype=torch.int64), torch.full((1,), n_x, dtype=torch.int64)
+    else:
+        start, length = _host_int64(seg_start, "seg_start"), _host_int64(seg_len, "seg_len")
+    n = start.numel()
+    if length.numel() != n or not 1 <= n <= HISTOGRAM_MAX_SEGMENTS:
+        raise LpmError(f"histogram_segments: need 1 <= segments <= {HISTOGRAM_MAX_SEGMENTS} and as many lengths as starts "
+                       f"({n} starts, {length.numel()} lengths)")
+    if int(length.min()) < 1:
+        raise LpmError("histogram_segments: every segment needs at least one element")
+    if int(start.min()) < 0 or int((start + length).max()) > n_x:
+        raise LpmError(f"histogram_segments: a segment reaches outside the tensor's {n_x} elements")
+    if limits is None:
+        lim = _DEFAULT_LIMITS.get(x.device)
+        if lim is None:
+            from . import summaries
+            lim = _DEFAULT_LIMITS[x.device] = torch.tensor(summaries.default_bucket_limits(), dtype=torch.float64).to(x.device)
+    else:
+        host = torch.as_tensor(limits.detach().cpu() if isinstance(limits, torch.Tensor) else limits, dtype=torch.float64).reshape(-1)
+        if not 1 <= host.numel() <= HISTOGRAM_MAX_LIMITS:
+            raise LpmError(f"histogram_segments: need 1 <= limits <= {HISTOGRAM_MAX_LIMITS} (got {host.numel()})")
+        if bool(torch.isnan(host).any()) or bool((host[1:] < host[:-1]).any()):
+            raise LpmError("histogram_segments: the bucket limits must ascend")
+        if float(host[-1]) < float(torch.finfo(torch.float32).max):
+            raise LpmError("histogram_segments: the last bucket limit must be at least FLT_MAX, so that every finite value has a bucket")
+        lim = host.to(x.device)
+    lib = _capi.load()
+    x = x.contiguous().reshape(-1)
+    dev, L, longest = x.device, lim.numel(), int(length.max())
+    d_start, d_len = start.to(dev), length.to(dev)
+    out = Histogram(counts=torch.empty((n, L), dtype=torch.int64, device=dev), stats=torch.empty((n, 5), dtype=torch.float64, device=dev),
+                    nonfinite=torch.empty(n, dtype=torch.int64, device=dev))
+    ws_bytes = int(lib._lpm_histogram_segments_workspace_bytes(n, longest))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    lib.check(lib._lpm_histogram_segments(ptr(x), n_x, ptr(d_start), ptr(d_len), n, longest, ptr(lim), L, ptr(out.counts), ptr(out.stats),
+                                          ptr(out.nonfinite), ptr(ws), ws_bytes, stream_ptr()), "lpm_histogram_segments")
+    return out
+
+
+def histogram_frames_q8(q, num_frames) -> torch.Tensor:
+    """Byte-value counts of quantised frames q uint8 [B, max_frames, F] (F % 4 == 0) over the frames t < num_frames[b] -> int64 [257] on
+    the device: entries 0..255 the byte values, entry 256 the number of elements in the padded frames (lpm_histogram_frames_q8)."""
+    if not isinstance(q, torch.Tensor) or q.dtype != torch.uint8 or q.dim() != 3:
+        raise LpmError("histogram_frames_q8: expected uint8 frames [batch, max_frames, features]")
+    if not isinstance(num_frames, torch.Tensor) or num_frames.dim() != 1 or num_frames.numel() != q.shape[0] or num_frames.dtype.is_floating_point:
+        raise LpmError("histogram_frames_q8: expected integer num_frames [batch]")
+    if not (q.is_cuda and num_frames.is_cuda and q.device == num_frames.device):
+        raise LpmError("histogram_frames_q8: frames and num_frames must be on the same GPU device (no CPU fallback)")
+    B, MF, F = q.shape
+    if B < 1 or MF < 1 or F < 4 or F % 4:
+        raise LpmError(f"histogram_frames_q8: need a non-empty batch and a feature size that is a multiple of 4 (shape {tuple(q.shape)})")
+    lib = _capi.load()
+    q = q.contiguous()
+    nf = num_frames.to(torch.int32).contiguous()
+    counts = torch.empty(257, dtype=torch.int64, device=q.device)
+    lib.check(lib._lpm_histogram_frames_q8(ptr(q), ptr(nf), B, MF, F, ptr(counts), stream_ptr()), "lpm_histogram_frames_q8")
+    return counts
+
+
 GATHER_MAX_FEATURES = 8      # lpm_gather_frames' limit
 
 

@@ -1,7 +1,7 @@
 """The training run loop (reference: train.py:446-497, the loop of ``Trainer.run``; :546-575, ``get_meta_filename`` / resume; :160-184,
 the input pipeline; :44-112, the flags) around ``train.Trainer.step``:
 
-    files -> readers.YT8MFrameFeatureReader.training_batches (shuffled device batches) -> Trainer.step -> log line / checkpoint
+    files -> readers.YT8MFrameFeatureReader.training_batches (shuffled device batches) -> Trainer.step -> log line / checkpoint / summaries
 
 ``run`` steps until ``max_steps <= global_step`` or the batches end.  On steps with ``global_step % log_every == 0`` it computes
 Hit@1, PERR and GAP of the step's predictions against its labels (``evaluation.batch_metrics``: lpm_eval_rows + the pooled top-20
@@ -12,13 +12,25 @@ exit; on entry the newest ``model.ckpt-*.pt`` there is restored -- after ``Train
 ``start_new_model``, which removes the old ``model.ckpt-*.pt`` files instead (the reference deletes the whole directory).  The input
 stream restarts on resume, as the reference's does.
 
+With a ``summary_writer`` (summaries.SummaryWriter) every logged step also writes, at ``global_step``, the reference's scalars --
+``model/Training_Hit@1``, ``model/Training_Perr``, ``model/Training_GAP``, ``global_step/Examples/Second`` (train.py:470-480), ``label_loss``
+and ``learning_rate`` (train.py:250, 326) -- from the numbers the log line was formatted from: no further device read.  At the first logged
+step, and at every logged step at which ``histogram_steps`` steps have passed since the last histogram write (the checkpoint cadence's rule),
+it writes a histogram of every variable (``SummaryWriter.add_variables``: one HIP pass over the parameter arena) and of the raw input
+(``model/input_raw``); their results come to the host in one asynchronous copy.  ``summary_activations=True`` adds the activation
+histograms the models record with ``vs.summary`` (``store.summaries``): only the forward of a histogram step collects them, and because
+collecting makes the models take their materialising paths that step's arithmetic path changes -- the default set does not change one bit
+of the training result.
+
 Deviations from the reference, on purpose:
   * the steps between two logged ones log nothing and read nothing back from the device.  The reference prints "training step N | Loss
     ... Examples/sec ..." for every step, which takes the loss to the host -- a synchronisation per step that the GPU trainer's
     asynchronous step does not otherwise have;
   * Examples/sec is therefore measured over the interval since the previous logged step (the reference: one ``sess.run``);
   * the log line is emitted with or without ``train_dir`` (the reference's chief logs metrics only when it has one);
-  * checkpoints are ``torch.save`` files of ``Trainer.state_dict``; there is no SavedModel export and no TensorBoard summary.
+  * checkpoints are ``torch.save`` files of ``Trainer.state_dict``; there is no SavedModel export;
+  * summaries: ``reg_loss`` is not written -- on the GPU the L2 penalties enter as gradients and their value is never formed; the
+    histograms cover ALL variables, not only ``slim.get_model_variables()``; they follow a step cadence, not the Supervisor's 120 s.
 Multi-tower loops are out of scope: a trainer with ``num_towers > 1`` is refused.
 """
 from __future__ import annotations
@@ -64,18 +76,21 @@ def format_log_line(global_step, loss, examples_per_second, hit_at_one, perr, ga
 
 def run(trainer, batches: Iterable, max_steps: Optional[int] = None, log_every: int = 10, train_dir: Optional[str] = None,
         export_model_steps: int = 1000, start_new_model: bool = False, log: Callable[[str], None] = logging.info,
-        on_step: Optional[Callable] = None) -> Dict[str, object]:
+        on_step: Optional[Callable] = None, summary_writer=None, histogram_steps: int = 1000,
+        summary_activations: bool = False) -> Dict[str, object]:
     """Train ``trainer`` over ``batches`` of (ids, frames, labels, num_frames) -- see the module docstring.  ``on_step(step_result,
     batch)`` is called after every step with ``Trainer.step``'s dict and the batch.  -> {global_step, steps, num_examples, seconds,
     examples_per_second, last_loss, checkpoints}: the steps and examples of THIS call, the paths it wrote, the last step's loss (None
-    when no step ran)."""
+    when no step ran).  ``summary_writer`` / ``histogram_steps`` / ``summary_activations``: the module docstring; the writer is flushed on
+    exit and stays open (its owner closes it)."""
     if trainer.num_towers > 1:
         raise ValueError(f"training.run drives one tower; this trainer has num_towers = {trainer.num_towers} "
                          "(multi-tower run loops are out of scope)")
-    if int(log_every) < 1 or int(export_model_steps) < 1:
-        raise ValueError("training.run: log_every and export_model_steps must be at least 1")
+    if int(log_every) < 1 or int(export_model_steps) < 1 or int(histogram_steps) < 1:
+        raise ValueError("training.run: log_every, export_model_steps and histogram_steps must be at least 1")
     written: List[str] = []
     last_export = 0                       # train.py's last_model_export_step
+    last_histograms = 0                   # the same rule for the histogram writes
 
     def save(step):
         nonlocal last_export
@@ -107,7 +122,19 @@ def run(trainer, batches: Iterable, max_steps: Optional[int] = None, log_every: 
                 log(f"restored {resume}: global_step {trainer.global_step}")
         if max_steps is not None and max_steps <= trainer.global_step:
             break
-        last = trainer.step(frames, num_frames, labels)
+        # a histogram step is known before it runs: the logged step after which histogram_steps steps have passed
+        upcoming = trainer.global_step + 1
+        histograms = (summary_writer is not None and upcoming % log_every == 0
+                      and (last_histograms == 0 or upcoming - last_histograms >= histogram_steps))
+        collect = histograms and summary_activations and getattr(trainer, "store", None) is not None
+        if collect:
+            trainer.store.summaries = {}
+        try:
+            last = trainer.step(frames, num_frames, labels)
+        finally:
+            activations = trainer.store.summaries if collect else None
+            if collect:
+                trainer.store.summaries = None
         step = trainer.global_step
         n = int(labels.shape[0])
         steps, examples, interval_examples = steps + 1, examples + n, interval_examples + n
@@ -116,8 +143,22 @@ def run(trainer, batches: Iterable, max_steps: Optional[int] = None, log_every: 
             m = evaluation.batch_metrics(p, labels.to(p.device))
             loss, hit, perr, gap = torch.cat([last["loss"].detach().to(torch.float64).reshape(1), m.to(p.device)]).tolist()   # the one host copy
             now = time.perf_counter()
-            log(format_log_line(step, loss, interval_examples / max(now - interval_start, 1e-12), hit, perr, gap))
+            rate = interval_examples / max(now - interval_start, 1e-12)
+            log(format_log_line(step, loss, rate, hit, perr, gap))
             interval_start, interval_examples = now, 0
+            if summary_writer is not None:
+                scalars = {"model/Training_Hit@1": hit, "model/Training_Perr": perr, "model/Training_GAP": gap,
+                           "global_step/Examples/Second": rate, "label_loss": loss}                    # train.py:470-480, :326
+                if "learning_rate" in last:
+                    scalars["learning_rate"] = float(last["learning_rate"])                             # train.py:250
+                summary_writer.add_scalars(scalars, step)
+                if histograms and step == upcoming:
+                    summary_writer.add_variables(trainer, step)
+                    summary_writer.add_input(frames, num_frames, step)
+                    for name, t in (activations or {}).items():
+                        summary_writer.add_histogram(name, t, step)
+                    summary_writer.commit()          # one asynchronous copy; encoded when it has arrived
+                    last_histograms = step
             if train_dir and (last_export == 0 or step - last_export >= export_model_steps):
                 save(step)
         if on_step is not None:
@@ -127,6 +168,8 @@ def run(trainer, batches: Iterable, max_steps: Optional[int] = None, log_every: 
     if train_dir and trainer.arena is not None and steps and last_export != trainer.global_step:
         save(trainer.global_step)
     last_loss = float(last["loss"]) if last is not None else None        # (waits for the last step)
+    if summary_writer is not None:
+        summary_writer.flush()
     seconds = time.perf_counter() - t0
     return {"global_step": trainer.global_step, "steps": steps, "num_examples": examples, "seconds": seconds,
             "examples_per_second": examples / seconds if seconds > 0 else float("inf"), "last_loss": last_loss, "checkpoints": written}
@@ -148,6 +191,8 @@ def _parser() -> argparse.ArgumentParser:
     ap.add_argument("--num_epochs", type=int, default=5, help="train.py:93")
     ap.add_argument("--max_steps", type=int, default=None, help="train.py:95")
     ap.add_argument("--export_model_steps", type=int, default=1000, help="train.py:97")
+    ap.add_argument("--summary_dir", default="", help="write TensorBoard event files here (empty: none; may equal --train_dir)")
+    ap.add_argument("--histogram_steps", type=int, default=1000, help="steps between histogram summaries (with --summary_dir)")
     ap.add_argument("--start_new_model", type=_flag_value(False), nargs="?", const=True, default=False, help="train.py:68")
     ap.add_argument("--feature_names", default="rgb,audio", help="train.py:55 (frame-level default)")
     ap.add_argument("--feature_sizes", default="1024,128", help="train.py:57")
@@ -166,7 +211,7 @@ def _parser() -> argparse.ArgumentParser:
 
 def main(argv=None) -> Dict[str, object]:
     """train.py's ``main``: flags -> reader + Trainer + ``run``.  -> run's dict."""
-    from . import readers, registry
+    from . import readers, registry, summaries
     from .train import Trainer
     args = _parser().parse_args(argv)
     for name in FLAGS._defaults:
@@ -185,11 +230,15 @@ def main(argv=None) -> Dict[str, object]:
     trainer = Trainer(registry.get_model(args.model), vocab_size=args.num_classes, batch_size=FLAGS.batch_size, device=device, seed=args.seed)
     kw = dict(reader_threads=args.reader_threads) if device.type == "cuda" else {}
     batches = reader.training_batches(files, FLAGS.batch_size, device=device, num_epochs=args.num_epochs, seed=args.seed, **kw)
+    writer = summaries.SummaryWriter(args.summary_dir) if args.summary_dir else None
     try:
         return run(trainer, batches, max_steps=args.max_steps, log_every=args.log_every, train_dir=args.train_dir,
-                   export_model_steps=args.export_model_steps, start_new_model=args.start_new_model)
+                   export_model_steps=args.export_model_steps, start_new_model=args.start_new_model, summary_writer=writer,
+                   histogram_steps=args.histogram_steps)
     finally:
         batches.close()
+        if writer is not None:
+            writer.close()
 
 
 if __name__ == "__main__":
