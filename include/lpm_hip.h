@@ -992,6 +992,28 @@ int lpm_histogram_segments(const float* x, int64_t x_len, const int64_t* seg_sta
                            void* workspace, size_t workspace_bytes, lpm_stream_t stream);
 int lpm_histogram_frames_q8(const void* q, const int32_t* num_frames, int B, int max_frames, int F, int64_t* counts, lpm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Triangulation-embedding pooling (video_pooling_modules.py:1395-1497 WeightedTriangulationEmbedding + TriangulationTemporalEmbedding
+ * followed by aggregation_modules.py's MaxMeanPoolingModule on both, frame_level_models.py:1201-1215), fused: nothing of size T * K * D
+ * is written in either direction.
+ *   x [B * T, D] (a clip's T rows contiguous, 16-byte aligned), anchors [D, K] (as the variable is stored), per (b, t, k):
+ *     r = x[b,t,:] - anchors[:,k];  e = scale * r * rsqrt(max(sum r^2, 1e-12));
+ *     t >= 1:  u = e[t] - e[t-1];  f = u * rsqrt(max(sum u^2, 1e-12))                 (both tf.nn.l2_normalize)
+ *   -> max_d, mean_d = max / mean over t = 0..T-1 of e;  max_t, mean_t = max / mean over t = 1..T-1 of f: four fp32 [B, K * D] tensors,
+ *   k-major (element k * D + d), and argmax int32 [B, K * D]: the frame of max_d in the low and of max_t in the high 16 bits -- the FIRST
+ *   frame that attains the maximum.  scale = 1 is TriangulationEmbedding's block (its anchors normalised by the caller), scale =
+ *   1 / sqrt(K) WeightedTriangulationEmbedding's second l2_normalize over all K * D (every anchor block has unit norm).
+ * Backward: the four upstream gradients [B, K * D] + x, anchors, argmax -> dx [B * T, D], danchors [D, K] (both overwritten); e, u and f are
+ * recomputed.  No floating-point atomics: every sum (over k into dx, over clips and frames into danchors) has a fixed order, the same
+ * inputs give the same bits.  workspace: 16-byte aligned, lpm_triangulation_pool_workspace_bytes(B, T, D, K) bytes (the backward only).
+ * D in {128, 1024}, 2 <= T <= 32767, K >= 1; anything else LPM_ERR_UNSUPPORTED_SHAPE / LPM_ERR_BADARG before any launch. */
+size_t lpm_triangulation_pool_workspace_bytes(int B, int T, int D, int K);
+int lpm_triangulation_pool_fwd(const float* x, const float* anchors, int B, int T, int D, int K, float scale, float* max_d, float* mean_d,
+                               float* max_t, float* mean_t, int32_t* argmax, lpm_stream_t stream);
+int lpm_triangulation_pool_bwd(const float* x, const float* anchors, const int32_t* argmax, const float* g_max_d, const float* g_mean_d,
+                               const float* g_max_t, const float* g_mean_t, int B, int T, int D, int K, float scale, float* dx,
+                               float* danchors, void* workspace, size_t workspace_bytes, lpm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,14 @@ FLAGS.define("dense_arithmetic", "fp16x2", "build extension, the encoders' dense
              "run stay on split-bf16) -- forward products keep three terms (~1e-6), input gradients two (the weight rounded once to fp16: "
              "1.4e-4 per GEMM), weight gradients one (both operands rounded once: 2e-4, not carried further down the backward) -- against "
              "split-bf16's three terms everywhere; 'bf16x3' = split-bf16 throughout (rounds 1-4)")
+FLAGS.define("wtm_video_anchor_size", 64, "RegularizedTriangulationModel (frame_level_models.py:1160): anchors of the video stream")
+FLAGS.define("wtm_audio_anchor_size", 64, "RegularizedTriangulationModel (frame_level_models.py:1161): anchors of the audio stream")
+FLAGS.define("triangulation_fused", True, "build extension: on the GPU each stream of RegularizedTriangulationModel is ONE ops.triangulation_pool "
+             "call (csrc/triangulation_pool.hip: the four pooled vectors without any [B, T, K*D] tensor); False: the materialising modules of "
+             "video_pooling_modules / aggregation_modules compose it (the CPU path; same variables, same results)")
+FLAGS.define("wtm_projection_l1", 1e-5, "layers.l1_l2_regularizer(1e-5) on dis_projection_2 / temp_projection_2 (frame_level_models.py:1272,1287): "
+             "tf.contrib's first positional argument is scale_l1")
+FLAGS.define("wtm_projection_l2", 1.0, "... and its scale_l2 keeps the default 1.0: the penalty is l1 * sum |w| + l2 * sum(w^2) / 2 (SURVEY App. B)")
 # video_level_models.py
 FLAGS.define("moe_num_mixtures", 2, "video_level_models.py:27")
 FLAGS.define("moe_l2", 1e-8, ":35")

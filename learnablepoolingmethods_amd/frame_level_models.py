@@ -1,5 +1,6 @@
 """NetVLAD prototypes behind the reference's model-registry API
-(reference: frame_level_models.py:2193-2513 NetVladV1 / NetVladV2, :2765-2877 NetVLAD / LightVLAD).
+(reference: frame_level_models.py:2193-2513 NetVladV1 / NetVladV2, :2765-2877 NetVLAD / LightVLAD) and the triangulation-embedding
+family's RegularizedTriangulationModel (:1148-1307).
 
 Same names, ``create_model`` signature, variable names and output contract as the reference; the hot
 ops (frame sampling + input_bn, soft-assignment GEMM, fused softmax/residual aggregation/normalise,
@@ -13,7 +14,7 @@ import math
 
 import torch
 
-from . import FLAGS, layers, model_utils, models, ops, transformer_utils, video_level_models, video_pooling_modules
+from . import FLAGS, aggregation_modules, layers, model_utils, models, ops, transformer_utils, video_level_models, video_pooling_modules
 from . import variables as vs
 
 
@@ -320,6 +321,81 @@ class WillowModelReg(models.BaseModel):
                 vlad = torch.cat([vlad, audio_NetVLAD.forward(reshaped_input[:, 1024:])], 1)
         return _project_gate_classify(vlad, vocab_size, cluster_size, hidden1_size, add_batch_norm, relu, gating,
                                       remove_diag, is_training, **unused_params)
+
+
+class RegularizedTriangulationModel(models.BaseModel):
+    """Weighted triangulation embedding of both streams, its temporal differences, max-mean pooling of both, five projections with
+    batch norms and the three-layer classifier (frame_level_models.py:1148-1307).  Defect resolutions: SURVEY App. C17-C21.
+
+    On the GPU with FLAGS.triangulation_fused each stream is ONE ops.triangulation_pool call: the embedding [B, T, D*K] and the temporal
+    embedding (79 MB per clip each at the defaults T = 300, K = 64, D = 1024) are never written; otherwise the materialising modules of
+    video_pooling_modules / aggregation_modules compose the same graph.  The variables and the results are the same either way.
+    ``frame_uniform`` [B, iterations] replaces the random draw of SampleRandomFrames, ``dropout_masks`` {"fc1", "fc2"} the classifier's."""
+
+    def create_model(self, model_input, vocab_size, num_frames, iterations=None, add_batch_norm=None, sample_random_frames=None,
+                     hidden_size=None, is_training=True, frame_uniform=None, video_anchor_size=None, audio_anchor_size=None,
+                     **unused_params):
+        iterations = iterations or FLAGS.iterations
+        video_anchor_size = int(video_anchor_size or FLAGS.wtm_video_anchor_size)                             # :1160
+        audio_anchor_size = int(audio_anchor_size or FLAGS.wtm_audio_anchor_size)                             # :1161
+        model_input = model_utils.SampleRandomFrames(model_input, num_frames.reshape(-1, 1), iterations, uniform=frame_uniform)  # :1163-1165
+        max_frames, feature_size = model_input.shape[1], model_input.shape[2]
+        if feature_size <= 1024:
+            raise ValueError("RegularizedTriangulationModel slices a 1024-wide video and a 128-wide audio stream out of its input "
+                             f"(frame_level_models.py:1202,1210); got {feature_size} features")
+        dev = model_input.device
+        reshaped_input = model_input.reshape(-1, feature_size)
+        # add_batch_norm is accepted and unused, as written: the modules store it and never read it (:1176-1192)
+        streams = (("video_t_emb", 1024, video_anchor_size, slice(0, 1024)), ("audio_t_emb", feature_size - 1024, audio_anchor_size, slice(1024, None)))
+        d_modules = [video_pooling_modules.WeightedTriangulationEmbedding(D, max_frames, K, add_batch_norm, is_training) for _, D, K, _ in streams]
+        mean_max_pool = aggregation_modules.MaxMeanPoolingModule(l2_normalize=False)                          # :1183
+        t_modules = [video_pooling_modules.TriangulationTemporalEmbedding(D, max_frames, K, add_batch_norm, is_training) for _, D, K, _ in streams]
+        reshaped_input = layers.batch_norm(reshaped_input, is_training, "input_bn")                           # :1194-1199
+        fused = bool(FLAGS.triangulation_fused and reshaped_input.is_cuda and max_frames >= 2)
+        agg_d, agg_t, orthogonal_reg = [], [], 0.0
+        for (scope, D, K, cols), d_module, t_module in zip(streams, d_modules, t_modules):
+            with vs.variable_scope(scope):                                                                    # :1201-1215
+                x = reshaped_input[:, cols]
+                if fused:
+                    anchors, ortho = d_module.variables(dev)
+                    max_d, mean_d, max_t, mean_t = ops.triangulation_pool(x.contiguous(), anchors, max_frames, scale=1 / math.sqrt(K))
+                    agg_d.append(torch.cat([max_d, mean_d], 1))
+                    agg_t.append(torch.cat([max_t, mean_t], 1))
+                else:
+                    emb_d, ortho = d_module.forward(x)
+                    emb_t = t_module.forward(emb_d)
+                    agg_d.append(mean_max_pool.forward(emb_d))
+                    agg_t.append(mean_max_pool.forward(emb_t))
+            orthogonal_reg = orthogonal_reg + ortho                                                           # :1217
+        (agg_video_d, agg_audio_d), (agg_video_t, agg_audio_t) = agg_d, agg_t
+
+        def project(x, name, units, regularised=False):
+            w = vs.get_variable(name, [x.shape[1], units], vs.random_normal_initializer(1 / math.sqrt(units)), device=dev)
+            if regularised:                                          # layers.l1_l2_regularizer(1e-5) = (scale_l1 = 1e-5, scale_l2 = 1.0): App. B
+                store = vs.default_store()
+                if FLAGS.wtm_projection_l1:
+                    store.add_regularization_loss(FLAGS.wtm_projection_l1 * w.abs().sum())
+                if FLAGS.wtm_projection_l2:
+                    store.add_l2_regularizer(w, FLAGS.wtm_projection_l2)
+            return x.matmul(w)
+
+        video_projection_activation = layers.batch_norm(project(agg_video_d, "video_projection", 1024), is_training,
+                                                        "video_projection_bn")                               # :1219-1231
+        # :1239 multiplies the integer agg_audio_d_dim; the intent is agg_audio_d (App. C17)
+        audio_projection_activation = layers.batch_norm(project(agg_audio_d, "audio_projection", 128), is_training,
+                                                        "audio_projection_bn")                               # :1233-1245
+        dis_projection_activation = torch.cat([video_projection_activation, audio_projection_activation], 1)  # :1247
+        agg_temp = torch.cat([agg_video_t, agg_audio_t], 1)                                                   # :1251
+        temp_projection_activation = layers.batch_norm(project(agg_temp, "temp_projection_1", 1152), is_training,
+                                                       "temp_projection_bn")                                 # :1253-1263
+        dis_activation = layers.batch_norm(project(dis_projection_activation, "dis_projection_2", 2048, regularised=True), is_training,
+                                           "dis_activation_bn")                                              # :1266-1279
+        temp_activation = layers.batch_norm(project(temp_projection_activation, "temp_projection_2", 2048, regularised=True), is_training,
+                                            "temp_activation_bn")                                            # :1282-1294
+        activation = torch.cat([dis_activation, temp_activation], 1)                                          # :1297
+        aggregated_model = getattr(video_level_models, "ClassLearningThreeNnModel")
+        return aggregated_model().create_model(model_input=activation, vocab_size=vocab_size, is_training=is_training,
+                                               ortho_reg=orthogonal_reg, **unused_params)                    # :1299-1307
 
 
 class NetVladV2(models.BaseModel):

@@ -3897,3 +3897,68 @@ def clip_adam_step(param, grad, m, v, offsets, ntensors, clip_norm, lr, step, be
                                                       float(clip_norm), float(lr), beta1, beta2, eps, int(step), ptr(scratch),
                                                       stream_ptr()), "lpm_multi_tensor_clip_adam")
     return scratch
+
+
+# ----------------------------------------------------------------------------------------------
+# triangulation-embedding pooling (csrc/triangulation_pool.hip)
+# ----------------------------------------------------------------------------------------------
+TRIANGULATION_FEATURES = (128, 1024)      # the two feature sizes the reference hard-codes (frame_level_models.py:1173-1193)
+
+
+class _TriangulationPool(torch.autograd.Function):
+    """lpm_triangulation_pool_fwd / _bwd: the saved state is the inputs and one int32 [B, K*D] arg-max tensor; e, u and f are
+    recomputed in the backward, whose workspace lives for that call only."""
+
+    @staticmethod
+    def forward(ctx, x, anchors, T, scale):
+        lib = _capi.load()
+        D, K = anchors.shape
+        B = x.shape[0] // T
+        outs = [_empty((B, K * D), x) for _ in range(4)]
+        argmax = torch.empty((B, K * D), dtype=torch.int32, device=x.device)
+        with _timed("triangulation_pool_fwd", (B, T, D, K)):
+            lib.check(lib._lpm_triangulation_pool_fwd(ptr(x), ptr(anchors), B, T, D, K, float(scale), *(ptr(o) for o in outs), ptr(argmax),
+                                                      stream_ptr()), "lpm_triangulation_pool_fwd")
+        ctx.save_for_backward(x, anchors, argmax)
+        ctx.dims = (B, T, D, K, float(scale))
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, g_max_d, g_mean_d, g_max_t, g_mean_t):
+        lib = _capi.load()
+        x, anchors, argmax = ctx.saved_tensors
+        B, T, D, K, scale = ctx.dims
+        grads = [g.contiguous() for g in (g_max_d, g_mean_d, g_max_t, g_mean_t)]
+        dx, danchors = torch.empty_like(x), torch.empty_like(anchors)
+        wsb = int(lib._lpm_triangulation_pool_workspace_bytes(B, T, D, K))
+        ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+        with _timed("triangulation_pool_bwd", (B, T, D, K)):
+            lib.check(lib._lpm_triangulation_pool_bwd(ptr(x), ptr(anchors), ptr(argmax), *(ptr(g) for g in grads), B, T, D, K, scale, ptr(dx),
+                                                      ptr(danchors), ptr(ws), wsb, stream_ptr()), "lpm_triangulation_pool_bwd")
+        return dx, danchors, None, None
+
+
+def triangulation_pool(x, anchors, max_frames, scale=1.0):
+    """The pooled triangulation embedding of a stream in one kernel each way (lpm_triangulation_pool_fwd / _bwd):
+    x [B * max_frames, D] (a clip's rows contiguous), anchors [D, K] -> (max_d, mean_d, max_t, mean_t), each [B, K * D] k-major
+    (element k * D + d): the maximum and the mean over the frames of  e = scale * l2_normalize(x - anchor_k)  and, over frames
+    1 .. max_frames - 1, of  f = l2_normalize(e[t] - e[t-1])  -- WeightedTriangulationEmbedding (scale = 1 / sqrt(K)) or
+    TriangulationEmbedding (scale = 1, anchors normalised by the caller) + TriangulationTemporalEmbedding + MaxMeanPoolingModule
+    without any [B, T, K * D] tensor.  GPU only; D in TRIANGULATION_FEATURES, max_frames >= 2, contiguous fp32 input."""
+    what = "triangulation_pool"
+    if not (torch.is_tensor(x) and torch.is_tensor(anchors)) or x.dim() != 2 or anchors.dim() != 2:
+        raise LpmError(f"{what}: expected x [B * max_frames, D] and anchors [D, K]")
+    _f32(x, what + " x"), _f32(anchors, what + " anchors")
+    if not (x.is_cuda and anchors.is_cuda and x.device == anchors.device):
+        raise LpmError(f"{what}: needs tensors on one MI355X (cuda/hip device); got {x.device} / {anchors.device}.  There is no CPU "
+                       "fallback: video_pooling_modules' TriangulationEmbedding classes are the host path")
+    if not x.is_contiguous():
+        raise LpmError(f"{what}: x must be contiguous (a column slice of a wider matrix is not: copy the stream's block first)")
+    T = int(max_frames)
+    D, K = anchors.shape
+    if D not in TRIANGULATION_FEATURES or x.shape[1] != D or K < 1:
+        raise LpmError(f"{what}: need a feature size in {TRIANGULATION_FEATURES} shared by x and anchors (x {tuple(x.shape)}, anchors {tuple(anchors.shape)})")
+    if T < 2 or x.shape[0] == 0 or x.shape[0] % T:
+        raise LpmError(f"{what}: need max_frames >= 2 dividing the {x.shape[0]} rows of x (max_frames = {T}): the temporal embedding is a "
+                       "frame-to-frame difference")
+    return _TriangulationPool.apply(x, anchors.contiguous(), T, float(scale))

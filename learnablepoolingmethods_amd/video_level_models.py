@@ -1,4 +1,4 @@
-"""MoeModel (reference: video_level_models.py:48-158) -- host-side PyTorch per the north-star."""
+"""MoeModel (reference: video_level_models.py:48-158) and ClassLearningThreeNnModel (:687-714) -- host-side PyTorch per the north-star."""
 from __future__ import annotations
 
 import math
@@ -76,3 +76,44 @@ class MoeModel(models.BaseModel):
             gates = layers.batch_norm(gates, is_training, "gating_prob_bn")                                # :149-154
             probabilities = probabilities * torch.sigmoid(gates)                                           # :156-158
         return {"predictions": probabilities}                                                             # :158
+
+
+class ClassLearningThreeNnModel(models.BaseModel):
+    """Three fully connected layers of width vocab_size (video_level_models.py:687-714): bias-free + layer_norm + leaky_relu(0.2)
+    (+ dropout, keep probability 0.5, in training) twice, then sigmoid with a bias initialised to 0.1.  Variable names are slim's:
+    fully_connected[_1|_2]/weights, fully_connected_2/biases, LayerNorm[_1]/{beta,gamma}.  ``dropout_masks`` {"fc1", "fc2"}: KEEP
+    masks [B, vocab_size] (non-zero = kept) in place of the random draw (App. C10: the default is faithful, parity tests hand masks in)."""
+
+    KEEP_PROB = 0.5
+
+    def create_model(self, model_input, vocab_size, is_training=True, l2_penalty=1e-8, ortho_reg=0, dropout_masks=None,
+                     **unused_params):
+        from . import layers
+        dev = model_input.device
+        store = vs.default_store()
+        masks = dropout_masks or {}
+
+        def fully_connected(x, scope, biases):
+            with vs.variable_scope(scope):
+                w = vs.get_variable("weights", [x.shape[1], vocab_size], vs.glorot_uniform_initializer(), device=dev)
+                b = vs.get_variable("biases", [vocab_size], lambda shape, d, gen: torch.full(shape, 0.1, device=d), device=dev) if biases else None
+            store.add_l2_regularizer(w, l2_penalty)                                   # slim.l2_regularizer :697,704,711
+            y = x.matmul(w)
+            return y + b if biases else y
+
+        def dropout(x, key):
+            if not is_training:
+                return x
+            keep = masks.get(key)
+            if keep is None:
+                keep = torch.rand(x.shape, device=dev) < self.KEEP_PROB
+            return x * keep.to(device=dev).ne(0).to(x.dtype) / self.KEEP_PROB          # tf.nn.dropout(keep_prob=0.5) :700,707
+
+        fc1 = fully_connected(model_input, "fully_connected", False)                   # :695-697
+        fc1 = torch.nn.functional.leaky_relu(layers.layer_norm(fc1, "LayerNorm"), 0.2)  # :698
+        fc1 = dropout(fc1, "fc1")
+        fc2 = fully_connected(fc1, "fully_connected_1", False)                          # :702-704
+        fc2 = torch.nn.functional.leaky_relu(layers.layer_norm(fc2, "LayerNorm_1"), 0.2)  # :705
+        fc2 = dropout(fc2, "fc2")
+        fc3 = torch.sigmoid(fully_connected(fc2, "fully_connected_2", True))            # :709-711
+        return {"predictions": fc3, "regularization_loss": ortho_reg}

@@ -1,4 +1,5 @@
-"""NetVladOrthoReg and NetVladAttenCluster (reference: video_pooling_modules.py:1499-1586, 1589-1663)."""
+"""NetVladOrthoReg and NetVladAttenCluster (reference: video_pooling_modules.py:1499-1586, 1589-1663) and the triangulation
+embeddings (TriangulationEmbedding :376-428, WeightedTriangulationEmbedding :1395-1459, TriangulationTemporalEmbedding :1462-1497)."""
 from __future__ import annotations
 
 import math
@@ -73,3 +74,87 @@ class NetVladAttenCluster(modules.BaseModule):
                                           device=inputs.device)                                # :1641-1643
         # sum_n sims * (x - c), intra-L2, flatten, L2 (:1646-1658; App. C6/C7) -- HIP kernel K2
         return ops.vlad_aggregate(cluster_similarities, inputs, cluster_centres, self.max_frames, lazy=lazy, grad_join=join)
+
+
+def _anchor_weights(feature_size, anchor_size, scope_id, device):
+    """``anchor_weights{scope_id}`` [D, K], N(0, 1 / K) (:401-405, :1423-1426)."""
+    sid = "" if scope_id is None else str(scope_id)
+    return vs.get_variable("anchor_weights" + sid, [feature_size, anchor_size],
+                           vs.random_normal_initializer(1 / math.sqrt(anchor_size)), device=device)
+
+
+def _anchor_residuals(inputs, anchor_weights):
+    """tile / subtract / reshape / l2_normalize(2) of :414-424 without the tile: [M, D], [D, K] -> [M, K, D], every (row, anchor)
+    block l2-normalised.  Anchor k is the k-th block of the flattened row (element k * D + d), the reference's transpose + reshape."""
+    return layers.l2_normalize(inputs.unsqueeze(1) - anchor_weights.t().unsqueeze(0), 2)
+
+
+class TriangulationEmbedding(modules.BaseModule):
+    """Triangulation embedding of every frame (:376-428): the unit vectors from each L2-normalised anchor column to the frame.
+    This forward MATERIALISES [(B*T), D*K] -- the drop-in surface and the small-shape path; ops.triangulation_pool(scale=1) pools the
+    same embedding (and its temporal differences) without it."""
+
+    def __init__(self, feature_size, max_frames, anchor_size, batch_norm, is_training, scope_id=None):
+        self.feature_size = feature_size
+        self.max_frames = max_frames
+        self.batch_norm = batch_norm
+        self.anchor_size = int(anchor_size)
+        self.is_training = is_training
+        self.scope_id = scope_id
+
+    def forward(self, inputs, **unused_params):
+        """inputs [(B*max_frames), D] -> [(B*max_frames), D*K]."""
+        anchor_weights = _anchor_weights(self.feature_size, self.anchor_size, self.scope_id, inputs.device)
+        vs.summary("anchor_weights" + ("" if self.scope_id is None else str(self.scope_id)), anchor_weights)
+        anchor_weights = layers.l2_normalize(anchor_weights, 0)                                    # :410
+        t_emb = _anchor_residuals(inputs, anchor_weights)                                          # :413-424
+        return t_emb.reshape(-1, self.feature_size * self.anchor_size)
+
+
+class WeightedTriangulationEmbedding(modules.BaseModule):
+    """:1395-1459: the anchors enter as they are, and the whole row of K blocks is l2-normalised once more -- every block has unit
+    norm, so that is a division by sqrt(K) (ops.triangulation_pool(scale=1/sqrt(K)); SURVEY App. C19 for the one case where it is
+    not).  Returns ([B, T, D*K], det_reg); det_reg is identically 0 as written (``identity = tf.identity(det_reg)``, App. C18)."""
+
+    def __init__(self, feature_size, max_frames, anchor_size, batch_norm, is_training, scope_id=None):
+        self.feature_size = feature_size
+        self.max_frames = max_frames
+        self.batch_norm = batch_norm
+        self.anchor_size = int(anchor_size)
+        self.is_training = is_training
+        self.det_reg = True
+        self.det_reg_lambda = 1e-5
+        self.scope_id = scope_id
+
+    def variables(self, device):
+        """(anchor_weights, det_reg) without a forward: what the fused path needs."""
+        anchor_weights = _anchor_weights(self.feature_size, self.anchor_size, self.scope_id, device)
+        vs.summary("anchor_weights" + ("" if self.scope_id is None else str(self.scope_id)), anchor_weights)
+        det_reg = anchor_weights.new_zeros(()) if self.det_reg else None                           # :1431-1439: |A - identity(A)| = 0
+        return anchor_weights, det_reg
+
+    def forward(self, inputs, **unused_params):
+        """inputs [(B*max_frames), D] -> ([B, max_frames, D*K], det_reg)."""
+        anchor_weights, det_reg = self.variables(inputs.device)
+        t_emb = _anchor_residuals(inputs, anchor_weights)                                          # :1442-1453
+        t_emb = layers.l2_normalize(t_emb.reshape(-1, self.feature_size * self.anchor_size), 1)    # :1454-1455
+        return t_emb.reshape(-1, self.max_frames, self.feature_size * self.anchor_size), det_reg
+
+
+class TriangulationTemporalEmbedding(modules.BaseModule):
+    """:1462-1497: the l2-normalised (per anchor block) difference of consecutive frames' embeddings.  The reference rolls the frame
+    axis by one and deletes frame 0 afterwards: exactly the differences t = 1 .. T-1."""
+
+    def __init__(self, feature_size, max_frames, anchor_size, batch_norm, is_training, scope_id=None):
+        self.feature_size = feature_size
+        self.max_frames = max_frames
+        self.batch_norm = batch_norm
+        self.anchor_size = int(anchor_size)
+        self.is_training = is_training
+        self.scope_id = scope_id
+
+    def forward(self, inputs, **unused_params):
+        """inputs [B, max_frames, D*K] (or [(B*max_frames), D*K]) -> [B, max_frames - 1, D*K]."""
+        x = inputs.reshape(-1, self.max_frames, self.anchor_size, self.feature_size)
+        temp_info = layers.l2_normalize(x[:, 1:] - x[:, :-1], 3)                                   # :1485-1490, frame 0 dropped (:1494-1496)
+        return temp_info.reshape(-1, self.max_frames - 1, self.feature_size * self.anchor_size)
