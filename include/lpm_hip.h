@@ -1014,6 +1014,35 @@ int lpm_triangulation_pool_bwd(const float* x, const float* anchors, const int32
                                const float* g_max_t, const float* g_mean_t, int B, int T, int D, int K, float scale, float* dx,
                                float* danchors, void* workspace, size_t workspace_bytes, lpm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Soft-attention pooling of the triangulation embedding (aggregation_modules.py:74-108 IndirectClusterMaxMeanPoolModule over
+ * TriangulationEmbedding + TriangulationTemporalEmbedding, frame_level_models.py:1031-1051), csrc/triangulation_attention.hip.
+ * x, anchors, scale, e and f as for lpm_triangulation_pool_*.  With v = e (T' = T frames) or v = f (T' = T - 1 differences):
+ *     G[t,s] = <v_t, v_s> over all K * D;  l[t] = sum_s relu(G[t,s]);  w = softmax_t(l);  mean = (1/T') sum_t w[t] v_t;  max = max_t v_t
+ * Nothing of size T * K * D is written in either direction, no floating-point atomics (the same inputs give the same bits); the Gram
+ * and the backward's M V products are exact-fp32 MFMAs.  relu, row sums, softmax and their backward are [B, T, T] work of the caller:
+ *   _gram:     -> gram_d [B, T, T], gram_t [B, T-1, T-1] (both overwritten)
+ *   _pool_fwd: w_d [B, T], w_t [B, T-1] -> mean_d, max_d, mean_t, max_t fp32 [B, K * D] k-major, argmax as lpm_triangulation_pool_fwd's
+ *   _dw:       g_mean_d, g_mean_t [B, K * D] -> dw_d [B, T], dw_t [B, T-1]:  dw[b,t] = <g_mean[b], v_t> / T'
+ *   _bwd:      m_d [B, T, T], m_t [B, T-1, T-1]: M = dG + dG^T with dG[t,s] = dl[t] [G[t,s] > 0] (SYMMETRIC: read along rows), and the
+ *              four upstream gradients -> dx [B * T, D], danchors [D, K] (both overwritten)
+ * workspace: 16-byte aligned, lpm_triangulation_attention_workspace_bytes(which, ...) bytes with which = 0 (_gram; may be 0 bytes),
+ * 1 (_dw), 2 (_bwd).  D in {128, 1024}, 2 <= T <= lpm_triangulation_attention_max_frames() (320), K >= 1; anything else
+ * LPM_ERR_UNSUPPORTED_SHAPE / LPM_ERR_BADARG before any launch. */
+int lpm_triangulation_attention_max_frames(void);
+size_t lpm_triangulation_attention_workspace_bytes(int which, int B, int T, int D, int K);
+int lpm_triangulation_attention_gram(const float* x, const float* anchors, int B, int T, int D, int K, float scale, float* gram_d,
+                                     float* gram_t, void* workspace, size_t workspace_bytes, lpm_stream_t stream);
+int lpm_triangulation_attention_pool_fwd(const float* x, const float* anchors, const float* w_d, const float* w_t, int B, int T, int D, int K,
+                                         float scale, float* mean_d, float* max_d, float* mean_t, float* max_t, int32_t* argmax,
+                                         lpm_stream_t stream);
+int lpm_triangulation_attention_dw(const float* x, const float* anchors, const float* g_mean_d, const float* g_mean_t, int B, int T, int D,
+                                   int K, float scale, float* dw_d, float* dw_t, void* workspace, size_t workspace_bytes, lpm_stream_t stream);
+int lpm_triangulation_attention_bwd(const float* x, const float* anchors, const int32_t* argmax, const float* w_d, const float* w_t,
+                                    const float* m_d, const float* m_t, const float* g_mean_d, const float* g_max_d, const float* g_mean_t,
+                                    const float* g_max_t, int B, int T, int D, int K, float scale, float* dx, float* danchors,
+                                    void* workspace, size_t workspace_bytes, lpm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,6 +70,16 @@ FLAGS.define("wtm_audio_anchor_size", 64, "RegularizedTriangulationModel (frame_
 FLAGS.define("triangulation_fused", True, "build extension: on the GPU each stream of RegularizedTriangulationModel is ONE ops.triangulation_pool "
              "call (csrc/triangulation_pool.hip: the four pooled vectors without any [B, T, K*D] tensor); False: the materialising modules of "
              "video_pooling_modules / aggregation_modules compose it (the CPU path; same variables, same results)")
+FLAGS.define("sftm_iterations", 64, "SoftAttentionTriangulationModel (frame_level_models.py:945): sampled frames per clip")
+FLAGS.define("sftm_add_batch_norm", True, "SoftAttentionTriangulationModel (:947): batch norm on the streams and after every projection")
+FLAGS.define("sftm_video_anchor_size", 128, "SoftAttentionTriangulationModel (:951): anchors of the video stream")
+FLAGS.define("sftm_audio_anchor_size", 16, "SoftAttentionTriangulationModel (:953): anchors of the audio stream")
+FLAGS.define("sftm_video_bottleneck", 100, "SoftAttentionTriangulationModel (:955): width of the video stream's projections")
+FLAGS.define("sftm_audio_bottleneck", 16, "SoftAttentionTriangulationModel (:957): width of the audio stream's projections")
+FLAGS.define("soft_attention_fused", True, "build extension: on the GPU each stream of SoftAttentionTriangulationModel is ONE "
+             "ops.triangulation_attention_pool call (csrc/triangulation_attention.hip: the Grams, the softmax weights and the four pooled "
+             "vectors without any [B, T, K*D] tensor); False: the materialising modules of video_pooling_modules / aggregation_modules "
+             "compose it (the CPU path; same variables, same results)")
 FLAGS.define("wtm_projection_l1", 1e-5, "layers.l1_l2_regularizer(1e-5) on dis_projection_2 / temp_projection_2 (frame_level_models.py:1272,1287): "
              "tf.contrib's first positional argument is scale_l1")
 FLAGS.define("wtm_projection_l2", 1.0, "... and its scale_l2 keeps the default 1.0: the penalty is l1 * sum |w| + l2 * sum(w^2) / 2 (SURVEY App. B)")

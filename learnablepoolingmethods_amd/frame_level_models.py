@@ -1,6 +1,6 @@
 """NetVLAD prototypes behind the reference's model-registry API
 (reference: frame_level_models.py:2193-2513 NetVladV1 / NetVladV2, :2765-2877 NetVLAD / LightVLAD) and the triangulation-embedding
-family's RegularizedTriangulationModel (:1148-1307).
+family's RegularizedTriangulationModel (:1148-1307) and SoftAttentionTriangulationModel (:965-1145).
 
 Same names, ``create_model`` signature, variable names and output contract as the reference; the hot
 ops (frame sampling + input_bn, soft-assignment GEMM, fused softmax/residual aggregation/normalise,
@@ -396,6 +396,76 @@ class RegularizedTriangulationModel(models.BaseModel):
         aggregated_model = getattr(video_level_models, "ClassLearningThreeNnModel")
         return aggregated_model().create_model(model_input=activation, vocab_size=vocab_size, is_training=is_training,
                                                ortho_reg=orthogonal_reg, **unused_params)                    # :1299-1307
+
+
+class SoftAttentionTriangulationModel(models.BaseModel):
+    """Triangulation embedding of both streams, its temporal differences, soft-attention mean and max pooling of all four, six
+    projections with batch norms and the four-layer classifier (frame_level_models.py:965-1145).  As written: SURVEY App. C22-C25.
+
+    On the GPU with FLAGS.soft_attention_fused each stream is ONE ops.triangulation_attention_pool call: the embedding [B, T, D*K] and
+    the temporal embedding (33.5 MB per clip each at the defaults T = 64, K = 128, D = 1024) are never written; otherwise the
+    materialising modules of video_pooling_modules / aggregation_modules compose the same graph.  The variables and the results are
+    the same either way.  ``frame_uniform`` [B, iterations] replaces the random draw of SampleRandomFrames; ``video_anchor_size``,
+    ``audio_anchor_size``, ``video_bottleneck`` and ``audio_bottleneck`` override the flags (the reference reads the flags only)."""
+
+    def create_model(self, model_input, vocab_size, num_frames, iterations=None, add_batch_norm=None, sample_random_frames=None,
+                     hidden_size=None, is_training=True, frame_uniform=None, video_anchor_size=None, audio_anchor_size=None,
+                     video_bottleneck=None, audio_bottleneck=None, **unused_params):
+        iterations = iterations or FLAGS.sftm_iterations                                                      # :976
+        add_batch_norm = add_batch_norm or FLAGS.sftm_add_batch_norm                                          # :977 (False cannot switch it off: C23)
+        video_anchor_size = int(video_anchor_size or FLAGS.sftm_video_anchor_size)                            # :978-981
+        audio_anchor_size = int(audio_anchor_size or FLAGS.sftm_audio_anchor_size)
+        video_bottleneck = int(video_bottleneck or FLAGS.sftm_video_bottleneck)
+        audio_bottleneck = int(audio_bottleneck or FLAGS.sftm_audio_bottleneck)
+        # sample_random_frames and hidden_size are accepted and read nowhere, as written (C24)
+        model_input = model_utils.SampleRandomFrames(model_input, num_frames.reshape(-1, 1), iterations, uniform=frame_uniform)  # :983-984
+        max_frames, feature_size = model_input.shape[1], model_input.shape[2]
+        if feature_size <= 1024:
+            raise ValueError("SoftAttentionTriangulationModel slices a 1024-wide video and a 128-wide audio stream out of its input "
+                             f"(frame_level_models.py:991-992); got {feature_size} features")
+        dev = model_input.device
+        reshaped_input = model_input.reshape(-1, feature_size)
+        streams = (("video", 1024, video_anchor_size, video_bottleneck, slice(0, 1024)),
+                   ("audio", feature_size - 1024, audio_anchor_size, audio_bottleneck, slice(1024, None)))
+        features = []
+        for name, _, _, _, cols in streams:                                                                   # :991-1006
+            x = reshaped_input[:, cols]
+            features.append(layers.batch_norm(x, is_training, name + "_bn") if add_batch_norm else x)
+        d_modules = [video_pooling_modules.TriangulationEmbedding(D, max_frames, K, add_batch_norm, is_training) for _, D, K, _, _ in streams]
+        cluster_pool = aggregation_modules.IndirectClusterMaxMeanPoolModule(l2_normalize=False)               # :1019
+        t_modules = [video_pooling_modules.TriangulationTemporalEmbedding(D, max_frames, K, add_batch_norm, is_training) for _, D, K, _, _ in streams]
+        fused = bool(FLAGS.soft_attention_fused and reshaped_input.is_cuda and max_frames >= 2)
+        agg = {}
+        for (name, D, K, _, _), x, d_module, t_module in zip(streams, features, d_modules, t_modules):
+            with vs.variable_scope(name + "_triangulation_embedding"):                                        # :1031-1051
+                if fused:
+                    mean_d, max_d, mean_t, max_t = ops.triangulation_attention_pool(x.contiguous(), d_module.variables(dev), max_frames)
+                    agg[name + "_d"] = torch.cat([mean_d, max_d], 1)
+                    agg[name + "_t"] = torch.cat([mean_t, max_t], 1)
+                else:
+                    emb_d = d_module.forward(x)
+                    emb_t = t_module.forward(emb_d)                                                           # (the frame differences: C22)
+                    agg[name + "_d"] = cluster_pool.forward(emb_d.reshape(-1, max_frames, D * K))
+                    agg[name + "_t"] = cluster_pool.forward(emb_t)
+
+        def project(x, name, units):
+            w = vs.get_variable(name, [x.shape[1], units], vs.random_normal_initializer(1 / math.sqrt(units)), device=dev)
+            return x.matmul(w)
+
+        def bn(x, scope):
+            return layers.batch_norm(x, is_training, scope) if add_batch_norm else x
+
+        # the four projection variables are created before any of their batch norms (:1054-1071, then :1078-1102)
+        acts = {f"{name}_{kind}": project(agg[f"{name}_{kind}"], f"{name}_{kind}_projection", units)
+                for name, _, _, units, _ in streams for kind in ("d", "t")}
+        acts = {key: bn(a, key + "_activation_bn") for key, a in acts.items()}
+        fused_streams = []
+        for name, _, _, units, _ in streams:                                                                  # :1105-1120
+            fused_streams.append(project(torch.cat([acts[name + "_d"], acts[name + "_t"]], 1), name + "_projection", units))
+        activation = torch.cat([bn(a, name + "_activation_bn") for a, (name, *_) in zip(fused_streams, streams)], 1)   # :1122-1137
+        aggregated_model = getattr(video_level_models, "ClassLearningFourNnModel")
+        return aggregated_model().create_model(model_input=activation, vocab_size=vocab_size, is_training=is_training,
+                                               **unused_params)                                              # :1139-1145
 
 
 class NetVladV2(models.BaseModel):

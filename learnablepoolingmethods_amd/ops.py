@@ -3962,3 +3962,117 @@ def triangulation_pool(x, anchors, max_frames, scale=1.0):
         raise LpmError(f"{what}: need max_frames >= 2 dividing the {x.shape[0]} rows of x (max_frames = {T}): the temporal embedding is a "
                        "frame-to-frame difference")
     return _TriangulationPool.apply(x, anchors.contiguous(), T, float(scale))
+
+
+# ----------------------------------------------------------------------------------------------
+# soft-attention pooling of the triangulation embedding (csrc/triangulation_attention.hip)
+# ----------------------------------------------------------------------------------------------
+def _attention_gram(lib, x, anchors, B, T, D, K, scale):
+    """lpm_triangulation_attention_gram -> (G_d [B, T, T], G_t [B, T-1, T-1])."""
+    gram_d, gram_t = _empty((B, T, T), x), _empty((B, T - 1, T - 1), x)
+    wsb = int(lib._lpm_triangulation_attention_workspace_bytes(0, B, T, D, K))
+    ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+    with _timed("triangulation_attention_gram", (B, T, D, K)):
+        lib.check(lib._lpm_triangulation_attention_gram(ptr(x), ptr(anchors), B, T, D, K, scale, ptr(gram_d), ptr(gram_t),
+                                                        ptr(ws) if wsb else None, wsb, stream_ptr()), "lpm_triangulation_attention_gram")
+    return gram_d, gram_t
+
+
+def _attention_weights(gram):
+    """softmax over the frames of the row sums of relu(G): [B, T, T] -> [B, T] (aggregation_modules.py:93-97)."""
+    return torch.softmax(torch.relu(gram).sum(dim=2), dim=1)
+
+
+def _attention_weights_bwd(gram, w, dw):
+    """dw [B, T] -> M = dG + dG^T [B, T, T] with dG[t,s] = dl[t] [G[t,s] > 0], dl the softmax's backward."""
+    dl = w * (dw - (w * dw).sum(dim=1, keepdim=True))
+    dG = dl.unsqueeze(2) * (gram > 0).to(dl.dtype)
+    return (dG + dG.transpose(1, 2)).contiguous()
+
+
+class _TriangulationAttentionPool(torch.autograd.Function):
+    """The saved state is the inputs, the int32 [B, K*D] arg-max tensor, the two Grams and the two weight vectors; e, u and f are
+    recomputed in the backward, whose workspaces live for that call only."""
+
+    @staticmethod
+    def forward(ctx, x, anchors, T, scale):
+        lib = _capi.load()
+        D, K = anchors.shape
+        B = x.shape[0] // T
+        dims = (B, T, D, K)
+        gram_d, gram_t = _attention_gram(lib, x, anchors, B, T, D, K, scale)
+        with _timed("triangulation_attention_softmax", dims):
+            w_d, w_t = _attention_weights(gram_d), _attention_weights(gram_t)
+        outs = [_empty((B, K * D), x) for _ in range(4)]
+        argmax = torch.empty((B, K * D), dtype=torch.int32, device=x.device)
+        with _timed("triangulation_attention_pool_fwd", dims):
+            lib.check(lib._lpm_triangulation_attention_pool_fwd(ptr(x), ptr(anchors), ptr(w_d), ptr(w_t), B, T, D, K, scale,
+                                                                *(ptr(o) for o in outs), ptr(argmax), stream_ptr()),
+                      "lpm_triangulation_attention_pool_fwd")
+        ctx.save_for_backward(x, anchors, argmax, gram_d, gram_t, w_d, w_t)
+        ctx.dims = (B, T, D, K, scale)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, g_mean_d, g_max_d, g_mean_t, g_max_t):
+        lib = _capi.load()
+        x, anchors, argmax, gram_d, gram_t, w_d, w_t = ctx.saved_tensors
+        B, T, D, K, scale = ctx.dims
+        dims = (B, T, D, K)
+        grads = [g.contiguous() for g in (g_mean_d, g_max_d, g_mean_t, g_max_t)]
+        dw_d, dw_t = _empty((B, T), x), _empty((B, T - 1), x)
+        wsb = int(lib._lpm_triangulation_attention_workspace_bytes(1, B, T, D, K))
+        ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+        with _timed("triangulation_attention_dw", dims):
+            lib.check(lib._lpm_triangulation_attention_dw(ptr(x), ptr(anchors), ptr(grads[0]), ptr(grads[2]), B, T, D, K, scale, ptr(dw_d),
+                                                          ptr(dw_t), ptr(ws), wsb, stream_ptr()), "lpm_triangulation_attention_dw")
+        with _timed("triangulation_attention_softmax_bwd", dims):
+            m_d, m_t = _attention_weights_bwd(gram_d, w_d, dw_d), _attention_weights_bwd(gram_t, w_t, dw_t)
+        dx, danchors = torch.empty_like(x), torch.empty_like(anchors)
+        wsb = int(lib._lpm_triangulation_attention_workspace_bytes(2, B, T, D, K))
+        ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+        with _timed("triangulation_attention_bwd", dims):
+            lib.check(lib._lpm_triangulation_attention_bwd(ptr(x), ptr(anchors), ptr(argmax), ptr(w_d), ptr(w_t), ptr(m_d), ptr(m_t),
+                                                           *(ptr(g) for g in grads), B, T, D, K, scale, ptr(dx), ptr(danchors), ptr(ws), wsb,
+                                                           stream_ptr()), "lpm_triangulation_attention_bwd")
+        return dx, danchors, None, None
+
+
+def _attention_args(what, x, anchors, max_frames):
+    if not (torch.is_tensor(x) and torch.is_tensor(anchors)) or x.dim() != 2 or anchors.dim() != 2:
+        raise LpmError(f"{what}: expected x [B * max_frames, D] and anchors [D, K]")
+    _f32(x, what + " x"), _f32(anchors, what + " anchors")
+    if not (x.is_cuda and anchors.is_cuda and x.device == anchors.device):
+        raise LpmError(f"{what}: needs tensors on one MI355X (cuda/hip device); got {x.device} / {anchors.device}.  There is no CPU "
+                       "fallback: aggregation_modules.IndirectClusterMaxMeanPoolModule over video_pooling_modules' embeddings is the host path")
+    if not x.is_contiguous():
+        raise LpmError(f"{what}: x must be contiguous (a column slice of a wider matrix is not: copy the stream's block first)")
+    T = int(max_frames)
+    D, K = anchors.shape
+    if D not in TRIANGULATION_FEATURES or x.shape[1] != D or K < 1:
+        raise LpmError(f"{what}: need a feature size in {TRIANGULATION_FEATURES} shared by x and anchors (x {tuple(x.shape)}, anchors {tuple(anchors.shape)})")
+    most = int(_capi.load()._lpm_triangulation_attention_max_frames())
+    if T < 2 or T > most or x.shape[0] == 0 or x.shape[0] % T:
+        raise LpmError(f"{what}: need 2 <= max_frames <= {most} dividing the {x.shape[0]} rows of x (max_frames = {T}): the temporal embedding "
+                       "is a frame-to-frame difference, and the backward keeps a [max_frames, 32] tile of each embedding on chip")
+    return T
+
+
+def triangulation_attention_pool(x, anchors, max_frames, scale=1.0):
+    """The soft-attention pooled triangulation embedding of a stream (csrc/triangulation_attention.hip):
+    x [B * max_frames, D] (a clip's rows contiguous), anchors [D, K] (normalised by the caller: TriangulationEmbedding's are
+    l2_normalize(anchor_weights, 0)) -> (mean_d, max_d, mean_t, max_t), each [B, K * D] k-major (element k * D + d).  With e and f as in
+    ``triangulation_pool`` and v = e (T' = max_frames) or v = f (T' = max_frames - 1):
+        G = V V^T over all K * D;  w = softmax_t(sum_s relu(G[t,s]));  mean = (1/T') sum_t w[t] v_t;  max = max_t v_t
+    -- TriangulationEmbedding + TriangulationTemporalEmbedding + IndirectClusterMaxMeanPoolModule without any [B, T, K * D] tensor.
+    GPU only; D in TRIANGULATION_FEATURES, 2 <= max_frames <= 320, contiguous fp32 input; the same inputs give the same bits."""
+    T = _attention_args("triangulation_attention_pool", x, anchors, max_frames)
+    return _TriangulationAttentionPool.apply(x, anchors.contiguous(), T, float(scale))
+
+
+def triangulation_attention_gram(x, anchors, max_frames, scale=1.0):
+    """The two Gram matrices ``triangulation_attention_pool`` takes its weights from: (G_d [B, T, T], G_t [B, T-1, T-1]); no gradient."""
+    T = _attention_args("triangulation_attention_gram", x, anchors, max_frames)
+    D, K = anchors.shape
+    with torch.no_grad():
+        return _attention_gram(_capi.load(), x, anchors.contiguous(), x.shape[0] // T, T, D, K, float(scale))

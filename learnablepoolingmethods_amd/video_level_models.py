@@ -1,4 +1,5 @@
-"""MoeModel (reference: video_level_models.py:48-158) and ClassLearningThreeNnModel (:687-714) -- host-side PyTorch per the north-star."""
+"""MoeModel (reference: video_level_models.py:48-158), ClassLearningThreeNnModel (:687-714) and ClassLearningFourNnModel (:717-749) --
+host-side PyTorch per the north-star."""
 from __future__ import annotations
 
 import math
@@ -78,6 +79,17 @@ class MoeModel(models.BaseModel):
         return {"predictions": probabilities}                                                             # :158
 
 
+def _class_learning_fc(x, scope, biases, vocab_size, l2_penalty):
+    """slim.fully_connected of the ClassLearning*NnModel classifiers: width vocab_size, l2-regularised weights, a bias (0.1) or none."""
+    dev = x.device
+    with vs.variable_scope(scope):
+        w = vs.get_variable("weights", [x.shape[1], vocab_size], vs.glorot_uniform_initializer(), device=dev)
+        b = vs.get_variable("biases", [vocab_size], lambda shape, d, gen: torch.full(shape, 0.1, device=d), device=dev) if biases else None
+    vs.default_store().add_l2_regularizer(w, l2_penalty)                          # slim.l2_regularizer :697,704,711 / :727-746
+    y = x.matmul(w)
+    return y + b if biases else y
+
+
 class ClassLearningThreeNnModel(models.BaseModel):
     """Three fully connected layers of width vocab_size (video_level_models.py:687-714): bias-free + layer_norm + leaky_relu(0.2)
     (+ dropout, keep probability 0.5, in training) twice, then sigmoid with a bias initialised to 0.1.  Variable names are slim's:
@@ -90,16 +102,10 @@ class ClassLearningThreeNnModel(models.BaseModel):
                      **unused_params):
         from . import layers
         dev = model_input.device
-        store = vs.default_store()
         masks = dropout_masks or {}
 
         def fully_connected(x, scope, biases):
-            with vs.variable_scope(scope):
-                w = vs.get_variable("weights", [x.shape[1], vocab_size], vs.glorot_uniform_initializer(), device=dev)
-                b = vs.get_variable("biases", [vocab_size], lambda shape, d, gen: torch.full(shape, 0.1, device=d), device=dev) if biases else None
-            store.add_l2_regularizer(w, l2_penalty)                                   # slim.l2_regularizer :697,704,711
-            y = x.matmul(w)
-            return y + b if biases else y
+            return _class_learning_fc(x, scope, biases, vocab_size, l2_penalty)
 
         def dropout(x, key):
             if not is_training:
@@ -117,3 +123,19 @@ class ClassLearningThreeNnModel(models.BaseModel):
         fc2 = dropout(fc2, "fc2")
         fc3 = torch.sigmoid(fully_connected(fc2, "fully_connected_2", True))            # :709-711
         return {"predictions": fc3, "regularization_loss": ortho_reg}
+
+
+class ClassLearningFourNnModel(models.BaseModel):
+    """Four fully connected layers of width vocab_size (video_level_models.py:717-749): bias-free + layer_norm + leaky_relu(0.2) three
+    times -- NO dropout: the reference's dropout lines are commented out (:729-730, :736-737) -- then sigmoid with a bias initialised
+    to 0.1.  Variable names are slim's: fully_connected[_1|_2|_3]/weights, fully_connected_3/biases, LayerNorm[_1|_2]/{beta,gamma}."""
+
+    def create_model(self, model_input, vocab_size, is_training=True, l2_penalty=1e-8, ortho_reg=0, **unused_params):
+        from . import layers
+        h = model_input
+        for i in range(3):                                                              # :725-742
+            suffix = f"_{i}" if i else ""
+            h = _class_learning_fc(h, "fully_connected" + suffix, False, vocab_size, l2_penalty)
+            h = torch.nn.functional.leaky_relu(layers.layer_norm(h, "LayerNorm" + suffix), 0.2)
+        fc4 = torch.sigmoid(_class_learning_fc(h, "fully_connected_3", True, vocab_size, l2_penalty))   # :744-746
+        return {"predictions": fc4, "regularization_loss": ortho_reg}

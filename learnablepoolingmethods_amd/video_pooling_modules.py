@@ -102,11 +102,15 @@ class TriangulationEmbedding(modules.BaseModule):
         self.is_training = is_training
         self.scope_id = scope_id
 
+    def variables(self, device):
+        """The L2-normalised anchors [D, K] (:401-410) without a forward: what the fused path needs."""
+        anchor_weights = _anchor_weights(self.feature_size, self.anchor_size, self.scope_id, device)
+        vs.summary("anchor_weights" + ("" if self.scope_id is None else str(self.scope_id)), anchor_weights)
+        return layers.l2_normalize(anchor_weights, 0)                                              # :410
+
     def forward(self, inputs, **unused_params):
         """inputs [(B*max_frames), D] -> [(B*max_frames), D*K]."""
-        anchor_weights = _anchor_weights(self.feature_size, self.anchor_size, self.scope_id, inputs.device)
-        vs.summary("anchor_weights" + ("" if self.scope_id is None else str(self.scope_id)), anchor_weights)
-        anchor_weights = layers.l2_normalize(anchor_weights, 0)                                    # :410
+        anchor_weights = self.variables(inputs.device)
         t_emb = _anchor_residuals(inputs, anchor_weights)                                          # :413-424
         return t_emb.reshape(-1, self.feature_size * self.anchor_size)
 
