@@ -1043,6 +1043,32 @@ int lpm_triangulation_attention_bwd(const float* x, const float* anchors, const 
                                     const float* g_max_t, int B, int T, int D, int K, float scale, float* dx, float* danchors,
                                     void* workspace, size_t workspace_bytes, lpm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mean-only pooling of the triangulation embedding (frame_level_models.py:859-915 TriangulationCnnClusterModel:
+ * IndirectClusterMeanPoolModule / MeanStdPoolModule behind TriangulationCnnModule, whose per-anchor linear map commutes with the
+ * pooling and is left to the caller), csrc/triangulation_mean.hip.  x, anchors, scale, e and f as for lpm_triangulation_pool_*:
+ *     G_d[t,s] = <e_t, e_s> over all K * D;  w = softmax_t(sum_s relu(G_d[t,s]));  m_d = (1/T) sum_t w[t] e_t;  m_t = (1/(T-1)) sum_t f_t
+ * Nothing of size T * K * D is written in either direction, no floating-point atomics (the same inputs give the same bits); the Gram
+ * and the backward's M E product are exact-fp32 MFMAs.  No temporal Gram, no maxima, no arg-max tensor.
+ *   _gram:     -> gram_d [B, T, T] (relu, row sums and the softmax are the caller's)
+ *   _pool_fwd: w_d [B, T] -> m_d, m_t [B, K * D] k-major
+ *   _dw:       g_d [B, K * D] -> dw_d [B, T]:  dw[b,t] = <g_d[b], e_t> / T
+ *   _bwd:      m_d [B, T, T] = dG + dG^T with dG[t,s] = dl[t] [G[t,s] > 0] (SYMMETRIC: read along rows) and the two upstream gradients
+ *              g_d, g_t [B, K * D] -> dx [B * T, D], danchors [D, K] (both overwritten)
+ * workspace: 16-byte aligned, lpm_triangulation_mean_workspace_bytes(which, ...) bytes with which = 0 (_gram; may be 0 bytes),
+ * 1 (_dw), 2 (_bwd).  D in {128, 1024}, 2 <= T <= lpm_triangulation_attention_max_frames(), K >= 1; anything else
+ * LPM_ERR_UNSUPPORTED_SHAPE / LPM_ERR_BADARG before any launch. */
+size_t lpm_triangulation_mean_workspace_bytes(int which, int B, int T, int D, int K);
+int lpm_triangulation_mean_gram(const float* x, const float* anchors, int B, int T, int D, int K, float scale, float* gram_d, void* workspace,
+                                size_t workspace_bytes, lpm_stream_t stream);
+int lpm_triangulation_mean_pool_fwd(const float* x, const float* anchors, const float* w_d, int B, int T, int D, int K, float scale, float* m_d,
+                                    float* m_t, lpm_stream_t stream);
+int lpm_triangulation_mean_dw(const float* x, const float* anchors, const float* g_d, int B, int T, int D, int K, float scale, float* dw_d,
+                              void* workspace, size_t workspace_bytes, lpm_stream_t stream);
+int lpm_triangulation_mean_bwd(const float* x, const float* anchors, const float* w_d, const float* m_d, const float* g_d, const float* g_t,
+                               int B, int T, int D, int K, float scale, float* dx, float* danchors, void* workspace, size_t workspace_bytes,
+                               lpm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

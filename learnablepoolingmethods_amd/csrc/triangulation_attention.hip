@@ -37,13 +37,6 @@
 
 namespace lpm {
 
-constexpr int TA_MAX_FRAMES = 320;    // the backward keeps three [T, 33] tiles in LDS (135 KB at 320)
-constexpr int TA_CH = 32;             // columns of D per chunk
-constexpr int TA_LD = TA_CH + 1;      // LDS row stride (floats): rows 33 apart fall on different banks
-constexpr int TA_WAVES = 4;
-constexpr int TA_WALK_WAVES = 4;    // (clip, anchor) pairs per workgroup of the two frame walks
-constexpr int TA_MAX_SLICES = 16;     // partial Grams per clip
-constexpr int TA_MAX_GROUPS = 16;     // dx partials per clip: the workspace stays <= TA_MAX_GROUPS x the size of the frames
 constexpr int TA_MAX_JOBS = (2 * (TA_MAX_FRAMES / 32) + TA_WAVES - 1) / TA_WAVES;    // 32-row tiles of M V per wave and chunk
 
 // The norms of the frames f0 .. f0 + n - 1 of one (clip, anchor): iq = rsqrt(max(|x - a|^2, eps)), ip the same of u = e_t - e_{t-1},
@@ -86,9 +79,6 @@ __device__ __forceinline__ void ta_norms(const float* __restrict__ xb, const flo
         }
     }
 }
-
-// e[t, c] of a frame from its norm: ((x - a) iq) s, the bits tp_unit followed by the scale gives
-__device__ __forceinline__ float ta_eh(float x, float a, float iq) { return (x - a) * iq; }
 
 template <int D>
 __global__ __launch_bounds__(64 * TA_WAVES) void ta_gram_kernel(const float* __restrict__ x, const float* __restrict__ anchors, int T, int K,
@@ -535,40 +525,34 @@ __global__ __launch_bounds__(256) void ta_da_reduce_kernel(const float* __restri
     danchors[(int64_t)d * K + k] = -tot;
 }
 
-static int ta_tiles(int T) { return (T + 63) / 64; }
 static int ta_slices(int B, int T, int K) {
     const int64_t wg = (int64_t)B * ta_tiles(T) * ta_tiles(T);
     int64_t want = (512 + wg - 1) / wg;
     want = want < 1 ? 1 : (want > TA_MAX_SLICES ? TA_MAX_SLICES : want);
     return (int)(K < want ? K : want);
 }
-static int ta_groups(int B, int K) {                       // at most two workgroups per CU (512 in all), where the anchors allow
-    int want = 512 / B;
-    want = want < 1 ? 1 : (want > TA_MAX_GROUPS ? TA_MAX_GROUPS : want);
-    return K < want ? K : want;
-}
-constexpr int TA_FAST_FRAMES = 64;    // ta_bwd_kernel<D, 64>
 static size_t ta_bwd_lds(int T) {
     const bool fast = T <= TA_FAST_FRAMES;
     const int Tp = fast ? TA_FAST_FRAMES : (T + 31) & ~31;
     return ((size_t)3 * Tp * TA_LD + 8 * Tp + 8 * 32 + (fast ? 2 * TA_FAST_FRAMES * TA_FAST_FRAMES : 0)) * sizeof(float);
 }
 
-static int ta_check(const char* name, int B, int T, int D, int K) {
-    LPM_REQUIRE(B > 0 && K > 0 && T > 0, LPM_ERR_BADARG, "%s: need B, T, K >= 1 (B=%d T=%d K=%d)", name, B, T, K);
-    LPM_REQUIRE(D == 128 || D == 1024, LPM_ERR_UNSUPPORTED_SHAPE, "%s: need D in {128, 1024} (D=%d)", name, D);
-    LPM_REQUIRE(T >= 2 && T <= TA_MAX_FRAMES, LPM_ERR_UNSUPPORTED_SHAPE,
-                "%s: need 2 <= T <= %d frames (T=%d): the temporal embedding is a frame-to-frame difference, and the backward keeps a "
-                "[T, %d] tile of each embedding in LDS", name, TA_MAX_FRAMES, T, TA_CH);
-    LPM_REQUIRE((int64_t)K * D < (1ll << 31) && (int64_t)B * K * ta_tiles(T) * ta_tiles(T) < (1ll << 31), LPM_ERR_UNSUPPORTED_SHAPE,
-                "%s: B * K or K * D too large (B=%d K=%d)", name, B, K);
-    return LPM_OK;
-}
-
-static int ta_sum_slices(const float* part, int64_t outer, int64_t n, int S, float* out, hipStream_t s, const char* name) {
+int ta_sum_slices(const float* part, int64_t outer, int64_t n, int S, float* out, hipStream_t s, const char* name) {
     const int64_t total = outer * n;
     LPM_REQUIRE((total + 255) / 256 < (1ll << 31), LPM_ERR_UNSUPPORTED_SHAPE, "%s: too large", name);
     hipLaunchKernelGGL(ta_sum_slices_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, part, total, n, S, out);
+    return LPM_OK;
+}
+
+int ta_reduce_partials(const float* dx_part, const float* da_part, int B, int T, int D, int K, int G, float* dx, float* danchors,
+                       hipStream_t s, const char* name) {
+    if (G > 1) {
+        const int64_t n4 = (int64_t)T * D / 4, total4 = n4 * B;
+        LPM_REQUIRE((total4 + 255) / 256 < (1ll << 31), LPM_ERR_UNSUPPORTED_SHAPE, "%s: B * T * D too large", name);
+        hipLaunchKernelGGL(ta_dx_reduce_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, (const float4*)dx_part, total4, n4, G,
+                           (float4*)dx);
+    }
+    hipLaunchKernelGGL(ta_da_reduce_kernel, dim3((K * D + 255) / 256), dim3(256), 0, s, da_part, B, K, D, danchors);
     return LPM_OK;
 }
 
@@ -698,12 +682,6 @@ extern "C" int lpm_triangulation_attention_bwd(const float* x, const float* anch
         if (D == 1024) TA_LAUNCH_BWD(1024, 0); else TA_LAUNCH_BWD(128, 0);
     }
 #undef TA_LAUNCH_BWD
-    if (G > 1) {
-        const int64_t n4 = (int64_t)T * D / 4, total4 = n4 * B;
-        LPM_REQUIRE((total4 + 255) / 256 < (1ll << 31), LPM_ERR_UNSUPPORTED_SHAPE, "%s: B * T * D too large", name);
-        hipLaunchKernelGGL(ta_dx_reduce_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, (const float4*)dx_part, total4, n4, G,
-                           (float4*)dx);
-    }
-    hipLaunchKernelGGL(ta_da_reduce_kernel, dim3((K * D + 255) / 256), dim3(256), 0, s, (const float*)da_part, B, K, D, danchors);
+    if (const int rc = ta_reduce_partials(dx_part, da_part, B, T, D, K, G, dx, danchors, s, name)) return rc;
     return check_launch(name);
 }

@@ -80,6 +80,18 @@ FLAGS.define("soft_attention_fused", True, "build extension: on the GPU each str
              "ops.triangulation_attention_pool call (csrc/triangulation_attention.hip: the Grams, the softmax weights and the four pooled "
              "vectors without any [B, T, K*D] tensor); False: the materialising modules of video_pooling_modules / aggregation_modules "
              "compose it (the CPU path; same variables, same results)")
+FLAGS.define("tccm_iterations", 200, "TriangulationCnnClusterModel (frame_level_models.py:737): sampled frames per clip")
+FLAGS.define("tccm_add_batch_norm", True, "TriangulationCnnClusterModel (:739): batch norm on the streams and on each stream's pooled vector")
+FLAGS.define("tccm_video_anchor_size", 128, "TriangulationCnnClusterModel (:743): anchors of the video stream")
+FLAGS.define("tccm_audio_anchor_size", 32, "TriangulationCnnClusterModel (:745): anchors of the audio stream")
+FLAGS.define("tccm_video_kernel_size", 128, "TriangulationCnnClusterModel (:747): filters per anchor of the video stream's two convolutions")
+FLAGS.define("tccm_audio_kernel_size", 128, "TriangulationCnnClusterModel (:749): filters per anchor of the audio stream's two convolutions")
+FLAGS.define("tccm_video_hidden", 2048, "TriangulationCnnClusterModel (:751): width of the video stream's hidden layer")
+FLAGS.define("tccm_audio_hidden", 256, "TriangulationCnnClusterModel (:753): width of the audio stream's hidden layer")
+FLAGS.define("triangulation_cnn_fused", True, "build extension: on the GPU each stream of TriangulationCnnClusterModel is ONE "
+             "ops.triangulation_cnn_pool call (csrc/triangulation_mean.hip: the Gram, the softmax weights and the two pooled means without "
+             "any [B, T, K*D] tensor, then the per-anchor convolution on the pooled means); False: the materialising modules of "
+             "video_pooling_modules / aggregation_modules compose it (the CPU path; same variables, same results)")
 FLAGS.define("wtm_projection_l1", 1e-5, "layers.l1_l2_regularizer(1e-5) on dis_projection_2 / temp_projection_2 (frame_level_models.py:1272,1287): "
              "tf.contrib's first positional argument is scale_l1")
 FLAGS.define("wtm_projection_l2", 1.0, "... and its scale_l2 keeps the default 1.0: the penalty is l1 * sum |w| + l2 * sum(w^2) / 2 (SURVEY App. B)")

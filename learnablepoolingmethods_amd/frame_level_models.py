@@ -468,6 +468,83 @@ class SoftAttentionTriangulationModel(models.BaseModel):
                                                **unused_params)                                              # :1139-1145
 
 
+class TriangulationCnnClusterModel(models.BaseModel):
+    """Triangulation embedding of both streams and its temporal differences, a per-anchor 1x1 convolution over each, soft-attention
+    mean pooling of the first and mean pooling of the second, one hidden layer per stream and the four-layer classifier
+    (frame_level_models.py:757-939).  As written: SURVEY App. C26-C28 (and C22, C23, C25).
+
+    On the GPU with FLAGS.triangulation_cnn_fused each stream is ONE ops.triangulation_cnn_pool call: the convolution has no bias and
+    no activation, so it commutes with both poolings and runs on the pooled means -- neither the embeddings [B, T, D*K] (105 MB per
+    clip at the defaults T = 200, K = 128, D = 1024) nor the convolutions' [B, T, K*F] results are written; otherwise the
+    materialising modules of video_pooling_modules / aggregation_modules compose the reference's graph.  The variables and the results
+    are the same either way.  ``frame_uniform`` [B, iterations] replaces the random draw of SampleRandomFrames; ``video_anchor_size``,
+    ``audio_anchor_size``, ``video_kernel_size``, ``audio_kernel_size``, ``video_hidden`` and ``audio_hidden`` override the flags (the
+    reference reads the flags only)."""
+
+    def create_model(self, model_input, vocab_size, num_frames, iterations=None, add_batch_norm=None, sample_random_frames=None,
+                     hidden_size=None, is_training=True, frame_uniform=None, video_anchor_size=None, audio_anchor_size=None,
+                     video_kernel_size=None, audio_kernel_size=None, video_hidden=None, audio_hidden=None, **unused_params):
+        iterations = iterations or FLAGS.tccm_iterations                                                      # :768
+        add_batch_norm = add_batch_norm or FLAGS.tccm_add_batch_norm                                          # :769 (C23)
+        video_anchor_size = int(video_anchor_size or FLAGS.tccm_video_anchor_size)                            # :770-775
+        audio_anchor_size = int(audio_anchor_size or FLAGS.tccm_audio_anchor_size)
+        video_kernel_size = int(video_kernel_size or FLAGS.tccm_video_kernel_size)
+        audio_kernel_size = int(audio_kernel_size or FLAGS.tccm_audio_kernel_size)
+        video_hidden = int(video_hidden or FLAGS.tccm_video_hidden)
+        audio_hidden = int(audio_hidden or FLAGS.tccm_audio_hidden)
+        # sample_random_frames and hidden_size are accepted and read nowhere, as written (C26)
+        model_input = model_utils.SampleRandomFrames(model_input, num_frames.reshape(-1, 1), iterations, uniform=frame_uniform)  # :777-778
+        max_frames, feature_size = model_input.shape[1], model_input.shape[2]
+        if feature_size <= 1024:
+            raise ValueError("TriangulationCnnClusterModel slices a 1024-wide video and a 128-wide audio stream out of its input "
+                             f"(frame_level_models.py:785-786); got {feature_size} features")
+        dev = model_input.device
+        reshaped_input = model_input.reshape(-1, feature_size)
+        streams = (("video", 1024, video_anchor_size, video_kernel_size, video_hidden, slice(0, 1024)),
+                   ("audio", feature_size - 1024, audio_anchor_size, audio_kernel_size, audio_hidden, slice(1024, None)))
+        features = []
+        for name, _, _, _, _, cols in streams:                                                                # :785-800
+            x = reshaped_input[:, cols]
+            features.append(layers.batch_norm(x, is_training, name + "_bn") if add_batch_norm else x)
+        d_modules = [video_pooling_modules.TriangulationEmbedding(D, max_frames, K, add_batch_norm, is_training) for _, D, K, _, _, _ in streams]
+        cnn_modules = [(video_pooling_modules.TriangulationCnnModule(D, max_frames, F, K, add_batch_norm, is_training, name + "_d"),
+                        video_pooling_modules.TriangulationCnnModule(D, max_frames - 1, F, K, add_batch_norm, is_training, name + "_t"))
+                       for name, D, K, F, _, _ in streams]                                                    # :813-843 (max_frames - 1: C28)
+        ic_mean_pool = aggregation_modules.IndirectClusterMeanPoolModule(l2_normalize=False)                  # :845
+        mean_std_pool = aggregation_modules.MeanStdPoolModule(l2_normalize=False)                             # :846 (the mean only: C27)
+        t_modules = [video_pooling_modules.TriangulationTemporalEmbedding(D, max_frames, K, add_batch_norm, is_training) for _, D, K, _, _, _ in streams]
+        fused = bool(FLAGS.triangulation_cnn_fused and reshaped_input.is_cuda and max_frames >= 2)
+        agg = []
+        for (name, D, K, _, _, _), x, d_module, (d_cnn, t_cnn), t_module in zip(streams, features, d_modules, cnn_modules, t_modules):
+            with vs.variable_scope(name + "_triangulation_embedding"):                                        # :859-915
+                if fused:
+                    anchors = d_module.variables(dev)
+                    with vs.variable_scope(name + "_d"):
+                        cnn_d = d_cnn.variables(dev)
+                    with vs.variable_scope(name + "_t"):
+                        cnn_t = t_cnn.variables(dev)
+                    agg_d, agg_t = ops.triangulation_cnn_pool(x.contiguous(), anchors, cnn_d, cnn_t, max_frames)
+                else:
+                    emb_d = d_module.forward(x)
+                    with vs.variable_scope(name + "_d"):
+                        emb_d_cnn = d_cnn.forward(emb_d)
+                    agg_d = ic_mean_pool.forward(emb_d.reshape(-1, max_frames, D * K), emb_d_cnn)             # (weights from e, pooling over the convolution)
+                    emb_t = t_module.forward(emb_d)                                                           # (the frame differences: C22)
+                    with vs.variable_scope(name + "_t"):
+                        emb_t_cnn = t_cnn.forward(emb_t.reshape(-1, D * K))
+                    agg_t = mean_std_pool.forward(emb_t_cnn)
+                a = torch.cat([agg_d, agg_t], 1)
+                agg.append(layers.batch_norm(a, is_training, f"agg_{name}_bn") if add_batch_norm else a)
+        acts = []
+        for (name, _, _, _, units, _), a in zip(streams, agg):                                                # :917-929
+            w = vs.get_variable(name + "_hidden", [a.shape[1], units], vs.random_normal_initializer(1 / math.sqrt(units)), device=dev)
+            acts.append(a.matmul(w))
+        activation = torch.cat(acts, 1)                                                                       # :931
+        aggregated_model = getattr(video_level_models, "ClassLearningFourNnModel")
+        return aggregated_model().create_model(model_input=activation, vocab_size=vocab_size, is_training=is_training,
+                                               **unused_params)                                              # :933-939
+
+
 class NetVladV2(models.BaseModel):
     """Paper prototype 2: attention-based cluster similarities (frame_level_models.py:2383-2513)."""
 

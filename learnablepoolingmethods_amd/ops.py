@@ -4076,3 +4076,103 @@ def triangulation_attention_gram(x, anchors, max_frames, scale=1.0):
     D, K = anchors.shape
     with torch.no_grad():
         return _attention_gram(_capi.load(), x, anchors.contiguous(), x.shape[0] // T, T, D, K, float(scale))
+
+
+# ----------------------------------------------------------------------------------------------
+# mean-only pooling of the triangulation embedding and the per-anchor projection behind it (csrc/triangulation_mean.hip)
+# ----------------------------------------------------------------------------------------------
+def _mean_gram(lib, x, anchors, B, T, D, K, scale):
+    """lpm_triangulation_mean_gram -> G_d [B, T, T]."""
+    gram_d = _empty((B, T, T), x)
+    wsb = int(lib._lpm_triangulation_mean_workspace_bytes(0, B, T, D, K))
+    ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+    with _timed("triangulation_mean_gram", (B, T, D, K)):
+        lib.check(lib._lpm_triangulation_mean_gram(ptr(x), ptr(anchors), B, T, D, K, scale, ptr(gram_d), ptr(ws) if wsb else None, wsb,
+                                                   stream_ptr()), "lpm_triangulation_mean_gram")
+    return gram_d
+
+
+class _TriangulationMeanPool(torch.autograd.Function):
+    """The saved state is the inputs, G_d [B, T, T] and w [B, T]; e and f are recomputed in the backward, whose workspaces live for
+    that call only."""
+
+    @staticmethod
+    def forward(ctx, x, anchors, T, scale):
+        lib = _capi.load()
+        D, K = anchors.shape
+        B = x.shape[0] // T
+        dims = (B, T, D, K)
+        gram_d = _mean_gram(lib, x, anchors, B, T, D, K, scale)
+        with _timed("triangulation_mean_softmax", dims):
+            w_d = _attention_weights(gram_d)
+        m_d, m_t = _empty((B, K * D), x), _empty((B, K * D), x)
+        with _timed("triangulation_mean_pool_fwd", dims):
+            lib.check(lib._lpm_triangulation_mean_pool_fwd(ptr(x), ptr(anchors), ptr(w_d), B, T, D, K, scale, ptr(m_d), ptr(m_t), stream_ptr()),
+                      "lpm_triangulation_mean_pool_fwd")
+        ctx.save_for_backward(x, anchors, gram_d, w_d)
+        ctx.dims = (B, T, D, K, scale)
+        return m_d, m_t
+
+    @staticmethod
+    def backward(ctx, g_d, g_t):
+        lib = _capi.load()
+        x, anchors, gram_d, w_d = ctx.saved_tensors
+        B, T, D, K, scale = ctx.dims
+        dims = (B, T, D, K)
+        g_d, g_t = g_d.contiguous(), g_t.contiguous()
+        dw_d = _empty((B, T), x)
+        wsb = int(lib._lpm_triangulation_mean_workspace_bytes(1, B, T, D, K))
+        ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+        with _timed("triangulation_mean_dw", dims):
+            lib.check(lib._lpm_triangulation_mean_dw(ptr(x), ptr(anchors), ptr(g_d), B, T, D, K, scale, ptr(dw_d), ptr(ws), wsb, stream_ptr()),
+                      "lpm_triangulation_mean_dw")
+        with _timed("triangulation_mean_softmax_bwd", dims):
+            m_d = _attention_weights_bwd(gram_d, w_d, dw_d)
+        dx, danchors = torch.empty_like(x), torch.empty_like(anchors)
+        wsb = int(lib._lpm_triangulation_mean_workspace_bytes(2, B, T, D, K))
+        ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+        with _timed("triangulation_mean_bwd", dims):
+            lib.check(lib._lpm_triangulation_mean_bwd(ptr(x), ptr(anchors), ptr(w_d), ptr(m_d), ptr(g_d), ptr(g_t), B, T, D, K, scale, ptr(dx),
+                                                      ptr(danchors), ptr(ws), wsb, stream_ptr()), "lpm_triangulation_mean_bwd")
+        return dx, danchors, None, None
+
+
+def triangulation_mean_pool(x, anchors, max_frames, scale=1.0):
+    """The two pooled means TriangulationCnnClusterModel takes of a stream's triangulation embedding (csrc/triangulation_mean.hip):
+    x [B * max_frames, D] (a clip's rows contiguous), anchors [D, K] (normalised by the caller) -> (m_d, m_t), each [B, K * D] k-major
+    (element k * D + d).  With e and f as in ``triangulation_pool``, T = max_frames:
+        G_d = E E^T over all K * D;  w = softmax_t(sum_s relu(G_d[t,s]));  m_d = (1/T) sum_t w[t] e_t;  m_t = (1/(T-1)) sum_t f_t
+    -- ``triangulation_attention_pool`` without the temporal Gram, the maxima and their arg-max tensor.  GPU only; D in
+    TRIANGULATION_FEATURES, 2 <= max_frames <= 320, contiguous fp32 input; the same inputs give the same bits."""
+    T = _attention_args("triangulation_mean_pool", x, anchors, max_frames)
+    return _TriangulationMeanPool.apply(x, anchors.contiguous(), T, float(scale))
+
+
+def triangulation_mean_gram(x, anchors, max_frames, scale=1.0):
+    """The Gram matrix ``triangulation_mean_pool`` takes its weights from: G_d [B, T, T]; no gradient."""
+    T = _attention_args("triangulation_mean_gram", x, anchors, max_frames)
+    D, K = anchors.shape
+    with torch.no_grad():
+        return _mean_gram(_capi.load(), x, anchors.contiguous(), x.shape[0] // T, T, D, K, float(scale))
+
+
+def triangulation_cnn_pool(x, anchors, cnn_d, cnn_t, max_frames, scale=1.0):
+    """One stream of TriangulationCnnClusterModel: TriangulationEmbedding / TriangulationTemporalEmbedding, TriangulationCnnModule over
+    each (``cnn_d``, ``cnn_t`` [K, F, D], as the variables are stored) and the two poolings -> (agg_d, agg_t), each [B, K * F] (element
+    k * F + j).  The per-anchor map is linear, without bias or activation, so it is applied to the pooled means of
+    ``triangulation_mean_pool`` (a batched [B, D] x [D, F] product per anchor) instead of to every frame."""
+    what = "triangulation_cnn_pool"
+    T = _attention_args(what, x, anchors, max_frames)
+    D, K = anchors.shape
+    for name, cnn in (("cnn_d", cnn_d), ("cnn_t", cnn_t)):
+        if not torch.is_tensor(cnn) or cnn.dim() != 3 or cnn.shape[0] != K or cnn.shape[2] != D or cnn.shape[1] < 1:
+            raise LpmError(f"{what}: {name} must be [K, F, D] = [{K}, F, {D}] (got {tuple(cnn.shape) if torch.is_tensor(cnn) else type(cnn)})")
+        _f32(cnn, f"{what} {name}")
+        if cnn.device != x.device:
+            raise LpmError(f"{what}: {name} is on {cnn.device}, x on {x.device}")
+    m_d, m_t = _TriangulationMeanPool.apply(x, anchors.contiguous(), T, float(scale))
+    B = m_d.shape[0]
+    with _timed("triangulation_cnn_projection", (B, T, D, K)):
+        agg = [torch.bmm(m.view(B, K, D).transpose(0, 1), cnn.transpose(1, 2)).transpose(0, 1).reshape(B, K * cnn.shape[1])
+               for m, cnn in ((m_d, cnn_d), (m_t, cnn_t))]
+    return agg[0], agg[1]

@@ -115,6 +115,33 @@ class TriangulationEmbedding(modules.BaseModule):
         return t_emb.reshape(-1, self.feature_size * self.anchor_size)
 
 
+class TriangulationCnnModule(modules.BaseModule):
+    """:1345-1392: a 1x1 convolution per anchor over every frame of a triangulation embedding -- ``cnn_weights`` [K, F, D],
+    N(0, 1 / (F D)); no bias, no activation.  MATERIALISES [B, T, K*F] from a [(B*T), K*D] input: the drop-in surface and the CPU path;
+    the map is linear, so ops.triangulation_cnn_pool applies it to the pooled means instead."""
+
+    def __init__(self, feature_size, max_frames, num_filters, anchor_size, batch_norm, is_training, scope_id=None):
+        self.feature_size = feature_size
+        self.max_frames = max_frames
+        self.batch_norm = batch_norm
+        self.num_filters = int(num_filters)
+        self.anchor_size = int(anchor_size)
+        self.is_training = is_training
+        self.scope_id = scope_id
+
+    def variables(self, device):
+        """``cnn_weights`` [K, F, D] without a forward: what the fused path needs."""
+        return vs.get_variable("cnn_weights", [self.anchor_size, self.num_filters, self.feature_size],
+                               vs.random_normal_initializer(1 / math.sqrt(self.num_filters * self.feature_size)), device=device)
+
+    def forward(self, inputs, **unused_params):
+        """inputs [(B*max_frames), D*K] (any leading shape with that many elements) -> [B, max_frames, K*F] (element k * F + j)."""
+        cnn_weights = self.variables(inputs.device).transpose(1, 2)                                 # :1383 -> [K, D, F]
+        reshaped_inputs = inputs.reshape(-1, self.anchor_size, self.feature_size).transpose(0, 1)   # :1386-1387 -> [K, B*T, D]
+        output = reshaped_inputs.matmul(cnn_weights).transpose(0, 1)                                # :1388-1389 -> [B*T, K, F]
+        return output.reshape(-1, self.max_frames, self.anchor_size * self.num_filters)
+
+
 class WeightedTriangulationEmbedding(modules.BaseModule):
     """:1395-1459: the anchors enter as they are, and the whole row of K blocks is l2-normalised once more -- every block has unit
     norm, so that is a division by sqrt(K) (ops.triangulation_pool(scale=1/sqrt(K)); SURVEY App. C19 for the one case where it is
