@@ -1069,6 +1069,32 @@ int lpm_triangulation_mean_bwd(const float* x, const float* anchors, const float
                                int B, int T, int D, int K, float scale, float* dx, float* danchors, void* workspace, size_t workspace_bytes,
                                lpm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Pooled convolution moments of the triangulation embedding (video_pooling_modules.py:182-276 TriangulationV5Module, the pooling
+ * of JuhanTestModelV5), csrc/triangulation_moments.hip.  x [B * T, D] (a clip's rows contiguous), anchors [D, K] AS THEY ARE (not
+ * normalised), cnn_s, cnn_t [K, F, D].  Per row m and anchor k:
+ *     q = |x - a_k|^2, n = sqrt(q), e = (x - a_k) rsqrt(max(q, 1e-12));   g[k,d] = e[k,d] - e[k,d-1], e[k,-1] := e[(k-1) mod K, D-1]
+ *     (the roll over the feature axis, :216), frames t >= 1 only;   p = |g|^2, tau = sqrt(p), h = g rsqrt(max(p, 1e-12))
+ *     so[m,k,f] = <cnn_s[k,f,:], e[m,k,:]>,  to[m,k,f] = <cnn_t[k,f,:], h[m,k,:]>
+ *     pool_s = [mean | var] over the T frames of [so (element k * F + f) | n],  pool_t = the same over the T - 1 frames of [to | tau]
+ * (var = the mean of squared deviations from the mean), each [B, 2 (K * F + K)].  Nothing of size B * T * K * D is written in either
+ * direction; no floating-point atomics (the same inputs give the same bits); all products are exact-fp32 MFMAs.
+ *   _fwd: -> q, p [2, B * T, K] (the squared norms, p = -1 on frame 0 of a clip, then 1 / sqrt(max(., 1e-12)), 0 on frame 0), so, to
+ *         [B * T, K * F] (to = 0 on frame 0), pool_s, pool_t, corr [2, B, K * F + K] (the mean of each column's deviations from its
+ *         rounded mean: the backward subtracts it again): all kept by the caller for _bwd
+ *   _bwd: g_s, g_t [B, 2 (K * F + K)] -> dx [B * T, D], danchors [D, K], dcnn_s, dcnn_t [K, F, D] (all overwritten).  Where a squared
+ *         norm does not exceed 1e-12 the gradient of that norm output is zero.
+ * workspace (_bwd): 16-byte aligned, lpm_triangulation_moments_workspace_bytes(...) bytes.  D in {128, 1024},
+ * 2 <= T <= lpm_triangulation_attention_max_frames(), K >= 1, F >= 1; anything else LPM_ERR_UNSUPPORTED_SHAPE / LPM_ERR_BADARG before
+ * any launch. */
+size_t lpm_triangulation_moments_workspace_bytes(int B, int T, int D, int K, int F);
+int lpm_triangulation_moments_fwd(const float* x, const float* anchors, const float* cnn_s, const float* cnn_t, int B, int T, int D, int K,
+                                  int F, float* q, float* p, float* so, float* to, float* pool_s, float* pool_t, float* corr, lpm_stream_t stream);
+int lpm_triangulation_moments_bwd(const float* x, const float* anchors, const float* cnn_s, const float* cnn_t, const float* q, const float* p,
+                                  const float* so, const float* to, const float* pool_s, const float* pool_t, const float* corr, const float* g_s,
+                                  const float* g_t, int B, int T, int D, int K, int F, float* dx, float* danchors, float* dcnn_s,
+                                  float* dcnn_t, void* workspace, size_t workspace_bytes, lpm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,597 @@
+// The pooled convolution moments of TriangulationV5Module (video_pooling_modules.py:182-276, JuhanTestModelV5): per anchor k of the
+// [D, K] anchors (as they are: not normalised) and frame row m = b T + t of x [(B T), D]
+//   q = |x - a_k|^2, n = sqrt(q), e = (x - a_k) rsqrt(max(q, 1e-12))                                    (tf.norm, tf.nn.l2_normalize)
+//   g[k,d] = e[k,d] - e[k,d-1] with e[k,-1] := e[(k-1) mod K, D-1]  (tf.manip.roll over the FEATURE axis of the flattened [K D] row,
+//   :216), frame 0 of every clip dropped;  p = |g|^2, tau = sqrt(p), h = g rsqrt(max(p, 1e-12))
+//   so[m,k,f] = sum_d Ws[k,f,d] e[m,k,d]       to[m,k,f] = sum_d Wt[k,f,d] h[m,k,d]                      (the per-anchor convolutions)
+//   pool = [mean_t | mean_t (. - mean)^2] of [so | n] over the T frames and of [to | tau] over the T - 1 frames t >= 1.
+// The variance does not commute with the convolution, so both products run over every frame: 2 (B T) K F D FLOP each.  Nothing of
+// size B T K D is written in either direction: e and h are generated from the frames where a product reads them (the residual x - a
+// is formed first, as tp_unit does; h takes column d-1 from the frames as well).  What IS written: q, p [2, B T, K] (the squared norms and their clamped reciprocal roots), so, to [B T, K F]
+// (saved for the backward: the gradient of a variance needs every frame's value), and in the backward the two upstream tensors
+// dso, dto [B T, K F], a handful of [B T, K] sums, one danchors partial per 128-row tile and at most TV_MAX_GROUPS partial copies of dx.
+// No floating-point atomics: every cross-workgroup sum has a fixed order.  All products on v_mfma_f32_32x32x2_f32 (exact fp32).
+//
+// forward: tv_norms (one wave per frame row and 16 anchors: q, p by direct sums of squares) -> tv_conv (a workgroup owns an anchor, 32
+// filters and 128 frame rows ACROSS clips: per 32-column chunk of D the e and h tiles [128, 33] and the two weight tiles go to LDS, one
+// 32x32 product per wave and stream; the row tiles of one weight tile are neighbours in the grid) -> tv_moments (a thread per clip and
+// column: the mean, then the squared deviations from it, both two-level over t).
+//
+// backward, with (gm, gv) the upstream gradient of a pool and T' its frame count: dout[t] = (gm + 2 gv ((out[t] - mean) - c)) / T', where
+// c = mean_t (out[t] - mean) is what the rounded mean is off by (zero in exact arithmetic; autograd has the same term through d mean /
+// d out: without it the error of the mean, the same for every frame of a clip, adds up over the frames in danchors).
+//   dW[k] = sum_m dout (x) operand:  tv_dw, a wave owns a 32 x 32 tile of dW[k] and walks all B T rows (operands straight from the
+//   frames into the MFMA's registers; two-level over the rows).
+//   operand gradients ge = Ws_k^T dso, gh = Wt_k^T dto, then the two normalisations with the norms' own gradients dn, dtau:
+//     gg[d] = itau (gh[d] - h[d] (h . gh) [p > eps]) + dtau [p > eps] h[d]              (gradient of g; (h . gh) = sum_f dto to)
+//     get[d] = ge[d] + gg[d] - gg[next(d)]     (next(k, D-1) = (k+1 mod K, 0): the boundary term, taken from tv_dout's [B T, K] column)
+//     gr[d] = iq (get[d] - e[d] (e . get) [q > eps]) + dn [q > eps] e[d]                dx = sum_k gr,  danchors[:,k] = - sum_m gr
+//   (e . get) needs no sweep of its own:  (e . get) = sum_f dso so + ([p > eps] ? dtau tau : (h . gh)) + e[k-1,D-1] gg[k,0] - e[k,D-1] gg[k+1,0].
+//   tv_dout (a wave per (row, anchor): dso, dto, the sums over f, gg at the first column of every d-range) -> tv_s2 -> tv_dx (a
+//   workgroup owns 128 rows, a d-range and the anchors g, g + G, ...: per 32-column chunk, from the top of the range down, ge and gh on
+//   the matrix cores over F in 32-filter steps, then the chain with a thread per (row, column); dx accumulates in the workgroup's own
+//   block).  Where a squared norm does not exceed eps the norm's gradient is defined as zero (the reference: 0 / 0).
+#include "triangulation_common.h"
+
+// no product may be fused into the differences e[d] - e[d-1] and out[t] - mean
+#pragma clang fp contract(off)
+
+namespace lpm {
+
+constexpr int TV_ROWS = 128;          // frame rows per workgroup of tv_conv and tv_dx (one 32-row tile per wave)
+constexpr int TV_KC = 16;             // anchors per wave of tv_norms
+constexpr int TV_MAX_GROUPS = 8;      // dx partials per row tile
+constexpr int TV_MAX_RANGES = 8;      // d-ranges of tv_dx
+
+// 1 / sqrt(max(sq, eps)) from the correctly rounded root and quotient; taken once per (row, anchor) by tv_norms and stored beside the
+// squared norm, so every later kernel scales by the same bits
+__device__ __forceinline__ float tv_inv(float sq) { return 1.f / sqrtf(fmaxf(sq, kL2Eps)); }
+
+static int tv_range(int D) { return D >= 1024 ? 256 : D; }               // columns per d-range of tv_dx
+static int tv_row_tiles(int64_t BT) { return (int)((BT + TV_ROWS - 1) / TV_ROWS); }
+static int tv_groups(int64_t BT, int D, int K) {
+    const int64_t wg = (int64_t)tv_row_tiles(BT) * (D / tv_range(D));
+    int64_t want = 256 / wg;
+    want = want < 1 ? 1 : (want > TV_MAX_GROUPS ? TV_MAX_GROUPS : want);
+    return (int)(K < want ? K : want);
+}
+
+// q[m,k] = |x_m - a_k|^2, p[m,k] = |g|^2 (-1 for frame 0 of a clip) and their clamped reciprocal roots: direct sums of squares, one wave per row
+template <int D>
+__global__ __launch_bounds__(64 * TA_WAVES) void tv_norms_kernel(const float* __restrict__ x, const float* __restrict__ anchors, int64_t BT, int T,
+                                                                 int K, float* __restrict__ q, float* __restrict__ p) {
+    constexpr int N = TpVec<D>::N, V = TpVec<D>::V;
+    float* __restrict__ iqo = q + BT * K;                  // the second halves: 1 / max(norm, 1e-6); 0 where there is no temporal row
+    float* __restrict__ ito = p + BT * K;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nkc = (K + TV_KC - 1) / TV_KC;
+    const int64_t wid = (int64_t)blockIdx.x * TA_WAVES + wave;
+    if (wid >= BT * nkc) return;                           // (wave-uniform; no barrier in this kernel)
+    const int64_t row = wid / nkc;
+    const int k0 = (int)(wid % nkc) * TV_KC, k1 = min(k0 + TV_KC, K);
+    const float* xr = x + row * D;
+    const bool first_frame = row % T == 0;
+    float xv[N], xs[N], a[N];
+    tp_load<D>(xr, lane, xv);
+#pragma unroll
+    for (int j = 0; j < N; ++j) {                          // the frame shifted by one column: element d - 1 (d = 0: D - 1)
+        const int d = (j / V * 64 + lane) * V + j % V;
+        xs[j] = xr[d ? d - 1 : D - 1];
+    }
+    int km1 = (k0 + K - 1) % K;
+    tp_load_anchor<D>(anchors, K, km1, lane, a);
+    float sq = 0.f;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const float r = xv[j] - a[j];
+        sq = fmaf(r, r, sq);
+    }
+    float iq_prev = tv_inv(wave_sum_dpp(sq));
+    for (int k = k0; k < k1; ++k) {
+        tp_load_anchor<D>(anchors, K, k, lane, a);
+        sq = 0.f;
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const float r = xv[j] - a[j];
+            sq = fmaf(r, r, sq);
+        }
+        sq = wave_sum_dpp(sq);
+        const float iq = tv_inv(sq);
+        float pp = -1.f;
+        if (!first_frame) {                                // (wave-uniform)
+            pp = 0.f;
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                const int d = (j / V * 64 + lane) * V + j % V;
+                const float ap = d ? anchors[(int64_t)(d - 1) * K + k] : anchors[(int64_t)(D - 1) * K + km1];
+                const float g = ta_eh(xv[j], a[j], iq) - ta_eh(xs[j], ap, d ? iq : iq_prev);
+                pp = fmaf(g, g, pp);
+            }
+            pp = wave_sum_dpp(pp);
+        }
+        if (lane == 0) {
+            q[row * K + k] = sq;
+            p[row * K + k] = pp;
+            iqo[row * K + k] = iq;
+            ito[row * K + k] = first_frame ? 0.f : tv_inv(pp);
+        }
+        iq_prev = iq;
+        km1 = k;
+    }
+}
+
+// so[m,k,f], to[m,k,f] for 128 rows, one anchor and 32 filters (to = 0 on frame 0 of a clip)
+template <int D>
+__global__ __launch_bounds__(64 * TA_WAVES) void tv_conv_kernel(const float* __restrict__ x, const float* __restrict__ anchors,
+                                                                const float* __restrict__ ws, const float* __restrict__ wt,
+                                                                const float* __restrict__ iq, const float* __restrict__ it, int64_t BT, int K, int F,
+                                                                int NR, float* __restrict__ so, float* __restrict__ to) {
+    __shared__ float tE[TV_ROWS][TA_LD], tH[TV_ROWS][TA_LD], tWs[32][TA_LD], tWt[32][TA_LD];
+    __shared__ float iqs[TV_ROWS], iqp[TV_ROWS], its[TV_ROWS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int NF = (F + 31) / 32;
+    int id = blockIdx.x;
+    const int rt = id % NR; id /= NR;                      // (the row tiles of one weight tile are neighbours)
+    const int ft = id % NF, k = id / NF;
+    const int km1 = (k + K - 1) % K, f0 = ft * 32;
+    const int64_t R0 = (int64_t)rt * TV_ROWS;
+    if (threadIdx.x < TV_ROWS) {
+        const int64_t R = R0 + threadIdx.x;
+        const bool valid = R < BT;
+        iqs[threadIdx.x] = valid ? iq[R * K + k] : 0.f;
+        iqp[threadIdx.x] = valid ? iq[R * K + km1] : 0.f;
+        its[threadIdx.x] = valid ? it[R * K + k] : 0.f;
+    }
+    __syncthreads();
+    const int c = threadIdx.x & 31, r0 = threadIdx.x >> 5;
+    f32x16 acc_s, acc_t;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc_s[r] = acc_t[r] = 0.f;
+    for (int c0 = 0; c0 < D; c0 += TA_CH) {
+        const int d = c0 + c, dp = d ? d - 1 : D - 1;
+        const float av = anchors[(int64_t)d * K + k], ap = anchors[(int64_t)dp * K + (d ? k : km1)];
+#pragma unroll 4
+        for (int i = 0; i < TV_ROWS / 8; ++i) {
+            const int row = r0 + 8 * i;
+            const int64_t R = R0 + row;
+            float xv = 0.f, xp = 0.f;
+            if (R < BT) {
+                xv = x[R * D + d];
+                xp = x[R * D + dp];
+            }
+            const float e = ta_eh(xv, av, iqs[row]);        // (0 outside the rows: the factor is 0 there)
+            const float ep = ta_eh(xp, ap, d ? iqs[row] : iqp[row]);
+            tE[row][c] = e;
+            tH[row][c] = (e - ep) * its[row];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int f = r0 + 8 * i, ff = f0 + f;
+            tWs[f][c] = ff < F ? ws[((int64_t)k * F + ff) * D + d] : 0.f;
+            tWt[f][c] = ff < F ? wt[((int64_t)k * F + ff) * D + d] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < TA_CH; kk += 2) {
+            const int col = kk + (lane >> 5), rr = 32 * wave + (lane & 31);
+            acc_s = mfma32(tE[rr][col], tWs[lane & 31][col], acc_s);
+            acc_t = mfma32(tH[rr][col], tWt[lane & 31][col], acc_t);
+        }
+        __syncthreads();
+    }
+    const int f = f0 + (lane & 31);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int64_t R = R0 + 32 * wave + mfma32_row(r, lane);
+        if (R < BT && f < F) {
+            so[(R * K + k) * F + f] = acc_s[r];
+            to[(R * K + k) * F + f] = acc_t[r];
+        }
+    }
+}
+
+// a thread per (clip, column of [conv | norm]): the mean over the frames, then the mean of the squared deviations from it and the mean of
+// the deviations themselves (corr [2, B, W]: the rounding error of the mean, which the backward takes out again); blockIdx.y = pool
+__global__ __launch_bounds__(256) void tv_moments_kernel(const float* __restrict__ so, const float* __restrict__ to, const float* __restrict__ q,
+                                                         const float* __restrict__ p, int B, int T, int K, int F, float* __restrict__ pool_s,
+                                                         float* __restrict__ pool_t, float* __restrict__ corr) {
+    const int64_t KF = (int64_t)K * F, W = KF + K;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= B * W) return;
+    const int64_t b = i / W, j = i % W;
+    const bool temporal = blockIdx.y == 1, conv = j < KF;
+    const int lo = temporal ? 1 : 0;
+    const float* v = conv ? (temporal ? to : so) + b * T * KF + j : (temporal ? p : q) + b * T * K + (j - KF);
+    const int64_t stride = conv ? KF : K;
+    const float cnt = (float)(T - lo);
+    float tot = 0.f, part = 0.f;
+    for (int t = lo; t < T; ++t) {
+        const float val = conv ? v[t * stride] : sqrtf(v[t * stride]);
+        part += val;
+        if (((t - lo) & (TP_SUM_CHUNK - 1)) == TP_SUM_CHUNK - 1) {
+            tot += part;
+            part = 0.f;
+        }
+    }
+    const float mean = (tot + part) / cnt;
+    tot = part = 0.f;
+    float dtot = 0.f, dpart = 0.f;                         // the deviations' own sum: what the rounded mean is off by, times the count
+    for (int t = lo; t < T; ++t) {
+        const float dev = (conv ? v[t * stride] : sqrtf(v[t * stride])) - mean;
+        part = fmaf(dev, dev, part);
+        dpart += dev;
+        if (((t - lo) & (TP_SUM_CHUNK - 1)) == TP_SUM_CHUNK - 1) {
+            tot += part;
+            dtot += dpart;
+            part = dpart = 0.f;
+        }
+    }
+    float* pool = (temporal ? pool_t : pool_s) + b * 2 * W;
+    pool[j] = mean;
+    pool[W + j] = (tot + part) / cnt;
+    corr[((int64_t)blockIdx.y * B + b) * W + j] = (dtot + dpart) / cnt;
+}
+
+// one wave per (row, anchor): dso, dto [B T, K F]; sa = sum_f dso so + ([p > eps] ? dtau tau : (h . gh)); s1g = (h . gh) [p > eps];
+// dtg = dtau [p > eps]; dn (ungated: tv_s2 gates it); ggb[m,k,r] = gg at column r DR
+template <int D>
+__global__ __launch_bounds__(64 * TA_WAVES) void tv_dout_kernel(const float* __restrict__ x, const float* __restrict__ anchors,
+                                                                const float* __restrict__ wt, const float* __restrict__ q, const float* __restrict__ p,
+                                                                const float* __restrict__ so, const float* __restrict__ to,
+                                                                const float* __restrict__ pool_s, const float* __restrict__ pool_t,
+                                                                const float* __restrict__ corr, const float* __restrict__ g_s,
+                                                                const float* __restrict__ g_t, int64_t BT, int T, int K,
+                                                                int F, int DR, float* __restrict__ dso, float* __restrict__ dto,
+                                                                float* __restrict__ sa, float* __restrict__ s1g, float* __restrict__ dtg,
+                                                                float* __restrict__ dn, float* __restrict__ ggb) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t wid = (int64_t)blockIdx.x * TA_WAVES + wave;
+    if (wid >= BT * K) return;                             // (wave-uniform; no barrier in this kernel)
+    const int64_t R = wid / K;
+    const int k = (int)(wid % K), km1 = (k + K - 1) % K, NDR = D / DR;
+    const int64_t b = R / T, KF = (int64_t)K * F, W = KF + K;
+    const bool has_t = R % T != 0;
+    const float cnt_s = (float)T, cnt_t = (float)(T - 1);
+    const float *iqa = q + BT * K, *ita = p + BT * K;
+    const float *cs = corr + b * W, *ct = corr + (BT / T + b) * W;
+    const float *ps = pool_s + b * 2 * W, *pt = pool_t + b * 2 * W, *gs = g_s + b * 2 * W, *gt = g_t + b * 2 * W;
+    float sso = 0.f, s1 = 0.f, gh[TV_MAX_RANGES];
+#pragma unroll
+    for (int r = 0; r < TV_MAX_RANGES; ++r) gh[r] = 0.f;
+    for (int f = lane; f < F; f += 64) {
+        const int64_t j = (int64_t)k * F + f, o = R * KF + j;
+        const float vs = so[o];
+        const float ds = (gs[j] + 2.f * gs[W + j] * ((vs - ps[j]) - cs[j])) / cnt_s;
+        dso[o] = ds;
+        sso = fmaf(ds, vs, sso);
+        float dt = 0.f;
+        if (has_t) {
+            const float vt = to[o];
+            dt = (gt[j] + 2.f * gt[W + j] * ((vt - pt[j]) - ct[j])) / cnt_t;
+            s1 = fmaf(dt, vt, s1);
+#pragma unroll
+            for (int r = 0; r < TV_MAX_RANGES; ++r)
+                if (r < NDR) gh[r] = fmaf(dt, wt[j * D + r * DR], gh[r]);
+        }
+        dto[o] = dt;
+    }
+    sso = wave_sum_dpp(sso);
+    s1 = wave_sum_dpp(s1);
+#pragma unroll
+    for (int r = 0; r < TV_MAX_RANGES; ++r) gh[r] = wave_sum_dpp(gh[r]);
+    const int64_t m = R * K + k, jn = KF + k;
+    const float qq = q[m], pp = p[m];
+    const float iq = iqa[m], iqm = iqa[R * K + km1], itau = ita[m];
+    const float gp = pp > kL2Eps ? 1.f : 0.f;
+    const float tau = has_t ? sqrtf(pp) : 0.f;
+    const float dtau = has_t ? (gt[jn] + 2.f * gt[W + jn] * ((tau - pt[jn]) - ct[jn])) / cnt_t : 0.f;
+    const float* xr = x + R * D;
+#pragma unroll
+    for (int r = 0; r < TV_MAX_RANGES; ++r) {
+        if (r < NDR && lane == r) {
+            const int d = r * DR, dp = d ? d - 1 : D - 1;
+            const float e = ta_eh(xr[d], anchors[(int64_t)d * K + k], iq);
+            const float ep = ta_eh(xr[dp], anchors[(int64_t)dp * K + (d ? k : km1)], d ? iq : iqm);
+            const float h = (e - ep) * itau;
+            ggb[m * NDR + r] = itau * (gh[r] - h * (s1 * gp)) + (dtau * gp) * h;
+        }
+    }
+    if (lane == 0) {
+        const float n = sqrtf(qq);
+        dn[m] = (gs[jn] + 2.f * gs[W + jn] * ((n - ps[jn]) - cs[jn])) / cnt_s;
+        sa[m] = sso + (gp != 0.f ? dtau * tau : s1);
+        s1g[m] = s1 * gp;
+        dtg[m] = dtau * gp;
+    }
+}
+
+// a thread per (row, anchor): s2g = (e . get) [q > eps], dn *= [q > eps]
+__global__ __launch_bounds__(256) void tv_s2_kernel(const float* __restrict__ x, const float* __restrict__ anchors, const float* __restrict__ q,
+                                                    const float* __restrict__ sa, const float* __restrict__ ggb, int64_t BT, int D, int K, int NDR,
+                                                    float* __restrict__ s2g, float* __restrict__ dn) {
+    const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (m >= BT * K) return;
+    const int64_t R = m / K;
+    const int k = (int)(m % K), km1 = (k + K - 1) % K, kp1 = (k + 1) % K;
+    const float qq = q[m], xl = x[R * D + D - 1];
+    const float* iqa = q + BT * K;
+    const float e_last = ta_eh(xl, anchors[(int64_t)(D - 1) * K + k], iqa[m]);
+    const float e_prev = ta_eh(xl, anchors[(int64_t)(D - 1) * K + km1], iqa[R * K + km1]);
+    const float gq = qq > kL2Eps ? 1.f : 0.f;
+    const float s2 = sa[m] + e_prev * ggb[m * NDR] - e_last * ggb[(R * K + kp1) * NDR];
+    s2g[m] = s2 * gq;
+    dn[m] *= gq;
+}
+
+// dW[k,f,d] = sum_m dout[m,k,f] operand[m,k,d]: a wave owns 32 filters x 32 columns of one anchor and walks all rows
+template <int D>
+__global__ __launch_bounds__(64 * TA_WAVES) void tv_dw_kernel(const float* __restrict__ x, const float* __restrict__ anchors,
+                                                              const float* __restrict__ iqa, const float* __restrict__ ita, const float* __restrict__ dso,
+                                                              const float* __restrict__ dto, int64_t BT, int K, int F, float* __restrict__ dws,
+                                                              float* __restrict__ dwt) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr int NQ = D / (32 * TA_WAVES);
+    const int NF = (F + 31) / 32;
+    int id = blockIdx.x;
+    const int dq = id % NQ; id /= NQ;
+    const int ft = id % NF, k = id / NF;
+    const int km1 = (k + K - 1) % K, f0 = ft * 32, d0 = (dq * TA_WAVES + wave) * 32;
+    const int c = lane & 31, hp = lane >> 5;
+    const int d = d0 + c, dp = d ? d - 1 : D - 1, f = f0 + c;
+    const float av = anchors[(int64_t)d * K + k], ap = anchors[(int64_t)dp * K + (d ? k : km1)];
+    f32x16 tot_s, tot_t;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) tot_s[r] = tot_t[r] = 0.f;
+    for (int64_t rb = 0; rb < BT; rb += TP_SUM_CHUNK) {    // two-level over the rows
+        f32x16 acc_s, acc_t;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc_s[r] = acc_t[r] = 0.f;
+#pragma unroll 4
+        for (int i = 0; i < TP_SUM_CHUNK / 2; ++i) {
+            const int64_t R = rb + 2 * i + hp;
+            float a_s = 0.f, a_t = 0.f, e = 0.f, h = 0.f;
+            if (R < BT) {
+                const float iq = iqa[R * K + k], itau = ita[R * K + k];
+                const float iqp = d ? iq : iqa[R * K + km1];
+                e = ta_eh(x[R * D + d], av, iq);
+                h = (e - ta_eh(x[R * D + dp], ap, iqp)) * itau;
+                if (f < F) {
+                    a_s = dso[(R * K + k) * F + f];
+                    a_t = dto[(R * K + k) * F + f];
+                }
+            }
+            acc_s = mfma32(a_s, e, acc_s);
+            acc_t = mfma32(a_t, h, acc_t);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            tot_s[r] += acc_s[r];
+            tot_t[r] += acc_t[r];
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int ff = f0 + mfma32_row(r, lane);
+        if (ff < F) {
+            dws[((int64_t)k * F + ff) * D + d] = tot_s[r];
+            dwt[((int64_t)k * F + ff) * D + d] = tot_t[r];
+        }
+    }
+}
+
+// dx partials and danchors partials: 128 rows, the d-range dr and the anchors g, g + G, ... per workgroup
+template <int D>
+__global__ __launch_bounds__(64 * TA_WAVES) void tv_dx_kernel(const float* __restrict__ x, const float* __restrict__ anchors,
+                                                              const float* __restrict__ ws, const float* __restrict__ wt, const float* __restrict__ iqa,
+                                                              const float* __restrict__ ita, const float* __restrict__ dso,
+                                                              const float* __restrict__ dto, const float* __restrict__ s1g_,
+                                                              const float* __restrict__ dtg_, const float* __restrict__ s2g_,
+                                                              const float* __restrict__ dng_, const float* __restrict__ ggb, int64_t BT, int K, int F,
+                                                              int DR, int G, float* __restrict__ dx_part, float* __restrict__ da_part) {
+    __shared__ float tA[TV_ROWS][TA_LD], tB[TV_ROWS][TA_LD], tG[TV_ROWS][TA_LD];
+    __shared__ float halo[2][TV_ROWS], iqs[TV_ROWS], iqp[TV_ROWS], its[TV_ROWS], s1g[TV_ROWS], dtg[TV_ROWS], s2g[TV_ROWS], dng[TV_ROWS];
+    __shared__ float dacc[8 * 32];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int NDR = D / DR;
+    int id = blockIdx.x;
+    const int dr = id % NDR; id /= NDR;
+    const int g = id % G, rt = id / G;
+    const int64_t R0 = (int64_t)rt * TV_ROWS;
+    const int c = threadIdx.x & 31, r0 = threadIdx.x >> 5, hp = lane >> 5;
+    // this workgroup's own [128, D] block (dx itself when G == 1: rows past the end are never touched)
+    float* dxo = G > 1 ? dx_part + ((int64_t)rt * G + g) * TV_ROWS * D : dx_part + R0 * D;
+    for (int k = g; k < K; k += G) {
+        const bool first = k == g;
+        const int km1 = (k + K - 1) % K;
+        __syncthreads();
+        if (threadIdx.x < TV_ROWS) {
+            const int row = threadIdx.x;
+            const int64_t R = R0 + row, m = R * K + k;
+            const bool valid = R < BT;
+            iqs[row] = valid ? iqa[m] : 0.f;
+            iqp[row] = valid ? iqa[R * K + km1] : 0.f;
+            its[row] = valid ? ita[m] : 0.f;
+            s1g[row] = valid ? s1g_[m] : 0.f;
+            dtg[row] = valid ? dtg_[m] : 0.f;
+            s2g[row] = valid ? s2g_[m] : 0.f;
+            dng[row] = valid ? dng_[m] : 0.f;
+            // gg of the column behind the range: the next range's first column, or column 0 of the next anchor
+            const bool wrap = (dr + 1) * DR == D;
+            halo[0][row] = valid ? (wrap ? ggb[(R * K + (k + 1) % K) * NDR] : ggb[m * NDR + dr + 1]) : 0.f;
+        }
+        __syncthreads();
+        int hb = 0;
+        for (int c0 = (dr + 1) * DR - TA_CH; c0 >= dr * DR; c0 -= TA_CH) {      // from the top of the range down
+            const int d = c0 + c, dp = d ? d - 1 : D - 1;
+            const float av = anchors[(int64_t)d * K + k], ap = anchors[(int64_t)dp * K + (d ? k : km1)];
+            f32x16 acc_e, acc_h;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc_e[r] = acc_h[r] = 0.f;
+            for (int f0 = 0; f0 < F; f0 += 32) {
+                const int ff = f0 + c;
+#pragma unroll 4
+                for (int i = 0; i < TV_ROWS / 8; ++i) {
+                    const int row = r0 + 8 * i;
+                    const int64_t R = R0 + row;
+                    const bool in = R < BT && ff < F;
+                    tA[row][c] = in ? dso[(R * K + k) * F + ff] : 0.f;
+                    tB[row][c] = in ? dto[(R * K + k) * F + ff] : 0.f;
+                }
+                __syncthreads();
+#pragma unroll
+                for (int kk = 0; kk < 32; kk += 2) {
+                    const int fc = kk + hp, fw = f0 + fc, rr = 32 * wave + (lane & 31);
+                    const float bs = fw < F ? ws[((int64_t)k * F + fw) * D + d] : 0.f;
+                    const float bt = fw < F ? wt[((int64_t)k * F + fw) * D + d] : 0.f;
+                    acc_e = mfma32(tA[rr][fc], bs, acc_e);
+                    acc_h = mfma32(tB[rr][fc], bt, acc_h);
+                }
+                __syncthreads();
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = 32 * wave + mfma32_row(r, lane);
+                tA[row][lane & 31] = acc_e[r];              // ge
+                tB[row][lane & 31] = acc_h[r];              // gh
+            }
+            __syncthreads();
+            float ev[TV_ROWS / 8];
+#pragma unroll 4
+            for (int i = 0; i < TV_ROWS / 8; ++i) {
+                const int row = r0 + 8 * i;
+                const int64_t R = R0 + row;
+                float xv = 0.f, xp = 0.f;
+                if (R < BT) {
+                    xv = x[R * D + d];
+                    xp = x[R * D + dp];
+                }
+                const float e = ta_eh(xv, av, iqs[row]);
+                const float h = (e - ta_eh(xp, ap, d ? iqs[row] : iqp[row])) * its[row];
+                const float gg = its[row] * (tB[row][c] - h * s1g[row]) + dtg[row] * h;
+                tG[row][c] = gg;
+                if (c == 0) halo[hb ^ 1][row] = gg;
+                ev[i] = e;
+            }
+            __syncthreads();
+            float da = 0.f;
+#pragma unroll 4
+            for (int i = 0; i < TV_ROWS / 8; ++i) {
+                const int row = r0 + 8 * i;
+                const int64_t R = R0 + row;
+                const float nxt = c < 31 ? tG[row][c + 1] : halo[hb][row];
+                const float get = tA[row][c] + tG[row][c] - nxt;
+                const float gr = iqs[row] * (get - ev[i] * s2g[row]) + dng[row] * ev[i];
+                if (R < BT) {
+                    float* o = dxo + (int64_t)row * D + d;
+                    *o = first ? gr : *o + gr;             // (an earlier anchor of this workgroup: this thread wrote it)
+                    da += gr;
+                }
+            }
+            dacc[r0 * 32 + c] = da;
+            __syncthreads();
+            if (threadIdx.x < 32) {
+                float acc_a = dacc[c];
+                for (int r = 1; r < 8; ++r) acc_a += dacc[r * 32 + c];
+                da_part[((int64_t)rt * K + k) * D + d] = acc_a;
+            }
+            hb ^= 1;
+            __syncthreads();
+        }
+    }
+}
+
+// dx[m] = sum_g dx_part[tile(m)][g][m - tile start], g = 0, 1, ...
+__global__ __launch_bounds__(256) void tv_dx_reduce_kernel(const float* __restrict__ part, int64_t total, int D, int G, float* __restrict__ dx) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int64_t R = i / D, rt = R / TV_ROWS, blk = (int64_t)TV_ROWS * D;
+    const float* pp = part + rt * G * blk + (i - rt * blk);
+    float acc = pp[0];
+    for (int g = 1; g < G; ++g) acc += pp[g * blk];
+    dx[i] = acc;
+}
+
+static int tv_check(const char* name, int B, int T, int D, int K, int F) {
+    if (const int rc = ta_check(name, B, T, D, K)) return rc;
+    LPM_REQUIRE(F >= 1, LPM_ERR_BADARG, "%s: need F >= 1 (F=%d)", name, F);
+    const int64_t BT = (int64_t)B * T, NF = (F + 31) / 32;
+    LPM_REQUIRE(BT * K * F < (1ll << 31) && (int64_t)K * NF * (D / 128) < (1ll << 31), LPM_ERR_UNSUPPORTED_SHAPE,
+                "%s: B * T * K * F or K * F * D too large (B=%d T=%d K=%d F=%d)", name, B, T, K, F);
+    return LPM_OK;
+}
+
+}  // namespace lpm
+
+extern "C" size_t lpm_triangulation_moments_workspace_bytes(int B, int T, int D, int K, int F) {
+    using namespace lpm;
+    if (B <= 0 || T <= 1 || K <= 0 || F <= 0 || (D != 128 && D != 1024)) return 0;
+    const size_t BT = (size_t)B * T, NRT = tv_row_tiles(BT), NDR = D / tv_range(D), G = tv_groups(BT, D, K);
+    // dso, dto; sa, s1g, dtg, dn, s2g; ggb; danchors partials; dx partials
+    return (2 * BT * K * F + (5 + NDR) * BT * K + NRT * K * D + (G > 1 ? NRT * G * TV_ROWS * D : 0)) * sizeof(float);
+}
+
+extern "C" int lpm_triangulation_moments_fwd(const float* x, const float* anchors, const float* cnn_s, const float* cnn_t, int B, int T, int D,
+                                             int K, int F, float* q, float* p, float* so, float* to, float* pool_s, float* pool_t,
+                                             float* corr, lpm_stream_t stream) {
+    using namespace lpm;
+    const char* name = "lpm_triangulation_moments_fwd";
+    LPM_REQUIRE(x && anchors && cnn_s && cnn_t && q && p && so && to && pool_s && pool_t && corr, LPM_ERR_BADARG, "%s: null pointer", name);
+    if (const int rc = tv_check(name, B, T, D, K, F)) return rc;
+    LPM_REQUIRE(((uintptr_t)x & 15) == 0, LPM_ERR_BADARG, "%s: x must be 16-byte aligned", name);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t BT = (int64_t)B * T;
+    const int NR = tv_row_tiles(BT), NF = (F + 31) / 32;
+    const dim3 block(64 * TA_WAVES);
+    const dim3 grid_n((unsigned)((BT * ((K + TV_KC - 1) / TV_KC) + TA_WAVES - 1) / TA_WAVES)), grid_c((unsigned)((int64_t)K * NF * NR));
+    if (D == 1024) {
+        hipLaunchKernelGGL(tv_norms_kernel<1024>, grid_n, block, 0, s, x, anchors, BT, T, K, q, p);
+        hipLaunchKernelGGL(tv_conv_kernel<1024>, grid_c, block, 0, s, x, anchors, cnn_s, cnn_t, q + BT * K, p + BT * K, BT, K, F, NR, so, to);
+    } else {
+        hipLaunchKernelGGL(tv_norms_kernel<128>, grid_n, block, 0, s, x, anchors, BT, T, K, q, p);
+        hipLaunchKernelGGL(tv_conv_kernel<128>, grid_c, block, 0, s, x, anchors, cnn_s, cnn_t, q + BT * K, p + BT * K, BT, K, F, NR, so, to);
+    }
+    const int64_t cols = (int64_t)B * ((int64_t)K * F + K);
+    hipLaunchKernelGGL(tv_moments_kernel, dim3((unsigned)((cols + 255) / 256), 2), dim3(256), 0, s, so, to, q, p, B, T, K, F, pool_s, pool_t, corr);
+    return check_launch(name);
+}
+
+extern "C" int lpm_triangulation_moments_bwd(const float* x, const float* anchors, const float* cnn_s, const float* cnn_t, const float* q,
+                                             const float* p, const float* so, const float* to, const float* pool_s, const float* pool_t,
+                                             const float* corr, const float* g_s, const float* g_t, int B, int T, int D, int K, int F, float* dx, float* danchors,
+                                             float* dcnn_s, float* dcnn_t, void* workspace, size_t workspace_bytes, lpm_stream_t stream) {
+    using namespace lpm;
+    const char* name = "lpm_triangulation_moments_bwd";
+    LPM_REQUIRE(x && anchors && cnn_s && cnn_t && q && p && so && to && pool_s && pool_t && corr && g_s && g_t && dx && danchors && dcnn_s && dcnn_t,
+                LPM_ERR_BADARG, "%s: null pointer", name);
+    if (const int rc = tv_check(name, B, T, D, K, F)) return rc;
+    LPM_REQUIRE(workspace && workspace_bytes >= lpm_triangulation_moments_workspace_bytes(B, T, D, K, F), LPM_ERR_WORKSPACE,
+                "%s: workspace too small", name);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t BT = (int64_t)B * T, BTK = BT * K;
+    const int DR = tv_range(D), NDR = D / DR, NRT = tv_row_tiles(BT), G = tv_groups(BT, D, K), NF = (F + 31) / 32;
+    float* dso = (float*)workspace;
+    float* dto = dso + BTK * F;
+    float* sa = dto + BTK * F;
+    float *s1g = sa + BTK, *dtg = s1g + BTK, *dn = dtg + BTK, *s2g = dn + BTK, *ggb = s2g + BTK;
+    float* da_part = ggb + BTK * NDR;
+    float* dx_part = G > 1 ? da_part + (int64_t)NRT * K * D : dx;
+    const dim3 block(64 * TA_WAVES);
+    const dim3 grid_o((unsigned)((BTK + TA_WAVES - 1) / TA_WAVES)), grid_w((unsigned)((int64_t)K * NF * (D / (32 * TA_WAVES)))),
+        grid_x((unsigned)((int64_t)NRT * G * NDR));
+#define TV_LAUNCH_BWD(DD)                                                                                                                       \
+    hipLaunchKernelGGL(tv_dout_kernel<DD>, grid_o, block, 0, s, x, anchors, cnn_t, q, p, so, to, pool_s, pool_t, corr, g_s, g_t, BT, T, K, F, DR, dso, \
+                       dto, sa, s1g, dtg, dn, ggb);                                                                                             \
+    hipLaunchKernelGGL(tv_s2_kernel, dim3((unsigned)((BTK + 255) / 256)), dim3(256), 0, s, x, anchors, q, sa, ggb, BT, D, K, NDR, s2g, dn);     \
+    hipLaunchKernelGGL(tv_dw_kernel<DD>, grid_w, block, 0, s, x, anchors, q + BTK, p + BTK, dso, dto, BT, K, F, dcnn_s, dcnn_t);                            \
+    hipLaunchKernelGGL(tv_dx_kernel<DD>, grid_x, block, 0, s, x, anchors, cnn_s, cnn_t, q + BTK, p + BTK, dso, dto, s1g, dtg, s2g, dn, ggb, BT, K, F, DR, G, \
+                       dx_part, da_part)
+    if (D == 1024) { TV_LAUNCH_BWD(1024); } else { TV_LAUNCH_BWD(128); }
+#undef TV_LAUNCH_BWD
+    if (G > 1) {
+        const int64_t total = BT * D;
+        hipLaunchKernelGGL(tv_dx_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, dx_part, total, D, G, dx);
+    }
+    // danchors[d][k] = - sum over the row tiles, in order (the dx partials are reduced above: the tiles are not clips)
+    if (const int rc = ta_reduce_partials(dx, da_part, NRT, TV_ROWS, D, K, 1, dx, danchors, s, name)) return rc;
+    return check_launch(name);
+}

@@ -92,6 +92,20 @@ FLAGS.define("triangulation_cnn_fused", True, "build extension: on the GPU each 
              "ops.triangulation_cnn_pool call (csrc/triangulation_mean.hip: the Gram, the softmax weights and the two pooled means without "
              "any [B, T, K*D] tensor, then the per-anchor convolution on the pooled means); False: the materialising modules of "
              "video_pooling_modules / aggregation_modules compose it (the CPU path; same variables, same results)")
+FLAGS.define("jtmv5_iteration", 30, "JuhanTestModelV5 (frame_level_models.py:491): sampled frames per clip")
+FLAGS.define("jtmv5_add_batch_norm", True, "JuhanTestModelV5 (:493): batch norm on the streams and inside each stream's module")
+FLAGS.define("jtmv5_video_anchor_size", 256, "JuhanTestModelV5 (:497): anchors of the video stream")
+FLAGS.define("jtmv5_audio_anchor_size", 32, "JuhanTestModelV5 (:499): anchors of the audio stream")
+FLAGS.define("jtmv5_video_kernel_size", 512, "JuhanTestModelV5 (:501): filters per anchor of the video stream's two convolutions")
+FLAGS.define("jtmv5_audio_kernel_size", 64, "JuhanTestModelV5 (:503): filters per anchor of the audio stream's two convolutions")
+FLAGS.define("jtmv5_video_hidden", 2048, "JuhanTestModelV5 (:505): width of the video stream's two hidden layers")
+FLAGS.define("jtmv5_video_output_dim", 4096, "JuhanTestModelV5 (:507): width of the video stream's fused output")
+FLAGS.define("jtmv5_audio_hidden", 256, "JuhanTestModelV5 (:509): width of the audio stream's two hidden layers")
+FLAGS.define("jtmv5_audio_output_dim", 512, "JuhanTestModelV5 (:511): width of the audio stream's fused output")
+FLAGS.define("triangulation_v5_fused", True, "build extension: on the GPU each stream of JuhanTestModelV5 is ONE ops.triangulation_cnn_moments "
+             "call (csrc/triangulation_moments.hip: the per-anchor convolutions of the embedding and of its rolled differences over every "
+             "frame, and the mean and variance over the frames, without any [B, T, K*D] tensor); False: TriangulationV5Module.forward "
+             "materialises it (the CPU path; same variables, same results)")
 FLAGS.define("wtm_projection_l1", 1e-5, "layers.l1_l2_regularizer(1e-5) on dis_projection_2 / temp_projection_2 (frame_level_models.py:1272,1287): "
              "tf.contrib's first positional argument is scale_l1")
 FLAGS.define("wtm_projection_l2", 1.0, "... and its scale_l2 keeps the default 1.0: the penalty is l1 * sum |w| + l2 * sum(w^2) / 2 (SURVEY App. B)")

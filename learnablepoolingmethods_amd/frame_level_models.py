@@ -1,6 +1,7 @@
 """NetVLAD prototypes behind the reference's model-registry API
 (reference: frame_level_models.py:2193-2513 NetVladV1 / NetVladV2, :2765-2877 NetVLAD / LightVLAD) and the triangulation-embedding
-family's RegularizedTriangulationModel (:1148-1307) and SoftAttentionTriangulationModel (:965-1145).
+family's RegularizedTriangulationModel (:1148-1307), SoftAttentionTriangulationModel (:965-1145), TriangulationCnnClusterModel
+(:757-939) and JuhanTestModelV5 (:491-606).
 
 Same names, ``create_model`` signature, variable names and output contract as the reference; the hot
 ops (frame sampling + input_bn, soft-assignment GEMM, fused softmax/residual aggregation/normalise,
@@ -543,6 +544,64 @@ class TriangulationCnnClusterModel(models.BaseModel):
         aggregated_model = getattr(video_level_models, "ClassLearningFourNnModel")
         return aggregated_model().create_model(model_input=activation, vocab_size=vocab_size, is_training=is_training,
                                                **unused_params)                                              # :933-939
+
+
+class JuhanTestModelV5(models.BaseModel):
+    """Batch norm of both streams, one TriangulationV5Module per stream (the per-anchor convolutions of the triangulation embedding and
+    of its rolled differences over EVERY frame, the mean and variance over the frames, two hidden layers and a fusion layer) and the
+    four-layer batch-norm classifier (frame_level_models.py:491-606).  As written: SURVEY App. C29-C31 (and C23, C24).
+
+    On the GPU with FLAGS.triangulation_v5_fused each stream's pooling is ONE ops.triangulation_cnn_moments call: neither embedding
+    [B, T, D*K] (31 MB per clip at the defaults T = 30, K = 256, D = 1024) is written; otherwise TriangulationV5Module.forward
+    materialises them.  The variables and the results are the same either way.  ``frame_uniform`` [B, iterations] replaces the random
+    draw of SampleRandomFrames; ``video_anchor_size``, ``audio_anchor_size``, ``video_kernel_size``, ``audio_kernel_size``,
+    ``video_hidden``, ``audio_hidden``, ``video_output_dim`` and ``audio_output_dim`` override the flags (the reference reads the flags
+    only)."""
+
+    def create_model(self, model_input, vocab_size, num_frames, iterations=None, add_batch_norm=None, sample_random_frames=None,
+                     hidden_size=None, is_training=True, frame_uniform=None, video_anchor_size=None, audio_anchor_size=None,
+                     video_kernel_size=None, audio_kernel_size=None, video_hidden=None, audio_hidden=None, video_output_dim=None,
+                     audio_output_dim=None, **unused_params):
+        iterations = iterations or FLAGS.jtmv5_iteration                                                      # :526
+        add_batch_norm = add_batch_norm or FLAGS.jtmv5_add_batch_norm                                         # :527 (C23)
+        video_anchor_size = int(video_anchor_size or FLAGS.jtmv5_video_anchor_size)                           # :528-535
+        audio_anchor_size = int(audio_anchor_size or FLAGS.jtmv5_audio_anchor_size)
+        video_kernel_size = int(video_kernel_size or FLAGS.jtmv5_video_kernel_size)
+        audio_kernel_size = int(audio_kernel_size or FLAGS.jtmv5_audio_kernel_size)
+        video_hidden = int(video_hidden or FLAGS.jtmv5_video_hidden)
+        audio_hidden = int(audio_hidden or FLAGS.jtmv5_audio_hidden)
+        video_output_dim = int(video_output_dim or FLAGS.jtmv5_video_output_dim)
+        audio_output_dim = int(audio_output_dim or FLAGS.jtmv5_audio_output_dim)
+        # sample_random_frames and hidden_size are accepted and read nowhere, as written (C30)
+        model_input = model_utils.SampleRandomFrames(model_input, num_frames.reshape(-1, 1), iterations, uniform=frame_uniform)  # :537-538
+        max_frames, feature_size = model_input.shape[1], model_input.shape[2]
+        if feature_size <= 1024:
+            raise ValueError("JuhanTestModelV5 slices a 1024-wide video and a 128-wide audio stream out of its input "
+                             f"(frame_level_models.py:546-547); got {feature_size} features")
+        dev = model_input.device
+        reshaped_input = model_input.reshape(-1, feature_size)
+        streams = (("video", 1024, video_anchor_size, video_kernel_size, video_hidden, video_output_dim, slice(0, 1024)),
+                   ("audio", feature_size - 1024, audio_anchor_size, audio_kernel_size, audio_hidden, audio_output_dim, slice(1024, None)))
+        features = []
+        for name, *_, cols in streams:                                                                        # :546-562
+            x = reshaped_input[:, cols]
+            features.append(layers.batch_norm(x, is_training, name + "_bn") if add_batch_norm else x)
+        v5_modules = [video_pooling_modules.TriangulationV5Module(
+            feature_size=D, max_frames=max_frames, anchor_size=K, kernel_size=F, self_attention=False, hidden_layer_size=H, output_dim=O,
+            add_relu=True, batch_norm=add_batch_norm, is_training=is_training, scope_id=None) for _, D, K, F, H, O, _ in streams]   # :564-588
+        fused = bool(FLAGS.triangulation_v5_fused and reshaped_input.is_cuda and max_frames >= 2)
+        acts = []
+        for (name, *_), x, module in zip(streams, features, v5_modules):
+            with vs.variable_scope(name + "_triangulation_embedding"):                                        # :590-596
+                if fused:
+                    anchors, cnn_s, cnn_t = module.variables(dev)
+                    acts.append(module.head(*ops.triangulation_cnn_moments(x.contiguous(), anchors, cnn_s, cnn_t, max_frames)))
+                else:
+                    acts.append(module.forward(x))
+        activation = torch.cat(acts, 1)                                                                       # :598
+        aggregated_model = getattr(video_level_models, "FourLayerBatchNeuralModel")
+        return aggregated_model().create_model(model_input=activation, vocab_size=vocab_size, is_training=is_training,
+                                               **unused_params)                                              # :600-606
 
 
 class NetVladV2(models.BaseModel):

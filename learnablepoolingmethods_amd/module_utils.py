@@ -1,4 +1,4 @@
-"""Regularisers (reference: module_utils.py:55-90)."""
+"""Regularisers (reference: module_utils.py:55-90) and reduce_var (:93-106)."""
 import numbers
 
 import torch
@@ -22,3 +22,10 @@ def orthogonal_regularizer(scale, scope=None):
         det_reg = w.t().matmul(w) - torch.eye(w.shape[1], dtype=w.dtype, device=w.device)
         return scale * det_reg.abs().sum()
     return orthogonal_sum
+
+
+def reduce_var(x, axis=None, keep_dim=False):
+    """Variance of a tensor along ``axis`` (all elements for None): the mean of squared deviations from the mean (module_utils.py:93-106)."""
+    dims = tuple(range(x.dim())) if axis is None else axis
+    m = x.mean(dim=dims, keepdim=True)
+    return ((x - m) ** 2).mean(dim=dims, keepdim=keep_dim)

@@ -4176,3 +4176,68 @@ def triangulation_cnn_pool(x, anchors, cnn_d, cnn_t, max_frames, scale=1.0):
         agg = [torch.bmm(m.view(B, K, D).transpose(0, 1), cnn.transpose(1, 2)).transpose(0, 1).reshape(B, K * cnn.shape[1])
                for m, cnn in ((m_d, cnn_d), (m_t, cnn_t))]
     return agg[0], agg[1]
+
+
+# ----------------------------------------------------------------------------------------------
+# pooled convolution moments of the triangulation embedding: TriangulationV5Module's pooling (csrc/triangulation_moments.hip)
+# ----------------------------------------------------------------------------------------------
+class _TriangulationCnnMoments(torch.autograd.Function):
+    """The saved state is the inputs, the squared norms and their reciprocal roots q, p [2, B*T, K], the convolutions' results so, to [B*T, K*F] (the gradient of a
+    variance needs every frame's value) and the two pools (their mean halves); e and h are recomputed in the backward, whose workspace
+    lives for that call only."""
+
+    @staticmethod
+    def forward(ctx, x, anchors, cnn_s, cnn_t, T):
+        lib = _capi.load()
+        D, K = anchors.shape
+        F = cnn_s.shape[1]
+        B = x.shape[0] // T
+        q, p = _empty((2, B * T, K), x), _empty((2, B * T, K), x)      # squared norms; their clamped reciprocal roots
+        so, to = _empty((B * T, K * F), x), _empty((B * T, K * F), x)
+        pool_s, pool_t = _empty((B, 2 * (K * F + K)), x), _empty((B, 2 * (K * F + K)), x)
+        corr = _empty((2, B, K * F + K), x)                             # what each column's rounded mean is off by
+        with _timed("triangulation_moments_fwd", (B, T, D, K, F)):
+            lib.check(lib._lpm_triangulation_moments_fwd(ptr(x), ptr(anchors), ptr(cnn_s), ptr(cnn_t), B, T, D, K, F, ptr(q), ptr(p), ptr(so),
+                                                         ptr(to), ptr(pool_s), ptr(pool_t), ptr(corr), stream_ptr()), "lpm_triangulation_moments_fwd")
+        ctx.save_for_backward(x, anchors, cnn_s, cnn_t, q, p, so, to, pool_s, pool_t, corr)
+        ctx.dims = (B, T, D, K, F)
+        return pool_s, pool_t
+
+    @staticmethod
+    def backward(ctx, g_s, g_t):
+        lib = _capi.load()
+        x, anchors, cnn_s, cnn_t, q, p, so, to, pool_s, pool_t, corr = ctx.saved_tensors
+        B, T, D, K, F = ctx.dims
+        g_s, g_t = g_s.contiguous(), g_t.contiguous()
+        dx, danchors, dcnn_s, dcnn_t = torch.empty_like(x), torch.empty_like(anchors), torch.empty_like(cnn_s), torch.empty_like(cnn_t)
+        wsb = int(lib._lpm_triangulation_moments_workspace_bytes(B, T, D, K, F))
+        ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+        with _timed("triangulation_moments_bwd", (B, T, D, K, F)):
+            lib.check(lib._lpm_triangulation_moments_bwd(ptr(x), ptr(anchors), ptr(cnn_s), ptr(cnn_t), ptr(q), ptr(p), ptr(so), ptr(to),
+                                                         ptr(pool_s), ptr(pool_t), ptr(corr), ptr(g_s), ptr(g_t), B, T, D, K, F, ptr(dx), ptr(danchors),
+                                                         ptr(dcnn_s), ptr(dcnn_t), ptr(ws), wsb, stream_ptr()), "lpm_triangulation_moments_bwd")
+        return dx, danchors, dcnn_s, dcnn_t, None
+
+
+def triangulation_cnn_moments(x, anchors, cnn_s, cnn_t, max_frames):
+    """One stream of TriangulationV5Module's pooling (video_pooling_modules.py:182-276; csrc/triangulation_moments.hip): x [B * max_frames, D]
+    (a clip's rows contiguous), anchors [D, K] as they are (NOT normalised), ``cnn_s``, ``cnn_t`` [K, F, D] as the variables are stored ->
+    (spatial_pool, temporal_pool), each [B, 2 (K*F + K)] = [mean | variance] over the frames of [convolution (element k * F + f) | norm]:
+        n = |x - a_k|, e = l2_normalize(x - a_k);  g = e - roll(e, 1) over the FEATURE axis of the flattened [K*D] row, frame 0 dropped;
+        tau = |g|, h = l2_normalize(g);  spatial: [<cnn_s[k,f], e_k> | n] over max_frames frames, temporal: [<cnn_t[k,f], h_k> | tau] over
+        max_frames - 1.
+    The variance is the mean of squared deviations from the mean.  Differentiable in all four tensors; where a squared norm does not
+    exceed 1e-12 the gradient of that norm output is zero.  Nothing of size B * T * K * D is written.  GPU only; D in
+    TRIANGULATION_FEATURES, 2 <= max_frames <= 320, contiguous fp32 input; the same inputs give the same bits."""
+    what = "triangulation_cnn_moments"
+    T = _attention_args(what, x, anchors, max_frames)
+    D, K = anchors.shape
+    for name, cnn in (("cnn_s", cnn_s), ("cnn_t", cnn_t)):
+        if not torch.is_tensor(cnn) or cnn.dim() != 3 or cnn.shape[0] != K or cnn.shape[2] != D or cnn.shape[1] < 1:
+            raise LpmError(f"{what}: {name} must be [K, F, D] = [{K}, F, {D}] (got {tuple(cnn.shape) if torch.is_tensor(cnn) else type(cnn)})")
+        _f32(cnn, f"{what} {name}")
+        if cnn.device != x.device:
+            raise LpmError(f"{what}: {name} is on {cnn.device}, x on {x.device}")
+    if cnn_s.shape != cnn_t.shape:
+        raise LpmError(f"{what}: cnn_s {tuple(cnn_s.shape)} and cnn_t {tuple(cnn_t.shape)} must have one shape")
+    return _TriangulationCnnMoments.apply(x, anchors.contiguous(), cnn_s.contiguous(), cnn_t.contiguous(), T)

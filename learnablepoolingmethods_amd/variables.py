@@ -136,9 +136,14 @@ def ones_initializer():
 
 
 def glorot_uniform_initializer():
-    """tf.layers.dense default kernel init / slim xavier_initializer (uniform)."""
+    """tf.layers.dense default kernel init / slim xavier_initializer (uniform).  Beyond two dimensions the leading ones are the
+    receptive field, as in TF (fan_in = shape[-2] * prod(shape[:-2]), fan_out = shape[-1] * prod(shape[:-2])): a [K, F, D] variable
+    draws from +-sqrt(6 / (K (F + D)))."""
     def init(shape, dev, gen):
         fan_in, fan_out = shape[0], shape[-1]
+        if len(shape) > 2:
+            receptive = math.prod(shape[:-2])
+            fan_in, fan_out = shape[-2] * receptive, shape[-1] * receptive
         lim = math.sqrt(6.0 / (fan_in + fan_out))
         return (torch.rand(shape, device=dev, generator=gen) * 2 - 1) * lim
     return init

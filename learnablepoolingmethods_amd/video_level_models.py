@@ -1,4 +1,5 @@
-"""MoeModel (reference: video_level_models.py:48-158), ClassLearningThreeNnModel (:687-714) and ClassLearningFourNnModel (:717-749) --
+"""MoeModel (reference: video_level_models.py:48-158), FourLayerBatchNeuralModel (:625-684), ClassLearningThreeNnModel (:687-714) and
+ClassLearningFourNnModel (:717-749) --
 host-side PyTorch per the north-star."""
 from __future__ import annotations
 
@@ -77,6 +78,25 @@ class MoeModel(models.BaseModel):
             gates = layers.batch_norm(gates, is_training, "gating_prob_bn")                                # :149-154
             probabilities = probabilities * torch.sigmoid(gates)                                           # :156-158
         return {"predictions": probabilities}                                                             # :158
+
+
+class FourLayerBatchNeuralModel(models.BaseModel):
+    """Four bias-free layers of width vocab_size (video_level_models.py:625-684): relu BEFORE batch norm on the first three
+    (``fc{1,2,3}_weights``, ``fc{1,2,3}_activation_bn``), then ``fc4_weights`` with ``fc4_bias`` (initialised to 0.01) and a sigmoid.
+    Every weight is xavier; ``l2_penalty`` is accepted and read nowhere, as written (no regulariser is attached)."""
+
+    def create_model(self, model_input, vocab_size, is_training=True, l2_penalty=1e-7, **unused_params):
+        from . import layers
+        dev = model_input.device
+        h = model_input
+        for i in (1, 2, 3):                                                             # :632-670
+            w = vs.get_variable(f"fc{i}_weights", [h.shape[1], vocab_size], vs.glorot_uniform_initializer(), device=dev)
+            vs.summary(f"fc{i}_weights", w)
+            h = layers.batch_norm(torch.relu(h.matmul(w)), is_training, f"fc{i}_activation_bn")
+        fc4_weights = vs.get_variable("fc4_weights", [vocab_size, vocab_size], vs.glorot_uniform_initializer(), device=dev)   # :672-675
+        fc4_bias = vs.get_variable("fc4_bias", [vocab_size], lambda shape, d, gen: torch.full(shape, 0.01, device=d), device=dev)
+        vs.summary("fc4_bias", fc4_bias)
+        return {"predictions": torch.sigmoid(h.matmul(fc4_weights) + fc4_bias)}          # :680-684
 
 
 def _class_learning_fc(x, scope, biases, vocab_size, l2_penalty):

@@ -1,8 +1,11 @@
 """NetVladOrthoReg and NetVladAttenCluster (reference: video_pooling_modules.py:1499-1586, 1589-1663) and the triangulation
-embeddings (TriangulationEmbedding :376-428, WeightedTriangulationEmbedding :1395-1459, TriangulationTemporalEmbedding :1462-1497)."""
+embeddings (TriangulationEmbedding :376-428, WeightedTriangulationEmbedding :1395-1459, TriangulationTemporalEmbedding :1462-1497,
+TriangulationV5Module :142-373)."""
 from __future__ import annotations
 
 import math
+
+import torch
 
 from . import layers, module_utils, modules, ops, transformer_utils
 from . import variables as vs
@@ -189,3 +192,86 @@ class TriangulationTemporalEmbedding(modules.BaseModule):
         x = inputs.reshape(-1, self.max_frames, self.anchor_size, self.feature_size)
         temp_info = layers.l2_normalize(x[:, 1:] - x[:, :-1], 3)                                   # :1485-1490, frame 0 dropped (:1494-1496)
         return temp_info.reshape(-1, self.max_frames - 1, self.feature_size * self.anchor_size)
+
+
+class TriangulationV5Module(modules.BaseModule):
+    """:142-373 (JuhanTestModelV5's module): the triangulation embedding of every frame against the anchors AS THEY ARE (xavier, not
+    normalised) and its "temporal" part -- ``tf.manip.roll(spatial, shift=1, axis=1)`` of the 2-D [(B*T), K*D] tensor rolls the FEATURE
+    axis (:216): g[t,k,d] = e[t,k,d] - e[t,k,d-1] with e[t,k,-1] = e[t,(k-1) mod K, D-1], frame 0 dropped -- a 1x1
+    convolution per anchor over each (``spatial_cnn_weights``, ``temporal_cnn_weights`` [K, F, D]), the two tf.norm columns appended, the
+    mean and reduce_var over the frames, and per stream batch norm, two hidden layers with batch norm and relu, then the fusion layer.
+    ``self_attention``, ``add_relu`` and ``scope_id``'s absence aside, the arguments are the reference's; ``self_attention`` and
+    ``add_relu`` are stored and read nowhere (C30).  ``forward`` MATERIALISES [(B*T), K*D] twice: the drop-in surface and the CPU path;
+    ``variables`` + ops.triangulation_cnn_moments + ``head`` is the fused one."""
+
+    def __init__(self, feature_size, max_frames, anchor_size, self_attention, hidden_layer_size, kernel_size, output_dim, add_relu,
+                 batch_norm, is_training, scope_id=None):
+        self.feature_size = feature_size
+        self.max_frames = max_frames
+        self.anchor_size = int(anchor_size)
+        self.self_attention = self_attention
+        self.hidden_layer_size = int(hidden_layer_size)
+        self.kernel_size = int(kernel_size)
+        self.output_dim = int(output_dim)
+        self.add_relu = add_relu
+        self.batch_norm = batch_norm
+        self.is_training = is_training
+        self.scope_id = scope_id
+
+    def variables(self, device):
+        """(anchor_weights [D, K], spatial_cnn_weights, temporal_cnn_weights [K, F, D]) without a forward, created in the reference's
+        order (:190-193, :238-247): what the fused path needs."""
+        sid = "" if self.scope_id is None else str(self.scope_id)
+        D, K, F = self.feature_size, self.anchor_size, self.kernel_size
+        anchor_weights = vs.get_variable("anchor_weights" + sid, [D, K], vs.glorot_uniform_initializer(), device=device)
+        vs.summary("anchor_weights" + sid, anchor_weights)
+        spatial_cnn_weights = vs.get_variable("spatial_cnn_weights" + sid, [K, F, D], vs.glorot_uniform_initializer(), device=device)
+        temporal_cnn_weights = vs.get_variable("temporal_cnn_weights" + sid, [K, F, D], vs.glorot_uniform_initializer(), device=device)
+        return anchor_weights, spatial_cnn_weights, temporal_cnn_weights
+
+    def pool(self, inputs):
+        """inputs [(B*max_frames), D] -> (spatial_pool, temporal_pool), each [B, 2 (K*F + K)] (:198-276)."""
+        D, K, F, T = self.feature_size, self.anchor_size, self.kernel_size, self.max_frames
+        anchor_weights, spatial_cnn_weights, temporal_cnn_weights = self.variables(inputs.device)
+        spatial = inputs.unsqueeze(1) - anchor_weights.t().unsqueeze(0)                                # :198-205 -> [M, K, D]
+        spatial_norm = torch.linalg.vector_norm(spatial, dim=2)                                        # :206
+        spatial = layers.l2_normalize(spatial, 2).reshape(-1, K * D)                                   # :208-209
+        temporal = spatial - torch.roll(spatial, shifts=1, dims=1)                                     # :216-217: the feature axis (C29)
+        temporal = temporal.reshape(-1, T, K * D)[:, 1:].reshape(-1, K, D)                             # :218-223
+        temporal_norm = torch.linalg.vector_norm(temporal, dim=2)                                      # :224
+        temporal = layers.l2_normalize(temporal, 2)                                                    # :225
+        spatial = spatial.reshape(-1, K, D)
+        spatial_output = spatial.transpose(0, 1).matmul(spatial_cnn_weights.transpose(1, 2)).transpose(0, 1)      # :249-258 -> [M, K, F]
+        temporal_output = temporal.transpose(0, 1).matmul(temporal_cnn_weights.transpose(1, 2)).transpose(0, 1)
+        spatial_output = torch.cat([spatial_output.reshape(-1, T, K * F), spatial_norm.reshape(-1, T, K)], 2)      # :261-267
+        temporal_output = torch.cat([temporal_output.reshape(-1, T - 1, K * F), temporal_norm.reshape(-1, T - 1, K)], 2)
+        spatial_pool = torch.cat([spatial_output.mean(dim=1), module_utils.reduce_var(spatial_output, 1)], 1)      # :269-276
+        temporal_pool = torch.cat([temporal_output.mean(dim=1), module_utils.reduce_var(temporal_output, 1)], 1)
+        return spatial_pool, temporal_pool
+
+    def head(self, spatial_pool, temporal_pool):
+        """The two pools -> [B, output_dim] (:278-373)."""
+        dev, H = spatial_pool.device, self.hidden_layer_size
+
+        def bn(x, scope):
+            return layers.batch_norm(x, self.is_training, scope) if self.batch_norm else x
+
+        def weights(name, rows, units):
+            return vs.get_variable(name, [rows, units], vs.glorot_uniform_initializer(), device=dev)
+        spatial_pool, temporal_pool = bn(spatial_pool, "spatial_pool_bn"), bn(temporal_pool, "temporal_pool_bn")            # :278-290
+        spatial_weights = weights("spatial_hidden", spatial_pool.shape[1], H)                                            # :292-300
+        temporal_weights = weights("temporal_hidden", temporal_pool.shape[1], H)
+        spatial_activation, temporal_activation = spatial_pool.matmul(spatial_weights), temporal_pool.matmul(temporal_weights)
+        spatial_activation = torch.relu(bn(spatial_activation, "spatial_activation_bn"))                                 # :305-321
+        temporal_activation = torch.relu(bn(temporal_activation, "temporal_activation_bn"))
+        spatial_weights2, temporal_weights2 = weights("spatial_hidden2", H, H), weights("temporal_hidden2", H, H)         # :323-329
+        spatial_activation, temporal_activation = spatial_activation.matmul(spatial_weights2), temporal_activation.matmul(temporal_weights2)
+        spatial_activation = torch.relu(bn(spatial_activation, "spatial_pool2_bn"))                                      # :334-349
+        temporal_activation = torch.relu(bn(temporal_activation, "temporal_pool2_bn"))
+        spatial_temporal_concat = torch.cat([spatial_activation, temporal_activation], 1)                                 # :354
+        sp_weights = weights("spa_temp_fusion", spatial_temporal_concat.shape[1], self.output_dim)                        # :356-360
+        return torch.relu(bn(spatial_temporal_concat.matmul(sp_weights), "st_fuse_activation_bn"))                        # :362-370
+
+    def forward(self, inputs, **unused_params):
+        """inputs [(B*max_frames), D] -> [B, output_dim]."""
+        return self.head(*self.pool(inputs))
