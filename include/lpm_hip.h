@@ -1095,6 +1095,44 @@ int lpm_triangulation_moments_bwd(const float* x, const float* anchors, const fl
                                   const float* g_t, int B, int T, int D, int K, int F, float* dx, float* danchors, float* dcnn_s,
                                   float* dcnn_t, void* workspace, size_t workspace_bytes, lpm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Batch-normalised attention moments of the triangulation embedding (video_pooling_modules.py:431-571
+ * TriangulationCnnIndirectAttentionModule, the pooling of JuhanTestModelV1), csrc/triangulation_bn_moments.hip.  x [B * T, D] (a clip's
+ * rows contiguous), anchors [D, K] AS THEY ARE (not normalised), J = K * D, feature j = k * D + d.  Per row n:
+ *     e[n,j] = (x[n,d] - a[d,k]) / sqrt(max(|x_n - a_k|^2, 1e-12));   g[n,j] = e[n,j] - e[n,(j-1) mod J] (the roll over the feature axis),
+ *     frames t >= 1 only, not normalised again;   V_s = sc_s (e - mu_s) + beta_s,  V_t = sc_t (g - mu_t) + beta_t   (batch norm, per feature)
+ *     G = V V^T per clip,  w = softmax_t(sum_u relu(G[t,u])),  pool = [(1/T') sum_t w_t V_t | mean_t (V_t - mean_t V)^2]  [B, 2 J]
+ * aff [8, J] = sc, mu, beta, rsqrt(var + eps) of the spatial stream, then of the temporal one (without batch norm: 1, 0, 0, 1).  Nothing
+ * of size B * T * K * D is written in either direction; no floating-point atomics (the same inputs give the same bits); the Gram and the
+ * backward's M V products are exact-fp32 MFMAs.  relu, row sums, softmax and their backward are [B, T, T] work of the caller.
+ *   _stats: -> q [2, B * T, K] (the squared norms, then 1 / sqrt(max(., 1e-12))), and with want_stats the batch statistics
+ *           stats [4, J] = mean_s, var_s (over the B T rows), mean_t, var_t (over the B (T - 1) rows), biased, from deviations
+ *           (the mean of the deviations is added onto the mean once: it is correct to rounding)
+ *   _gram:  iq = q + B * T * K -> gram_s [B, T, T], gram_t [B, T-1, T-1] (both overwritten)
+ *   _pool:  w_s [B, T], w_t [B, T-1] (both null: the plain mean) -> pool_s, pool_t [B, 2 J], rawbar, corr [2, B, J] (each clip's mean
+ *           of e / g and the mean of the deviations from it: kept for _bwd)
+ *   _dw:    g_s, g_t [B, 2 J] (the pools' gradients) -> dw_s [B, T], dw_t [B, T-1]:  dw[b,t] = <V_t, g_mean[b]> / T'
+ *   _bwd:   m_s [B, T, T], m_t [B, T-1, T-1]: M[t,u] = [G[t,u] > 0] (dr_t + dr_u) (SYMMETRIC; null with w: no attention) -> dx [B * T, D],
+ *           danchors [D, K], dgrad [4, J] = dbeta_s, dgamma_s, dbeta_t, dgamma_t (all overwritten; dgrad zero without affine_grads).
+ *           training: the statistics in aff are the batch's own, and the gradient runs through them.
+ * workspace: 16-byte aligned, lpm_triangulation_bn_moments_workspace_bytes(which, ...) bytes with which = 0 (_stats), 1 (_gram; may be 0
+ * bytes), 2 (_bwd).  D in {128, 1024}, 2 <= T <= lpm_triangulation_attention_max_frames(), K >= 1; anything else
+ * LPM_ERR_UNSUPPORTED_SHAPE / LPM_ERR_BADARG before any launch. */
+size_t lpm_triangulation_bn_moments_workspace_bytes(int which, int B, int T, int D, int K);
+int lpm_triangulation_bn_moments_stats(const float* x, const float* anchors, int B, int T, int D, int K, int want_stats, float* q, float* stats,
+                                       void* workspace, size_t workspace_bytes, lpm_stream_t stream);
+int lpm_triangulation_bn_moments_gram(const float* x, const float* anchors, const float* iq, const float* aff, int B, int T, int D, int K,
+                                      float* gram_s, float* gram_t, void* workspace, size_t workspace_bytes, lpm_stream_t stream);
+int lpm_triangulation_bn_moments_pool(const float* x, const float* anchors, const float* iq, const float* aff, const float* w_s,
+                                      const float* w_t, int B, int T, int D, int K, float* pool_s, float* pool_t, float* rawbar, float* corr,
+                                      lpm_stream_t stream);
+int lpm_triangulation_bn_moments_dw(const float* x, const float* anchors, const float* iq, const float* aff, const float* g_s, const float* g_t,
+                                    int B, int T, int D, int K, float* dw_s, float* dw_t, lpm_stream_t stream);
+int lpm_triangulation_bn_moments_bwd(const float* x, const float* anchors, const float* q, const float* aff, const float* w_s, const float* w_t,
+                                     const float* m_s, const float* m_t, const float* rawbar, const float* corr, const float* g_s,
+                                     const float* g_t, int B, int T, int D, int K, int affine_grads, int training, float* dx, float* danchors,
+                                     float* dgrad, void* workspace, size_t workspace_bytes, lpm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

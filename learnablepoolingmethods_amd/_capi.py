@@ -214,6 +214,12 @@ SIGNATURES = {
     "lpm_triangulation_moments_workspace_bytes": (_s, [_i, _i, _i, _i, _i]),
     "lpm_triangulation_moments_fwd": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f]),
     "lpm_triangulation_moments_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _s, _f]),
+    "lpm_triangulation_bn_moments_workspace_bytes": (_s, [_i, _i, _i, _i, _i]),
+    "lpm_triangulation_bn_moments_stats": (_i, [_f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _s, _f]),
+    "lpm_triangulation_bn_moments_gram": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _f, _f, _f, _s, _f]),
+    "lpm_triangulation_bn_moments_pool": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f]),
+    "lpm_triangulation_bn_moments_dw": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _f, _f, _f]),
+    "lpm_triangulation_bn_moments_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _s, _f]),
     "lpm_multi_tensor_clip_adam_l2": (_i, [_f, _f, _f, _f, _f, _f, _i, _l, _fl, _fl, _fl, _fl, _fl, _l, _f, _f]),
     "lpm_weight_pack": (_i, [_f, _i, _f]),
     "lpm_sum_splits": (_i, [_f, _i, _i, _i, _f, _f, _f, _i, _f]),          # (jobs: a HOST array of WeightPackJob)

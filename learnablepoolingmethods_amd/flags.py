@@ -106,6 +106,22 @@ FLAGS.define("triangulation_v5_fused", True, "build extension: on the GPU each s
              "call (csrc/triangulation_moments.hip: the per-anchor convolutions of the embedding and of its rolled differences over every "
              "frame, and the mean and variance over the frames, without any [B, T, K*D] tensor); False: TriangulationV5Module.forward "
              "materialises it (the CPU path; same variables, same results)")
+FLAGS.define("jtmv1_iteration", 30, "JuhanTestModelV1 (frame_level_models.py:59): sampled frames per clip")
+FLAGS.define("jtmv1_add_batch_norm", True, "JuhanTestModelV1 (:61): batch norm inside each stream's module")
+FLAGS.define("jtmv1_sample_random_frames", True, "JuhanTestModelV1 (:63): defined and read nowhere, as written")
+FLAGS.define("jtmv1_video_anchor_size", 64, "JuhanTestModelV1 (:65): anchors of the video stream")
+FLAGS.define("jtmv1_audio_anchor_size", 16, "JuhanTestModelV1 (:67): anchors of the audio stream")
+FLAGS.define("jtmv1_video_hidden", 1024, "JuhanTestModelV1 (:69): width of the video stream's hidden layer")
+FLAGS.define("jtmv1_video_output_dim", 2048, "JuhanTestModelV1 (:71): width of the video stream's fused output")
+FLAGS.define("jtmv1_audio_hidden", 128, "JuhanTestModelV1 (:73): width of the audio stream's hidden layer")
+FLAGS.define("jtmv1_audio_output_dim", 256, "JuhanTestModelV1 (:75): width of the audio stream's fused output")
+FLAGS.define("jtmv1_use_attention", True, "JuhanTestModelV1 (:77): the soft-attention weights on the pooled means")
+FLAGS.define("jtmv1_use_relu", True, "JuhanTestModelV1 (:79): relu behind the hidden and the fusion layer")
+FLAGS.define("triangulation_v1_fused", False, "build extension: on the GPU each stream of JuhanTestModelV1 pools through "
+             "ops.triangulation_bn_moments (csrc/triangulation_bn_moments.hip: the batch-norm statistics, the Grams, the softmax weights and "
+             "the mean and variance over the frames without any [B, T, K*D] tensor); False: TriangulationCnnIndirectAttentionModule.pool "
+             "materialises it (the CPU path; same variables, same results).  Off until tools/bench_triangulation_v1.py has shown the fused "
+             "path not slower at both model-default shapes (profiles/bench_triangulation_v1.json)")
 FLAGS.define("wtm_projection_l1", 1e-5, "layers.l1_l2_regularizer(1e-5) on dis_projection_2 / temp_projection_2 (frame_level_models.py:1272,1287): "
              "tf.contrib's first positional argument is scale_l1")
 FLAGS.define("wtm_projection_l2", 1.0, "... and its scale_l2 keeps the default 1.0: the penalty is l1 * sum |w| + l2 * sum(w^2) / 2 (SURVEY App. B)")

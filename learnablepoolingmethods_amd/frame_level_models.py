@@ -604,6 +604,54 @@ class JuhanTestModelV5(models.BaseModel):
                                                **unused_params)                                              # :600-606
 
 
+class JuhanTestModelV1(models.BaseModel):
+    """One TriangulationCnnIndirectAttentionModule per stream (the triangulation embedding and its rolled differences, each batch-normed
+    over all K*D features, soft-attention weights from the relu'd Gram, the weighted mean and the variance over the frames, a hidden layer
+    and a fusion layer) and the class-learning four-layer classifier (frame_level_models.py:59-154).  No input batch norm.  As written:
+    SURVEY App. C29, C32-C35 (and C23).
+
+    On the GPU with FLAGS.triangulation_v1_fused each stream's pooling goes through ops.triangulation_bn_moments: no [(B*T), K*D] tensor
+    (126 MB at the video defaults B = 16, T = 30, K = 64, D = 1024) is written; otherwise TriangulationCnnIndirectAttentionModule.pool
+    materialises them.  The variables and the results are the same either way.  ``frame_uniform`` [B, iterations] replaces the random
+    draw of SampleRandomFrames; ``video_anchor_size``, ``audio_anchor_size``, ``video_hidden``, ``audio_hidden``, ``video_output_dim``
+    and ``audio_output_dim`` override the flags (the reference reads the flags only)."""
+
+    def create_model(self, model_input, vocab_size, num_frames, iterations=None, add_batch_norm=None, sample_random_frames=None,
+                     hidden_size=None, is_training=True, frame_uniform=None, video_anchor_size=None, audio_anchor_size=None,
+                     video_hidden=None, audio_hidden=None, video_output_dim=None, audio_output_dim=None, **unused_params):
+        iterations = iterations or FLAGS.jtmv1_iteration                                                      # :94
+        add_batch_norm = add_batch_norm or FLAGS.jtmv1_add_batch_norm                                         # :95 (C23)
+        video_anchor_size = int(video_anchor_size or FLAGS.jtmv1_video_anchor_size)                           # :96-101
+        audio_anchor_size = int(audio_anchor_size or FLAGS.jtmv1_audio_anchor_size)
+        video_hidden = int(video_hidden or FLAGS.jtmv1_video_hidden)
+        audio_hidden = int(audio_hidden or FLAGS.jtmv1_audio_hidden)
+        video_output_dim = int(video_output_dim or FLAGS.jtmv1_video_output_dim)
+        audio_output_dim = int(audio_output_dim or FLAGS.jtmv1_audio_output_dim)
+        use_attention, use_relu = FLAGS.jtmv1_use_attention, FLAGS.jtmv1_use_relu                             # :102-103
+        # sample_random_frames and hidden_size are accepted and read nowhere, as written
+        model_input = model_utils.SampleRandomFrames(model_input, num_frames.reshape(-1, 1), iterations, uniform=frame_uniform)  # :105-106
+        max_frames, feature_size = model_input.shape[1], model_input.shape[2]
+        if feature_size <= 1024:
+            raise ValueError("JuhanTestModelV1 slices a 1024-wide video and a 128-wide audio stream out of its input "
+                             f"(frame_level_models.py:137-141); got {feature_size} features")
+        reshaped_input = model_input.reshape(-1, feature_size)
+        streams = (("video", 1024, video_anchor_size, video_hidden, video_output_dim, slice(0, 1024)),
+                   ("audio", feature_size - 1024, audio_anchor_size, audio_hidden, audio_output_dim, slice(1024, None)))
+        v1_modules = [video_pooling_modules.TriangulationCnnIndirectAttentionModule(
+            feature_size=D, max_frames=max_frames, anchor_size=K, self_attention=use_attention, hidden_layer_size=H, output_dim=O,
+            add_relu=use_relu, batch_norm=add_batch_norm, is_training=is_training, scope_id=None) for _, D, K, H, O, _ in streams]   # :113-135
+        fused = bool(FLAGS.triangulation_v1_fused and reshaped_input.is_cuda and max_frames >= 2)
+        acts = []
+        for (name, *_, cols), module in zip(streams, v1_modules):
+            with vs.variable_scope(name + "_triangulation_embedding"):                                        # :137-143
+                x = reshaped_input[:, cols]
+                acts.append(module.head(*module.fused_pool(x.contiguous())) if fused else module.forward(x))
+        activation = torch.cat(acts, 1)                                                                       # :145
+        aggregated_model = getattr(video_level_models, "ClassLearningFourNnModel")
+        return aggregated_model().create_model(model_input=activation, vocab_size=vocab_size, is_training=is_training,
+                                               **unused_params)                                              # :147-154
+
+
 class NetVladV2(models.BaseModel):
     """Paper prototype 2: attention-based cluster similarities (frame_level_models.py:2383-2513)."""
 

@@ -4241,3 +4241,129 @@ def triangulation_cnn_moments(x, anchors, cnn_s, cnn_t, max_frames):
     if cnn_s.shape != cnn_t.shape:
         raise LpmError(f"{what}: cnn_s {tuple(cnn_s.shape)} and cnn_t {tuple(cnn_t.shape)} must have one shape")
     return _TriangulationCnnMoments.apply(x, anchors.contiguous(), cnn_s.contiguous(), cnn_t.contiguous(), T)
+
+
+# ----------------------------------------------------------------------------------------------
+# batch-normalised attention moments of the triangulation embedding: TriangulationCnnIndirectAttentionModule's pooling
+# (csrc/triangulation_bn_moments.hip)
+# ----------------------------------------------------------------------------------------------
+TRIANGULATION_BN_EPS = 1e-3         # slim.batch_norm's epsilon (layers.BN_EPS)
+
+
+class _TriangulationBnMoments(torch.autograd.Function):
+    """The saved state is the inputs, the norms q [2, B*T, K], the affine table [8, J], the two Grams and weight vectors and the per-clip
+    means rawbar, corr [2, B, J]; e and g are recomputed in the backward, whose workspace lives for that call only."""
+
+    @staticmethod
+    def forward(ctx, x, anchors, gamma_s, beta_s, gamma_t, beta_t, T, attention, batch_norm, stats):
+        lib = _capi.load()
+        D, K = anchors.shape
+        B, J = x.shape[0] // T, K * D
+        dims = (B, T, D, K)
+        q = _empty((2, B * T, K), x)
+        bstats = _empty((4, J), x) if batch_norm else None
+        wsb = int(lib._lpm_triangulation_bn_moments_workspace_bytes(0, B, T, D, K)) if batch_norm else 0
+        ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+        with _timed("triangulation_bn_moments_stats", dims):
+            lib.check(lib._lpm_triangulation_bn_moments_stats(ptr(x), ptr(anchors), B, T, D, K, int(batch_norm), ptr(q),
+                                                              ptr(bstats) if batch_norm else None, ptr(ws) if wsb else None, wsb, stream_ptr()),
+                      "lpm_triangulation_bn_moments_stats")
+        aff = _empty((8, J), x)
+        if batch_norm:
+            use = bstats if stats is None else torch.stack([s.detach() for s in stats])
+            for z, (gamma, beta) in enumerate(((gamma_s, beta_s), (gamma_t, beta_t))):
+                istd = torch.rsqrt(use[2 * z + 1] + TRIANGULATION_BN_EPS)
+                aff[4 * z], aff[4 * z + 1], aff[4 * z + 2], aff[4 * z + 3] = gamma.detach() * istd, use[2 * z], beta.detach(), istd
+        else:
+            aff.copy_(torch.tensor([1.0, 0.0, 0.0, 1.0] * 2, device=x.device).unsqueeze(1).expand(8, J))
+        iq = q[1]
+        gram_s = gram_t = w_s = w_t = None
+        if attention:
+            gram_s, gram_t = _empty((B, T, T), x), _empty((B, T - 1, T - 1), x)
+            wsb = int(lib._lpm_triangulation_bn_moments_workspace_bytes(1, B, T, D, K))
+            ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+            with _timed("triangulation_bn_moments_gram", dims):
+                lib.check(lib._lpm_triangulation_bn_moments_gram(ptr(x), ptr(anchors), ptr(iq), ptr(aff), B, T, D, K, ptr(gram_s), ptr(gram_t),
+                                                                 ptr(ws) if wsb else None, wsb, stream_ptr()), "lpm_triangulation_bn_moments_gram")
+            with _timed("triangulation_bn_moments_softmax", dims):
+                w_s, w_t = _attention_weights(gram_s), _attention_weights(gram_t)
+        pool_s, pool_t = _empty((B, 2 * J), x), _empty((B, 2 * J), x)
+        rawbar, corr = _empty((2, B, J), x), _empty((2, B, J), x)
+        with _timed("triangulation_bn_moments_pool", dims):
+            lib.check(lib._lpm_triangulation_bn_moments_pool(ptr(x), ptr(anchors), ptr(iq), ptr(aff), ptr(w_s) if attention else None,
+                                                             ptr(w_t) if attention else None, B, T, D, K, ptr(pool_s), ptr(pool_t), ptr(rawbar),
+                                                             ptr(corr), stream_ptr()), "lpm_triangulation_bn_moments_pool")
+        ctx.save_for_backward(x, anchors, q, aff, rawbar, corr, *((gram_s, gram_t, w_s, w_t) if attention else ()))
+        ctx.dims = (B, T, D, K, attention, batch_norm, batch_norm and stats is None)
+        if batch_norm:
+            ctx.mark_non_differentiable(bstats)
+            return pool_s, pool_t, bstats
+        return pool_s, pool_t, None
+
+    @staticmethod
+    def backward(ctx, g_s, g_t, _g_stats):
+        lib = _capi.load()
+        x, anchors, q, aff, rawbar, corr, *att = ctx.saved_tensors
+        B, T, D, K, attention, batch_norm, training = ctx.dims
+        dims, J = (B, T, D, K), K * D
+        g_s = (torch.zeros_like(rawbar[0]).repeat(1, 2) if g_s is None else g_s).contiguous()
+        g_t = (torch.zeros_like(rawbar[0]).repeat(1, 2) if g_t is None else g_t).contiguous()
+        w_s = w_t = m_s = m_t = None
+        if attention:
+            gram_s, gram_t, w_s, w_t = att
+            dw_s, dw_t = _empty((B, T), x), _empty((B, T - 1), x)
+            with _timed("triangulation_bn_moments_dw", dims):
+                lib.check(lib._lpm_triangulation_bn_moments_dw(ptr(x), ptr(anchors), ptr(q[1]), ptr(aff), ptr(g_s), ptr(g_t), B, T, D, K, ptr(dw_s),
+                                                               ptr(dw_t), stream_ptr()), "lpm_triangulation_bn_moments_dw")
+            with _timed("triangulation_bn_moments_softmax_bwd", dims):
+                m_s, m_t = _attention_weights_bwd(gram_s, w_s, dw_s), _attention_weights_bwd(gram_t, w_t, dw_t)
+        dx, danchors, dgrad = torch.empty_like(x), torch.empty_like(anchors), _empty((4, J), x)
+        wsb = int(lib._lpm_triangulation_bn_moments_workspace_bytes(2, B, T, D, K))
+        ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+        opt = (lambda t: ptr(t)) if attention else (lambda t: None)
+        with _timed("triangulation_bn_moments_bwd", dims):
+            lib.check(lib._lpm_triangulation_bn_moments_bwd(ptr(x), ptr(anchors), ptr(q), ptr(aff), opt(w_s), opt(w_t), opt(m_s), opt(m_t), ptr(rawbar),
+                                                            ptr(corr), ptr(g_s), ptr(g_t), B, T, D, K, int(batch_norm), int(training), ptr(dx),
+                                                            ptr(danchors), ptr(dgrad), ptr(ws), wsb, stream_ptr()), "lpm_triangulation_bn_moments_bwd")
+        if not batch_norm:
+            return dx, danchors, None, None, None, None, None, None, None, None
+        return dx, danchors, dgrad[1], dgrad[0], dgrad[3], dgrad[2], None, None, None, None
+
+
+def triangulation_bn_moments(x, anchors, gamma_s, beta_s, gamma_t, beta_t, max_frames, self_attention=True, batch_norm=True, stats=None):
+    """One stream of TriangulationCnnIndirectAttentionModule's pooling (video_pooling_modules.py:431-571; csrc/triangulation_bn_moments.hip):
+    x [B * max_frames, D] (a clip's rows contiguous), anchors [D, K] as they are (NOT normalised), J = K * D, feature j = k * D + d:
+        e = l2_normalize(x - a_k);  g = e - roll(e, 1) over the FEATURE axis of the flattened [J] row, frame 0 dropped, not normalised again;
+        batch norm per feature (gamma, beta [J]): of e over the B * max_frames rows, of g over the B * (max_frames - 1) rows;
+        per clip G = V V^T, w = softmax_t(sum_u relu(G[t,u]));  mean = (1/T') sum_t w_t V_t (the plain mean without ``self_attention``),
+        var = the mean of squared deviations from the unweighted mean.
+    -> (spatial_pool, temporal_pool, batch_stats): both pools [B, 2 J] = [mean | var]; batch_stats = (mean_s, var_s, mean_t, var_t), each
+    [J], the batch's own statistics with the BIASED variance, not differentiable (they feed the moving averages; None without
+    ``batch_norm``).  ``stats`` = (mean_s, var_s, mean_t, var_t): normalise with these constants instead (inference mode).  Without
+    ``batch_norm`` the four affine tensors may be None.  Differentiable in x, anchors and the four affine tensors; in training mode the
+    gradient runs through the batch statistics.  Nothing of size B * T * K * D is written.  GPU only; D in TRIANGULATION_FEATURES,
+    2 <= max_frames <= 320, contiguous fp32 input; the same inputs give the same bits."""
+    what = "triangulation_bn_moments"
+    T = _attention_args(what, x, anchors, max_frames)
+    D, K = anchors.shape
+    J = K * D
+    affine = (("gamma_s", gamma_s), ("beta_s", beta_s), ("gamma_t", gamma_t), ("beta_t", beta_t))
+    if batch_norm:
+        named = affine + (tuple(zip(("stats[0]", "stats[1]", "stats[2]", "stats[3]"), stats)) if stats is not None else ())
+        if stats is not None and len(stats) != 4:
+            raise LpmError(f"{what}: stats must be (mean_s, var_s, mean_t, var_t)")
+        for name, v in named:
+            if not torch.is_tensor(v) or tuple(v.shape) != (J,):
+                raise LpmError(f"{what}: {name} must be [K * D] = [{J}] (got {tuple(v.shape) if torch.is_tensor(v) else type(v)})")
+            _f32(v, f"{what} {name}")
+            if v.device != x.device:
+                raise LpmError(f"{what}: {name} is on {v.device}, x on {x.device}")
+        gamma_s, beta_s, gamma_t, beta_t = (v.contiguous() for _, v in affine)
+        stats = None if stats is None else tuple(s.contiguous() for s in stats)
+    else:
+        if stats is not None:
+            raise LpmError(f"{what}: stats given without batch_norm")
+        gamma_s = beta_s = gamma_t = beta_t = None
+    pool_s, pool_t, bstats = _TriangulationBnMoments.apply(x, anchors.contiguous(), gamma_s, beta_s, gamma_t, beta_t, T, bool(self_attention),
+                                                           bool(batch_norm), stats)
+    return pool_s, pool_t, (tuple(bstats.unbind(0)) if batch_norm else None)

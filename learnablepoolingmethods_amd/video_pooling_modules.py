@@ -1,6 +1,6 @@
 """NetVladOrthoReg and NetVladAttenCluster (reference: video_pooling_modules.py:1499-1586, 1589-1663) and the triangulation
 embeddings (TriangulationEmbedding :376-428, WeightedTriangulationEmbedding :1395-1459, TriangulationTemporalEmbedding :1462-1497,
-TriangulationV5Module :142-373)."""
+TriangulationV5Module :142-373, TriangulationCnnIndirectAttentionModule :431-631)."""
 from __future__ import annotations
 
 import math
@@ -271,6 +271,106 @@ class TriangulationV5Module(modules.BaseModule):
         spatial_temporal_concat = torch.cat([spatial_activation, temporal_activation], 1)                                 # :354
         sp_weights = weights("spa_temp_fusion", spatial_temporal_concat.shape[1], self.output_dim)                        # :356-360
         return torch.relu(bn(spatial_temporal_concat.matmul(sp_weights), "st_fuse_activation_bn"))                        # :362-370
+
+    def forward(self, inputs, **unused_params):
+        """inputs [(B*max_frames), D] -> [B, output_dim]."""
+        return self.head(*self.pool(inputs))
+
+
+class TriangulationCnnIndirectAttentionModule(modules.BaseModule):
+    """:431-631 (JuhanTestModelV1's module): the triangulation embedding of every frame against the anchors AS THEY ARE
+    (random_normal(1 / sqrt(K)), not normalised), its difference with itself rolled by one along the FEATURE axis (:506; SURVEY App. C29;
+    frame 0 dropped, not normalised again: C34), a batch norm over all K*D features of each (``spatial_bn`` over the B*T rows,
+    ``temporal_bn`` over the B*(T-1) rows: C35), soft-attention weights from the relu'd Gram matrix of the normalised rows, the weighted
+    mean divided by the frame count once more (C32) and the UNWEIGHTED reduce_var (C33) over the frames; then per stream a hidden layer,
+    batch norm and relu, and the fusion layer.  ``pool`` MATERIALISES [(B*T), K*D] several times: the drop-in surface and the CPU path;
+    ``variables`` + ops.triangulation_bn_moments + ``head`` is the fused one (``fused_pool``)."""
+
+    def __init__(self, feature_size, max_frames, anchor_size, self_attention, hidden_layer_size, output_dim, add_relu, batch_norm,
+                 is_training, scope_id=None):
+        self.feature_size = feature_size
+        self.max_frames = max_frames
+        self.anchor_size = int(anchor_size)
+        self.self_attention = self_attention
+        self.hidden_layer_size = int(hidden_layer_size)
+        self.output_dim = int(output_dim)
+        self.add_relu = add_relu
+        self.batch_norm = batch_norm
+        self.is_training = is_training
+        self.scope_id = scope_id
+
+    def variables(self, device):
+        """anchor_weights [D, K] without a forward (:476-482): what the fused path needs."""
+        sid = "" if self.scope_id is None else str(self.scope_id)
+        anchor_weights = vs.get_variable("anchor_weights" + sid, [self.feature_size, self.anchor_size],
+                                         vs.random_normal_initializer(1 / math.sqrt(self.anchor_size)), device=device)
+        vs.summary("anchor_weights" + sid, anchor_weights)
+        return anchor_weights
+
+    def pool(self, inputs):
+        """inputs [(B*max_frames), D] -> (spatial_pool, temporal_pool), each [B, 2 K*D] (:476-571)."""
+        D, K, T = self.feature_size, self.anchor_size, self.max_frames
+        anchor_weights = self.variables(inputs.device)
+        spatial = inputs.unsqueeze(1) - anchor_weights.t().unsqueeze(0)                                # :485-494 -> [M, K, D]
+        spatial = layers.l2_normalize(spatial, 2).reshape(-1, K * D)                                   # :496-497
+        temporal = spatial - torch.roll(spatial, shifts=1, dims=1)                                     # :506-507: the feature axis (C29)
+        temporal = temporal.reshape(-1, T, K * D)[:, 1:].reshape(-1, K * D)                            # :508-513
+        if self.batch_norm:                                                                            # :517-530
+            spatial = layers.batch_norm(spatial, self.is_training, "spatial_bn")
+            temporal = layers.batch_norm(temporal, self.is_training, "temporal_bn")
+        pools = []
+        for v in (spatial.reshape(-1, T, K * D), temporal.reshape(-1, T - 1, K * D)):                  # :533-571
+            if self.self_attention:
+                weight = torch.softmax(torch.relu(v.matmul(v.transpose(1, 2))).sum(dim=2), dim=1)      # :539-554
+                mean = (v * weight.unsqueeze(2)).mean(dim=1)                                           # :561-562 (C32)
+            else:
+                mean = v.mean(dim=1)
+            pools.append(torch.cat([mean, module_utils.reduce_var(v, 1)], 1))                          # :567-571 (C33)
+        return pools[0], pools[1]
+
+    def fused_pool(self, inputs):
+        """``pool`` through ops.triangulation_bn_moments: the same variables in the same order, the moving averages updated from the op's
+        batch statistics by layers.batch_norm's rank-2 rule (the unbiased estimate into the moving variance)."""
+        T, J = self.max_frames, self.feature_size * self.anchor_size
+        anchor_weights = self.variables(inputs.device)
+        if not self.batch_norm:
+            spatial_pool, temporal_pool, _ = ops.triangulation_bn_moments(inputs, anchor_weights, None, None, None, None, T,
+                                                                          self_attention=self.self_attention, batch_norm=False)
+            return spatial_pool, temporal_pool
+        gamma_s, beta_s, mm_s, mv_s = layers.bn_variables("spatial_bn", J, inputs.device)
+        gamma_t, beta_t, mm_t, mv_t = layers.bn_variables("temporal_bn", J, inputs.device)
+        stats = None if self.is_training else (mm_s, mv_s, mm_t, mv_t)
+        spatial_pool, temporal_pool, batch_stats = ops.triangulation_bn_moments(inputs, anchor_weights, gamma_s, beta_s, gamma_t, beta_t, T,
+                                                                                self_attention=self.self_attention, stats=stats)
+        if self.is_training:
+            B = inputs.shape[0] // T
+            with torch.no_grad():
+                for mm, mv, mean, var, n in ((mm_s, mv_s, batch_stats[0], batch_stats[1], B * T),
+                                             (mm_t, mv_t, batch_stats[2], batch_stats[3], B * (T - 1))):
+                    mm.mul_(layers.BN_DECAY).add_(mean, alpha=1 - layers.BN_DECAY)
+                    mv.mul_(layers.BN_DECAY).add_(var * (n / max(n - 1, 1)), alpha=1 - layers.BN_DECAY)
+        return spatial_pool, temporal_pool
+
+    def head(self, spatial_pool, temporal_pool):
+        """The two pools -> [B, output_dim] (:573-631)."""
+        dev, H = spatial_pool.device, self.hidden_layer_size
+
+        def bn(x, scope):
+            return layers.batch_norm(x, self.is_training, scope) if self.batch_norm else x
+
+        def act(x):
+            return torch.relu(x) if self.add_relu else x
+
+        def weights(name, rows, units):
+            return vs.get_variable(name, [rows, units], vs.random_normal_initializer(1 / math.sqrt(H)), device=dev)
+        spatial_weights = weights("spatial_hidden", spatial_pool.shape[1], H)                                            # :573-583
+        temporal_weights = weights("temporal_hidden", temporal_pool.shape[1], H)
+        spatial_activation, temporal_activation = spatial_pool.matmul(spatial_weights), temporal_pool.matmul(temporal_weights)
+        spatial_activation = act(bn(spatial_activation, "spatial_activation_bn"))                                        # :588-605
+        temporal_activation = act(bn(temporal_activation, "temporal_activation_bn"))
+        spatial_temporal_concat = torch.cat([spatial_activation, temporal_activation], 1)                                 # :610
+        sp_weights = weights("spa_temp_fusion", spatial_temporal_concat.shape[1], self.output_dim)                        # :612-616
+        return act(bn(spatial_temporal_concat.matmul(sp_weights), "activation_bn"))                                       # :617-628
 
     def forward(self, inputs, **unused_params):
         """inputs [(B*max_frames), D] -> [B, output_dim]."""
