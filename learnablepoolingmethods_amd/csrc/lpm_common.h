@@ -141,6 +141,16 @@ __device__ __forceinline__ float half_sum(float v) {
     for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// the same on the VALU: four DPP steps give every lane its row-of-16 total, two v_readlane join the rows of a half (__shfl_xor is a
+// round trip through the LDS crossbar on this target).  It adds in ANOTHER ORDER than half_sum: the two do not give the same bits.
+__device__ __forceinline__ float half_sum_dpp(float v) {
+    v += dpp_lanes<0xB1>(v);
+    v += dpp_lanes<0x4E>(v);
+    v += dpp_lanes<0x141>(v);
+    v += dpp_lanes<0x140>(v);
+    const float lo = lane_value(v, 0) + lane_value(v, 16), hi = lane_value(v, 32) + lane_value(v, 48);
+    return (threadIdx.x & 32) ? hi : lo;
+}
 
 // v_mfma_f32_32x32x2_f32: D[32x32] += A[32x2] * B[2x32], exact fp32.
 //   A operand: lane l supplies A[i = l & 31][k = l >> 5];  B operand: B[k = l >> 5][j = l & 31]

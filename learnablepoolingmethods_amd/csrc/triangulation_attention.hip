@@ -1,6 +1,7 @@
 // Soft-attention pooling of the triangulation embedding (aggregation_modules.py:74-108 IndirectClusterMaxMeanPoolModule over
 // video_pooling_modules' TriangulationEmbedding + TriangulationTemporalEmbedding), fused.  With v = e over the T frames or v = f over
-// the T - 1 frame-to-frame differences (e, f exactly as in triangulation_pool.hip: the same clamps, the same first-index maximum):
+// the T - 1 frame-to-frame differences (e, f exactly as in triangulation_pool.hip -- one walk, triangulation_common.h -- with the same
+// clamps and the same first-index maximum; tests/test_gpu_triangulation_family.py holds the two ops' maxima bitwise equal):
 //   G[t,s] = <v_t, v_s> over all K*D features;  l[t] = sum_s relu(G[t,s]);  w = softmax_t(l)
 //   mean = (1/T') sum_t w[t] v_t;  max = max_t v_t
 // Nothing of size T*K*D exists in either direction; the Grams [B,T,T] / [B,T-1,T-1] and the weights [B,T] / [B,T-1] do (the caller
@@ -9,14 +10,15 @@
 // sums of up to T*K terms that enter a softmax, a bf16 / fp16 pass would not do.
 //
 // lpm_triangulation_attention_gram: a workgroup (4 waves) owns a clip, a pair (I, J) of 64-frame tiles and a slice of the anchors
-// (k = slice, slice + S, ...).  Per anchor it takes the two norms of its frames once (one wave per frame, as the pooling kernel does),
+// (k = slice, slice + S, ...).  Per anchor it takes the two norms of its frames once (ta_norms: one wave per frame),
 // then walks D in 32-column chunks: the threads rebuild e and f of the chunk in LDS, each wave adds its 32x32 quadrant of
 // V_I V_J^T for both kinds on the matrix cores.  An anchor's product is summed in registers and added onto the slice's total (a
-// two-level sum, as the pooling kernel's over t); the slices' partial Grams are added s = 0, 1, ... by ta_sum_slices_kernel.
+// two-level sum, as the walk's over t); the slices' partial Grams are added s = 0, 1, ... by ta_sum_slices_kernel.
 //
-// lpm_triangulation_attention_pool_fwd: triangulation_pool.hip's forward walk (one wave per (clip, anchor)) with w[b,t] on the mean's terms.
+// lpm_triangulation_attention_pool_fwd: tp_walk_fwd_kernel<D, w_d, w_t, maxima> (triangulation_common.h).
 //
-// lpm_triangulation_attention_dw: dw[b,t] = <g_mean, v_t> / T', per (clip, anchor) by the same walk, then over anchors k = 0, 1, ....
+// lpm_triangulation_attention_dw: dw[b,t] = <g_mean, v_t> / T', per (clip, anchor) by tp_walk_dw_kernel<D, temporal>, then over anchors
+// k = 0, 1, ....
 //
 // lpm_triangulation_attention_bwd: with M = dG + dG^T (symmetric, from the caller) the per-frame cotangents of triangulation_pool.hip's
 // backward gain one term each:
@@ -28,57 +30,16 @@
 // symmetric; V's operand, e or f of a frame, is computed from the frames tile and the norms on the fly) into two more [T,33] tiles, and
 // a thread per (t, column) does the chain above (gu_{t+1} recomputed from row t + 1: no dependence between frames).  The two dot
 // products are sums over D, so D is walked three times: (f . gf), then (eh . ge), then gr.  A workgroup adds its anchors onto its own
-// [T, D] block in turn; G > 1 groups per clip write partials that a second pass adds g = 0, 1, ...; danchors as in
-// triangulation_pool.hip (per-(clip, anchor) sums, clips added b = 0, 1, ...).
+// [T, D] block in turn; G > 1 groups per clip write partials that a second pass adds g = 0, 1, ...; danchors from per-(clip, anchor)
+// sums, clips added b = 0, 1, ... (ta_reduce_partials below: the one pair of reduce kernels of the whole family).
 #include "triangulation_common.h"
 
-// u = e_t - e_{t-1} must be exactly zero for identical frames: no product may be fused into that difference
+// the contraction rule (triangulation_common.h) for everything below
 #pragma clang fp contract(off)
 
 namespace lpm {
 
 constexpr int TA_MAX_JOBS = (2 * (TA_MAX_FRAMES / 32) + TA_WAVES - 1) / TA_WAVES;    // 32-row tiles of M V per wave and chunk
-
-// The norms of the frames f0 .. f0 + n - 1 of one (clip, anchor): iq = rsqrt(max(|x - a|^2, eps)), ip the same of u = e_t - e_{t-1},
-// qg / pg = 1 where the squared norm exceeded eps (else 0).  One wave per frame; a (anchor) in the lane layout.  Frames outside
-// [0, T) get zeros.  Entry i belongs to frame f0 + i.
-template <int D>
-__device__ __forceinline__ void ta_norms(const float* __restrict__ xb, const float (&a)[D / 64], int T, int f0, int n, float s,
-                                         float* iq, float* qg, float* ip, float* pg) {
-    constexpr int N = TpVec<D>::N;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int i = wave; i < n; i += TA_WAVES) {
-        const int t = f0 + i;
-        float viq = 0.f, vqg = 0.f, vip = 0.f, vpg = 0.f;
-        if (t >= 0 && t < T) {                              // (wave-uniform)
-            float xv[N], e[N];
-            bool c;
-            tp_load<D>(xb + (int64_t)t * D, lane, xv);
-            viq = tp_unit<N>(xv, a, e, c);
-            vqg = c ? 0.f : 1.f;
-            if (t >= 1) {
-                float ep[N], p = 0.f;
-                bool c2;
-                tp_load<D>(xb + (int64_t)(t - 1) * D, lane, xv);
-                tp_unit<N>(xv, a, ep, c2);
-#pragma unroll
-                for (int j = 0; j < N; ++j) {
-                    const float u = e[j] * s - ep[j] * s;
-                    p = fmaf(u, u, p);
-                }
-                p = wave_sum_dpp(p);
-                vip = rsqrtf(fmaxf(p, kL2Eps));
-                vpg = p > kL2Eps ? 1.f : 0.f;
-            }
-        }
-        if (lane == 0) {
-            iq[i] = viq;
-            ip[i] = vip;
-            if (qg) qg[i] = vqg;
-            if (pg) pg[i] = vpg;
-        }
-    }
-}
 
 template <int D>
 __global__ __launch_bounds__(64 * TA_WAVES) void ta_gram_kernel(const float* __restrict__ x, const float* __restrict__ anchors, int T, int K,
@@ -108,7 +69,7 @@ __global__ __launch_bounds__(64 * TA_WAVES) void ta_gram_kernel(const float* __r
             float a[N];
             tp_load_anchor<D>(anchors, K, k, lane, a);
             for (int side = 0; side < nside; ++side)
-                ta_norms<D>(xb, a, T, (side ? tj : ti) * 64 - 1, 65, s, nrm[side][0], nullptr, nrm[side][1], nullptr);
+                ta_norms<D, TN_TEMPORAL>(xb, a, nullptr, T, (side ? tj : ti) * 64 - 1, 65, s, nrm[side][0], nullptr, nrm[side][1], nullptr, nullptr);
         }
         __syncthreads();
         f32x16 acc_d, acc_t;
@@ -174,150 +135,7 @@ __global__ __launch_bounds__(256) void ta_sum_slices_kernel(const float* __restr
     out[i] = acc;
 }
 
-// triangulation_pool.hip's forward walk (one wave per (clip, anchor)) with the softmax weights on the mean's terms
-template <int D>
-__global__ __launch_bounds__(64 * TA_WALK_WAVES) void ta_pool_fwd_kernel(const float* __restrict__ x, const float* __restrict__ anchors,
-                                                                         const float* __restrict__ w_d, const float* __restrict__ w_t, int T, int K,
-                                                                         float s, float* __restrict__ mean_d, float* __restrict__ max_d,
-                                                                         float* __restrict__ mean_t, float* __restrict__ max_t,
-                                                                         int* __restrict__ argmax) {
-    constexpr int N = TpVec<D>::N;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int kg = (K + TA_WALK_WAVES - 1) / TA_WALK_WAVES;
-    const int b = blockIdx.x / kg, k = (blockIdx.x % kg) * TA_WALK_WAVES + wave;
-    if (k >= K) return;                                   // (no barrier in this kernel)
-    float a[N], ep[N], tot_e[N], part_e[N], mx_e[N], tot_f[N], part_f[N], mx_f[N];
-    int idx[N];
-    tp_load_anchor<D>(anchors, K, k, lane, a);
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        ep[j] = 0.f;
-        tot_e[j] = part_e[j] = tot_f[j] = part_f[j] = 0.f;
-        mx_e[j] = mx_f[j] = -INFINITY;
-        idx[j] = 0;
-    }
-    const float* xb = x + (int64_t)b * T * D;
-    const float* wd = w_d + (int64_t)b * T;
-    const float* wt = w_t + (int64_t)b * (T - 1);
-    float xv[N], xn[N];
-    tp_load<D>(xb, lane, xv);
-    for (int t = 0; t < T; ++t) {
-        tp_load<D>(xb + (int64_t)min(t + 1, T - 1) * D, lane, xn);
-        float e[N];
-        bool clamped;
-        tp_unit<N>(xv, a, e, clamped);
-        const float we = wd[t];
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            e[j] *= s;
-            part_e[j] = fmaf(we, e[j], part_e[j]);
-            const bool up = e[j] > mx_e[j];
-            mx_e[j] = up ? e[j] : mx_e[j];
-            idx[j] = up ? ((idx[j] & (int)0xffff0000u) | t) : idx[j];
-        }
-        if (t > 0) {
-            float u[N], p = 0.f;
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-                u[j] = e[j] - ep[j];
-                p = fmaf(u[j], u[j], p);
-            }
-            p = wave_sum_dpp(p);
-            const float ip = rsqrtf(fmaxf(p, kL2Eps)), wf = wt[t - 1];
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-                const float f = u[j] * ip;
-                part_f[j] = fmaf(wf, f, part_f[j]);
-                const bool up = f > mx_f[j];
-                mx_f[j] = up ? f : mx_f[j];
-                idx[j] = up ? ((idx[j] & 0xffff) | (t << 16)) : idx[j];
-            }
-        }
-        if ((t & (TP_SUM_CHUNK - 1)) == TP_SUM_CHUNK - 1) {
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-                tot_e[j] += part_e[j];
-                tot_f[j] += part_f[j];
-                part_e[j] = part_f[j] = 0.f;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            ep[j] = e[j];
-            xv[j] = xn[j];
-        }
-    }
-    const float nd = (float)T, nt = (float)(T - 1);
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        tot_e[j] = (tot_e[j] + part_e[j]) / nd;
-        tot_f[j] = (tot_f[j] + part_f[j]) / nt;
-    }
-    const int64_t o = ((int64_t)b * K + k) * D;             // k-major: element k * D + d
-    tp_store<D>(mean_d + o, lane, tot_e);
-    tp_store<D>(max_d + o, lane, mx_e);
-    tp_store<D>(mean_t + o, lane, tot_f);
-    tp_store<D>(max_t + o, lane, mx_f);
-    tp_store<D>(argmax + o, lane, idx);
-}
-
-// the same walk for dw: part_d[b][k][t] = <g_mean_d[b, k, :], e_t> / T,  part_t[b][k][t-1] = <g_mean_t[b, k, :], f_t> / (T - 1)
-template <int D>
-__global__ __launch_bounds__(64 * TA_WALK_WAVES) void ta_dw_kernel(const float* __restrict__ x, const float* __restrict__ anchors,
-                                                                   const float* __restrict__ g_mean_d, const float* __restrict__ g_mean_t, int T,
-                                                                   int K, float s, float* __restrict__ part_d, float* __restrict__ part_t) {
-    constexpr int N = TpVec<D>::N;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int kg = (K + TA_WALK_WAVES - 1) / TA_WALK_WAVES;
-    const int b = blockIdx.x / kg, k = (blockIdx.x % kg) * TA_WALK_WAVES + wave;
-    if (k >= K) return;                                   // (no barrier in this kernel)
-    float a[N], ep[N], gd[N], gt[N];
-    const int64_t o = ((int64_t)b * K + k) * D;
-    tp_load_anchor<D>(anchors, K, k, lane, a);
-    tp_load<D>(g_mean_d + o, lane, gd);
-    tp_load<D>(g_mean_t + o, lane, gt);
-#pragma unroll
-    for (int j = 0; j < N; ++j) ep[j] = 0.f;
-    const float* xb = x + (int64_t)b * T * D;
-    float* od = part_d + ((int64_t)b * K + k) * T;
-    float* ot = part_t + ((int64_t)b * K + k) * (T - 1);
-    const float inv_d = 1.f / (float)T, inv_t = 1.f / (float)(T - 1);
-    for (int t = 0; t < T; ++t) {
-        float xv[N], e[N], dot = 0.f;
-        bool clamped;
-        tp_load<D>(xb + (int64_t)t * D, lane, xv);
-        tp_unit<N>(xv, a, e, clamped);
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            e[j] *= s;
-            dot = fmaf(e[j], gd[j], dot);
-        }
-        dot = wave_sum_dpp(dot);
-        if (lane == 0) od[t] = dot * inv_d;
-        if (t > 0) {
-            float u[N], p = 0.f, dt = 0.f;
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-                u[j] = e[j] - ep[j];
-                p = fmaf(u[j], u[j], p);
-            }
-            p = wave_sum_dpp(p);
-            const float ip = rsqrtf(fmaxf(p, kL2Eps));
-#pragma unroll
-            for (int j = 0; j < N; ++j) dt = fmaf(u[j] * ip, gt[j], dt);
-            dt = wave_sum_dpp(dt);
-            if (lane == 0) ot[t - 1] = dt * inv_t;
-        }
-#pragma unroll
-        for (int j = 0; j < N; ++j) ep[j] = e[j];
-    }
-}
-
-// e[t, c] from the chunk's frames in LDS: ((x - a) iq) s, the bits tp_unit followed by the scale gives; 0 for t >= T (iq = 0 there)
-__device__ __forceinline__ float ta_e(const float (*tX)[TA_LD], const float* iq, int t, int c, float av, float s) {
-    return ta_eh(tX[t][c], av, iq[t]) * s;
-}
-// f[t, c] likewise: 0 for t = 0 and t >= T (ip = 0 there)
+// f[t, c] as ta_e: 0 for t = 0 and t >= T (ip = 0 there)
 __device__ __forceinline__ float ta_f(const float (*tX)[TA_LD], const float* iq, const float* ip, int t, int c, float av, float s) {
     return (ta_e(tX, iq, t, c, av, s) - ta_e(tX, iq, max(t - 1, 0), c, av, s)) * ip[t];
 }
@@ -376,7 +194,7 @@ __global__ __launch_bounds__(64 * TA_WAVES) void ta_bwd_kernel(const float* __re
         {
             float a[N];
             tp_load_anchor<D>(anchors, K, k, lane, a);
-            ta_norms<D>(xb, a, T, 0, Tp, s, iq, qg, ip, pg);
+            ta_norms<D, TN_TEMPORAL | TN_GATES>(xb, a, nullptr, T, 0, Tp, s, iq, qg, ip, pg, nullptr);
         }
         for (int t = threadIdx.x; t < Tp; t += 64 * TA_WAVES) dotf[t] = dote[t] = 0.f;
         __syncthreads();
@@ -477,7 +295,9 @@ __global__ __launch_bounds__(64 * TA_WAVES) void ta_bwd_kernel(const float* __re
                         }
                     }
                     if (sweep < 3) {
-                        v = half_sum(v);                    // the 32 columns of the chunk: one half-wave per frame
+                        // the 32 columns of the chunk: one half-wave per frame.  (The shuffle form: half_sum_dpp adds in another order,
+                        // which would change this kernel's bits.)
+                        v = half_sum(v);
                         if (c == 0 && valid) (sweep == 1 ? dotf : dote)[t] += v;
                     }
                 }
@@ -497,7 +317,7 @@ __global__ __launch_bounds__(64 * TA_WAVES) void ta_bwd_kernel(const float* __re
 }
 
 // dx[b] = sum_g dx_part[b][g], g = 0, 1, ... (n4 = T * D / 4 float4 per block)
-__global__ __launch_bounds__(256) void ta_dx_reduce_kernel(const float4* __restrict__ part, int64_t total4, int64_t n4, int G,
+__global__ __launch_bounds__(256) void tp_dx_reduce_kernel(const float4* __restrict__ part, int64_t total4, int64_t n4, int G,
                                                            float4* __restrict__ dx) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total4) return;
@@ -511,15 +331,17 @@ __global__ __launch_bounds__(256) void ta_dx_reduce_kernel(const float4* __restr
     dx[i] = acc;
 }
 
-// danchors[d][k] = - sum_b da_part[b][k][d], b = 0, 1, ... (two-level: TP_SUM_CHUNK clips into a partial, partials into the total)
-__global__ __launch_bounds__(256) void ta_da_reduce_kernel(const float* __restrict__ part, int B, int K, int D, float* __restrict__ danchors) {
+// danchors[d][k] = - sum_b da_part[b][k][d], b = 0, 1, ... (two-level: `chunk` clips into a partial, partials into the total; every
+// partial starts from +0 and 0 + acc is exact, so chunk >= B gives the bits of a plain loop over the clips)
+__global__ __launch_bounds__(256) void tp_da_reduce_kernel(const float* __restrict__ part, int B, int K, int D, int chunk,
+                                                           float* __restrict__ danchors) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= K * D) return;
     const int k = i / D, d = i % D;
     float tot = 0.f;
-    for (int b0 = 0; b0 < B; b0 += TP_SUM_CHUNK) {
+    for (int b0 = 0; b0 < B; b0 += chunk) {
         float acc = 0.f;
-        for (int b = b0; b < min(b0 + TP_SUM_CHUNK, B); ++b) acc += part[(int64_t)b * K * D + i];
+        for (int b = b0; b < min(b0 + chunk, B); ++b) acc += part[(int64_t)b * K * D + i];
         tot += acc;
     }
     danchors[(int64_t)d * K + k] = -tot;
@@ -544,15 +366,15 @@ int ta_sum_slices(const float* part, int64_t outer, int64_t n, int S, float* out
     return LPM_OK;
 }
 
-int ta_reduce_partials(const float* dx_part, const float* da_part, int B, int T, int D, int K, int G, float* dx, float* danchors,
-                       hipStream_t s, const char* name) {
+int ta_reduce_partials(const float* dx_part, const float* da_part, int B, int T, int D, int K, int G, int da_chunk, float* dx,
+                       float* danchors, hipStream_t s, const char* name) {
     if (G > 1) {
         const int64_t n4 = (int64_t)T * D / 4, total4 = n4 * B;
         LPM_REQUIRE((total4 + 255) / 256 < (1ll << 31), LPM_ERR_UNSUPPORTED_SHAPE, "%s: B * T * D too large", name);
-        hipLaunchKernelGGL(ta_dx_reduce_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, (const float4*)dx_part, total4, n4, G,
+        hipLaunchKernelGGL(tp_dx_reduce_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, (const float4*)dx_part, total4, n4, G,
                            (float4*)dx);
     }
-    hipLaunchKernelGGL(ta_da_reduce_kernel, dim3((K * D + 255) / 256), dim3(256), 0, s, da_part, B, K, D, danchors);
+    hipLaunchKernelGGL(tp_da_reduce_kernel, dim3((K * D + 255) / 256), dim3(256), 0, s, da_part, B, K, D, da_chunk, danchors);
     return LPM_OK;
 }
 
@@ -586,10 +408,9 @@ extern "C" int lpm_triangulation_attention_gram(const float* x, const float* anc
     float* part_t = S > 1 ? part_d + (size_t)B * S * T * T : gram_t;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)(B * S * NT * NT)), block(64 * TA_WAVES);
-    if (D == 1024)
-        hipLaunchKernelGGL(ta_gram_kernel<1024>, grid, block, 0, s, x, anchors, T, K, scale, S, NT, part_d, part_t);
-    else
-        hipLaunchKernelGGL(ta_gram_kernel<128>, grid, block, 0, s, x, anchors, T, K, scale, S, NT, part_d, part_t);
+    tp_dispatch_d(D, [&](auto d) {
+        hipLaunchKernelGGL(ta_gram_kernel<decltype(d)::value>, grid, block, 0, s, x, anchors, T, K, scale, S, NT, part_d, part_t);
+    });
     if (S > 1) {
         if (const int rc = ta_sum_slices(part_d, B, (int64_t)T * T, S, gram_d, s, name)) return rc;
         if (const int rc = ta_sum_slices(part_t, B, (int64_t)T1 * T1, S, gram_t, s, name)) return rc;
@@ -606,12 +427,10 @@ extern "C" int lpm_triangulation_attention_pool_fwd(const float* x, const float*
     if (const int rc = ta_check(name, B, T, D, K)) return rc;
     LPM_REQUIRE((((uintptr_t)x | (uintptr_t)max_d | (uintptr_t)mean_d | (uintptr_t)max_t | (uintptr_t)mean_t | (uintptr_t)argmax) & 15) == 0,
                 LPM_ERR_BADARG, "%s: x and the outputs must be 16-byte aligned", name);
-    const dim3 grid(B * ((K + TA_WALK_WAVES - 1) / TA_WALK_WAVES)), block(64 * TA_WALK_WAVES);
-    hipStream_t s = (hipStream_t)stream;
-    if (D == 1024)
-        hipLaunchKernelGGL(ta_pool_fwd_kernel<1024>, grid, block, 0, s, x, anchors, w_d, w_t, T, K, scale, mean_d, max_d, mean_t, max_t, argmax);
-    else
-        hipLaunchKernelGGL(ta_pool_fwd_kernel<128>, grid, block, 0, s, x, anchors, w_d, w_t, T, K, scale, mean_d, max_d, mean_t, max_t, argmax);
+    tp_dispatch_d(D, [&](auto d) {
+        hipLaunchKernelGGL((tp_walk_fwd_kernel<decltype(d)::value, true, true, true>), dim3(tp_walk_grid(B, K)), dim3(64 * TP_WALK_WAVES), 0,
+                           (hipStream_t)stream, x, anchors, w_d, w_t, T, K, scale, mean_d, max_d, mean_t, max_t, argmax);
+    });
     return check_launch(name);
 }
 
@@ -628,12 +447,11 @@ extern "C" int lpm_triangulation_attention_dw(const float* x, const float* ancho
                 "%s: x and the gradients must be 16-byte aligned", name);
     float* part_d = (float*)workspace;
     float* part_t = part_d + (size_t)B * K * T;
-    const dim3 grid(B * ((K + TA_WALK_WAVES - 1) / TA_WALK_WAVES)), block(64 * TA_WALK_WAVES);
     hipStream_t s = (hipStream_t)stream;
-    if (D == 1024)
-        hipLaunchKernelGGL(ta_dw_kernel<1024>, grid, block, 0, s, x, anchors, g_mean_d, g_mean_t, T, K, scale, part_d, part_t);
-    else
-        hipLaunchKernelGGL(ta_dw_kernel<128>, grid, block, 0, s, x, anchors, g_mean_d, g_mean_t, T, K, scale, part_d, part_t);
+    tp_dispatch_d(D, [&](auto d) {
+        hipLaunchKernelGGL((tp_walk_dw_kernel<decltype(d)::value, true>), dim3(tp_walk_grid(B, K)), dim3(64 * TP_WALK_WAVES), 0, s, x, anchors,
+                           g_mean_d, T, K, scale, part_d, g_mean_t, part_t);
+    });
     if (const int rc = ta_sum_slices(part_d, B, T, K, dw_d, s, name)) return rc;
     if (const int rc = ta_sum_slices(part_t, B, T - 1, K, dw_t, s, name)) return rc;
     return check_launch(name);
@@ -659,29 +477,15 @@ extern "C" int lpm_triangulation_attention_bwd(const float* x, const float* anch
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(B * G), block(64 * TA_WAVES);
     const size_t lds = ta_bwd_lds(T);
-    static bool lds_set = false;                                           // (a race sets the same attribute twice)
-    if (!lds_set) {
-        const int most = (int)ta_bwd_lds(TA_MAX_FRAMES);                   // (more than the fast form's)
-        const void* kernels[] = {(const void*)ta_bwd_kernel<1024, 0>, (const void*)ta_bwd_kernel<128, 0>,
-                                 (const void*)ta_bwd_kernel<1024, TA_FAST_FRAMES>, (const void*)ta_bwd_kernel<128, TA_FAST_FRAMES>};
-        for (const void* kernel : kernels) {
-            if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess) {
-                (void)hipGetLastError();
-                set_error("%s: cannot reserve %d bytes of LDS", name, most);
-                return LPM_ERR_LAUNCH;
-            }
-        }
-        lds_set = true;
-    }
-#define TA_LAUNCH_BWD(DD, TT)                                                                                                             \
-    hipLaunchKernelGGL((ta_bwd_kernel<DD, TT>), grid, block, lds, s, x, anchors, argmax, w_d, w_t, m_d, m_t, g_mean_d, g_max_d, g_mean_t, \
-                       g_max_t, T, K, scale, G, dx_part, da_part)
-    if (T <= TA_FAST_FRAMES) {
-        if (D == 1024) TA_LAUNCH_BWD(1024, TA_FAST_FRAMES); else TA_LAUNCH_BWD(128, TA_FAST_FRAMES);
-    } else {
-        if (D == 1024) TA_LAUNCH_BWD(1024, 0); else TA_LAUNCH_BWD(128, 0);
-    }
-#undef TA_LAUNCH_BWD
-    if (const int rc = ta_reduce_partials(dx_part, da_part, B, T, D, K, G, dx, danchors, s, name)) return rc;
+    if (const int rc = tp_reserve_lds<ta_bwd_kernel<1024, 0>, ta_bwd_kernel<128, 0>, ta_bwd_kernel<1024, TA_FAST_FRAMES>,
+                                      ta_bwd_kernel<128, TA_FAST_FRAMES>>(name, (int)ta_bwd_lds(TA_MAX_FRAMES)))     // (more than the fast form's)
+        return rc;
+    tp_dispatch_d(D, [&](auto d) {
+        constexpr int DD = decltype(d)::value;
+        auto* kernel = T <= TA_FAST_FRAMES ? ta_bwd_kernel<DD, TA_FAST_FRAMES> : ta_bwd_kernel<DD, 0>;
+        hipLaunchKernelGGL(kernel, grid, block, lds, s, x, anchors, argmax, w_d, w_t, m_d, m_t, g_mean_d, g_max_d, g_mean_t, g_max_t, T, K, scale,
+                           G, dx_part, da_part);
+    });
+    if (const int rc = ta_reduce_partials(dx_part, da_part, B, T, D, K, G, TP_SUM_CHUNK, dx, danchors, s, name)) return rc;
     return check_launch(name);
 }

@@ -555,18 +555,16 @@ extern "C" int lpm_triangulation_bn_moments_stats(const float* x, const float* a
     const float* iq = q + BT * K;
     float* part = (float*)workspace;
     const float inv_s = 1.f / (float)BT, inv_t = 1.f / (float)(BT - B);
-#define TB_LAUNCH_STATS(DD)                                                                                                           \
-    hipLaunchKernelGGL(tb_norms_kernel<DD>, grid_n, block, 0, s, x, anchors, BT, K, q);                                               \
-    if (want_stats) {                                                                                                                 \
-        hipLaunchKernelGGL((tb_stats_kernel<DD, 0>), dim3(nj, B, 2), dim3(256), 0, s, x, anchors, iq, stats, B, T, K, part);          \
-        hipLaunchKernelGGL(tb_colsum_kernel, dim3(nj, 2), dim3(256), 0, s, part, B, J, (int64_t)2 * J, inv_s, inv_t, 0, stats);       \
-        hipLaunchKernelGGL((tb_stats_kernel<DD, 1>), dim3(nj, B, 2), dim3(256), 0, s, x, anchors, iq, stats, B, T, K, part);          \
-        hipLaunchKernelGGL(tb_colsum_kernel, dim3(nj, 2), dim3(256), 0, s, part, B, J, (int64_t)2 * J, inv_s, inv_t, 0, stats + J);   \
-        hipLaunchKernelGGL(tb_colsum_kernel, dim3(nj, 2), dim3(256), 0, s, part + (size_t)2 * B * J, B, J, (int64_t)2 * J, inv_s, inv_t, 1, \
-                           stats);                                                                                                    \
-    }
-    if (D == 1024) { TB_LAUNCH_STATS(1024) } else { TB_LAUNCH_STATS(128) }
-#undef TB_LAUNCH_STATS
+    tp_dispatch_d(D, [&](auto d) {
+        constexpr int DD = decltype(d)::value;
+        hipLaunchKernelGGL(tb_norms_kernel<DD>, grid_n, block, 0, s, x, anchors, BT, K, q);
+        if (!want_stats) return;
+        hipLaunchKernelGGL((tb_stats_kernel<DD, 0>), dim3(nj, B, 2), dim3(256), 0, s, x, anchors, iq, stats, B, T, K, part);
+        hipLaunchKernelGGL(tb_colsum_kernel, dim3(nj, 2), dim3(256), 0, s, part, B, J, (int64_t)2 * J, inv_s, inv_t, 0, stats);
+        hipLaunchKernelGGL((tb_stats_kernel<DD, 1>), dim3(nj, B, 2), dim3(256), 0, s, x, anchors, iq, stats, B, T, K, part);
+        hipLaunchKernelGGL(tb_colsum_kernel, dim3(nj, 2), dim3(256), 0, s, part, B, J, (int64_t)2 * J, inv_s, inv_t, 0, stats + J);
+        hipLaunchKernelGGL(tb_colsum_kernel, dim3(nj, 2), dim3(256), 0, s, part + (size_t)2 * B * J, B, J, (int64_t)2 * J, inv_s, inv_t, 1, stats);
+    });
     return check_launch(name);
 }
 
@@ -584,10 +582,9 @@ extern "C" int lpm_triangulation_bn_moments_gram(const float* x, const float* an
     float* part_t = S > 1 ? part_s + (size_t)B * S * T * T : gram_t;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)(B * S * NT * NT)), block(64 * TA_WAVES);
-    if (D == 1024)
-        hipLaunchKernelGGL(tb_gram_kernel<1024>, grid, block, 0, s, x, anchors, iq, aff, T, K, S, NT, part_s, part_t);
-    else
-        hipLaunchKernelGGL(tb_gram_kernel<128>, grid, block, 0, s, x, anchors, iq, aff, T, K, S, NT, part_s, part_t);
+    tp_dispatch_d(D, [&](auto d) {
+        hipLaunchKernelGGL(tb_gram_kernel<decltype(d)::value>, grid, block, 0, s, x, anchors, iq, aff, T, K, S, NT, part_s, part_t);
+    });
     if (S > 1) {
         if (const int rc = ta_sum_slices(part_s, B, (int64_t)T * T, S, gram_s, s, name)) return rc;
         if (const int rc = ta_sum_slices(part_t, B, (int64_t)T1 * T1, S, gram_t, s, name)) return rc;
@@ -604,10 +601,9 @@ extern "C" int lpm_triangulation_bn_moments_pool(const float* x, const float* an
     if (const int rc = tb_check(name, B, T, D, K)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((K * D + 255) / 256, B, 2), block(256);
-    if (D == 1024)
-        hipLaunchKernelGGL(tb_pool_kernel<1024>, grid, block, 0, s, x, anchors, iq, aff, w_s, w_t, B, T, K, pool_s, pool_t, rawbar, corr);
-    else
-        hipLaunchKernelGGL(tb_pool_kernel<128>, grid, block, 0, s, x, anchors, iq, aff, w_s, w_t, B, T, K, pool_s, pool_t, rawbar, corr);
+    tp_dispatch_d(D, [&](auto d) {
+        hipLaunchKernelGGL(tb_pool_kernel<decltype(d)::value>, grid, block, 0, s, x, anchors, iq, aff, w_s, w_t, B, T, K, pool_s, pool_t, rawbar, corr);
+    });
     return check_launch(name);
 }
 
@@ -619,10 +615,9 @@ extern "C" int lpm_triangulation_bn_moments_dw(const float* x, const float* anch
     if (const int rc = tb_check(name, B, T, D, K)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(B * T, 2), block(256);
-    if (D == 1024)
-        hipLaunchKernelGGL(tb_dw_kernel<1024>, grid, block, 0, s, x, anchors, iq, aff, g_s, g_t, T, K, dw_s, dw_t);
-    else
-        hipLaunchKernelGGL(tb_dw_kernel<128>, grid, block, 0, s, x, anchors, iq, aff, g_s, g_t, T, K, dw_s, dw_t);
+    tp_dispatch_d(D, [&](auto d) {
+        hipLaunchKernelGGL(tb_dw_kernel<decltype(d)::value>, grid, block, 0, s, x, anchors, iq, aff, g_s, g_t, T, K, dw_s, dw_t);
+    });
     return check_launch(name);
 }
 
@@ -643,20 +638,9 @@ extern "C" int lpm_triangulation_bn_moments_bwd(const float* x, const float* anc
     const int64_t BT = (int64_t)B * T;
     const int J = K * D;
     const size_t lds = tb_bwd_lds(T);
-    static bool lds_set = false;                                           // (a race sets the same attribute twice)
-    if (!lds_set) {
-        const int most = (int)tb_bwd_lds(TA_MAX_FRAMES);
-        const void* kernels[] = {(const void*)tb_bwd_kernel<1024, 1>, (const void*)tb_bwd_kernel<1024, 2>, (const void*)tb_bwd_kernel<1024, 3>,
-                                 (const void*)tb_bwd_kernel<128, 1>,  (const void*)tb_bwd_kernel<128, 2>,  (const void*)tb_bwd_kernel<128, 3>};
-        for (const void* kernel : kernels) {
-            if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess) {
-                (void)hipGetLastError();
-                set_error("%s: cannot reserve %d bytes of LDS", name, most);
-                return LPM_ERR_LAUNCH;
-            }
-        }
-        lds_set = true;
-    }
+    if (const int rc = tp_reserve_lds<tb_bwd_kernel<1024, 1>, tb_bwd_kernel<1024, 2>, tb_bwd_kernel<1024, 3>, tb_bwd_kernel<128, 1>,
+                                      tb_bwd_kernel<128, 2>, tb_bwd_kernel<128, 3>>(name, (int)tb_bwd_lds(TA_MAX_FRAMES)))
+        return rc;
     TbBwdArgs A;
     A.x = x; A.anchors = anchors; A.q = q; A.iq = q + BT * K; A.aff = aff; A.w_s = w_s; A.w_t = w_t; A.m_s = m_s; A.m_t = m_t;
     A.rawbar = rawbar; A.corr = corr; A.g_s = g_s; A.g_t = g_t; A.dgrad = dgrad;
@@ -668,17 +652,17 @@ extern "C" int lpm_triangulation_bn_moments_bwd(const float* x, const float* anc
     A.da_part = A.dot + (size_t)BT * K;
     A.dx = dx;
     const dim3 block(64 * TA_WAVES), grid_k((unsigned)(B * K)), grid_c((unsigned)(B * (D / TA_CH)));
-#define TB_LAUNCH_BWD(DD)                                                                                                      \
-    if (affine_grads) {                                                                                                        \
-        hipLaunchKernelGGL((tb_bwd_kernel<DD, 1>), grid_k, block, lds, s, A);                                                  \
-        hipLaunchKernelGGL(tb_colsum_kernel, dim3((J + 255) / 256, 4), dim3(256), 0, s, A.dpart, B, J, (int64_t)J, 1.f, 1.f, 0, dgrad); \
-    } else {                                                                                                                   \
-        (void)hipMemsetAsync(dgrad, 0, (size_t)4 * J * sizeof(float), s);                                                      \
-    }                                                                                                                          \
-    hipLaunchKernelGGL((tb_bwd_kernel<DD, 2>), grid_k, block, lds, s, A);                                                      \
-    hipLaunchKernelGGL((tb_bwd_kernel<DD, 3>), grid_c, block, lds, s, A)
-    if (D == 1024) { TB_LAUNCH_BWD(1024); } else { TB_LAUNCH_BWD(128); }
-#undef TB_LAUNCH_BWD
-    if (const int rc = ta_reduce_partials(dx, A.da_part, B, T, D, K, 1, dx, danchors, s, name)) return rc;
+    tp_dispatch_d(D, [&](auto d) {
+        constexpr int DD = decltype(d)::value;
+        if (affine_grads) {
+            hipLaunchKernelGGL((tb_bwd_kernel<DD, 1>), grid_k, block, lds, s, A);
+            hipLaunchKernelGGL(tb_colsum_kernel, dim3((J + 255) / 256, 4), dim3(256), 0, s, A.dpart, B, J, (int64_t)J, 1.f, 1.f, 0, dgrad);
+        } else {
+            (void)hipMemsetAsync(dgrad, 0, (size_t)4 * J * sizeof(float), s);
+        }
+        hipLaunchKernelGGL((tb_bwd_kernel<DD, 2>), grid_k, block, lds, s, A);
+        hipLaunchKernelGGL((tb_bwd_kernel<DD, 3>), grid_c, block, lds, s, A);
+    });
+    if (const int rc = ta_reduce_partials(dx, A.da_part, B, T, D, K, 1, TP_SUM_CHUNK, dx, danchors, s, name)) return rc;
     return check_launch(name);
 }

@@ -15,41 +15,24 @@
 // 32-column chunks -- e of the chunk to LDS, each wave adds its 32x32 quadrant of E_I E_J^T.  Two-level sums: an anchor's product in
 // registers, onto the slice's total; the slices' partial Grams are added s = 0, 1, ... by a second pass.
 //
-// lpm_triangulation_mean_pool_fwd / _dw: triangulation_pool.hip's forward walk (one wave per (clip, anchor)).
+// lpm_triangulation_mean_pool_fwd / _dw: tp_walk_fwd_kernel<D, w, no weight on f, no maxima> and tp_walk_dw_kernel<D, not temporal>
+// (triangulation_common.h; tests/test_gpu_triangulation_family.py holds m_t bitwise equal to triangulation_pool's mean_t).
 //
 // lpm_triangulation_mean_bwd: with M = dG_d + dG_d^T (symmetric, from the caller) and gf = g_t[k] / (T-1), ONE row per anchor:
 //   gu_t = ip (gf - f_t (f_t . gf) [p > 1e-12])  (t >= 1)         ge_t = (w[t] / T) g_d[k] + (M E_k)[t] + gu_t - gu_{t+1}
 //   gr_t = s iq (ge_t - eh_t (eh_t . ge_t) [q > 1e-12])           dx[b,t,:] = sum_k gr_t      danchors[:,k] = - sum_{b,t} gr_t
-// A workgroup owns a clip and the anchors k = g, g + G, ...; per anchor the pass that takes the norms of all frames (one wave per
-// frame, the whole row in registers) takes (f_t . gf) as well, so D is walked twice in 32-column chunks, not three times: (eh . ge),
+// A workgroup owns a clip and the anchors k = g, g + G, ...; per anchor the pass that takes the norms of all frames (ta_norms: one
+// wave per frame, the whole row in registers) takes (f_t . gf) as well, so D is walked twice in 32-column chunks, not three times: (eh . ge),
 // then gr.  Per chunk: the frames to LDS ([T,33]), M E on the matrix cores into a second [T,33] tile, a thread per (t, column) for the
 // chain.  Partials and their reductions as in triangulation_attention.hip.
 #include "triangulation_common.h"
 
-// u = e_t - e_{t-1} must be exactly zero for identical frames: no product may be fused into that difference
+// the contraction rule (triangulation_common.h) for everything below
 #pragma clang fp contract(off)
 
 namespace lpm {
 
 constexpr int TM_MAX_JOBS = (TA_MAX_FRAMES / 32 + TA_WAVES - 1) / TA_WAVES;    // 32-row tiles of M E per wave and chunk
-
-// iq = rsqrt(max(|x - a|^2, eps)) of the frames f0 .. f0 + n - 1 of one (clip, anchor), one wave per frame; 0 outside [0, T)
-template <int D>
-__device__ __forceinline__ void tm_iq(const float* __restrict__ xb, const float (&a)[D / 64], int T, int f0, int n, float* iq) {
-    constexpr int N = TpVec<D>::N;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int i = wave; i < n; i += TA_WAVES) {
-        const int t = f0 + i;
-        float v = 0.f;
-        if (t < T) {                                        // (wave-uniform)
-            float xv[N], e[N];
-            bool c;
-            tp_load<D>(xb + (int64_t)t * D, lane, xv);
-            v = tp_unit<N>(xv, a, e, c);
-        }
-        if (lane == 0) iq[i] = v;
-    }
-}
 
 static int tm_pairs(int T) { return ta_tiles(T) * (ta_tiles(T) + 1) / 2; }
 static int tm_slices(int B, int T, int K) {
@@ -96,7 +79,8 @@ __global__ __launch_bounds__(64 * TA_WAVES) void tm_gram_kernel(const float* __r
         {
             float a[N];
             tp_load_anchor<D>(anchors, K, k, lane, a);
-            for (int side = 0; side < nside; ++side) tm_iq<D>(xb, a, T, (side ? tj : ti) * 64, 64, nrm[side]);
+            for (int side = 0; side < nside; ++side)
+                ta_norms<D, 0>(xb, a, nullptr, T, (side ? tj : ti) * 64, 64, s, nrm[side], nullptr, nullptr, nullptr, nullptr);
         }
         __syncthreads();
         f32x16 acc;
@@ -151,160 +135,6 @@ __global__ __launch_bounds__(64 * TA_WAVES) void tm_gram_kernel(const float* __r
     }
 }
 
-// triangulation_pool.hip's forward walk (one wave per (clip, anchor)): the softmax weights on e's terms, none on f's; no maxima
-template <int D>
-__global__ __launch_bounds__(64 * TA_WALK_WAVES) void tm_pool_fwd_kernel(const float* __restrict__ x, const float* __restrict__ anchors,
-                                                                         const float* __restrict__ w, int T, int K, float s,
-                                                                         float* __restrict__ m_d, float* __restrict__ m_t) {
-    constexpr int N = TpVec<D>::N;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int kg = (K + TA_WALK_WAVES - 1) / TA_WALK_WAVES;
-    const int b = blockIdx.x / kg, k = (blockIdx.x % kg) * TA_WALK_WAVES + wave;
-    if (k >= K) return;                                   // (no barrier in this kernel)
-    float a[N], ep[N], tot_e[N], part_e[N], tot_f[N], part_f[N];
-    tp_load_anchor<D>(anchors, K, k, lane, a);
-#pragma unroll
-    for (int j = 0; j < N; ++j) ep[j] = tot_e[j] = part_e[j] = tot_f[j] = part_f[j] = 0.f;
-    const float* xb = x + (int64_t)b * T * D;
-    const float* wb = w + (int64_t)b * T;
-    float xv[N], xn[N];
-    tp_load<D>(xb, lane, xv);
-    for (int t = 0; t < T; ++t) {
-        tp_load<D>(xb + (int64_t)min(t + 1, T - 1) * D, lane, xn);
-        float e[N];
-        bool clamped;
-        tp_unit<N>(xv, a, e, clamped);
-        const float we = wb[t];
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            e[j] *= s;
-            part_e[j] = fmaf(we, e[j], part_e[j]);
-        }
-        if (t > 0) {
-            float u[N], p = 0.f;
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-                u[j] = e[j] - ep[j];
-                p = fmaf(u[j], u[j], p);
-            }
-            p = wave_sum_dpp(p);
-            const float ip = rsqrtf(fmaxf(p, kL2Eps));
-#pragma unroll
-            for (int j = 0; j < N; ++j) part_f[j] += u[j] * ip;
-        }
-        if ((t & (TP_SUM_CHUNK - 1)) == TP_SUM_CHUNK - 1) {
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-                tot_e[j] += part_e[j];
-                tot_f[j] += part_f[j];
-                part_e[j] = part_f[j] = 0.f;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            ep[j] = e[j];
-            xv[j] = xn[j];
-        }
-    }
-    const float nd = (float)T, nt = (float)(T - 1);
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        tot_e[j] = (tot_e[j] + part_e[j]) / nd;
-        tot_f[j] = (tot_f[j] + part_f[j]) / nt;
-    }
-    const int64_t o = ((int64_t)b * K + k) * D;             // k-major: element k * D + d
-    tp_store<D>(m_d + o, lane, tot_e);
-    tp_store<D>(m_t + o, lane, tot_f);
-}
-
-// the same walk for dw: part[b][k][t] = <g_d[b, k, :], e_t> / T
-template <int D>
-__global__ __launch_bounds__(64 * TA_WALK_WAVES) void tm_dw_kernel(const float* __restrict__ x, const float* __restrict__ anchors,
-                                                                   const float* __restrict__ g_d, int T, int K, float s,
-                                                                   float* __restrict__ part) {
-    constexpr int N = TpVec<D>::N;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int kg = (K + TA_WALK_WAVES - 1) / TA_WALK_WAVES;
-    const int b = blockIdx.x / kg, k = (blockIdx.x % kg) * TA_WALK_WAVES + wave;
-    if (k >= K) return;                                   // (no barrier in this kernel)
-    float a[N], gd[N];
-    tp_load_anchor<D>(anchors, K, k, lane, a);
-    tp_load<D>(g_d + ((int64_t)b * K + k) * D, lane, gd);
-    const float* xb = x + (int64_t)b * T * D;
-    float* o = part + ((int64_t)b * K + k) * T;
-    const float inv_d = 1.f / (float)T;
-    for (int t = 0; t < T; ++t) {
-        float xv[N], e[N], dot = 0.f;
-        bool clamped;
-        tp_load<D>(xb + (int64_t)t * D, lane, xv);
-        tp_unit<N>(xv, a, e, clamped);
-#pragma unroll
-        for (int j = 0; j < N; ++j) dot = fmaf(e[j] * s, gd[j], dot);
-        dot = wave_sum_dpp(dot);
-        if (lane == 0) o[t] = dot * inv_d;
-    }
-}
-
-// The backward's per-anchor pass over whole rows, one wave per frame (entry t belongs to frame t; zeros for t >= T):
-// iq, ip = rsqrt(max(., eps)) of |x - a|^2 and |e_t - e_{t-1}|^2, qg / pg = 1 where the squared norm exceeded eps,
-// dotf = (f_t . gf) with gf (= g_t[k] / (T-1)) in the lane layout
-template <int D>
-__device__ __forceinline__ void tm_bwd_norms(const float* __restrict__ xb, const float (&a)[D / 64], const float (&gf)[D / 64], int T, int n,
-                                             float s, float* iq, float* qg, float* ip, float* pg, float* dotf) {
-    constexpr int N = TpVec<D>::N;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int t = wave; t < n; t += TA_WAVES) {
-        float viq = 0.f, vqg = 0.f, vip = 0.f, vpg = 0.f, vdf = 0.f;
-        if (t < T) {                                        // (wave-uniform)
-            float xv[N], e[N];
-            bool c;
-            tp_load<D>(xb + (int64_t)t * D, lane, xv);
-            viq = tp_unit<N>(xv, a, e, c);
-            vqg = c ? 0.f : 1.f;
-            if (t >= 1) {
-                float ep[N], u[N], p = 0.f;
-                bool c2;
-                tp_load<D>(xb + (int64_t)(t - 1) * D, lane, xv);
-                tp_unit<N>(xv, a, ep, c2);
-#pragma unroll
-                for (int j = 0; j < N; ++j) {
-                    u[j] = e[j] * s - ep[j] * s;
-                    p = fmaf(u[j], u[j], p);
-                }
-                p = wave_sum_dpp(p);
-                vip = rsqrtf(fmaxf(p, kL2Eps));
-                vpg = p > kL2Eps ? 1.f : 0.f;
-#pragma unroll
-                for (int j = 0; j < N; ++j) vdf = fmaf(u[j] * vip, gf[j], vdf);
-                vdf = wave_sum_dpp(vdf);
-            }
-        }
-        if (lane == 0) {
-            iq[t] = viq;
-            qg[t] = vqg;
-            ip[t] = vip;
-            pg[t] = vpg;
-            dotf[t] = vdf;
-        }
-    }
-}
-
-// the sum over the 32 lanes that share (lane >> 5), on the VALU: four DPP steps give every lane its row-of-16 total, two v_readlane
-// join the rows of a half (__shfl_xor is a round trip through the LDS crossbar on this target)
-__device__ __forceinline__ float tm_half_sum(float v) {
-    v += dpp_lanes<0xB1>(v);
-    v += dpp_lanes<0x4E>(v);
-    v += dpp_lanes<0x141>(v);
-    v += dpp_lanes<0x140>(v);
-    const float lo = lane_value(v, 0) + lane_value(v, 16), hi = lane_value(v, 32) + lane_value(v, 48);
-    return (threadIdx.x & 32) ? hi : lo;
-}
-
-// e[t, c] from the chunk's frames in LDS; 0 for t >= T (iq = 0 there)
-__device__ __forceinline__ float tm_e(const float (*tX)[TA_LD], const float* iq, int t, int c, float av, float s) {
-    return ta_eh(tX[t][c], av, iq[t]) * s;
-}
-
 // TP = 64: T <= 64, every loop over the frames unrolled, M of the clip in LDS (two 32-row tiles of M E per chunk: waves 2 and 3 take
 // no part in the product); TP = 0: any T <= TA_MAX_FRAMES, M from global memory (L2), up to TM_MAX_JOBS tiles per wave.
 template <int D, int TP>
@@ -351,7 +181,7 @@ __global__ __launch_bounds__(64 * TA_WAVES) void tm_bwd_kernel(const float* __re
             tp_load<D>(g_t + o, lane, gf);
 #pragma unroll
             for (int j = 0; j < N; ++j) gf[j] *= inv_t;
-            tm_bwd_norms<D>(xb, a, gf, T, Tp, s, iq, qg, ip, pg, dotf);
+            ta_norms<D, TN_TEMPORAL | TN_GATES | TN_DOTF>(xb, a, gf, T, 0, Tp, s, iq, qg, ip, pg, dotf);
         }
         for (int t = threadIdx.x; t < Tp; t += 64 * TA_WAVES) dote[t] = 0.f;
         __syncthreads();
@@ -398,7 +228,7 @@ __global__ __launch_bounds__(64 * TA_WAVES) void tm_bwd_kernel(const float* __re
 #pragma unroll 8
                             for (int s2 = 0; s2 < TP; s2 += 2) {
                                 const int srow = s2 + (lane >> 5);
-                                ac = mfma32(mp[srow * TP], tm_e(tX, iq, srow, c, av, s), ac);
+                                ac = mfma32(mp[srow * TP], ta_e(tX, iq, srow, c, av, s), ac);
                             }
                         } else {
                             // M comes from L2: the 16 values of the NEXT 32 rows are in flight while the matrix cores take the
@@ -415,7 +245,7 @@ __global__ __launch_bounds__(64 * TA_WAVES) void tm_bwd_kernel(const float* __re
                                     nxt[i] = (tcol < T && srow < T) ? mp[(int64_t)srow * T] : 0.f;
                                 }
 #pragma unroll
-                                for (int i = 0; i < 16; ++i) ac = mfma32(cur[i], tm_e(tX, iq, s0 + 2 * i + sh, c, av, s), ac);
+                                for (int i = 0; i < 16; ++i) ac = mfma32(cur[i], ta_e(tX, iq, s0 + 2 * i + sh, c, av, s), ac);
 #pragma unroll
                                 for (int i = 0; i < 16; ++i) cur[i] = nxt[i];
                             }
@@ -446,11 +276,11 @@ __global__ __launch_bounds__(64 * TA_WAVES) void tm_bwd_kernel(const float* __re
                             const float eh = ta_eh(tX[t][c], av, iq[t]), e = eh * s;
                             float gu = 0.f, gun = 0.f;
                             if (t >= 1) {
-                                const float f = (e - tm_e(tX, iq, t - 1, c, av, s)) * ip[t];
+                                const float f = (e - ta_e(tX, iq, t - 1, c, av, s)) * ip[t];
                                 gu = ip[t] * (gmt - f * (dotf[t] * pg[t]));
                             }
                             if (t + 1 < T) {
-                                const float fn = (tm_e(tX, iq, t + 1, c, av, s) - e) * ip[t + 1];
+                                const float fn = (ta_e(tX, iq, t + 1, c, av, s) - e) * ip[t + 1];
                                 gun = ip[t + 1] * (gmt - fn * (dotf[t + 1] * pg[t + 1]));
                             }
                             const float ge = wl[t] * gmd + tP[t][c] + gu - gun;
@@ -463,7 +293,7 @@ __global__ __launch_bounds__(64 * TA_WAVES) void tm_bwd_kernel(const float* __re
                             }
                         }
                         if (sweep == 0) {
-                            v = tm_half_sum(v);             // the 32 columns of the chunk: one half-wave per frame
+                            v = half_sum_dpp(v);            // the 32 columns of the chunk: one half-wave per frame
                             if (c == 0 && valid) dote[t] += v;
                         }
                     }
@@ -515,10 +345,7 @@ extern "C" int lpm_triangulation_mean_gram(const float* x, const float* anchors,
     float* part = S > 1 ? (float*)workspace : gram_d;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)(B * S * tm_pairs(T))), block(64 * TA_WAVES);
-    if (D == 1024)
-        hipLaunchKernelGGL(tm_gram_kernel<1024>, grid, block, 0, s, x, anchors, T, K, scale, S, NT, part);
-    else
-        hipLaunchKernelGGL(tm_gram_kernel<128>, grid, block, 0, s, x, anchors, T, K, scale, S, NT, part);
+    tp_dispatch_d(D, [&](auto d) { hipLaunchKernelGGL(tm_gram_kernel<decltype(d)::value>, grid, block, 0, s, x, anchors, T, K, scale, S, NT, part); });
     if (S > 1) {
         if (const int rc = ta_sum_slices(part, B, (int64_t)T * T, S, gram_d, s, name)) return rc;
     }
@@ -532,12 +359,10 @@ extern "C" int lpm_triangulation_mean_pool_fwd(const float* x, const float* anch
     LPM_REQUIRE(x && anchors && w_d && m_d && m_t, LPM_ERR_BADARG, "%s: null pointer", name);
     if (const int rc = ta_check(name, B, T, D, K)) return rc;
     LPM_REQUIRE((((uintptr_t)x | (uintptr_t)m_d | (uintptr_t)m_t) & 15) == 0, LPM_ERR_BADARG, "%s: x and the outputs must be 16-byte aligned", name);
-    const dim3 grid(B * ((K + TA_WALK_WAVES - 1) / TA_WALK_WAVES)), block(64 * TA_WALK_WAVES);
-    hipStream_t s = (hipStream_t)stream;
-    if (D == 1024)
-        hipLaunchKernelGGL(tm_pool_fwd_kernel<1024>, grid, block, 0, s, x, anchors, w_d, T, K, scale, m_d, m_t);
-    else
-        hipLaunchKernelGGL(tm_pool_fwd_kernel<128>, grid, block, 0, s, x, anchors, w_d, T, K, scale, m_d, m_t);
+    tp_dispatch_d(D, [&](auto d) {
+        hipLaunchKernelGGL((tp_walk_fwd_kernel<decltype(d)::value, true, false, false>), dim3(tp_walk_grid(B, K)), dim3(64 * TP_WALK_WAVES), 0,
+                           (hipStream_t)stream, x, anchors, w_d, nullptr, T, K, scale, m_d, nullptr, m_t, nullptr, nullptr);
+    });
     return check_launch(name);
 }
 
@@ -551,12 +376,11 @@ extern "C" int lpm_triangulation_mean_dw(const float* x, const float* anchors, c
                 "%s: workspace too small", name);
     LPM_REQUIRE((((uintptr_t)x | (uintptr_t)g_d) & 15) == 0, LPM_ERR_BADARG, "%s: x and the gradient must be 16-byte aligned", name);
     float* part = (float*)workspace;
-    const dim3 grid(B * ((K + TA_WALK_WAVES - 1) / TA_WALK_WAVES)), block(64 * TA_WALK_WAVES);
     hipStream_t s = (hipStream_t)stream;
-    if (D == 1024)
-        hipLaunchKernelGGL(tm_dw_kernel<1024>, grid, block, 0, s, x, anchors, g_d, T, K, scale, part);
-    else
-        hipLaunchKernelGGL(tm_dw_kernel<128>, grid, block, 0, s, x, anchors, g_d, T, K, scale, part);
+    tp_dispatch_d(D, [&](auto d) {
+        hipLaunchKernelGGL((tp_walk_dw_kernel<decltype(d)::value, false>), dim3(tp_walk_grid(B, K)), dim3(64 * TP_WALK_WAVES), 0, s, x, anchors,
+                           g_d, T, K, scale, part, nullptr, nullptr);
+    });
     if (const int rc = ta_sum_slices(part, B, T, K, dw_d, s, name)) return rc;
     return check_launch(name);
 }
@@ -579,28 +403,14 @@ extern "C" int lpm_triangulation_mean_bwd(const float* x, const float* anchors, 
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(B * G), block(64 * TA_WAVES);
     const size_t lds = tm_bwd_lds(T);
-    static bool lds_set = false;                                           // (a race sets the same attribute twice)
-    if (!lds_set) {
-        const int most = (int)tm_bwd_lds(TA_MAX_FRAMES);                   // (more than the fast form's)
-        const void* kernels[] = {(const void*)tm_bwd_kernel<1024, 0>, (const void*)tm_bwd_kernel<128, 0>,
-                                 (const void*)tm_bwd_kernel<1024, TA_FAST_FRAMES>, (const void*)tm_bwd_kernel<128, TA_FAST_FRAMES>};
-        for (const void* kernel : kernels) {
-            if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess) {
-                (void)hipGetLastError();
-                set_error("%s: cannot reserve %d bytes of LDS", name, most);
-                return LPM_ERR_LAUNCH;
-            }
-        }
-        lds_set = true;
-    }
-#define TM_LAUNCH_BWD(DD, TT) \
-    hipLaunchKernelGGL((tm_bwd_kernel<DD, TT>), grid, block, lds, s, x, anchors, w_d, m_d, g_d, g_t, T, K, scale, G, dx_part, da_part)
-    if (T <= TA_FAST_FRAMES) {
-        if (D == 1024) TM_LAUNCH_BWD(1024, TA_FAST_FRAMES); else TM_LAUNCH_BWD(128, TA_FAST_FRAMES);
-    } else {
-        if (D == 1024) TM_LAUNCH_BWD(1024, 0); else TM_LAUNCH_BWD(128, 0);
-    }
-#undef TM_LAUNCH_BWD
-    if (const int rc = ta_reduce_partials(dx_part, da_part, B, T, D, K, G, dx, danchors, s, name)) return rc;
+    if (const int rc = tp_reserve_lds<tm_bwd_kernel<1024, 0>, tm_bwd_kernel<128, 0>, tm_bwd_kernel<1024, TA_FAST_FRAMES>,
+                                      tm_bwd_kernel<128, TA_FAST_FRAMES>>(name, (int)tm_bwd_lds(TA_MAX_FRAMES)))     // (more than the fast form's)
+        return rc;
+    tp_dispatch_d(D, [&](auto d) {
+        constexpr int DD = decltype(d)::value;
+        auto* kernel = T <= TA_FAST_FRAMES ? tm_bwd_kernel<DD, TA_FAST_FRAMES> : tm_bwd_kernel<DD, 0>;
+        hipLaunchKernelGGL(kernel, grid, block, lds, s, x, anchors, w_d, m_d, g_d, g_t, T, K, scale, G, dx_part, da_part);
+    });
+    if (const int rc = ta_reduce_partials(dx_part, da_part, B, T, D, K, G, TP_SUM_CHUNK, dx, danchors, s, name)) return rc;
     return check_launch(name);
 }

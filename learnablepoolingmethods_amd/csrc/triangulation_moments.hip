@@ -500,7 +500,8 @@ __global__ __launch_bounds__(64 * TA_WAVES) void tv_dx_kernel(const float* __res
     }
 }
 
-// dx[m] = sum_g dx_part[tile(m)][g][m - tile start], g = 0, 1, ...
+// dx[m] = sum_g dx_part[tile(m)][g][m - tile start], g = 0, 1, ...  (The sum of the attention poolings' dx pass over row tiles instead of
+// clips, but a float at a time: this op's workspace puts dx_part behind a count of floats that need not be a multiple of four.)
 __global__ __launch_bounds__(256) void tv_dx_reduce_kernel(const float* __restrict__ part, int64_t total, int D, int G, float* __restrict__ dx) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
@@ -543,13 +544,11 @@ extern "C" int lpm_triangulation_moments_fwd(const float* x, const float* anchor
     const int NR = tv_row_tiles(BT), NF = (F + 31) / 32;
     const dim3 block(64 * TA_WAVES);
     const dim3 grid_n((unsigned)((BT * ((K + TV_KC - 1) / TV_KC) + TA_WAVES - 1) / TA_WAVES)), grid_c((unsigned)((int64_t)K * NF * NR));
-    if (D == 1024) {
-        hipLaunchKernelGGL(tv_norms_kernel<1024>, grid_n, block, 0, s, x, anchors, BT, T, K, q, p);
-        hipLaunchKernelGGL(tv_conv_kernel<1024>, grid_c, block, 0, s, x, anchors, cnn_s, cnn_t, q + BT * K, p + BT * K, BT, K, F, NR, so, to);
-    } else {
-        hipLaunchKernelGGL(tv_norms_kernel<128>, grid_n, block, 0, s, x, anchors, BT, T, K, q, p);
-        hipLaunchKernelGGL(tv_conv_kernel<128>, grid_c, block, 0, s, x, anchors, cnn_s, cnn_t, q + BT * K, p + BT * K, BT, K, F, NR, so, to);
-    }
+    tp_dispatch_d(D, [&](auto d) {
+        constexpr int DD = decltype(d)::value;
+        hipLaunchKernelGGL(tv_norms_kernel<DD>, grid_n, block, 0, s, x, anchors, BT, T, K, q, p);
+        hipLaunchKernelGGL(tv_conv_kernel<DD>, grid_c, block, 0, s, x, anchors, cnn_s, cnn_t, q + BT * K, p + BT * K, BT, K, F, NR, so, to);
+    });
     const int64_t cols = (int64_t)B * ((int64_t)K * F + K);
     hipLaunchKernelGGL(tv_moments_kernel, dim3((unsigned)((cols + 255) / 256), 2), dim3(256), 0, s, so, to, q, p, B, T, K, F, pool_s, pool_t, corr);
     return check_launch(name);
@@ -578,20 +577,20 @@ extern "C" int lpm_triangulation_moments_bwd(const float* x, const float* anchor
     const dim3 block(64 * TA_WAVES);
     const dim3 grid_o((unsigned)((BTK + TA_WAVES - 1) / TA_WAVES)), grid_w((unsigned)((int64_t)K * NF * (D / (32 * TA_WAVES)))),
         grid_x((unsigned)((int64_t)NRT * G * NDR));
-#define TV_LAUNCH_BWD(DD)                                                                                                                       \
-    hipLaunchKernelGGL(tv_dout_kernel<DD>, grid_o, block, 0, s, x, anchors, cnn_t, q, p, so, to, pool_s, pool_t, corr, g_s, g_t, BT, T, K, F, DR, dso, \
-                       dto, sa, s1g, dtg, dn, ggb);                                                                                             \
-    hipLaunchKernelGGL(tv_s2_kernel, dim3((unsigned)((BTK + 255) / 256)), dim3(256), 0, s, x, anchors, q, sa, ggb, BT, D, K, NDR, s2g, dn);     \
-    hipLaunchKernelGGL(tv_dw_kernel<DD>, grid_w, block, 0, s, x, anchors, q + BTK, p + BTK, dso, dto, BT, K, F, dcnn_s, dcnn_t);                            \
-    hipLaunchKernelGGL(tv_dx_kernel<DD>, grid_x, block, 0, s, x, anchors, cnn_s, cnn_t, q + BTK, p + BTK, dso, dto, s1g, dtg, s2g, dn, ggb, BT, K, F, DR, G, \
-                       dx_part, da_part)
-    if (D == 1024) { TV_LAUNCH_BWD(1024); } else { TV_LAUNCH_BWD(128); }
-#undef TV_LAUNCH_BWD
+    tp_dispatch_d(D, [&](auto d) {
+        constexpr int DD = decltype(d)::value;
+        hipLaunchKernelGGL(tv_dout_kernel<DD>, grid_o, block, 0, s, x, anchors, cnn_t, q, p, so, to, pool_s, pool_t, corr, g_s, g_t, BT, T, K, F, DR, dso,
+                           dto, sa, s1g, dtg, dn, ggb);
+        hipLaunchKernelGGL(tv_s2_kernel, dim3((unsigned)((BTK + 255) / 256)), dim3(256), 0, s, x, anchors, q, sa, ggb, BT, D, K, NDR, s2g, dn);
+        hipLaunchKernelGGL(tv_dw_kernel<DD>, grid_w, block, 0, s, x, anchors, q + BTK, p + BTK, dso, dto, BT, K, F, dcnn_s, dcnn_t);
+        hipLaunchKernelGGL(tv_dx_kernel<DD>, grid_x, block, 0, s, x, anchors, cnn_s, cnn_t, q + BTK, p + BTK, dso, dto, s1g, dtg, s2g, dn, ggb, BT, K, F,
+                           DR, G, dx_part, da_part);
+    });
     if (G > 1) {
         const int64_t total = BT * D;
         hipLaunchKernelGGL(tv_dx_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, dx_part, total, D, G, dx);
     }
     // danchors[d][k] = - sum over the row tiles, in order (the dx partials are reduced above: the tiles are not clips)
-    if (const int rc = ta_reduce_partials(dx, da_part, NRT, TV_ROWS, D, K, 1, dx, danchors, s, name)) return rc;
+    if (const int rc = ta_reduce_partials(dx, da_part, NRT, TV_ROWS, D, K, 1, TP_SUM_CHUNK, dx, danchors, s, name)) return rc;
     return check_launch(name);
 }

@@ -5,12 +5,8 @@
 // The reference tiles every frame against every anchor and keeps [B, T, K*D] tensors (79 MB per clip at T = 300, K = 64, D = 1024)
 // through both normalisations and the pooling; here nothing of size T*K*D exists in either direction.
 //
-// Forward: ONE WAVE owns a (clip, anchor) pair and walks t.  D = 1024 is 16 elements per lane: the anchor, the previous e, two
-// two-level sums, two maxima and the packed arg-max indices stay in registers; |r|^2 and |u|^2 are wave reductions on the VALU
-// (wave_sum_dpp: every lane gets the same bits).  The maximum is the FIRST frame that attains it (strict > walking t upwards); its
-// index is what the backward gets (int16 pair per element): exact ties cannot be re-matched walking t downwards.
-// The sums over t are two-level (TP_SUM_CHUNK frames into a partial, partials into the total): mean_d's terms share a sign (the
-// anchor's direction), so a plain running sum rounds every term to the ulp of a total that keeps growing.
+// Forward: tp_walk_fwd_kernel<D, no weights, maxima> (triangulation_common.h: the walk, its two-level sums and first-index maxima, and
+// the contraction rule -- s eh is rounded before the difference u is taken, as the backward below forms u = s (eh_t - eh_{t-1})).
 //
 // Backward: the same ownership, t walked DOWNWARDS so that gu_{t+1} is at hand; e, u, f are recomputed from the frames.
 //   gf_t = g_mean_t / (T-1) + [t = argmax_t] g_max_t                         gu_t = ip (gf_t - f_t (f_t . gf_t) [p > 1e-12])
@@ -25,92 +21,9 @@
 
 namespace lpm {
 
-constexpr int TP_FWD_WAVES = 4;
 constexpr int TP_BWD_WAVES = 8;
 constexpr int TP_MAX_GROUPS = 8;      // dx partials per clip: the workspace stays <= TP_MAX_GROUPS x the size of the frames
 constexpr int TP_MAX_FRAMES = 32767;  // the arg-max indices are an int16 pair
-
-template <int D>
-__global__ __launch_bounds__(64 * TP_FWD_WAVES) void tp_fwd_kernel(const float* __restrict__ x, const float* __restrict__ anchors, int T, int K,
-                                                                   float s, float* __restrict__ max_d, float* __restrict__ mean_d,
-                                                                   float* __restrict__ max_t, float* __restrict__ mean_t,
-                                                                   int* __restrict__ argmax) {
-    constexpr int N = TpVec<D>::N;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int kg = (K + TP_FWD_WAVES - 1) / TP_FWD_WAVES;
-    const int b = blockIdx.x / kg, k = (blockIdx.x % kg) * TP_FWD_WAVES + wave;
-    if (k >= K) return;                                   // (no barrier in this kernel)
-    float a[N], ep[N], tot_e[N], part_e[N], mx_e[N], tot_f[N], part_f[N], mx_f[N];
-    int idx[N];
-    tp_load_anchor<D>(anchors, K, k, lane, a);
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        ep[j] = 0.f;
-        tot_e[j] = part_e[j] = tot_f[j] = part_f[j] = 0.f;
-        mx_e[j] = mx_f[j] = -INFINITY;
-        idx[j] = 0;
-    }
-    const float* xb = x + (int64_t)b * T * D;
-    float xv[N], xn[N];
-    tp_load<D>(xb, lane, xv);
-    for (int t = 0; t < T; ++t) {
-        tp_load<D>(xb + (int64_t)min(t + 1, T - 1) * D, lane, xn);          // the next frame is under way while this one is worked on
-        float e[N];
-        bool clamped;
-        tp_unit<N>(xv, a, e, clamped);
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            e[j] *= s;
-            part_e[j] += e[j];
-            const bool up = e[j] > mx_e[j];
-            mx_e[j] = up ? e[j] : mx_e[j];
-            idx[j] = up ? ((idx[j] & (int)0xffff0000u) | t) : idx[j];
-        }
-        if (t > 0) {
-            float u[N], p = 0.f;
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-                u[j] = e[j] - ep[j];
-                p = fmaf(u[j], u[j], p);
-            }
-            p = wave_sum_dpp(p);
-            const float ip = rsqrtf(fmaxf(p, kL2Eps));
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-                const float f = u[j] * ip;
-                part_f[j] += f;
-                const bool up = f > mx_f[j];
-                mx_f[j] = up ? f : mx_f[j];
-                idx[j] = up ? ((idx[j] & 0xffff) | (t << 16)) : idx[j];
-            }
-        }
-        if ((t & (TP_SUM_CHUNK - 1)) == TP_SUM_CHUNK - 1) {
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-                tot_e[j] += part_e[j];
-                tot_f[j] += part_f[j];
-                part_e[j] = part_f[j] = 0.f;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            ep[j] = e[j];
-            xv[j] = xn[j];
-        }
-    }
-    const float nd = (float)T, nt = (float)(T - 1);
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        tot_e[j] = (tot_e[j] + part_e[j]) / nd;
-        tot_f[j] = (tot_f[j] + part_f[j]) / nt;
-    }
-    const int64_t o = ((int64_t)b * K + k) * D;             // k-major: element k * D + d
-    tp_store<D>(max_d + o, lane, mx_e);
-    tp_store<D>(mean_d + o, lane, tot_e);
-    tp_store<D>(max_t + o, lane, mx_f);
-    tp_store<D>(mean_t + o, lane, tot_f);
-    tp_store<D>(argmax + o, lane, idx);
-}
 
 template <int D>
 __global__ __launch_bounds__(64 * TP_BWD_WAVES) void tp_bwd_kernel(const float* __restrict__ x, const float* __restrict__ anchors,
@@ -236,31 +149,6 @@ __global__ __launch_bounds__(64 * TP_BWD_WAVES) void tp_bwd_kernel(const float* 
     }
 }
 
-// dx[b] = sum_g dx_part[b][g], g = 0, 1, ... (n4 = T * D / 4 float4 per block)
-__global__ __launch_bounds__(256) void tp_dx_reduce_kernel(const float4* __restrict__ part, int64_t total4, int64_t n4, int G,
-                                                           float4* __restrict__ dx) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total4) return;
-    const int64_t b = i / n4, r = i % n4;
-    const float4* p = part + b * G * n4 + r;
-    float4 acc = p[0];
-    for (int g = 1; g < G; ++g) {
-        const float4 v = p[(int64_t)g * n4];
-        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-    }
-    dx[i] = acc;
-}
-
-// danchors[d][k] = - sum_b da_part[b][k][d], b = 0, 1, ...
-__global__ __launch_bounds__(256) void tp_da_reduce_kernel(const float* __restrict__ part, int B, int K, int D, float* __restrict__ danchors) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= K * D) return;
-    const int k = i / D, d = i % D;
-    float acc = 0.f;
-    for (int b = 0; b < B; ++b) acc += part[(int64_t)b * K * D + i];
-    danchors[(int64_t)d * K + k] = -acc;
-}
-
 static int tp_groups(int B, int K) {
     const int rounds = (K + TP_BWD_WAVES - 1) / TP_BWD_WAVES;
     int want = (256 + B - 1) / B;
@@ -268,14 +156,8 @@ static int tp_groups(int B, int K) {
     return rounds < want ? rounds : want;
 }
 
-static int tp_check(const char* name, int B, int T, int D, int K) {
-    LPM_REQUIRE(B > 0 && K > 0 && T > 0, LPM_ERR_BADARG, "%s: need B, T, K >= 1 (B=%d T=%d K=%d)", name, B, T, K);
-    LPM_REQUIRE(D == 128 || D == 1024, LPM_ERR_UNSUPPORTED_SHAPE, "%s: need D in {128, 1024} (D=%d)", name, D);
-    LPM_REQUIRE(T >= 2 && T <= TP_MAX_FRAMES, LPM_ERR_UNSUPPORTED_SHAPE,
-                "%s: need 2 <= T <= %d frames (T=%d): the temporal embedding is a frame-to-frame difference", name, TP_MAX_FRAMES, T);
-    LPM_REQUIRE((int64_t)K * D < (1ll << 31) && (int64_t)B * ((K + TP_FWD_WAVES - 1) / TP_FWD_WAVES) < (1ll << 31), LPM_ERR_UNSUPPORTED_SHAPE,
-                "%s: B * K or K * D too large (B=%d K=%d)", name, B, K);
-    return LPM_OK;
+static int tp_pool_check(const char* name, int B, int T, int D, int K) {
+    return tp_check(name, B, T, D, K, TP_MAX_FRAMES, "", (K + TP_WALK_WAVES - 1) / TP_WALK_WAVES);
 }
 
 }  // namespace lpm
@@ -290,15 +172,13 @@ extern "C" int lpm_triangulation_pool_fwd(const float* x, const float* anchors, 
                                           float* mean_d, float* max_t, float* mean_t, int32_t* argmax, lpm_stream_t stream) {
     using namespace lpm;
     LPM_REQUIRE(x && anchors && max_d && mean_d && max_t && mean_t && argmax, LPM_ERR_BADARG, "lpm_triangulation_pool_fwd: null pointer");
-    if (const int rc = tp_check("lpm_triangulation_pool_fwd", B, T, D, K)) return rc;
+    if (const int rc = tp_pool_check("lpm_triangulation_pool_fwd", B, T, D, K)) return rc;
     LPM_REQUIRE((((uintptr_t)x | (uintptr_t)max_d | (uintptr_t)mean_d | (uintptr_t)max_t | (uintptr_t)mean_t | (uintptr_t)argmax) & 15) == 0,
                 LPM_ERR_BADARG, "lpm_triangulation_pool_fwd: x and the outputs must be 16-byte aligned");
-    const dim3 grid(B * ((K + TP_FWD_WAVES - 1) / TP_FWD_WAVES)), block(64 * TP_FWD_WAVES);
-    hipStream_t s = (hipStream_t)stream;
-    if (D == 1024)
-        hipLaunchKernelGGL(tp_fwd_kernel<1024>, grid, block, 0, s, x, anchors, T, K, scale, max_d, mean_d, max_t, mean_t, argmax);
-    else
-        hipLaunchKernelGGL(tp_fwd_kernel<128>, grid, block, 0, s, x, anchors, T, K, scale, max_d, mean_d, max_t, mean_t, argmax);
+    tp_dispatch_d(D, [&](auto d) {
+        hipLaunchKernelGGL((tp_walk_fwd_kernel<decltype(d)::value, false, false, true>), dim3(tp_walk_grid(B, K)), dim3(64 * TP_WALK_WAVES), 0,
+                           (hipStream_t)stream, x, anchors, nullptr, nullptr, T, K, scale, mean_d, max_d, mean_t, max_t, argmax);
+    });
     return check_launch("lpm_triangulation_pool_fwd");
 }
 
@@ -309,7 +189,7 @@ extern "C" int lpm_triangulation_pool_bwd(const float* x, const float* anchors, 
     using namespace lpm;
     LPM_REQUIRE(x && anchors && argmax && g_max_d && g_mean_d && g_max_t && g_mean_t && dx && danchors, LPM_ERR_BADARG,
                 "lpm_triangulation_pool_bwd: null pointer");
-    if (const int rc = tp_check("lpm_triangulation_pool_bwd", B, T, D, K)) return rc;
+    if (const int rc = tp_pool_check("lpm_triangulation_pool_bwd", B, T, D, K)) return rc;
     LPM_REQUIRE(workspace && workspace_bytes >= lpm_triangulation_pool_workspace_bytes(B, T, D, K), LPM_ERR_WORKSPACE,
                 "lpm_triangulation_pool_bwd: workspace too small");
     LPM_REQUIRE((((uintptr_t)x | (uintptr_t)argmax | (uintptr_t)g_max_d | (uintptr_t)g_mean_d | (uintptr_t)g_max_t | (uintptr_t)g_mean_t |
@@ -322,28 +202,12 @@ extern "C" int lpm_triangulation_pool_bwd(const float* x, const float* anchors, 
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(B * G), block(64 * TP_BWD_WAVES);
     const size_t lds = (size_t)4 * TP_BWD_WAVES * D * sizeof(float);       // 128 KB at D = 1024
-    static bool lds_set = false;                                           // (a race sets the same attribute twice)
-    if (!lds_set) {
-        if (hipFuncSetAttribute((const void*)tp_bwd_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                4 * TP_BWD_WAVES * 1024 * (int)sizeof(float)) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("lpm_triangulation_pool_bwd: cannot reserve %d bytes of LDS", 4 * TP_BWD_WAVES * 1024 * (int)sizeof(float));
-            return LPM_ERR_LAUNCH;
-        }
-        lds_set = true;
-    }
-    if (D == 1024)
-        hipLaunchKernelGGL(tp_bwd_kernel<1024>, grid, block, lds, s, x, anchors, argmax, g_max_d, g_mean_d, g_max_t, g_mean_t, T, K, scale, G,
-                           dx_part, da_part);
-    else
-        hipLaunchKernelGGL(tp_bwd_kernel<128>, grid, block, lds, s, x, anchors, argmax, g_max_d, g_mean_d, g_max_t, g_mean_t, T, K, scale, G,
-                           dx_part, da_part);
-    if (G > 1) {
-        const int64_t n4 = (int64_t)T * D / 4, total4 = n4 * B;
-        LPM_REQUIRE((total4 + 255) / 256 < (1ll << 31), LPM_ERR_UNSUPPORTED_SHAPE, "lpm_triangulation_pool_bwd: B * T * D too large");
-        hipLaunchKernelGGL(tp_dx_reduce_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, (const float4*)dx_part, total4, n4, G,
-                           (float4*)dx);
-    }
-    hipLaunchKernelGGL(tp_da_reduce_kernel, dim3((K * D + 255) / 256), dim3(256), 0, s, (const float*)da_part, B, K, D, danchors);
+    if (const int rc = tp_reserve_lds<tp_bwd_kernel<1024>>("lpm_triangulation_pool_bwd", 4 * TP_BWD_WAVES * 1024 * (int)sizeof(float))) return rc;
+    tp_dispatch_d(D, [&](auto d) {
+        hipLaunchKernelGGL(tp_bwd_kernel<decltype(d)::value>, grid, block, lds, s, x, anchors, argmax, g_max_d, g_mean_d, g_max_t, g_mean_t, T, K,
+                           scale, G, dx_part, da_part);
+    });
+    // (clips added b = 0, 1, ... in one level)
+    if (const int rc = ta_reduce_partials(dx_part, da_part, B, T, D, K, G, B, dx, danchors, s, "lpm_triangulation_pool_bwd")) return rc;
     return check_launch("lpm_triangulation_pool_bwd");
 }

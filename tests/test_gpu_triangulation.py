@@ -116,10 +116,12 @@ def test_frame_equal_to_an_anchor():
     _check("frame == anchor", outs, dx, da, ref, grad_scale=float(ref["dx64"].abs().max()))
 
 
-def test_identical_consecutive_frames():
+# s = 1/3: a scale that is no power of two -- s eh must be rounded before the difference is taken (no product fused into it), or u is
+# the rounding error of s eh instead of zero and f, behind the clamped 1e6, something of the order of 1e-3
+@pytest.mark.parametrize("B,T,D,K,s", [(2, 6, 128, 3, 1.0), (2, 6, 128, 3, 1 / 3), (1, 4, 1024, 2, 1 / 3)])
+def test_identical_consecutive_frames(B, T, D, K, s):
     """p = 0: f = 0 for that frame pair, and e ties exactly between the two frames -- the first index wins on every side."""
     dev = cuda()
-    B, T, D, K, s = 2, 6, 128, 3, 1.0
     x, anchors, upstream = R.make_inputs(B, T, D, K, 6)
     x[3] = x[2]                                                 # clip 0: frames 2 and 3 identical
     ref = _reference(x, anchors, T, s, upstream)
