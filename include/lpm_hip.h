@@ -167,6 +167,31 @@ int lpm_frame_bn_bwd_split_q8(const float* dy_video, int64_t ldv, const float* d
                               const float* inv_norm, float max_quantized_value, float min_quantized_value, const int32_t* num_frames,
                               int B, int max_frames, int F, int S, const float* mean, const float* var, float eps, float* dgamma,
                               float* dbeta, void* workspace, size_t workspace_bytes, lpm_stream_t stream);
+/* The index-table forms: sampled row r = b*S + j reads frame frame_index[r] of clip b (int32 [B*S], clamped to [0, max_frames - 1]) instead
+ * of SampleUniformFrames' own index -- SampleRandomFrames (model_utils.py:60-78) for the triangulation models.  The same kernels with
+ * the index source exchanged: 32-row statistics blocks, one fixed summation order, no atomics.  The frames leave as TWO contiguous fp32
+ * matrices y_video [B*S, Dv] and y_audio [B*S, F - Dv] (v * scale + shift by fmaf; scale == NULL: the gathered frames as they are) and
+ * no operand tiles.  F %% 4 == 0, Dv %% 4 == 0, 0 < Dv < F; fp32 buffers 16-byte aligned, q 4-byte aligned.
+ * lpm_frame_inv_norm_q8_idx (F <= 2048): inv_norm [B*S], 0 where the clamped frame_index[r] >= num_frames[b]; each *_idx_q8 form reads q and
+ * inv_norm in place of `raw` and writes exactly the bytes its fp32 form writes from lpm_dequantize_l2_normalize's frames. */
+int lpm_frame_inv_norm_q8_idx(const unsigned char* q, const int32_t* num_frames, const int32_t* frame_index, int B, int max_frames, int F,
+                              int S, float max_quantized_value, float min_quantized_value, float* inv_norm, lpm_stream_t stream);
+int lpm_frame_stats_idx(const float* raw, const int32_t* frame_index, int B, int max_frames, int F, int S, float* partial,
+                        lpm_stream_t stream);
+int lpm_frame_stats_idx_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
+                           const int32_t* frame_index, int B, int max_frames, int F, int S, float* partial, lpm_stream_t stream);
+int lpm_frame_apply_split_idx(const float* raw, const int32_t* frame_index, int B, int max_frames, int F, int S, const float* scale,
+                              const float* shift, float* y_video, float* y_audio, int Dv, lpm_stream_t stream);
+int lpm_frame_apply_split_idx_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
+                                 const int32_t* frame_index, int B, int max_frames, int F, int S, const float* scale, const float* shift,
+                                 float* y_video, float* y_audio, int Dv, lpm_stream_t stream);
+int lpm_frame_bn_bwd_split_idx(const float* dy_video, int64_t ldv, const float* dy_audio, int64_t lda, int Dv, const float* raw,
+                               const int32_t* frame_index, int B, int max_frames, int F, int S, const float* mean, const float* var,
+                               float eps, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, lpm_stream_t stream);
+int lpm_frame_bn_bwd_split_idx_q8(const float* dy_video, int64_t ldv, const float* dy_audio, int64_t lda, int Dv, const unsigned char* q,
+                                  const float* inv_norm, float max_quantized_value, float min_quantized_value, const int32_t* frame_index,
+                                  int B, int max_frames, int F, int S, const float* mean, const float* var, float eps, float* dgamma,
+                                  float* dbeta, void* workspace, size_t workspace_bytes, lpm_stream_t stream);
 /* backward of input_bn's affine parameters only (the frames are data, never a trainable tensor, so no
  * gradient w.r.t. raw is produced): dgamma = sum dy*xhat, dbeta = sum dy over the gathered rows.
  * dy [B*S, F] with row stride lddy; mean/var = the batch statistics lpm_bn_fold returned.

@@ -54,6 +54,13 @@ SIGNATURES = {
     "lpm_frame_bn_bwd_q8": (_i, [_f, _l, _f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _fl, _f, _f, _f, _s, _f]),
     "lpm_frame_bn_bwd_split_q8": (_i, [_f, _l, _f, _l, _i, _f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _fl, _f, _f, _f, _s, _f]),
     "lpm_frame_inv_norm_q8": (_i, [_f, _f, _i, _i, _i, _i, _fl, _fl, _f, _f]),
+    "lpm_frame_inv_norm_q8_idx": (_i, [_f, _f, _f, _i, _i, _i, _i, _fl, _fl, _f, _f]),
+    "lpm_frame_stats_idx": (_i, [_f, _f, _i, _i, _i, _i, _f, _f]),
+    "lpm_frame_stats_idx_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f]),
+    "lpm_frame_apply_split_idx": (_i, [_f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _i, _f]),
+    "lpm_frame_apply_split_idx_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _f, _f, _i, _f]),
+    "lpm_frame_bn_bwd_split_idx": (_i, [_f, _l, _f, _l, _i, _f, _f, _i, _i, _i, _i, _f, _f, _fl, _f, _f, _f, _s, _f]),
+    "lpm_frame_bn_bwd_split_idx_q8": (_i, [_f, _l, _f, _l, _i, _f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _fl, _f, _f, _f, _s, _f]),
     "lpm_frame_apply_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _f, _f]),
     "lpm_frame_apply_tiles_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _f, _f, _i, _f, _i, _f]),
     "lpm_frame_apply_tiles_split_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _i, _f]),

@@ -25,6 +25,19 @@ __device__ __forceinline__ int sample_index(int j, float step, int nf) {
     return (int)__fmul_rn(fminf(v, 1.0f), (float)nf);
 }
 
+// Which frame of clip b the sampled row r = b S + j reads (before the clamp to [0, max_frames - 1], which every kernel applies itself).
+// UniformIdx: SampleUniformFrames' formula.  TableIdx: a frame_index table int32 [B S] the caller drew (SampleRandomFrames: model_utils.
+// random_frame_index) -- the *_idx entry points; one 4-byte read per row, the frame rows themselves are still gathered whole.
+struct UniformIdx {
+    const int32_t* __restrict__ num_frames;
+    float step;
+    __device__ __forceinline__ int operator()(int b, int j, int64_t) const { return sample_index(j, step, num_frames[b]); }
+};
+struct TableIdx {
+    const int32_t* __restrict__ table;
+    __device__ __forceinline__ int operator()(int, int, int64_t r) const { return table[r]; }
+};
+
 // One wave's share of a quantised frame row (lane owns the uchar4 columns lane + 64 i, F <= 2048): the dequantised values
 // (utils.Dequantize: u * range/255 + range/512 + min) into v, and the row's inverse L2 norm rsqrt(max(sum x^2, 1e-12)).
 // dequantize_l2_normalize_kernel and frame_inv_norm_q8_kernel both use it: one summation order, one rounding.
@@ -101,9 +114,8 @@ __device__ __forceinline__ void storew_f32(float* __restrict__ p, const float (&
     }
 }
 
-template <typename Src>
-__global__ __launch_bounds__(256) void frame_stats_kernel(Src raw, const int32_t* __restrict__ num_frames, int B,
-                                                          int max_frames, int F, int S, float step,
+template <typename Src, typename Idx>
+__global__ __launch_bounds__(256) void frame_stats_kernel(Src raw, Idx ix, int B, int max_frames, int F, int S,
                                                           float* __restrict__ partial) {
     constexpr int W = Src::W;
     const int r0 = blockIdx.x * FP_ROWS;
@@ -114,8 +126,7 @@ __global__ __launch_bounds__(256) void frame_stats_kernel(Src raw, const int32_t
         const int r = r0 + threadIdx.x;
         if (r < rows) {
             const int b = r / S, j = r % S;
-            int idx = sample_index(j, step, num_frames[b]);
-            idx = max(0, min(idx, max_frames - 1));
+            const int idx = max(0, min(ix(b, j, r), max_frames - 1));
             base[threadIdx.x] = ((int64_t)b * max_frames + idx) * F;
         }
     }
@@ -139,18 +150,18 @@ __global__ __launch_bounds__(256) void frame_stats_kernel(Src raw, const int32_t
     }
 }
 
-template <typename Src>
-__global__ __launch_bounds__(256) void frame_apply_kernel(Src raw, const int32_t* __restrict__ num_frames, int B,
-                                                          int max_frames, int F, int S, float step,
+// y2 != null: the column blocks [0, Dv) and [Dv, F) leave as TWO contiguous matrices, y [B S, Dv] and y2 [B S, F - Dv]
+template <typename Src, typename Idx>
+__global__ __launch_bounds__(256) void frame_apply_kernel(Src raw, Idx ix, int B, int max_frames, int F, int S,
                                                           const float* __restrict__ scale,
-                                                          const float* __restrict__ shift, float* __restrict__ y) {
+                                                          const float* __restrict__ shift, float* __restrict__ y,
+                                                          float* __restrict__ y2, int Dv) {
     const int F4 = F / 4;
     const int64_t total = (int64_t)B * S * F4;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int r = (int)(i / F4), c = (int)(i % F4) * 4;
         const int b = r / S, j = r % S;
-        int idx = sample_index(j, step, num_frames[b]);
-        idx = max(0, min(idx, max_frames - 1));
+        const int idx = max(0, min(ix(b, j, r), max_frames - 1));
         float4 v = raw.load4(((int64_t)b * max_frames + idx) * F + c, r);
         if (scale) {
             const float4 sc = *reinterpret_cast<const float4*>(scale + c);
@@ -158,7 +169,9 @@ __global__ __launch_bounds__(256) void frame_apply_kernel(Src raw, const int32_t
             v.x = fmaf(v.x, sc.x, sh.x); v.y = fmaf(v.y, sc.y, sh.y);
             v.z = fmaf(v.z, sc.z, sh.z); v.w = fmaf(v.w, sc.w, sh.w);
         }
-        *reinterpret_cast<float4*>(y + (int64_t)r * F + c) = v;
+        if (!y2) *reinterpret_cast<float4*>(y + (int64_t)r * F + c) = v;
+        else if (c < Dv) *reinterpret_cast<float4*>(y + (int64_t)r * Dv + c) = v;
+        else *reinterpret_cast<float4*>(y2 + (int64_t)r * (F - Dv) + (c - Dv)) = v;
     }
 }
 
@@ -232,10 +245,9 @@ __global__ __launch_bounds__(256) void frame_apply_tiles_kernel(Src raw, const i
 }
 
 // column partials of (sum dy, sum dy * x) over the gathered rows, for dgamma/dbeta of input_bn
-template <typename Src>
-__global__ __launch_bounds__(256) void frame_bn_bwd_partial_kernel(const float* __restrict__ dy, int64_t lddy, Src raw,
-                                                                   const int32_t* __restrict__ num_frames, int B,
-                                                                   int max_frames, int F, int S, float step,
+template <typename Src, typename Idx>
+__global__ __launch_bounds__(256) void frame_bn_bwd_partial_kernel(const float* __restrict__ dy, int64_t lddy, Src raw, Idx ix, int B,
+                                                                   int max_frames, int F, int S,
                                                                    float* __restrict__ partial, const float* __restrict__ dy2,
                                                                    int64_t lddy2, int Dv) {
     // dy2 != null: the gradient arrives as two matrices, columns [0, Dv) in dy and [Dv, F) in dy2 (lpm_frame_apply_tiles_split's outputs)
@@ -248,8 +260,7 @@ __global__ __launch_bounds__(256) void frame_bn_bwd_partial_kernel(const float* 
         const int r = r0 + threadIdx.x;
         if (r < rows) {
             const int b = r / S, j = r % S;
-            int idx = sample_index(j, step, num_frames[b]);
-            idx = max(0, min(idx, max_frames - 1));
+            const int idx = max(0, min(ix(b, j, r), max_frames - 1));
             base[threadIdx.x] = ((int64_t)b * max_frames + idx) * F;
         }
     }
@@ -318,8 +329,10 @@ __global__ __launch_bounds__(256) void dequantize_l2_normalize_kernel(const unsi
 // The inverse L2 norm of the dequantised frame behind every SAMPLED row r = b S + j (the frame idx = sample_index(j) of clip b), for
 // the FrameSrc<unsigned char> apply kernels: 1 byte read per feature of the S sampled frames, 4 bytes written per row.  A frame at
 // or past num_frames[b] -- zero after the reader's padding -- gets 0.  Same wave split and order as dequantize_l2_normalize_kernel.
+// (Idx = TableIdx: the frame frame_index[r], lpm_frame_inv_norm_q8_idx.)
+template <typename Idx>
 __global__ __launch_bounds__(256) void frame_inv_norm_q8_kernel(const unsigned char* __restrict__ q, const int32_t* __restrict__ num_frames,
-                                                                int B, int max_frames, int F, int S, float step, float scalar, float bias,
+                                                                Idx ix, int B, int max_frames, int F, int S, float scalar, float bias,
                                                                 float* __restrict__ inv) {
     const int lane = threadIdx.x & 63;
     const int F4 = F >> 2;
@@ -327,8 +340,7 @@ __global__ __launch_bounds__(256) void frame_inv_norm_q8_kernel(const unsigned c
     for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4) {
         const int b = (int)(r / S), j = (int)(r % S);
         const int nf = num_frames[b];
-        int idx = sample_index(j, step, nf);
-        idx = max(0, min(idx, max_frames - 1));
+        const int idx = max(0, min(ix(b, j, r), max_frames - 1));
         float s = 0.f;
         if (idx < nf) {                                   // wave-uniform
             float4 v[8];
@@ -459,22 +471,33 @@ extern "C" size_t lpm_frame_stats_workspace_bytes(int B, int S, int F) {
 }
 extern "C" int lpm_frame_stats_nblk(int B, int S) { return fp_nblk(B, S); }
 
-#define LPM_FRAME_CHECK(name)                                                                                       \
-    LPM_REQUIRE(raw && num_frames, LPM_ERR_BADARG, name ": null pointer");                                          \
+// index: num_frames (the uniform forms) or frame_index (the *_idx forms)
+#define LPM_FRAME_CHECK_(name, index)                                                                               \
+    LPM_REQUIRE(raw && index, LPM_ERR_BADARG, name ": null pointer");                                               \
     LPM_REQUIRE(B > 0 && max_frames > 0 && F > 0 && S > 0, LPM_ERR_BADARG, name ": bad sizes");                      \
     LPM_REQUIRE(F % 4 == 0, LPM_ERR_UNSUPPORTED_SHAPE, name ": need F %% 4 == 0 (F=%d)", F)
+#define LPM_FRAME_CHECK(name) LPM_FRAME_CHECK_(name, num_frames)
+// the *_idx fp32 forms: float4 reads of the frame rows
+#define LPM_FRAME_IDX_CHECK(name)                                                                                   \
+    LPM_FRAME_CHECK_(name, frame_index);                                                                            \
+    LPM_REQUIRE(((uintptr_t)raw & 15) == 0, LPM_ERR_UNSUPPORTED_SHAPE, name ": need 16-byte aligned frames")
 
 // The quantised forms (*_q8): q [B, max_frames, F] uint8 (4-byte aligned), inv_norm [B S] from lpm_frame_inv_norm_q8 with the same
 // num_frames / S / quantisation range.
-#define LPM_FRAME_Q8_CHECK(name)                                                                                                     \
-    LPM_REQUIRE(q && inv_norm && num_frames, LPM_ERR_BADARG, name ": null pointer");                                                 \
+#define LPM_FRAME_Q8_CHECK_(name, index)                                                                                             \
+    LPM_REQUIRE(q && inv_norm && index, LPM_ERR_BADARG, name ": null pointer");                                                      \
     LPM_REQUIRE(max_quantized_value > min_quantized_value, LPM_ERR_BADARG, name ": empty quantisation range");                       \
     LPM_REQUIRE(B > 0 && max_frames > 0 && F > 0 && S > 0, LPM_ERR_BADARG, name ": bad sizes");                                       \
     LPM_REQUIRE(F % 4 == 0 && ((uintptr_t)q & 3) == 0, LPM_ERR_UNSUPPORTED_SHAPE, name ": need F %% 4 == 0, aligned input (F=%d)", F)
+#define LPM_FRAME_Q8_CHECK(name) LPM_FRAME_Q8_CHECK_(name, num_frames)
+#define LPM_FRAME_Q8_IDX_CHECK(name) LPM_FRAME_Q8_CHECK_(name, frame_index)
 
 namespace {
 
 using lpm::FrameSrc;
+using lpm::TableIdx;
+
+lpm::UniformIdx uniform_idx(const int32_t* num_frames, int S) { return lpm::UniformIdx{num_frames, 1.0f / (float)S}; }
 
 // utils.Dequantize's affine, computed as lpm_dequantize_l2_normalize computes it
 FrameSrc<unsigned char> q8_src(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value) {
@@ -482,16 +505,19 @@ FrameSrc<unsigned char> q8_src(const unsigned char* q, const float* inv_norm, fl
     return FrameSrc<unsigned char>{q, inv_norm, range / 255.0f, range / 512.0f + min_quantized_value};
 }
 
-template <typename Src>
-int launch_frame_apply(Src raw, const int32_t* num_frames, int B, int max_frames, int F, int S, const float* scale, const float* shift,
-                       float* y, hipStream_t stream, const char* name) {
+// y2 == NULL: one [B S, F] matrix y; else y [B S, Dv] and y2 [B S, F - Dv] (the *_split_idx forms)
+template <typename Src, typename Idx>
+int launch_frame_apply(Src raw, Idx ix, int B, int max_frames, int F, int S, const float* scale, const float* shift, float* y, float* y2,
+                       int Dv, hipStream_t stream, const char* name) {
     using namespace lpm;
     LPM_REQUIRE(y && ((scale == nullptr) == (shift == nullptr)), LPM_ERR_BADARG, "%s: bad pointers", name);
-    const float step = 1.0f / (float)S;
+    if (y2 != nullptr)
+        LPM_REQUIRE(Dv > 0 && Dv < F && Dv % 4 == 0 && (((uintptr_t)y | (uintptr_t)y2 | (uintptr_t)scale | (uintptr_t)shift) & 15) == 0,
+                    LPM_ERR_UNSUPPORTED_SHAPE, "%s: need 0 < Dv < F, Dv %% 4 == 0, 16-byte aligned buffers (F=%d Dv=%d)", name, F, Dv);
     const int64_t total = (int64_t)B * S * (F / 4);
     const int64_t want = (total + 255) / 256;
-    hipLaunchKernelGGL(frame_apply_kernel<Src>, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, stream, raw, num_frames, B,
-                       max_frames, F, S, step, scale, shift, y);
+    hipLaunchKernelGGL((frame_apply_kernel<Src, Idx>), dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, stream, raw, ix, B,
+                       max_frames, F, S, scale, shift, y, y2, Dv);
     return check_launch(name);
 }
 
@@ -542,21 +568,18 @@ int launch_frame_apply_tiles_bf16(Src raw, const int32_t* num_frames, int B, int
     return check_launch(name);
 }
 
-template <typename Src>
-int launch_frame_stats(Src raw, const int32_t* num_frames, int B, int max_frames, int F, int S, float* partial, hipStream_t stream,
-                       const char* name) {
+template <typename Src, typename Idx>
+int launch_frame_stats(Src raw, Idx ix, int B, int max_frames, int F, int S, float* partial, hipStream_t stream, const char* name) {
     using namespace lpm;
     LPM_REQUIRE(partial, LPM_ERR_BADARG, "%s: null workspace", name);
     LPM_REQUIRE(Src::W == 1 || ((uintptr_t)partial & 15) == 0, LPM_ERR_UNSUPPORTED_SHAPE, "%s: need a 16-byte aligned workspace", name);
-    const float step = 1.0f / (float)S;
-    hipLaunchKernelGGL(frame_stats_kernel<Src>, dim3(fp_nblk(B, S)), dim3(256), 0, stream, raw, num_frames, B, max_frames, F, S, step,
-                       partial);
+    hipLaunchKernelGGL((frame_stats_kernel<Src, Idx>), dim3(fp_nblk(B, S)), dim3(256), 0, stream, raw, ix, B, max_frames, F, S, partial);
     return check_launch(name);
 }
 
 // dy2 == NULL: one gradient matrix dy [B S, F] (lpm_frame_bn_bwd); else dy [B S, Dv] and dy2 [B S, F - Dv] (lpm_frame_bn_bwd_split)
-template <typename Src>
-int launch_frame_bn_bwd(const float* dy, int64_t lddy, const float* dy2, int64_t lddy2, int Dv, Src raw, const int32_t* num_frames, int B,
+template <typename Src, typename Idx>
+int launch_frame_bn_bwd(const float* dy, int64_t lddy, const float* dy2, int64_t lddy2, int Dv, Src raw, Idx ix, int B,
                         int max_frames, int F, int S, const float* mean, const float* var, float eps, float* dgamma, float* dbeta,
                         void* workspace, size_t workspace_bytes, hipStream_t stream, const char* name) {
     using namespace lpm;
@@ -570,10 +593,9 @@ int launch_frame_bn_bwd(const float* dy, int64_t lddy, const float* dy2, int64_t
         LPM_REQUIRE((((uintptr_t)dy | (uintptr_t)dy2 | (uintptr_t)workspace) & 15) == 0 && lddy % 4 == 0 &&
                         (dy2 == nullptr || (lddy2 % 4 == 0 && Dv % 4 == 0)),
                     LPM_ERR_UNSUPPORTED_SHAPE, "%s: need 16-byte aligned gradients and workspace, row strides and Dv multiples of 4", name);
-    const float step = 1.0f / (float)S;
     const int nblk = fp_nblk(B, S);
-    hipLaunchKernelGGL(frame_bn_bwd_partial_kernel<Src>, dim3(nblk), dim3(256), 0, stream, dy, lddy, raw, num_frames, B, max_frames, F, S,
-                       step, (float*)workspace, dy2, lddy2, dy2 ? Dv : F);
+    hipLaunchKernelGGL((frame_bn_bwd_partial_kernel<Src, Idx>), dim3(nblk), dim3(256), 0, stream, dy, lddy, raw, ix, B, max_frames, F, S,
+                       (float*)workspace, dy2, lddy2, dy2 ? Dv : F);
     hipLaunchKernelGGL(frame_bn_bwd_reduce_kernel, dim3((F + 15) / 16), dim3(1024), 0, stream, (const float*)workspace, nblk, F, mean, var,
                        eps, dgamma, dbeta);
     return check_launch(name);
@@ -584,13 +606,14 @@ int launch_frame_bn_bwd(const float* dy, int64_t lddy, const float* dy2, int64_t
 extern "C" int lpm_frame_stats(const float* raw, const int32_t* num_frames, int B, int max_frames, int F, int S,
                                float* partial, lpm_stream_t stream) {
     LPM_FRAME_CHECK("lpm_frame_stats");
-    return launch_frame_stats(FrameSrc<float>{raw}, num_frames, B, max_frames, F, S, partial, (hipStream_t)stream, "lpm_frame_stats");
+    return launch_frame_stats(FrameSrc<float>{raw}, uniform_idx(num_frames, S), B, max_frames, F, S, partial, (hipStream_t)stream, "lpm_frame_stats");
 }
 
 extern "C" int lpm_frame_apply(const float* raw, const int32_t* num_frames, int B, int max_frames, int F, int S,
                                const float* scale, const float* shift, float* y, lpm_stream_t stream) {
     LPM_FRAME_CHECK("lpm_frame_apply");
-    return launch_frame_apply(FrameSrc<float>{raw}, num_frames, B, max_frames, F, S, scale, shift, y, (hipStream_t)stream, "lpm_frame_apply");
+    return launch_frame_apply(FrameSrc<float>{raw}, uniform_idx(num_frames, S), B, max_frames, F, S, scale, shift, y, nullptr, F,
+                              (hipStream_t)stream, "lpm_frame_apply");
 }
 
 extern "C" int lpm_frame_apply_tiles(const float* raw, const int32_t* num_frames, int B, int max_frames, int F, int S,
@@ -632,24 +655,33 @@ extern "C" int lpm_frame_apply_tiles2(const float* raw, const int32_t* num_frame
 }
 
 // ---- eval mode from the reader's quantised frames -----------------------------------------------------------------------------
-extern "C" int lpm_frame_inv_norm_q8(const unsigned char* q, const int32_t* num_frames, int B, int max_frames, int F, int S,
-                                     float max_quantized_value, float min_quantized_value, float* inv_norm, lpm_stream_t stream) {
+namespace {
+template <typename Idx>
+int launch_frame_inv_norm_q8(const unsigned char* q, const int32_t* num_frames, Idx ix, int B, int max_frames, int F, int S,
+                             float max_quantized_value, float min_quantized_value, float* inv_norm, hipStream_t stream, const char* name) {
     using namespace lpm;
-    LPM_FRAME_Q8_CHECK("lpm_frame_inv_norm_q8");
-    LPM_REQUIRE(F <= 2048, LPM_ERR_UNSUPPORTED_SHAPE, "lpm_frame_inv_norm_q8: need F <= 2048 (F=%d)", F);
+    LPM_REQUIRE(F <= 2048, LPM_ERR_UNSUPPORTED_SHAPE, "%s: need F <= 2048 (F=%d)", name, F);
     const FrameSrc<unsigned char> src = q8_src(q, inv_norm, max_quantized_value, min_quantized_value);
     const int64_t rows = (int64_t)B * S, want = (rows + 3) / 4;
-    hipLaunchKernelGGL(frame_inv_norm_q8_kernel, dim3((unsigned)(want < 16384 ? want : 16384)), dim3(256), 0, (hipStream_t)stream, q,
-                       num_frames, B, max_frames, F, S, 1.0f / (float)S, src.scalar, src.bias, inv_norm);
-    return check_launch("lpm_frame_inv_norm_q8");
+    hipLaunchKernelGGL(frame_inv_norm_q8_kernel<Idx>, dim3((unsigned)(want < 16384 ? want : 16384)), dim3(256), 0, stream, q, num_frames, ix,
+                       B, max_frames, F, S, src.scalar, src.bias, inv_norm);
+    return check_launch(name);
+}
+}  // namespace
+
+extern "C" int lpm_frame_inv_norm_q8(const unsigned char* q, const int32_t* num_frames, int B, int max_frames, int F, int S,
+                                     float max_quantized_value, float min_quantized_value, float* inv_norm, lpm_stream_t stream) {
+    LPM_FRAME_Q8_CHECK("lpm_frame_inv_norm_q8");
+    return launch_frame_inv_norm_q8(q, num_frames, uniform_idx(num_frames, S), B, max_frames, F, S, max_quantized_value, min_quantized_value,
+                                    inv_norm, (hipStream_t)stream, "lpm_frame_inv_norm_q8");
 }
 
 extern "C" int lpm_frame_apply_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
                                   const int32_t* num_frames, int B, int max_frames, int F, int S, const float* scale, const float* shift,
                                   float* y, lpm_stream_t stream) {
     LPM_FRAME_Q8_CHECK("lpm_frame_apply_q8");
-    return launch_frame_apply(q8_src(q, inv_norm, max_quantized_value, min_quantized_value), num_frames, B, max_frames, F, S, scale, shift,
-                              y, (hipStream_t)stream, "lpm_frame_apply_q8");
+    return launch_frame_apply(q8_src(q, inv_norm, max_quantized_value, min_quantized_value), uniform_idx(num_frames, S), B, max_frames, F, S,
+                              scale, shift, y, nullptr, F, (hipStream_t)stream, "lpm_frame_apply_q8");
 }
 
 extern "C" int lpm_frame_apply_tiles_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value,
@@ -696,8 +728,8 @@ extern "C" int lpm_frame_bn_bwd(const float* dy, int64_t lddy, const float* raw,
                                 float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
                                 lpm_stream_t stream) {
     LPM_FRAME_CHECK("lpm_frame_bn_bwd");
-    return launch_frame_bn_bwd(dy, lddy, nullptr, 0, F, FrameSrc<float>{raw}, num_frames, B, max_frames, F, S, mean, var, eps, dgamma, dbeta,
-                               workspace, workspace_bytes, (hipStream_t)stream, "lpm_frame_bn_bwd");
+    return launch_frame_bn_bwd(dy, lddy, nullptr, 0, F, FrameSrc<float>{raw}, uniform_idx(num_frames, S), B, max_frames, F, S, mean, var, eps,
+                               dgamma, dbeta, workspace, workspace_bytes, (hipStream_t)stream, "lpm_frame_bn_bwd");
 }
 // ... with the gradient as two matrices: dy_video [B S, Dv] (row stride ldv) and dy_audio [B S, F - Dv] (row stride lda)
 extern "C" int lpm_frame_bn_bwd_split(const float* dy_video, int64_t ldv, const float* dy_audio, int64_t lda, int Dv, const float* raw,
@@ -705,8 +737,8 @@ extern "C" int lpm_frame_bn_bwd_split(const float* dy_video, int64_t ldv, const 
                                       float eps, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, lpm_stream_t stream) {
     LPM_FRAME_CHECK("lpm_frame_bn_bwd_split");
     LPM_REQUIRE(dy_audio, LPM_ERR_BADARG, "lpm_frame_bn_bwd_split: bad pointers / strides");
-    return launch_frame_bn_bwd(dy_video, ldv, dy_audio, lda, Dv, FrameSrc<float>{raw}, num_frames, B, max_frames, F, S, mean, var, eps, dgamma,
-                               dbeta, workspace, workspace_bytes, (hipStream_t)stream, "lpm_frame_bn_bwd_split");
+    return launch_frame_bn_bwd(dy_video, ldv, dy_audio, lda, Dv, FrameSrc<float>{raw}, uniform_idx(num_frames, S), B, max_frames, F, S, mean, var,
+                               eps, dgamma, dbeta, workspace, workspace_bytes, (hipStream_t)stream, "lpm_frame_bn_bwd_split");
 }
 
 // ---- training mode from the reader's quantised frames: the batch statistics and the dgamma / dbeta partials, bit for bit those of the
@@ -714,8 +746,8 @@ extern "C" int lpm_frame_bn_bwd_split(const float* dy_video, int64_t ldv, const 
 extern "C" int lpm_frame_stats_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
                                   const int32_t* num_frames, int B, int max_frames, int F, int S, float* partial, lpm_stream_t stream) {
     LPM_FRAME_Q8_CHECK("lpm_frame_stats_q8");
-    return launch_frame_stats(q8_src(q, inv_norm, max_quantized_value, min_quantized_value), num_frames, B, max_frames, F, S, partial,
-                              (hipStream_t)stream, "lpm_frame_stats_q8");
+    return launch_frame_stats(q8_src(q, inv_norm, max_quantized_value, min_quantized_value), uniform_idx(num_frames, S), B, max_frames, F, S,
+                              partial, (hipStream_t)stream, "lpm_frame_stats_q8");
 }
 
 extern "C" int lpm_frame_bn_bwd_q8(const float* dy, int64_t lddy, const unsigned char* q, const float* inv_norm, float max_quantized_value,
@@ -723,9 +755,9 @@ extern "C" int lpm_frame_bn_bwd_q8(const float* dy, int64_t lddy, const unsigned
                                    const float* mean, const float* var, float eps, float* dgamma, float* dbeta, void* workspace,
                                    size_t workspace_bytes, lpm_stream_t stream) {
     LPM_FRAME_Q8_CHECK("lpm_frame_bn_bwd_q8");
-    return launch_frame_bn_bwd(dy, lddy, nullptr, 0, F, q8_src(q, inv_norm, max_quantized_value, min_quantized_value), num_frames, B,
-                               max_frames, F, S, mean, var, eps, dgamma, dbeta, workspace, workspace_bytes, (hipStream_t)stream,
-                               "lpm_frame_bn_bwd_q8");
+    return launch_frame_bn_bwd(dy, lddy, nullptr, 0, F, q8_src(q, inv_norm, max_quantized_value, min_quantized_value),
+                               uniform_idx(num_frames, S), B, max_frames, F, S, mean, var, eps, dgamma, dbeta, workspace, workspace_bytes,
+                               (hipStream_t)stream, "lpm_frame_bn_bwd_q8");
 }
 
 extern "C" int lpm_frame_bn_bwd_split_q8(const float* dy_video, int64_t ldv, const float* dy_audio, int64_t lda, int Dv,
@@ -735,9 +767,72 @@ extern "C" int lpm_frame_bn_bwd_split_q8(const float* dy_video, int64_t ldv, con
                                          size_t workspace_bytes, lpm_stream_t stream) {
     LPM_FRAME_Q8_CHECK("lpm_frame_bn_bwd_split_q8");
     LPM_REQUIRE(dy_audio, LPM_ERR_BADARG, "lpm_frame_bn_bwd_split_q8: bad pointers / strides");
-    return launch_frame_bn_bwd(dy_video, ldv, dy_audio, lda, Dv, q8_src(q, inv_norm, max_quantized_value, min_quantized_value), num_frames, B,
-                               max_frames, F, S, mean, var, eps, dgamma, dbeta, workspace, workspace_bytes, (hipStream_t)stream,
-                               "lpm_frame_bn_bwd_split_q8");
+    return launch_frame_bn_bwd(dy_video, ldv, dy_audio, lda, Dv, q8_src(q, inv_norm, max_quantized_value, min_quantized_value),
+                               uniform_idx(num_frames, S), B, max_frames, F, S, mean, var, eps, dgamma, dbeta, workspace, workspace_bytes,
+                               (hipStream_t)stream, "lpm_frame_bn_bwd_split_q8");
+}
+
+// ---- the index-table forms (*_idx): sampled row r = b S + j reads frame frame_index[r] of clip b (clamped to [0, max_frames - 1]) instead
+// of SampleUniformFrames' own index -- SampleRandomFrames for the triangulation models.  Same kernels, same arithmetic; the frames leave
+// as two contiguous fp32 matrices and no operand tiles.  The q8 forms take inv_norm from lpm_frame_inv_norm_q8_idx with the same table. ----
+extern "C" int lpm_frame_inv_norm_q8_idx(const unsigned char* q, const int32_t* num_frames, const int32_t* frame_index, int B, int max_frames,
+                                         int F, int S, float max_quantized_value, float min_quantized_value, float* inv_norm,
+                                         lpm_stream_t stream) {
+    LPM_FRAME_Q8_CHECK("lpm_frame_inv_norm_q8_idx");
+    LPM_REQUIRE(frame_index, LPM_ERR_BADARG, "lpm_frame_inv_norm_q8_idx: null pointer");
+    return launch_frame_inv_norm_q8(q, num_frames, TableIdx{frame_index}, B, max_frames, F, S, max_quantized_value, min_quantized_value,
+                                    inv_norm, (hipStream_t)stream, "lpm_frame_inv_norm_q8_idx");
+}
+
+extern "C" int lpm_frame_stats_idx(const float* raw, const int32_t* frame_index, int B, int max_frames, int F, int S, float* partial,
+                                   lpm_stream_t stream) {
+    LPM_FRAME_IDX_CHECK("lpm_frame_stats_idx");
+    return launch_frame_stats(FrameSrc<float>{raw}, TableIdx{frame_index}, B, max_frames, F, S, partial, (hipStream_t)stream,
+                              "lpm_frame_stats_idx");
+}
+extern "C" int lpm_frame_stats_idx_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
+                                      const int32_t* frame_index, int B, int max_frames, int F, int S, float* partial, lpm_stream_t stream) {
+    LPM_FRAME_Q8_IDX_CHECK("lpm_frame_stats_idx_q8");
+    return launch_frame_stats(q8_src(q, inv_norm, max_quantized_value, min_quantized_value), TableIdx{frame_index}, B, max_frames, F, S,
+                              partial, (hipStream_t)stream, "lpm_frame_stats_idx_q8");
+}
+
+extern "C" int lpm_frame_apply_split_idx(const float* raw, const int32_t* frame_index, int B, int max_frames, int F, int S, const float* scale,
+                                         const float* shift, float* y_video, float* y_audio, int Dv, lpm_stream_t stream) {
+    LPM_FRAME_IDX_CHECK("lpm_frame_apply_split_idx");
+    LPM_REQUIRE(y_video && y_audio, LPM_ERR_BADARG, "lpm_frame_apply_split_idx: bad pointers");
+    return launch_frame_apply(FrameSrc<float>{raw}, TableIdx{frame_index}, B, max_frames, F, S, scale, shift, y_video, y_audio, Dv,
+                              (hipStream_t)stream, "lpm_frame_apply_split_idx");
+}
+extern "C" int lpm_frame_apply_split_idx_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value,
+                                            float min_quantized_value, const int32_t* frame_index, int B, int max_frames, int F, int S,
+                                            const float* scale, const float* shift, float* y_video, float* y_audio, int Dv,
+                                            lpm_stream_t stream) {
+    LPM_FRAME_Q8_IDX_CHECK("lpm_frame_apply_split_idx_q8");
+    LPM_REQUIRE(y_video && y_audio, LPM_ERR_BADARG, "lpm_frame_apply_split_idx_q8: bad pointers");
+    return launch_frame_apply(q8_src(q, inv_norm, max_quantized_value, min_quantized_value), TableIdx{frame_index}, B, max_frames, F, S, scale,
+                              shift, y_video, y_audio, Dv, (hipStream_t)stream, "lpm_frame_apply_split_idx_q8");
+}
+
+extern "C" int lpm_frame_bn_bwd_split_idx(const float* dy_video, int64_t ldv, const float* dy_audio, int64_t lda, int Dv, const float* raw,
+                                          const int32_t* frame_index, int B, int max_frames, int F, int S, const float* mean,
+                                          const float* var, float eps, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
+                                          lpm_stream_t stream) {
+    LPM_FRAME_IDX_CHECK("lpm_frame_bn_bwd_split_idx");
+    LPM_REQUIRE(dy_audio, LPM_ERR_BADARG, "lpm_frame_bn_bwd_split_idx: bad pointers / strides");
+    return launch_frame_bn_bwd(dy_video, ldv, dy_audio, lda, Dv, FrameSrc<float>{raw}, TableIdx{frame_index}, B, max_frames, F, S, mean, var,
+                               eps, dgamma, dbeta, workspace, workspace_bytes, (hipStream_t)stream, "lpm_frame_bn_bwd_split_idx");
+}
+extern "C" int lpm_frame_bn_bwd_split_idx_q8(const float* dy_video, int64_t ldv, const float* dy_audio, int64_t lda, int Dv,
+                                             const unsigned char* q, const float* inv_norm, float max_quantized_value,
+                                             float min_quantized_value, const int32_t* frame_index, int B, int max_frames, int F, int S,
+                                             const float* mean, const float* var, float eps, float* dgamma, float* dbeta, void* workspace,
+                                             size_t workspace_bytes, lpm_stream_t stream) {
+    LPM_FRAME_Q8_IDX_CHECK("lpm_frame_bn_bwd_split_idx_q8");
+    LPM_REQUIRE(dy_audio, LPM_ERR_BADARG, "lpm_frame_bn_bwd_split_idx_q8: bad pointers / strides");
+    return launch_frame_bn_bwd(dy_video, ldv, dy_audio, lda, Dv, q8_src(q, inv_norm, max_quantized_value, min_quantized_value),
+                               TableIdx{frame_index}, B, max_frames, F, S, mean, var, eps, dgamma, dbeta, workspace, workspace_bytes,
+                               (hipStream_t)stream, "lpm_frame_bn_bwd_split_idx_q8");
 }
 
 extern "C" int lpm_l2_normalize_rows(const float* x, int64_t rows, int F, float* y, lpm_stream_t stream) {

@@ -184,3 +184,10 @@ FLAGS.define("train_quantised_frames", True, "build extension: Trainer.build / s
              "forms, lpm_frame_bn_bwd*_q8) instead of first writing the dequantised, L2-normalised fp32 frames of all max_frames "
              "(ops.dequantize_l2_normalize) -- the same results bit for bit.  False: the fp32 detour (A/B).  fp32 input, the CPU and other "
              "models are not affected")
+FLAGS.define("gather_frames_fused", False, "build extension: the reader's uint8 frames on the GPU go unnormalised to the five triangulation "
+             "models as well (RegularizedTriangulationModel, SoftAttentionTriangulationModel, TriangulationCnnClusterModel, JuhanTestModelV5, "
+             "JuhanTestModelV1), which draw SampleRandomFrames' index table and gather, dequantise, L2-normalise and batch-normalise the "
+             "sampled frames only (ops.frame_gather_bn_split: the *_idx frame-prep kernels).  False: these models take the normalise-everything "
+             "route (ops.dequantize_l2_normalize over all max_frames, then the fp32 path).  fp32 input and the CPU are not affected.  Off by "
+             "default until tools/bench_frame_gather.py has shown the new route not slower at every model shape on an MI355X: it has not run "
+             "yet (profiles/bench_frame_gather.json)")

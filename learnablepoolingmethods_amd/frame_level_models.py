@@ -17,6 +17,7 @@ import torch
 
 from . import FLAGS, aggregation_modules, layers, model_utils, models, ops, transformer_utils, video_level_models, video_pooling_modules
 from . import variables as vs
+from ._capi import LpmError
 
 
 class NetVLAD():
@@ -148,6 +149,54 @@ def _sample_and_normalise(model_input, num_frames, iterations, add_batch_norm, i
     return ops.frame_sample_bn(model_input, num_frames.reshape(-1), iterations, *bn, is_training=is_training, storage=storage,
                                materialize=storage == "f32" or vs.default_store().summaries is not None,
                                quantised_training=quantised_training)
+
+
+def _gather_and_normalise(model_input, num_frames, iterations, frame_uniform, bn_scopes, is_training, quantised_training):
+    """The triangulation models' input stage from the reader's uint8 batch on the GPU: SampleRandomFrames' index table
+    (model_utils.random_frame_index) + ops.frame_gather_bn_split -> (video [B*S, 1024], audio [B*S, F - 1024]), contiguous.  bn_scopes:
+    ("input_bn",) one batch norm over [F]; ("video_bn", "audio_bn") one per stream -- their variables concatenated for the kernels, which
+    treat every column alone, and the moving statistics bn_fold updated copied back into each scope; (): no batch norm."""
+    if not model_input.is_cuda:
+        raise LpmError("uint8 (quantised) frames reach this model on the GPU only: on the CPU normalise them first (train.normalize_input)")
+    dev, feature_size = model_input.device, model_input.shape[2]
+    nf = num_frames.reshape(-1).to(dev)
+    frame_index = model_utils.random_frame_index(nf, iterations, uniform=frame_uniform)
+    widths = (feature_size,) if len(bn_scopes) == 1 else (1024, feature_size - 1024)
+    parts = [layers.bn_variables(scope, width, dev) for scope, width in zip(bn_scopes, widths)]
+    if len(parts) == 2:
+        bn = [torch.cat(pair) for pair in zip(*parts)]                    # gamma, beta, moving_mean, moving_variance over [F]
+    else:
+        bn = list(parts[0]) if parts else [None] * 4
+    video, audio = ops.frame_gather_bn_split(model_input, nf, frame_index, *bn, is_training, 1024, quantised_training)
+    if len(parts) == 2 and is_training:
+        with torch.no_grad():
+            for (_, _, mm, mv), cols in zip(parts, (slice(0, 1024), slice(1024, None))):
+                mm.copy_(bn[2][cols])
+                mv.copy_(bn[3][cols])
+    return video, audio
+
+
+def _random_frames(model_input, num_frames, iterations, frame_uniform):
+    """-> (quantised, frames, max_frames, feature_size): SampleRandomFrames of fp32 frames; a uint8 batch stays as it is for
+    _gather_and_normalise, which samples where it reads."""
+    if model_input.dtype == torch.uint8:
+        return True, model_input, iterations, model_input.shape[2]
+    model_input = model_utils.SampleRandomFrames(model_input, num_frames.reshape(-1, 1), iterations, uniform=frame_uniform)
+    return False, model_input, model_input.shape[1], model_input.shape[2]
+
+
+def _stream_features(quantised, model_input, num_frames, iterations, frame_uniform, add_batch_norm, is_training, quantised_training):
+    """-> [video [B*S, 1024], audio [B*S, F - 1024]] behind the scopes video_bn / audio_bn (add_batch_norm): column slices of the sampled
+    fp32 frames through layers.batch_norm, or (a uint8 batch) two contiguous matrices from _gather_and_normalise."""
+    if quantised:
+        scopes = ("video_bn", "audio_bn") if add_batch_norm else ()
+        return list(_gather_and_normalise(model_input, num_frames, iterations, frame_uniform, scopes, is_training, quantised_training))
+    reshaped_input = model_input.reshape(-1, model_input.shape[2])
+    features = []
+    for name, cols in (("video", slice(0, 1024)), ("audio", slice(1024, None))):
+        x = reshaped_input[:, cols]
+        features.append(layers.batch_norm(x, is_training, name + "_bn") if add_batch_norm else x)
+    return features
 
 
 class NetVladV1(models.BaseModel):
@@ -335,28 +384,29 @@ class RegularizedTriangulationModel(models.BaseModel):
 
     def create_model(self, model_input, vocab_size, num_frames, iterations=None, add_batch_norm=None, sample_random_frames=None,
                      hidden_size=None, is_training=True, frame_uniform=None, video_anchor_size=None, audio_anchor_size=None,
-                     **unused_params):
+                     quantised_training=False, **unused_params):
         iterations = iterations or FLAGS.iterations
         video_anchor_size = int(video_anchor_size or FLAGS.wtm_video_anchor_size)                             # :1160
         audio_anchor_size = int(audio_anchor_size or FLAGS.wtm_audio_anchor_size)                             # :1161
-        model_input = model_utils.SampleRandomFrames(model_input, num_frames.reshape(-1, 1), iterations, uniform=frame_uniform)  # :1163-1165
-        max_frames, feature_size = model_input.shape[1], model_input.shape[2]
+        quantised, model_input, max_frames, feature_size = _random_frames(model_input, num_frames, iterations, frame_uniform)  # :1163-1165
         if feature_size <= 1024:
             raise ValueError("RegularizedTriangulationModel slices a 1024-wide video and a 128-wide audio stream out of its input "
                              f"(frame_level_models.py:1202,1210); got {feature_size} features")
         dev = model_input.device
-        reshaped_input = model_input.reshape(-1, feature_size)
         # add_batch_norm is accepted and unused, as written: the modules store it and never read it (:1176-1192)
         streams = (("video_t_emb", 1024, video_anchor_size, slice(0, 1024)), ("audio_t_emb", feature_size - 1024, audio_anchor_size, slice(1024, None)))
         d_modules = [video_pooling_modules.WeightedTriangulationEmbedding(D, max_frames, K, add_batch_norm, is_training) for _, D, K, _ in streams]
         mean_max_pool = aggregation_modules.MaxMeanPoolingModule(l2_normalize=False)                          # :1183
         t_modules = [video_pooling_modules.TriangulationTemporalEmbedding(D, max_frames, K, add_batch_norm, is_training) for _, D, K, _ in streams]
-        reshaped_input = layers.batch_norm(reshaped_input, is_training, "input_bn")                           # :1194-1199
-        fused = bool(FLAGS.triangulation_fused and reshaped_input.is_cuda and max_frames >= 2)
+        if quantised:       # the reader's uint8 batch: sampled, dequantised, normalised and batch-normalised by the frame-prep kernels
+            stream_inputs = _gather_and_normalise(model_input, num_frames, iterations, frame_uniform, ("input_bn",), is_training, quantised_training)
+        else:
+            reshaped_input = layers.batch_norm(model_input.reshape(-1, feature_size), is_training, "input_bn")   # :1194-1199
+            stream_inputs = [reshaped_input[:, cols] for *_, cols in streams]
+        fused = bool(FLAGS.triangulation_fused and dev.type == "cuda" and max_frames >= 2)
         agg_d, agg_t, orthogonal_reg = [], [], 0.0
-        for (scope, D, K, cols), d_module, t_module in zip(streams, d_modules, t_modules):
+        for (scope, D, K, _), x, d_module, t_module in zip(streams, stream_inputs, d_modules, t_modules):
             with vs.variable_scope(scope):                                                                    # :1201-1215
-                x = reshaped_input[:, cols]
                 if fused:
                     anchors, ortho = d_module.variables(dev)
                     max_d, mean_d, max_t, mean_t = ops.triangulation_pool(x.contiguous(), anchors, max_frames, scale=1 / math.sqrt(K))
@@ -411,7 +461,7 @@ class SoftAttentionTriangulationModel(models.BaseModel):
 
     def create_model(self, model_input, vocab_size, num_frames, iterations=None, add_batch_norm=None, sample_random_frames=None,
                      hidden_size=None, is_training=True, frame_uniform=None, video_anchor_size=None, audio_anchor_size=None,
-                     video_bottleneck=None, audio_bottleneck=None, **unused_params):
+                     video_bottleneck=None, audio_bottleneck=None, quantised_training=False, **unused_params):
         iterations = iterations or FLAGS.sftm_iterations                                                      # :976
         add_batch_norm = add_batch_norm or FLAGS.sftm_add_batch_norm                                          # :977 (False cannot switch it off: C23)
         video_anchor_size = int(video_anchor_size or FLAGS.sftm_video_anchor_size)                            # :978-981
@@ -419,23 +469,19 @@ class SoftAttentionTriangulationModel(models.BaseModel):
         video_bottleneck = int(video_bottleneck or FLAGS.sftm_video_bottleneck)
         audio_bottleneck = int(audio_bottleneck or FLAGS.sftm_audio_bottleneck)
         # sample_random_frames and hidden_size are accepted and read nowhere, as written (C24)
-        model_input = model_utils.SampleRandomFrames(model_input, num_frames.reshape(-1, 1), iterations, uniform=frame_uniform)  # :983-984
-        max_frames, feature_size = model_input.shape[1], model_input.shape[2]
+        quantised, model_input, max_frames, feature_size = _random_frames(model_input, num_frames, iterations, frame_uniform)  # :983-984
         if feature_size <= 1024:
             raise ValueError("SoftAttentionTriangulationModel slices a 1024-wide video and a 128-wide audio stream out of its input "
                              f"(frame_level_models.py:991-992); got {feature_size} features")
         dev = model_input.device
-        reshaped_input = model_input.reshape(-1, feature_size)
         streams = (("video", 1024, video_anchor_size, video_bottleneck, slice(0, 1024)),
                    ("audio", feature_size - 1024, audio_anchor_size, audio_bottleneck, slice(1024, None)))
-        features = []
-        for name, _, _, _, cols in streams:                                                                   # :991-1006
-            x = reshaped_input[:, cols]
-            features.append(layers.batch_norm(x, is_training, name + "_bn") if add_batch_norm else x)
+        features = _stream_features(quantised, model_input, num_frames, iterations, frame_uniform, add_batch_norm, is_training,
+                                    quantised_training)                                                       # :991-1006
         d_modules = [video_pooling_modules.TriangulationEmbedding(D, max_frames, K, add_batch_norm, is_training) for _, D, K, _, _ in streams]
         cluster_pool = aggregation_modules.IndirectClusterMaxMeanPoolModule(l2_normalize=False)               # :1019
         t_modules = [video_pooling_modules.TriangulationTemporalEmbedding(D, max_frames, K, add_batch_norm, is_training) for _, D, K, _, _ in streams]
-        fused = bool(FLAGS.soft_attention_fused and reshaped_input.is_cuda and max_frames >= 2)
+        fused = bool(FLAGS.soft_attention_fused and dev.type == "cuda" and max_frames >= 2)
         agg = {}
         for (name, D, K, _, _), x, d_module, t_module in zip(streams, features, d_modules, t_modules):
             with vs.variable_scope(name + "_triangulation_embedding"):                                        # :1031-1051
@@ -484,7 +530,8 @@ class TriangulationCnnClusterModel(models.BaseModel):
 
     def create_model(self, model_input, vocab_size, num_frames, iterations=None, add_batch_norm=None, sample_random_frames=None,
                      hidden_size=None, is_training=True, frame_uniform=None, video_anchor_size=None, audio_anchor_size=None,
-                     video_kernel_size=None, audio_kernel_size=None, video_hidden=None, audio_hidden=None, **unused_params):
+                     video_kernel_size=None, audio_kernel_size=None, video_hidden=None, audio_hidden=None, quantised_training=False,
+                     **unused_params):
         iterations = iterations or FLAGS.tccm_iterations                                                      # :768
         add_batch_norm = add_batch_norm or FLAGS.tccm_add_batch_norm                                          # :769 (C23)
         video_anchor_size = int(video_anchor_size or FLAGS.tccm_video_anchor_size)                            # :770-775
@@ -494,19 +541,15 @@ class TriangulationCnnClusterModel(models.BaseModel):
         video_hidden = int(video_hidden or FLAGS.tccm_video_hidden)
         audio_hidden = int(audio_hidden or FLAGS.tccm_audio_hidden)
         # sample_random_frames and hidden_size are accepted and read nowhere, as written (C26)
-        model_input = model_utils.SampleRandomFrames(model_input, num_frames.reshape(-1, 1), iterations, uniform=frame_uniform)  # :777-778
-        max_frames, feature_size = model_input.shape[1], model_input.shape[2]
+        quantised, model_input, max_frames, feature_size = _random_frames(model_input, num_frames, iterations, frame_uniform)  # :777-778
         if feature_size <= 1024:
             raise ValueError("TriangulationCnnClusterModel slices a 1024-wide video and a 128-wide audio stream out of its input "
                              f"(frame_level_models.py:785-786); got {feature_size} features")
         dev = model_input.device
-        reshaped_input = model_input.reshape(-1, feature_size)
         streams = (("video", 1024, video_anchor_size, video_kernel_size, video_hidden, slice(0, 1024)),
                    ("audio", feature_size - 1024, audio_anchor_size, audio_kernel_size, audio_hidden, slice(1024, None)))
-        features = []
-        for name, _, _, _, _, cols in streams:                                                                # :785-800
-            x = reshaped_input[:, cols]
-            features.append(layers.batch_norm(x, is_training, name + "_bn") if add_batch_norm else x)
+        features = _stream_features(quantised, model_input, num_frames, iterations, frame_uniform, add_batch_norm, is_training,
+                                    quantised_training)                                                       # :785-800
         d_modules = [video_pooling_modules.TriangulationEmbedding(D, max_frames, K, add_batch_norm, is_training) for _, D, K, _, _, _ in streams]
         cnn_modules = [(video_pooling_modules.TriangulationCnnModule(D, max_frames, F, K, add_batch_norm, is_training, name + "_d"),
                         video_pooling_modules.TriangulationCnnModule(D, max_frames - 1, F, K, add_batch_norm, is_training, name + "_t"))
@@ -514,7 +557,7 @@ class TriangulationCnnClusterModel(models.BaseModel):
         ic_mean_pool = aggregation_modules.IndirectClusterMeanPoolModule(l2_normalize=False)                  # :845
         mean_std_pool = aggregation_modules.MeanStdPoolModule(l2_normalize=False)                             # :846 (the mean only: C27)
         t_modules = [video_pooling_modules.TriangulationTemporalEmbedding(D, max_frames, K, add_batch_norm, is_training) for _, D, K, _, _, _ in streams]
-        fused = bool(FLAGS.triangulation_cnn_fused and reshaped_input.is_cuda and max_frames >= 2)
+        fused = bool(FLAGS.triangulation_cnn_fused and dev.type == "cuda" and max_frames >= 2)
         agg = []
         for (name, D, K, _, _, _), x, d_module, (d_cnn, t_cnn), t_module in zip(streams, features, d_modules, cnn_modules, t_modules):
             with vs.variable_scope(name + "_triangulation_embedding"):                                        # :859-915
@@ -561,7 +604,7 @@ class JuhanTestModelV5(models.BaseModel):
     def create_model(self, model_input, vocab_size, num_frames, iterations=None, add_batch_norm=None, sample_random_frames=None,
                      hidden_size=None, is_training=True, frame_uniform=None, video_anchor_size=None, audio_anchor_size=None,
                      video_kernel_size=None, audio_kernel_size=None, video_hidden=None, audio_hidden=None, video_output_dim=None,
-                     audio_output_dim=None, **unused_params):
+                     audio_output_dim=None, quantised_training=False, **unused_params):
         iterations = iterations or FLAGS.jtmv5_iteration                                                      # :526
         add_batch_norm = add_batch_norm or FLAGS.jtmv5_add_batch_norm                                         # :527 (C23)
         video_anchor_size = int(video_anchor_size or FLAGS.jtmv5_video_anchor_size)                           # :528-535
@@ -573,23 +616,19 @@ class JuhanTestModelV5(models.BaseModel):
         video_output_dim = int(video_output_dim or FLAGS.jtmv5_video_output_dim)
         audio_output_dim = int(audio_output_dim or FLAGS.jtmv5_audio_output_dim)
         # sample_random_frames and hidden_size are accepted and read nowhere, as written (C30)
-        model_input = model_utils.SampleRandomFrames(model_input, num_frames.reshape(-1, 1), iterations, uniform=frame_uniform)  # :537-538
-        max_frames, feature_size = model_input.shape[1], model_input.shape[2]
+        quantised, model_input, max_frames, feature_size = _random_frames(model_input, num_frames, iterations, frame_uniform)  # :537-538
         if feature_size <= 1024:
             raise ValueError("JuhanTestModelV5 slices a 1024-wide video and a 128-wide audio stream out of its input "
                              f"(frame_level_models.py:546-547); got {feature_size} features")
         dev = model_input.device
-        reshaped_input = model_input.reshape(-1, feature_size)
         streams = (("video", 1024, video_anchor_size, video_kernel_size, video_hidden, video_output_dim, slice(0, 1024)),
                    ("audio", feature_size - 1024, audio_anchor_size, audio_kernel_size, audio_hidden, audio_output_dim, slice(1024, None)))
-        features = []
-        for name, *_, cols in streams:                                                                        # :546-562
-            x = reshaped_input[:, cols]
-            features.append(layers.batch_norm(x, is_training, name + "_bn") if add_batch_norm else x)
+        features = _stream_features(quantised, model_input, num_frames, iterations, frame_uniform, add_batch_norm, is_training,
+                                    quantised_training)                                                       # :546-562
         v5_modules = [video_pooling_modules.TriangulationV5Module(
             feature_size=D, max_frames=max_frames, anchor_size=K, kernel_size=F, self_attention=False, hidden_layer_size=H, output_dim=O,
             add_relu=True, batch_norm=add_batch_norm, is_training=is_training, scope_id=None) for _, D, K, F, H, O, _ in streams]   # :564-588
-        fused = bool(FLAGS.triangulation_v5_fused and reshaped_input.is_cuda and max_frames >= 2)
+        fused = bool(FLAGS.triangulation_v5_fused and dev.type == "cuda" and max_frames >= 2)
         acts = []
         for (name, *_), x, module in zip(streams, features, v5_modules):
             with vs.variable_scope(name + "_triangulation_embedding"):                                        # :590-596
@@ -618,7 +657,8 @@ class JuhanTestModelV1(models.BaseModel):
 
     def create_model(self, model_input, vocab_size, num_frames, iterations=None, add_batch_norm=None, sample_random_frames=None,
                      hidden_size=None, is_training=True, frame_uniform=None, video_anchor_size=None, audio_anchor_size=None,
-                     video_hidden=None, audio_hidden=None, video_output_dim=None, audio_output_dim=None, **unused_params):
+                     video_hidden=None, audio_hidden=None, video_output_dim=None, audio_output_dim=None, quantised_training=False,
+                     **unused_params):
         iterations = iterations or FLAGS.jtmv1_iteration                                                      # :94
         add_batch_norm = add_batch_norm or FLAGS.jtmv1_add_batch_norm                                         # :95 (C23)
         video_anchor_size = int(video_anchor_size or FLAGS.jtmv1_video_anchor_size)                           # :96-101
@@ -629,22 +669,21 @@ class JuhanTestModelV1(models.BaseModel):
         audio_output_dim = int(audio_output_dim or FLAGS.jtmv1_audio_output_dim)
         use_attention, use_relu = FLAGS.jtmv1_use_attention, FLAGS.jtmv1_use_relu                             # :102-103
         # sample_random_frames and hidden_size are accepted and read nowhere, as written
-        model_input = model_utils.SampleRandomFrames(model_input, num_frames.reshape(-1, 1), iterations, uniform=frame_uniform)  # :105-106
-        max_frames, feature_size = model_input.shape[1], model_input.shape[2]
+        quantised, model_input, max_frames, feature_size = _random_frames(model_input, num_frames, iterations, frame_uniform)  # :105-106
         if feature_size <= 1024:
             raise ValueError("JuhanTestModelV1 slices a 1024-wide video and a 128-wide audio stream out of its input "
                              f"(frame_level_models.py:137-141); got {feature_size} features")
-        reshaped_input = model_input.reshape(-1, feature_size)
         streams = (("video", 1024, video_anchor_size, video_hidden, video_output_dim, slice(0, 1024)),
                    ("audio", feature_size - 1024, audio_anchor_size, audio_hidden, audio_output_dim, slice(1024, None)))
+        features = _stream_features(quantised, model_input, num_frames, iterations, frame_uniform, False, is_training,
+                                    quantised_training)                                                       # (no input batch norm)
         v1_modules = [video_pooling_modules.TriangulationCnnIndirectAttentionModule(
             feature_size=D, max_frames=max_frames, anchor_size=K, self_attention=use_attention, hidden_layer_size=H, output_dim=O,
             add_relu=use_relu, batch_norm=add_batch_norm, is_training=is_training, scope_id=None) for _, D, K, H, O, _ in streams]   # :113-135
-        fused = bool(FLAGS.triangulation_v1_fused and reshaped_input.is_cuda and max_frames >= 2)
+        fused = bool(FLAGS.triangulation_v1_fused and model_input.is_cuda and max_frames >= 2)
         acts = []
-        for (name, *_, cols), module in zip(streams, v1_modules):
+        for (name, *_), x, module in zip(streams, features, v1_modules):
             with vs.variable_scope(name + "_triangulation_embedding"):                                        # :137-143
-                x = reshaped_input[:, cols]
                 acts.append(module.head(*module.fused_pool(x.contiguous())) if fused else module.forward(x))
         activation = torch.cat(acts, 1)                                                                       # :145
         aggregated_model = getattr(video_level_models, "ClassLearningFourNnModel")

@@ -29,6 +29,15 @@ def SampleRandomSequence(model_input, num_frames, num_samples, uniform=None):
     return _gather_frames(model_input, frame_index)
 
 
+def random_frame_index(num_frames, num_samples, uniform=None):
+    """-> int32 [B, num_samples]: the frame index SampleRandomFrames gathers with, int32(fp32(u) * fp32(num_frames)); ``uniform``
+    [B, num_samples] ~ U[0,1) replaces the draw (made on num_frames' device when None).  For ops.frame_gather_bn_split."""
+    nf = num_frames.reshape(-1, 1).to(torch.float32)
+    if uniform is None:
+        uniform = torch.rand((nf.shape[0], num_samples), device=nf.device)
+    return (uniform.to(nf.device, torch.float32) * nf).to(torch.int32)
+
+
 def SampleRandomFrames(model_input, num_frames, num_samples, uniform=None):
     """model_utils.py:60-78: num_samples frames drawn independently, idx = int32(u * num_frames); ``uniform`` [B, S] as above."""
     B = model_input.shape[0]

@@ -816,6 +816,120 @@ def frame_sample_bn_split(raw, num_frames, S, gamma, beta, moving_mean, moving_v
     return _FrameSampleBNSplit.apply(raw, num_frames, gamma, beta, moving_mean, moving_var, int(S), bool(is_training), int(Dv))
 
 
+def _idx_call(lib, name, raw, inv, *args):
+    """lpm_<name>_idx(raw, *args), or lpm_<name>_idx_q8(q, inv_norm, range, *args) when inv is given."""
+    if inv is None:
+        lib.check(getattr(lib, f"_lpm_{name}_idx")(ptr(raw), *args), f"lpm_{name}_idx")
+    else:
+        lib.check(getattr(lib, f"_lpm_{name}_idx_q8")(ptr(raw), ptr(inv), QUANT_MAX, QUANT_MIN, *args), f"lpm_{name}_idx_q8")
+
+
+class _FrameGatherBNSplit(torch.autograd.Function):
+    """_FrameSampleBNSplit with the sampled frames named by an index table (the *_idx entry points) and no operand tiles: the
+    triangulation models' SampleRandomFrames + batch norm(s) + contiguous stream blocks."""
+
+    @staticmethod
+    def forward(ctx, raw, num_frames, frame_index, gamma, beta, moving_mean, moving_var, is_training, Dv):
+        lib = _capi.load()
+        B, MF, F = raw.shape
+        S = frame_index.shape[1]
+        nf = num_frames.to(device=raw.device, dtype=torch.int32).reshape(-1).contiguous()
+        idx = frame_index.contiguous()
+        raw = raw.contiguous()
+        inv = None
+        if raw.dtype == torch.uint8:
+            inv = _empty((B * S,), raw)
+            lib.check(lib._lpm_frame_inv_norm_q8_idx(ptr(raw), ptr(nf), ptr(idx), B, MF, F, S, QUANT_MAX, QUANT_MIN, ptr(inv), stream_ptr()),
+                      "lpm_frame_inv_norm_q8_idx")
+        use_bn = gamma is not None
+        mean = var = scale = shift = None
+        if use_bn and is_training:
+            nblk = lib._lpm_frame_stats_nblk(B, S)
+            partial = _empty((nblk, 2, F), raw)
+            _idx_call(lib, "frame_stats", raw, inv, ptr(idx), B, MF, F, S, ptr(partial), stream_ptr())
+            mean, var, scale, shift = bn_fold(partial, nblk, F, B * S, gamma, beta, moving_mean, moving_var)
+        elif use_bn:
+            scale, shift = folded_eval_affine(gamma, beta, moving_mean, moving_var)
+            scale, shift = scale.contiguous(), shift.contiguous()
+            mean, var = moving_mean.detach().clone(), moving_var.detach().clone()
+        yv, ya = _empty((B * S, Dv), raw), _empty((B * S, F - Dv), raw)
+        _idx_call(lib, "frame_apply_split", raw, inv, ptr(idx), B, MF, F, S, ptr(scale), ptr(shift), ptr(yv), ptr(ya), Dv, stream_ptr())
+        ctx.S, ctx.Dv, ctx.q8, ctx.is_training, ctx.use_bn = S, Dv, inv is not None, is_training, use_bn
+        if use_bn and ctx.q8:
+            if is_training:       # the uint8 frames, the table and the inverse norms stand in for the fp32 frames
+                ctx.save_for_backward(raw, idx, inv, mean, var)
+        elif use_bn:
+            ctx.save_for_backward(raw, idx, mean, var)
+        return yv, ya
+
+    @staticmethod
+    def backward(ctx, dv, da):
+        if not ctx.use_bn:
+            return (None,) * 9
+        if ctx.q8 and not ctx.is_training:
+            raise LpmError("frame_gather_bn_split: no gradient through the eval-mode path of uint8 frames")
+        lib = _capi.load()
+        if ctx.q8:
+            raw, idx, inv, mean, var = ctx.saved_tensors
+        else:
+            (raw, idx, mean, var), inv = ctx.saved_tensors, None
+        B, MF, F = raw.shape
+        Dv, M = ctx.Dv, B * ctx.S
+        dv = _rows(dv.contiguous(), "dy") if dv is not None else torch.zeros((M, Dv), dtype=torch.float32, device=raw.device)
+        da = _rows(da.contiguous(), "dy") if da is not None else torch.zeros((M, F - Dv), dtype=torch.float32, device=raw.device)
+        dgamma, dbeta = _empty((F,), dv), _empty((F,), dv)
+        wsb = lib._lpm_frame_stats_workspace_bytes(B, ctx.S, F)
+        ws = torch.empty(wsb // 4, dtype=torch.float32, device=raw.device)
+        args = (ptr(idx), B, MF, F, ctx.S, ptr(mean), ptr(var), BN_EPS, ptr(dgamma), ptr(dbeta), ptr(ws), wsb, stream_ptr())
+        if ctx.q8:
+            lib.check(lib._lpm_frame_bn_bwd_split_idx_q8(ptr(dv), dv.stride(0), ptr(da), da.stride(0), Dv, ptr(raw), ptr(inv), QUANT_MAX,
+                                                         QUANT_MIN, *args), "lpm_frame_bn_bwd_split_idx_q8")
+        else:
+            lib.check(lib._lpm_frame_bn_bwd_split_idx(ptr(dv), dv.stride(0), ptr(da), da.stride(0), Dv, ptr(raw), *args),
+                      "lpm_frame_bn_bwd_split_idx")
+        return None, None, None, dgamma, dbeta, None, None, None, None
+
+
+def frame_gather_bn_split_ok(raw, Dv, is_training=True, quantised_training=False):
+    """Whether ops.frame_gather_bn_split takes these frames: on the GPU, fp32 or (in eval mode, or with ``quantised_training``) uint8,
+    at a feature size and a split the *_idx kernels accept."""
+    dtype_ok = raw.dtype == torch.float32 or (raw.dtype == torch.uint8 and (not is_training or quantised_training))
+    return bool(raw.is_cuda and raw.dim() == 3 and dtype_ok and raw.shape[2] % 4 == 0 and raw.shape[2] <= 2048
+                and 0 < Dv < raw.shape[2] and Dv % 4 == 0)
+
+
+def frame_gather_bn_split(raw, num_frames, frame_index, gamma, beta, moving_mean, moving_var, is_training, Dv, quantised_training=False):
+    """-> (video [B*S, Dv], audio [B*S, F - Dv]): the frames frame_index [B, S] (int32; model_utils.random_frame_index) names, gathered
+    from ``raw`` [B, max_frames, F] (indices clamped to [0, max_frames - 1]), through one batch norm over [F] (``gamma ... moving_var``
+    all None: none), as two contiguous matrices.  Training mode: batch statistics, the moving statistics updated in place (unbiased
+    variance, BN_DECAY); gamma / beta receive their gradients, the frames are data.  uint8 ``raw`` is the reader's quantised batch
+    (eval mode, or training with ``quantised_training``): only the sampled rows are read, dequantised and L2-normalised, and every
+    result equals the fp32 form's on ops.dequantize_l2_normalize(raw, num_frames) bit for bit; autograd keeps (q, table, inverse
+    norms, mean, var).  No fp32 tensor of size [B, max_frames, F] exists on this path."""
+    _check_q8_eval(raw, is_training, "frame_gather_bn_split", quantised_training)
+    if not raw.is_cuda:
+        raise LpmError("frame_gather_bn_split: the frames must be on the GPU (there is no CPU path)")
+    if raw.dim() != 3 or raw.dtype not in (torch.uint8, torch.float32):
+        raise LpmError("frame_gather_bn_split: expected a uint8 or float32 [batch, max_frames, feature] tensor")
+    B, MF, F = raw.shape
+    Dv = int(Dv)
+    if not frame_gather_bn_split_ok(raw, Dv, is_training, quantised_training):
+        raise LpmError(f"frame_gather_bn_split: need F % 4 == 0, F <= 2048, Dv % 4 == 0, 0 < Dv < F (F={F}, Dv={Dv})")
+    if (not torch.is_tensor(frame_index) or frame_index.dtype != torch.int32 or frame_index.dim() != 2 or frame_index.shape[0] != B
+            or frame_index.shape[1] < 1 or frame_index.device != raw.device):
+        raise LpmError("frame_gather_bn_split: frame_index must be an int32 [batch, samples] tensor on the frames' device")
+    if num_frames.numel() != B:
+        raise LpmError("frame_gather_bn_split: num_frames must have one entry per clip")
+    bn = (gamma, beta, moving_mean, moving_var)
+    if any(t is None for t in bn) != all(t is None for t in bn):
+        raise LpmError("frame_gather_bn_split: gamma, beta, moving_mean and moving_var go together (all None: no batch norm)")
+    if gamma is not None:
+        for t in bn:
+            if t.shape != (F,) or t.dtype != torch.float32 or t.device != raw.device or not t.is_contiguous():
+                raise LpmError(f"frame_gather_bn_split: batch-norm tensors must be contiguous float32 [{F}] on the frames' device")
+    return _FrameGatherBNSplit.apply(raw, num_frames, frame_index, gamma, beta, moving_mean, moving_var, bool(is_training), Dv)
+
+
 # ----------------------------------------------------------------------------------------------
 # K1 + K2 (+K3): NetVLAD pooling
 # ----------------------------------------------------------------------------------------------

@@ -5,7 +5,8 @@ video).
 A ``Predictor`` holds a snapshot of a model's weights and batch-norm moving statistics in a variable store of its own -- no Adam
 slots, no gradient arena, nothing a running ``Trainer`` writes -- and runs the eval-mode forward of the registry model on it.  The
 reader's quantised uint8 frames go straight into the frame-prep kernels for NetVladV1 / NetVladV2 (ops.frame_sample_bn: the
-dequantisation and per-frame L2 normalisation happen for the sampled frames only); other models, and fp32 frames, are normalised
+dequantisation and per-frame L2 normalisation happen for the sampled frames only) and for the five triangulation models
+(ops.frame_gather_bn_split, FLAGS.gather_frames_fused); other models, and fp32 frames, are normalised
 first exactly as ``Trainer.predict`` does it.
 """
 from __future__ import annotations
@@ -21,6 +22,20 @@ from .train import normalize_input
 
 # models whose frame-prep op reads uint8 frames in eval mode (ops.frame_sample_bn / frame_sample_bn_split)
 FUSED_Q8_MODELS = ("NetVladV1", "NetVladV2")
+# models that gather SampleRandomFrames' frames from the uint8 batch themselves (ops.frame_gather_bn_split), FLAGS.gather_frames_fused
+GATHER_Q8_MODELS = ("RegularizedTriangulationModel", "SoftAttentionTriangulationModel", "TriangulationCnnClusterModel", "JuhanTestModelV5",
+                    "JuhanTestModelV1")
+
+
+def takes_quantised_frames(model, frames) -> bool:
+    """Whether a uint8 batch goes to this model unnormalised: on the GPU, and either a NetVLAD model (uniform sampling) or -- with
+    FLAGS.gather_frames_fused, at a feature size the q8 kernels accept -- one of the triangulation models (random sampling)."""
+    name = type(model).__name__
+    if not (frames.dtype == torch.uint8 and frames.is_cuda and frames.dim() == 3):
+        return False
+    if name in FUSED_Q8_MODELS:
+        return True
+    return bool(name in GATHER_Q8_MODELS and FLAGS.gather_frames_fused and frames.shape[2] % 4 == 0 and frames.shape[2] <= 2048)
 # checkpoint entries that are not variables (train.Trainer.state_dict)
 _NOT_VARIABLES = ("global_step", "bn_statistics_synced", "hidden1_adam_shard")
 _H1 = "tower/hidden1_weights"
@@ -114,7 +129,7 @@ class Predictor:
         self._check_inputs(frames, num_frames)
         frames = frames.to(self.device)
         nf = num_frames.to(self.device)
-        if frames.dtype == torch.float32 or not (frames.is_cuda and type(self.model).__name__ in FUSED_Q8_MODELS):
+        if not takes_quantised_frames(self.model, frames):
             frames = normalize_input(frames, nf)
         with vs.use_store(self.store):
             with vs.variable_scope("tower"):

@@ -536,10 +536,10 @@ class Trainer:
     def _quantised_frames(self, raw) -> bool:
         """FLAGS.train_quantised_frames: the reader's uint8 batch on the GPU goes to the model as it is (the frame-prep kernels
         dequantise and normalise the sampled frames where they read them) -- for the models whose frame op takes it, at a feature size
-        the q8 kernels accept (lpm_frame_inv_norm_q8)."""
-        from .predictor import FUSED_Q8_MODELS
-        return bool(FLAGS.train_quantised_frames and raw.dtype == torch.uint8 and raw.is_cuda and raw.dim() == 3
-                    and type(self.model).__name__ in FUSED_Q8_MODELS and raw.shape[2] % 4 == 0 and raw.shape[2] <= 2048)
+        the q8 kernels accept (lpm_frame_inv_norm_q8); the triangulation models with FLAGS.gather_frames_fused."""
+        from .predictor import takes_quantised_frames
+        return bool(FLAGS.train_quantised_frames and raw.dim() == 3 and raw.shape[2] % 4 == 0 and raw.shape[2] <= 2048
+                    and takes_quantised_frames(self.model, raw))
 
     def _model_input(self, raw, num_frames, kw):
         """-> (model input, model keywords): train.py:262-264's normalised fp32 frames, or the uint8 batch itself (_quantised_frames)."""
