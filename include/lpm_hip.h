@@ -989,6 +989,27 @@ int lpm_yt8m_locate(const void* buf, int64_t nbytes, const int64_t* rec_offset, 
  * inside [0, nbytes) gives zeros, never a read outside the allocation. */
 int lpm_gather_frames(const void* buf, int64_t nbytes, int64_t capacity, const int64_t* frame_offset, const int32_t* num_frames, int B,
                       int max_frames, const int* feature_sizes, int num_features, void* out, lpm_stream_t stream);
+/* The same two steps for the video-level files (readers.YT8MAggregatedFeatureReader.device_batches): tf.train.Example records whose
+ * selected features are float lists of exactly feature_sizes[f] values.
+ *
+ * Locating (host): lpm_yt8m_locate's inputs, walked with the semantics of readers.parse_example / prepare_serialized_examples.  Per
+ * record and feature: feature_offset int64 / feature_stride int32 [n, num_features], the byte offset from buf of the first value and the
+ * distance between values -- stride 4, one packed run of 4 * size bytes and nothing else (offset: the run); stride 5, nothing but size
+ * one-byte-tagged fixed32 values (offset: the first value's payload); stride 0 with offset -1, any other encoding the Python parser
+ * accepts (several runs, a mix, unknown fields, non-minimal tags): not an error, the caller repacks that feature.  Labels, ids,
+ * *labels_needed, *failed_record and the status codes as lpm_yt8m_locate; LPM_ERR_DATA also for a selected feature that is missing, is no
+ * float list or has another number of values.
+ *
+ * Gathering (device): buf as for lpm_gather_frames + the two tables (device) -> out fp32 [B, sum(feature_sizes)] (16-byte aligned):
+ * value i of feature f of example b is the four bytes at feature_offset[b, f] + feature_stride[b, f] * i, copied bit for bit.  One
+ * launch; aligned loads only.  feature_sizes (a HOST array): any positive sizes.  A feature whose offset is negative, whose stride is
+ * not 4 or 5 or whose last value would end beyond nbytes is written as zero bits; no load starts outside [0, capacity). */
+int lpm_yt8m_locate_examples(const void* buf, int64_t nbytes, const int64_t* rec_offset, const int64_t* rec_length, int num_records,
+                             int64_t record_base, const char* const* feature_names, const int* feature_sizes, int num_features,
+                             int num_classes, int64_t* feature_offset, int32_t* feature_stride, int32_t* label_start, int32_t* label_index,
+                             int64_t label_capacity, int64_t* labels_needed, int64_t* id_offset, int32_t* id_length, int* failed_record);
+int lpm_gather_examples(const void* buf, int64_t nbytes, int64_t capacity, const int64_t* feature_offset, const int32_t* feature_stride,
+                        int B, const int* feature_sizes, int num_features, void* out, lpm_stream_t stream);
 /* CSR label lists (device; duplicates and empty lists are legal) -> out uint8 0 / 1 [B, num_classes], zeros included. */
 int lpm_labels_dense(const int32_t* label_start, const int32_t* label_index, int num_labels, int B, int num_classes, void* out,
                      lpm_stream_t stream);

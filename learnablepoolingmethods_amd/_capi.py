@@ -201,6 +201,8 @@ SIGNATURES = {
     "lpm_yt8m_locate": (_i, [_f, _l, _f, _f, _i, _l, _f, _f, _i, _i, _i, _f, _f, _f, _f, _l, _f, _f, _f, _f]),
     "lpm_gather_frames": (_i, [_f, _l, _l, _f, _f, _i, _i, _f, _i, _f, _f]),
     "lpm_labels_dense": (_i, [_f, _f, _i, _i, _i, _f, _f]),
+    "lpm_yt8m_locate_examples": (_i, [_f, _l, _f, _f, _i, _l, _f, _f, _i, _i, _f, _f, _f, _f, _l, _f, _f, _f, _f]),
+    "lpm_gather_examples": (_i, [_f, _l, _l, _f, _f, _i, _f, _i, _f, _f]),
     "lpm_histogram_segments_workspace_bytes": (_s, [_i, _l]),
     "lpm_histogram_segments": (_i, [_f, _l, _f, _f, _i, _l, _f, _i, _f, _f, _f, _f, _s, _f]),
     "lpm_histogram_frames_q8": (_i, [_f, _f, _i, _i, _i, _f, _f]),

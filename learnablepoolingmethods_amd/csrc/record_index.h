@@ -571,14 +571,14 @@ inline int locate_one(const uint8_t* buf, Span rec, const Selection& sel, int32_
     return LPM_OK;
 }
 
-// All records of a buffer (frame_records' output).  Per clip: num_frames (capped at max_frames), frame_offset [clip, feature, max_frames]
-// (byte offsets from buf of the frame payloads; -1 at and beyond num_frames), the labels in [0, num_classes) as a CSR list
-// (label_start [num_records + 1], label_index [label_capacity]) and the video id's offset / length (0 / 0 without one).  LPM_ERR_DATA:
-// a malformed example, *failed_record its index; LPM_ERR_WORKSPACE: label_capacity is too small, *labels_needed says how many there are.
-inline int locate_records(const uint8_t* buf, int64_t nbytes, const int64_t* rec_offset, const int64_t* rec_length, int num_records,
-                          int64_t record_base, const Selection& sel, int32_t* num_frames, int64_t* frame_offset, int32_t* label_start,
-                          int32_t* label_index, int64_t label_capacity, int64_t* labels_needed, int64_t* id_offset, int32_t* id_length,
-                          int* failed_record, const Err& err) {
+// The loop over the records of a buffer (frame_records' output) that both locators share: bounds of every record, the CSR label list
+// (label_start [num_records + 1], label_index [label_capacity]) and the error's record index.  one(i, rec, sink, why, why_n) locates
+// record i.  LPM_ERR_DATA: a malformed example, *failed_record its index; LPM_ERR_WORKSPACE: label_capacity is too small,
+// *labels_needed says how many there are.
+template <class One>
+inline int locate_each(const uint8_t* buf, int64_t nbytes, const int64_t* rec_offset, const int64_t* rec_length, int num_records,
+                       int64_t record_base, int32_t* label_start, int32_t* label_index, int64_t label_capacity, int64_t* labels_needed,
+                       int* failed_record, const Err& err, One one) {
     LabelSink sink{label_index, label_capacity, 0};
     *failed_record = -1;
     for (int i = 0; i < num_records; ++i) {
@@ -591,8 +591,7 @@ inline int locate_records(const uint8_t* buf, int64_t nbytes, const int64_t* rec
         label_start[i] = (int32_t)sink.n;
         char why[200] = "";
         const Span rec{buf + rec_offset[i], buf + rec_offset[i] + rec_length[i]};
-        const int st = locate_one(buf, rec, sel, num_frames + i, frame_offset + (int64_t)i * sel.num_features * sel.max_frames, sink,
-                                  id_offset + i, id_length + i, why, sizeof why);
+        const int st = one(i, rec, sink, why, sizeof why);
         if (st != LPM_OK) {
             err.set("record %lld: %s", (long long)(record_base + i), why);
             *failed_record = i;
@@ -611,6 +610,267 @@ inline int locate_records(const uint8_t* buf, int64_t nbytes, const int64_t* rec
         return LPM_ERR_WORKSPACE;
     }
     return LPM_OK;
+}
+
+// All SequenceExample records of a buffer.  Per clip: num_frames (capped at max_frames), frame_offset [clip, feature, max_frames]
+// (byte offsets from buf of the frame payloads; -1 at and beyond num_frames), the labels in [0, num_classes) as a CSR list and the
+// video id's offset / length (0 / 0 without one).
+inline int locate_records(const uint8_t* buf, int64_t nbytes, const int64_t* rec_offset, const int64_t* rec_length, int num_records,
+                          int64_t record_base, const Selection& sel, int32_t* num_frames, int64_t* frame_offset, int32_t* label_start,
+                          int32_t* label_index, int64_t label_capacity, int64_t* labels_needed, int64_t* id_offset, int32_t* id_length,
+                          int* failed_record, const Err& err) {
+    return locate_each(buf, nbytes, rec_offset, rec_length, num_records, record_base, label_start, label_index, label_capacity, labels_needed,
+                       failed_record, err, [&](int i, Span rec, LabelSink& sink, char* why, size_t why_n) {
+                           return locate_one(buf, rec, sel, num_frames + i, frame_offset + (int64_t)i * sel.num_features * sel.max_frames,
+                                             sink, id_offset + i, id_length + i, why, why_n);
+                       });
+}
+
+// ---- tf.train.Example records (readers.YT8MAggregatedFeatureReader: parse_example + prepare_serialized_examples) ------------------------
+// Example { Features features = 1 },  Features { map<string, Feature> feature = 1 }.  The walk is the one above with these additions,
+// again the Python parser's way, which looks at EVERY entry of the map whether selected or not:
+//   * every key, and the id, has to be UTF-8 as Python's strict decoder takes it (no overlong forms, no surrogates, nothing beyond
+//     U+10FFFF); a varint where a message is expected stands for that many zero bytes, which is a message only when their number is even;
+//   * every value is parsed: an unselected feature with a malformed list refuses the record as well;
+//   * a FloatList is the concatenation of all its fields numbered 1, whatever their wire type: a length-delimited run, a fixed32, a
+//     fixed64 (two floats), a varint (that many zero bytes); every one has to be a whole number of floats;
+//   * a selected feature has to be a float list of exactly feature_size values (tf.FixedLenFeature) in the LAST entry of its key.
+// A float list that passes is reported by the stride between its values: 4, one packed run and nothing else, as every writer emits it
+// (offset: the run); 5, nothing but one-byte-tagged fixed32 values (offset: the first one's payload); 0, anything else that is valid
+// (several runs, a mix, unknown fields, non-minimal tags; offset -1: the caller repacks that feature with the Python parser).
+
+// Python's bytes.decode("utf-8")
+inline bool utf8_ok(Span s) {
+    const uint8_t* p = s.p;
+    while (p < s.e) {
+        const uint8_t c = *p++;
+        if (c < 0x80) continue;
+        int more;
+        uint8_t lo = 0x80, hi = 0xBF;                   // the range of the first continuation byte
+        if (c >= 0xC2 && c <= 0xDF) more = 1;
+        else if (c >= 0xE0 && c <= 0xEF) more = 2, lo = c == 0xE0 ? 0xA0 : 0x80, hi = c == 0xED ? 0x9F : 0xBF;
+        else if (c >= 0xF0 && c <= 0xF4) more = 3, lo = c == 0xF0 ? 0x90 : 0x80, hi = c == 0xF4 ? 0x8F : 0xBF;
+        else return false;
+        for (int i = 0; i < more; ++i, lo = 0x80, hi = 0xBF)
+            if (p >= s.e || *p < lo || *p++ > hi) return false;
+    }
+    return true;
+}
+
+// a varint in place of a message: Python walks that many zero bytes, pairs of (field 0, varint 0)
+inline bool message_ok(const Field& f) { return f.wt != 0 || (!f.val_big && !(f.val & 1)); }
+
+// FloatList: the number of values, or -1 where the Python walk raises
+inline int64_t float_list(Span s) {
+    const uint8_t* p = s.p;
+    Field f;
+    int64_t n = 0;
+    for (;;) {
+        const int r = next_field(p, s.e, f);
+        if (r == FIELD_BAD) return -1;
+        if (r == FIELD_END) return n;
+        if (!f.is(1)) continue;
+        u128 bytes = f.wt == 0 ? f.val : (u128)f.s.size();
+        if ((f.wt == 0 && f.val_big) || (bytes & 3) || bytes > ((u128)1 << 40)) return -1;
+        n += (int64_t)(bytes >> 2);
+    }
+}
+
+// what _parse_feature does with a value nobody selected: true where it returns
+inline bool feature_parses(Span val) {
+    int kind;
+    Span list;
+    if (!parse_feature(val, kind, list)) return false;
+    if (kind == KIND_BYTES) {
+        const uint8_t* p = list.p;                       // (bytes_list refuses a first value that does not lie in the file: not an error here)
+        Field f;
+        for (;;) {
+            const int r = next_field(p, list.e, f);
+            if (r != FIELD_OK) return r == FIELD_END;
+        }
+    }
+    if (kind == KIND_FLOAT) return float_list(list) >= 0;
+    if (kind == KIND_INT64) {
+        LabelSink none{nullptr, 0, 0};
+        return collect_labels(kind, list, 0, none);
+    }
+    return true;
+}
+
+// The bytes of a Feature that holds one packed float run, as every protobuf encoder writes them (minimal varints):
+//   12 len(FloatList)  0A 4 * size   -- Feature.float_list = 2 { FloatList.value = 1, packed }
+inline size_t canonical_float_header(int size, uint8_t* out) {
+    uint8_t l0[10], l1[10];
+    const size_t n0 = put_varint(4 * (uint64_t)size, l0);
+    const size_t n1 = put_varint(1 + n0 + 4 * (uint64_t)size, l1);
+    size_t n = 0;
+    out[n++] = 0x12;
+    memcpy(out + n, l1, n1), n += n1;
+    out[n++] = 0x0A;
+    memcpy(out + n, l0, n0), n += n0;
+    return n;
+}
+
+enum { FEAT_MISSING = 0, FEAT_NO_VALUE, FEAT_NOT_FLOAT, FEAT_FLOAT };
+
+// One Example.  feature_offset / feature_stride: [num_features] for this record.
+inline int locate_example(const uint8_t* buf, Span rec, const Selection& sel, const uint8_t (*canon)[CANON_MAX], const size_t* canon_n,
+                          int64_t* feature_offset, int32_t* feature_stride, LabelSink& labels, int64_t* id_offset, int32_t* id_length,
+                          char* why, size_t why_n) {
+    const Err err{why, why_n};
+    bool id_present = false, id_ok = false;
+    Span id = Span{rec.p, rec.p};
+    const int64_t labels_mark = labels.n;
+    int state[MAX_FEATURES];
+    int64_t count[MAX_FEATURES];
+    for (int j = 0; j < sel.num_features; ++j) state[j] = FEAT_MISSING, count[j] = 0;
+
+    const uint8_t* p = rec.p;
+    Field top;
+    for (;;) {
+        const int r = next_field(p, rec.e, top);
+        if (r == FIELD_BAD) {
+            err.set("malformed Example");
+            return LPM_ERR_DATA;
+        }
+        if (r == FIELD_END) break;
+        if (!top.is(1)) continue;
+        // features: a second field replaces the first (which has been walked, as in Python)
+        id_present = id_ok = false;
+        labels.n = labels_mark;
+        for (int j = 0; j < sel.num_features; ++j) state[j] = FEAT_MISSING;
+        if (!message_ok(top)) {
+            err.set("malformed features");
+            return LPM_ERR_DATA;
+        }
+        const uint8_t* q = top.s.p;
+        Field ent;
+        for (;;) {
+            const int r2 = next_field(q, top.s.e, ent);
+            if (r2 == FIELD_BAD) {
+                err.set("malformed features");
+                return LPM_ERR_DATA;
+            }
+            if (r2 == FIELD_END) break;
+            if (!ent.is(1)) continue;
+            Span key, val;
+            bool has_key, has_val;
+            if (!message_ok(ent) || !map_entry(ent.s, key, has_key, val, has_val) || (has_key && !utf8_ok(key))) {
+                err.set("malformed features entry");
+                return LPM_ERR_DATA;
+            }
+            int j = -1;
+            if (has_key)
+                for (int k = 0; k < sel.num_features; ++k)
+                    if (key_is(key, sel.names[k])) j = k;
+            if (j >= 0) {
+                // (a name selected twice: the later column only -- the reader refuses such a selection before it gets here)
+                if (!has_val) {
+                    state[j] = FEAT_NO_VALUE;
+                    continue;
+                }
+                // the feature every writer emits, byte for byte: one packed run of the feature's size and nothing else
+                if (val.size() == canon_n[j] + 4 * (size_t)sel.sizes[j] && memcmp(val.p, canon[j], canon_n[j]) == 0) {
+                    state[j] = FEAT_FLOAT, count[j] = sel.sizes[j];
+                    feature_offset[j] = (int64_t)(val.p + canon_n[j] - buf), feature_stride[j] = 4;
+                    continue;
+                }
+                int kind;
+                Span list;
+                if (!parse_feature(val, kind, list)) {
+                    err.set("feature '%s' has no readable value", sel.names[j]);
+                    return LPM_ERR_DATA;
+                }
+                if (kind != KIND_FLOAT) {
+                    if (!feature_parses(val)) {
+                        err.set("feature '%s' has no readable value", sel.names[j]);
+                        return LPM_ERR_DATA;
+                    }
+                    state[j] = FEAT_NOT_FLOAT;
+                    continue;
+                }
+                const int64_t n = float_list(list);
+                if (n < 0) {
+                    err.set("feature '%s' is not a list of whole floats", sel.names[j]);
+                    return LPM_ERR_DATA;
+                }
+                state[j] = FEAT_FLOAT, count[j] = n;
+                feature_offset[j] = -1, feature_stride[j] = 0;
+                if (n == sel.sizes[j] && list.size() == 5 * (size_t)n) {
+                    bool tagged = true;
+                    for (int64_t i = 0; i < n && tagged; ++i) tagged = list.p[5 * i] == 0x0D;       // field 1, fixed32
+                    if (tagged) feature_offset[j] = (int64_t)(list.p + 1 - buf), feature_stride[j] = 5;
+                }
+                continue;
+            }
+            const bool is_id = has_key && key_is(key, "id"), is_labels = has_key && key_is(key, "labels");
+            if (!is_id && !is_labels) {
+                if (has_val && !feature_parses(val)) {
+                    err.set("malformed feature");
+                    return LPM_ERR_DATA;
+                }
+                continue;
+            }
+            int kind = KIND_EMPTY;
+            Span list = Span{rec.p, rec.p};
+            if (!has_val || !parse_feature(val, kind, list)) {
+                err.set("feature '%s' has no readable value", is_id ? "id" : "labels");
+                return LPM_ERR_DATA;
+            }
+            if (is_id) {
+                id_present = true;
+                id_ok = kind == KIND_BYTES && bytes_list(list, id) > 0 && utf8_ok(id);
+                if (kind != KIND_BYTES && !feature_parses(val)) {
+                    err.set("feature 'id' has no readable value");
+                    return LPM_ERR_DATA;
+                }
+            } else {
+                labels.n = labels_mark;
+                if (!collect_labels(kind, list, sel.num_classes, labels)) {
+                    err.set("feature 'labels' is not a list of class indices");
+                    return LPM_ERR_DATA;
+                }
+            }
+        }
+    }
+    if (id_present && !id_ok) {
+        err.set("feature 'id' is not a UTF-8 bytes value");
+        return LPM_ERR_DATA;
+    }
+    for (int j = 0; j < sel.num_features; ++j) {
+        if (state[j] == FEAT_MISSING || state[j] == FEAT_NO_VALUE) {
+            err.set("feature '%s' is missing", sel.names[j]);
+            return LPM_ERR_DATA;
+        }
+        if (state[j] == FEAT_NOT_FLOAT) {
+            err.set("feature '%s' is not a float list", sel.names[j]);
+            return LPM_ERR_DATA;
+        }
+        if (count[j] != sel.sizes[j]) {
+            err.set("feature '%s' has %lld values, expected %d", sel.names[j], (long long)count[j], sel.sizes[j]);
+            return LPM_ERR_DATA;
+        }
+    }
+    *id_offset = id_present ? (int64_t)(id.p - buf) : 0;
+    *id_length = id_present ? (int32_t)id.size() : 0;
+    return LPM_OK;
+}
+
+// All Example records of a buffer: locate_records' arguments and outputs, with feature_offset int64 / feature_stride int32
+// [num_records, num_features] (see above) in place of the frame tables; sel.max_frames is not looked at.
+inline int locate_example_records(const uint8_t* buf, int64_t nbytes, const int64_t* rec_offset, const int64_t* rec_length, int num_records,
+                                  int64_t record_base, const Selection& sel, int64_t* feature_offset, int32_t* feature_stride,
+                                  int32_t* label_start, int32_t* label_index, int64_t label_capacity, int64_t* labels_needed,
+                                  int64_t* id_offset, int32_t* id_length, int* failed_record, const Err& err) {
+    uint8_t canon[MAX_FEATURES][CANON_MAX];
+    size_t canon_n[MAX_FEATURES];
+    for (int j = 0; j < sel.num_features; ++j) canon_n[j] = canonical_float_header(sel.sizes[j], canon[j]);
+    return locate_each(buf, nbytes, rec_offset, rec_length, num_records, record_base, label_start, label_index, label_capacity, labels_needed,
+                       failed_record, err, [&](int i, Span rec, LabelSink& sink, char* why, size_t why_n) {
+                           return locate_example(buf, rec, sel, canon, canon_n, feature_offset + (int64_t)i * sel.num_features,
+                                                 feature_stride + (int64_t)i * sel.num_features, sink, id_offset + i, id_length + i, why,
+                                                 why_n);
+                       });
 }
 
 }  // namespace lpm_index

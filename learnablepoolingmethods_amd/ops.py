@@ -562,7 +562,7 @@ def histogram_frames_q8(q, num_frames) -> torch.Tensor:
     return counts
 
 
-GATHER_MAX_FEATURES = 8      # lpm_gather_frames' limit
+GATHER_MAX_FEATURES = 8      # lpm_gather_frames' / lpm_gather_examples' limit
 
 
 def gather_frames(raw, nbytes, frame_offset, num_frames, feature_sizes, max_frames):
@@ -586,6 +586,32 @@ def gather_frames(raw, nbytes, frame_offset, num_frames, feature_sizes, max_fram
         arr = (C.c_int * len(sizes))(*sizes)
         lib.check(lib._lpm_gather_frames(ptr(raw), nbytes, raw.numel(), ptr(frame_offset), ptr(num_frames), B, T,
                                          C.cast(arr, C.c_void_p), len(sizes), ptr(out), stream_ptr()), "lpm_gather_frames")
+    return out
+
+
+def gather_examples(raw, nbytes, feature_offset, feature_stride, feature_sizes):
+    """The video-level reader's gather (lpm_gather_examples): ``raw`` as for gather_frames, ``feature_offset`` int64 and
+    ``feature_stride`` int32 [B, len(feature_sizes)] (readers.locate_examples) -> float32 [B, sum(feature_sizes)]: value i of feature f
+    of example b is the four bytes at offset[b, f] + stride[b, f] * i, bit for bit.  Any positive feature sizes.  A feature whose offset
+    is negative, whose stride is not 4 or 5 or whose last value would end beyond ``nbytes`` comes out as zeros (LpmError for wrong
+    arguments; no fallback)."""
+    sizes = [int(s) for s in feature_sizes]
+    for name, t, dt in (("raw", raw, torch.uint8), ("feature_offset", feature_offset, torch.int64), ("feature_stride", feature_stride, torch.int32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise LpmError(f"gather_examples: {name} must be a contiguous {dt} tensor on the GPU (there is no CPU fallback)")
+    if raw.dim() != 1 or feature_offset.dim() != 2 or feature_offset.shape[1] != len(sizes) or feature_stride.shape != feature_offset.shape:
+        raise LpmError(f"gather_examples: expected raw [bytes], feature_offset and feature_stride [batch, {len(sizes)}]")
+    if not (feature_offset.device == raw.device == feature_stride.device):
+        raise LpmError("gather_examples: all tensors must be on the same device")
+    if not 1 <= len(sizes) <= GATHER_MAX_FEATURES or any(s < 1 for s in sizes):
+        raise LpmError(f"gather_examples: 1 to {GATHER_MAX_FEATURES} features of positive sizes (got {sizes})")
+    B, nbytes = int(feature_offset.shape[0]), int(nbytes)
+    lib = _capi.load()
+    out = torch.empty((B, sum(sizes)), dtype=torch.float32, device=raw.device)
+    if B:
+        arr = (C.c_int * len(sizes))(*sizes)
+        lib.check(lib._lpm_gather_examples(ptr(raw), nbytes, raw.numel(), ptr(feature_offset), ptr(feature_stride), B,
+                                           C.cast(arr, C.c_void_p), len(sizes), ptr(out), stream_ptr()), "lpm_gather_examples")
     return out
 
 

@@ -18,7 +18,7 @@ import torch
 from . import FLAGS, ops
 from . import variables as vs
 from ._capi import LpmError
-from .train import normalize_input
+from .train import check_input_rank, normalize_input
 
 # models whose frame-prep op reads uint8 frames in eval mode (ops.frame_sample_bn / frame_sample_bn_split)
 FUSED_Q8_MODELS = ("NetVladV1", "NetVladV2")
@@ -108,8 +108,12 @@ class Predictor:
 
     # -- inference ---------------------------------------------------------------------------------------------------------------
     def _check_inputs(self, frames, num_frames):
-        if not torch.is_tensor(frames) or frames.dim() != 3 or frames.dtype not in (torch.uint8, torch.float32):
-            raise LpmError("Predictor: frames must be a uint8 (quantised) or float32 [batch, max_frames, feature] tensor")
+        ok = torch.is_tensor(frames) and ((frames.dim() == 3 and frames.dtype in (torch.uint8, torch.float32))
+                                          or (frames.dim() == 2 and frames.dtype == torch.float32))
+        if not ok:
+            raise LpmError("Predictor: the input must be frames, a uint8 (quantised) or float32 [batch, max_frames, feature] tensor, or "
+                           "video-level features, a float32 [batch, feature] tensor")
+        check_input_rank(self.model, frames)
         if not torch.is_tensor(num_frames) or num_frames.dim() != 1 or num_frames.shape[0] != frames.shape[0]:
             raise LpmError("Predictor: num_frames must be a [batch] tensor")
         if num_frames.dtype.is_floating_point or num_frames.dtype == torch.bool:
@@ -125,7 +129,8 @@ class Predictor:
     # tensors by version counter, which inference tensors do not carry)
     @torch.no_grad()
     def predict(self, frames, num_frames) -> torch.Tensor:
-        """-> predictions [B, vocab_size]: the eval-mode forward (is_training=False, moving statistics, no operand scales)."""
+        """-> predictions [B, vocab_size]: the eval-mode forward (is_training=False, moving statistics, no operand scales).  ``frames``:
+        [B, max_frames, F] frames, or the video-level reader's float32 [B, F] features in front of a model of video_level_models."""
         self._check_inputs(frames, num_frames)
         frames = frames.to(self.device)
         nf = num_frames.to(self.device)

@@ -13,7 +13,11 @@ batches as tensors on the GPU: a thread reads the records into pinned memory, th
 ``locate_records``: lpm_tfrecord_frame, lpm_yt8m_locate) looks at their header bytes only, the record bytes go to the device as they
 are and ``ops.gather_frames`` / ``ops.labels_dense`` put frames and labels in place.
 
-There are no TFRecord fixtures in the reference; ``write_tfrecord`` / ``make_sequence_example`` produce files in the same
+``YT8MAggregatedFeatureReader`` is the reference's other input mode, and its default (readers.py:68-131): video-level files of
+tf.train.Example records whose features are float lists (``mean_rgb``, ``mean_audio``).  The same two routes: ``batches()`` in Python,
+``device_batches()`` through ``locate_examples`` (lpm_yt8m_locate_examples) and ``ops.gather_examples``.
+
+There are no TFRecord fixtures in the reference; ``write_tfrecord`` / ``make_sequence_example`` / ``make_example`` produce files in the same
 format for the round-trip tests and for synthetic data."""
 from __future__ import annotations
 
@@ -124,8 +128,9 @@ def _fields(buf: bytes) -> Iterator[Tuple[int, int, object]]:
         yield num, wt, v
 
 
-def _parse_feature(buf) -> Tuple[str, list]:
-    """tf.train.Feature: oneof bytes_list = 1 / float_list = 2 / int64_list = 3."""
+def _parse_feature(buf, float_array: bool = False) -> Tuple[str, list]:
+    """tf.train.Feature: oneof bytes_list = 1 / float_list = 2 / int64_list = 3.  ``float_array``: a float list comes back as a float32
+    array holding the file's bits (a Python float is a double: the round trip would quieten a signalling NaN)."""
     for num, _, v in _fields(bytes(buf)):
         if num == 1:
             return "bytes", [bytes(x) for n2, _, x in _fields(bytes(v)) if n2 == 1]
@@ -143,11 +148,10 @@ def _parse_feature(buf) -> Tuple[str, list]:
                         vals.append(val)
             return "int64", [val - (1 << 64) if val >= (1 << 63) else val for val in vals]
         if num == 2:
-            vals = []
-            for n2, wt, x in _fields(bytes(v)):
-                if n2 == 1:
-                    vals.extend(np.frombuffer(bytes(x), dtype="<f4").tolist())
-            return "float", vals
+            runs = [np.frombuffer(bytes(x), dtype="<f4") for n2, wt, x in _fields(bytes(v)) if n2 == 1]
+            if float_array:
+                return "float", np.concatenate(runs).astype(np.float32, copy=False) if runs else np.zeros(0, np.float32)
+            return "float", [x for run in runs for x in run.tolist()]
     return "empty", []
 
 
@@ -175,6 +179,16 @@ def parse_sequence_example(serialized: bytes):
         elif num == 2:
             lists = _parse_map(v, lambda fl: [_parse_feature(x) for n2, _, x in _fields(bytes(fl)) if n2 == 1])
     return context, lists
+
+
+def parse_example(serialized: bytes) -> Dict[str, Tuple[str, object]]:
+    """tf.train.Example -> {name: (kind, values)}; float lists as float32 arrays with the file's bits.  (Example.features = 1,
+    Features.feature = 1, a map: a later ``features`` field replaces an earlier one, the last entry of a name counts.)"""
+    features = {}
+    for num, _, v in _fields(serialized):
+        if num == 1:
+            features = _parse_map(v, lambda x: _parse_feature(x, float_array=True))
+    return features
 
 
 # ---- encoder (tests, synthetic data) ----------------------------------------------------------------------------------
@@ -211,6 +225,18 @@ def make_sequence_example(video_id: str, labels: Sequence[int], features: Dict[s
         flist = b"".join(_enc_ld(1, _enc_bytes_feature([row.tobytes()])) for row in mat)
         fl += _enc_ld(1, _enc_ld(1, name.encode("utf-8")) + _enc_ld(2, flist))
     return _enc_ld(1, ctx) + _enc_ld(2, fl)
+
+
+def make_example(video_id: str, labels: Sequence[int], features: Dict[str, np.ndarray], packed: bool = True) -> bytes:
+    """features: {name: float32 [feature_size]} -> serialized tf.train.Example (the video-level files' records).  ``packed``: one
+    length-delimited run per float list, as every writer emits it; ``packed=False``: one tagged fixed32 per value."""
+    out = _enc_ld(1, _enc_ld(1, b"id") + _enc_ld(2, _enc_bytes_feature([video_id.encode("utf-8")])))
+    out += _enc_ld(1, _enc_ld(1, b"labels") + _enc_ld(2, _enc_int64_feature(labels)))
+    for name, vec in features.items():
+        raw = np.ascontiguousarray(vec, dtype="<f4").reshape(-1).tobytes()
+        flist = _enc_ld(1, raw) if packed else b"".join(b"\x0d" + raw[i:i + 4] for i in range(0, len(raw), 4))
+        out += _enc_ld(1, _enc_ld(1, name.encode("utf-8")) + _enc_ld(2, _enc_ld(2, flist)))
+    return _enc_ld(1, out)
 
 
 # ---- the native indexer (liblpm_hip.so, host code: no GPU needed; ctypes releases the GIL during the calls) --------------------------
@@ -324,6 +350,50 @@ def locate_records(buf, rec_offset, rec_length, feature_names=("rgb", "audio"), 
         return idx
 
 
+class ExampleIndex(NamedTuple):
+    """locate_examples' per-record tables (numpy; offsets are bytes from the start of the buffer the records lie in)."""
+    feature_offset: np.ndarray  # int64 [n, features]: the first value's four bytes; -1 where the stride is 0
+    feature_stride: np.ndarray  # int32 [n, features]: 4 (one packed run), 5 (tagged fixed32 values back to back), 0 (anything else: repack)
+    label_start: np.ndarray     # int32 [n + 1]
+    label_index: np.ndarray     # int32 [>= label_start[n]]
+    id_offset: np.ndarray       # int64 [n]
+    id_length: np.ndarray       # int32 [n] (0 without an id)
+
+
+def _locate_examples_into(lib, a, rec_offset, rec_length, names_arr, sizes_arr, num_features, num_classes, record_base, idx: ExampleIndex):
+    """One lpm_yt8m_locate_examples call into caller-owned arrays -> (status, labels needed, failed record)."""
+    needed, failed = C.c_int64(0), C.c_int(-1)
+    st = lib._lpm_yt8m_locate_examples(_vp(a), a.size, _vp(rec_offset), _vp(rec_length), len(rec_offset), record_base,
+                                       C.cast(names_arr, C.c_void_p), C.cast(sizes_arr, C.c_void_p), num_features, num_classes,
+                                       _vp(idx.feature_offset), _vp(idx.feature_stride), _vp(idx.label_start), _vp(idx.label_index),
+                                       idx.label_index.size, C.byref(needed), _vp(idx.id_offset), _vp(idx.id_length), C.byref(failed))
+    return st, needed.value, failed.value
+
+
+def locate_examples(buf, rec_offset, rec_length, feature_names=("mean_rgb", "mean_audio"), feature_sizes=(1024, 128), num_classes=3862,
+                    record_base: int = 0) -> ExampleIndex:
+    """Where the float lists, labels and ids of the tf.train.Example records of ``buf`` lie (lpm_yt8m_locate_examples): the header bytes
+    are walked with parse_example's semantics, the values are never touched.  ValueError for what
+    YT8MAggregatedFeatureReader.prepare_serialized_examples refuses, naming the record.  A list in an encoding that has no constant
+    stride comes back with stride 0 and offset -1: valid, and for the caller to repack."""
+    a = _as_bytes_array(buf)
+    ro, rl = np.ascontiguousarray(rec_offset, np.int64), np.ascontiguousarray(rec_length, np.int64)
+    n, nf = len(ro), len(feature_names)
+    names, sizes = _feature_arrays(feature_names, feature_sizes)
+    lib = _capi.load()
+    cap = 8 * n + 16
+    while True:
+        idx = ExampleIndex(np.full((n, nf), -1, np.int64), np.zeros((n, nf), np.int32), np.zeros(n + 1, np.int32), np.zeros(cap, np.int32),
+                           np.zeros(n, np.int64), np.zeros(n, np.int32))
+        st, needed, _ = _locate_examples_into(lib, a, ro, rl, names, sizes, nf, int(num_classes), record_base, idx)
+        if st == _capi.LPM_ERR_WORKSPACE and needed > cap:
+            cap = needed
+            continue
+        if st != 0:
+            _raise_native(lib, st, "lpm_yt8m_locate_examples")
+        return idx
+
+
 # ---- the reader ---------------------------------------------------------------------------------------------------------
 class BaseReader(object):
     """readers.py:59-66."""
@@ -332,70 +402,15 @@ class BaseReader(object):
         raise NotImplementedError()
 
 
-class YT8MFrameFeatureReader(BaseReader):
-    """readers.py:134-271.  Same constructor; records come from files instead of a TF filename queue."""
-
-    def __init__(self, num_classes=3862, feature_sizes=(1024, 128), feature_names=("rgb", "audio"), max_frames=300):
-        assert len(feature_names) == len(feature_sizes), \
-            "length of feature_names (={}) != length of feature_sizes (={})".format(len(feature_names), len(feature_sizes))
-        assert len(feature_names) > 0, "No feature selected: feature_names is empty!"
-        self.num_classes = num_classes
-        self.feature_sizes = list(feature_sizes)
-        self.feature_names = list(feature_names)
-        self.max_frames = max_frames
-
-    def prepare_serialized_examples(self, serialized_example: bytes, max_quantized_value=2, min_quantized_value=-2,
-                                    dequantize=False):
-        """-> (video_id, frames [max_frames, sum(feature_sizes)], labels bool [num_classes], num_frames).  frames is uint8
-        (quantised, zero beyond num_frames) or, with dequantize=True, the reference's float32 matrix (readers.py:176-193)."""
-        context, lists = parse_sequence_example(serialized_example)
-        video_id = context["id"][1][0].decode("utf-8") if "id" in context else ""
-        labels = np.zeros(self.num_classes, dtype=bool)
-        for v in context.get("labels", ("int64", []))[1]:
-            if 0 <= v < self.num_classes:                      # sparse_to_dense(validate_indices=False)
-                labels[v] = True
-        num_frames, mats = -1, []
-        for name, size in zip(self.feature_names, self.feature_sizes):
-            rows = [np.frombuffer(vals[0], dtype=np.uint8) for _, vals in lists[name]]
-            mat = np.stack(rows).reshape(-1, size) if rows else np.zeros((0, size), dtype=np.uint8)
-            n = min(mat.shape[0], self.max_frames)
-            if num_frames == -1:
-                num_frames = n
-            elif n != num_frames:
-                raise ValueError(f"{video_id}: feature '{name}' has {n} frames, expected {num_frames}")
-            mats.append(mat[:n])
-        q = np.zeros((self.max_frames, sum(self.feature_sizes)), dtype=np.uint8)
-        q[:num_frames] = np.concatenate(mats, axis=1)
-        if dequantize:
-            f = np.zeros(q.shape, dtype=np.float32)
-            f[:num_frames] = utils.Dequantize(q[:num_frames].astype(np.float32), max_quantized_value, min_quantized_value)
-            return video_id, f, labels, num_frames
-        return video_id, q, labels, num_frames
-
-    def batches(self, files: Sequence[str], batch_size: int, drop_remainder: bool = False, verify_crc: bool = False):
-        """Yields (ids, frames uint8 [B, max_frames, F], labels bool [B, V], num_frames int32 [B]) as torch tensors."""
-        ids: List[str] = []
-        q, y, nf = [], [], []
-
-        def flush():
-            out = (list(ids), torch.from_numpy(np.stack(q)), torch.from_numpy(np.stack(y)), torch.tensor(nf, dtype=torch.int32))
-            ids.clear(); q.clear(); y.clear(); nf.clear()
-            return out
-        for path in files:
-            for rec in read_tfrecord(path, verify_crc=verify_crc):
-                vid, frames, labels, n = self.prepare_serialized_examples(rec)
-                ids.append(vid); q.append(frames); y.append(labels); nf.append(n)
-                if len(ids) == batch_size:
-                    yield flush()
-        if ids and not drop_remainder:
-            yield flush()
+class _RecordFileReader(BaseReader):
+    """What the two YT8M readers share: ``batches()`` of a subclass, on the device and shuffled."""
 
     def device_batches(self, files: Sequence[str], batch_size: int, device="cuda", drop_remainder: bool = False, verify_crc: bool = False,
                        prefetch: int = 2, reader_threads: int = 1, stats: Optional[dict] = None):
-        """What ``batches()`` yields, as tensors on the GPU: (ids, frames uint8 cuda [B, max_frames, F], labels bool cuda [B, V],
-        num_frames int32 cuda [B]), bit for bit.  A background thread reads the records of one batch back to back into a pinned host
+        """What ``batches()`` yields, as tensors on the GPU: (ids, frames uint8 cuda [B, max_frames, F] -- the video-level reader: features
+        float32 cuda [B, F] --, labels bool cuda [B, V], num_frames int32 cuda [B]), bit for bit.  A background thread reads the records of one batch back to back into a pinned host
         slot, runs the native indexer over their header bytes, copies slot and tables to the device on a side stream and launches
-        ``ops.gather_frames`` / ``ops.labels_dense`` there; the consumer's current stream waits for that batch's event.  The tensors belong
+        ``ops.gather_frames`` (the video-level reader: ``ops.gather_examples``) / ``ops.labels_dense`` there; the consumer's current stream waits for that batch's event.  The tensors belong
         to the consumer.  ``prefetch``: finished batches that may wait for the consumer (the ring has prefetch + reader_threads pinned slots).
         ``reader_threads``: threads that read whole batches into their slots (1: the thread that walks the record headers itself).  ``stats``: a dict that receives the host
         seconds spent reading and indexing, bytes, batches, and (``stats["time_gather"] = True``) device events before the copies, between copies and kernels and after them.
@@ -406,8 +421,7 @@ class YT8MFrameFeatureReader(BaseReader):
             raise _capi.LpmError("device_batches needs an MI355X (cuda/hip device); batches() is the host route")
         if dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
-        if any(int(s) <= 0 or int(s) % 4 for s in self.feature_sizes) or len(self.feature_sizes) > 8:
-            raise _capi.LpmError(f"device_batches: at most 8 features whose sizes are positive multiples of 4 (got {self.feature_sizes})")
+        self._check_device_features()
         if int(batch_size) < 1 or int(prefetch) < 1 or int(reader_threads) < 1:
             raise ValueError("device_batches: batch_size, prefetch and reader_threads must be at least 1")
         _capi.load()
@@ -462,6 +476,137 @@ class YT8MFrameFeatureReader(BaseReader):
             yield from ShufflePool(src, batch_size, capacity=capacity, min_after_dequeue=min_after_dequeue, rng=rng)
         finally:
             src.close()
+
+
+class YT8MFrameFeatureReader(_RecordFileReader):
+    """readers.py:134-271.  Same constructor; records come from files instead of a TF filename queue."""
+
+    def __init__(self, num_classes=3862, feature_sizes=(1024, 128), feature_names=("rgb", "audio"), max_frames=300):
+        assert len(feature_names) == len(feature_sizes), \
+            "length of feature_names (={}) != length of feature_sizes (={})".format(len(feature_names), len(feature_sizes))
+        assert len(feature_names) > 0, "No feature selected: feature_names is empty!"
+        self.num_classes = num_classes
+        self.feature_sizes = list(feature_sizes)
+        self.feature_names = list(feature_names)
+        self.max_frames = max_frames
+
+    def _check_device_features(self):
+        if any(int(s) <= 0 or int(s) % 4 for s in self.feature_sizes) or len(self.feature_sizes) > 8:
+            raise _capi.LpmError(f"device_batches: at most 8 features whose sizes are positive multiples of 4 (got {self.feature_sizes})")
+
+    def prepare_serialized_examples(self, serialized_example: bytes, max_quantized_value=2, min_quantized_value=-2,
+                                    dequantize=False):
+        """-> (video_id, frames [max_frames, sum(feature_sizes)], labels bool [num_classes], num_frames).  frames is uint8
+        (quantised, zero beyond num_frames) or, with dequantize=True, the reference's float32 matrix (readers.py:176-193)."""
+        context, lists = parse_sequence_example(serialized_example)
+        video_id = context["id"][1][0].decode("utf-8") if "id" in context else ""
+        labels = np.zeros(self.num_classes, dtype=bool)
+        for v in context.get("labels", ("int64", []))[1]:
+            if 0 <= v < self.num_classes:                      # sparse_to_dense(validate_indices=False)
+                labels[v] = True
+        num_frames, mats = -1, []
+        for name, size in zip(self.feature_names, self.feature_sizes):
+            rows = [np.frombuffer(vals[0], dtype=np.uint8) for _, vals in lists[name]]
+            mat = np.stack(rows).reshape(-1, size) if rows else np.zeros((0, size), dtype=np.uint8)
+            n = min(mat.shape[0], self.max_frames)
+            if num_frames == -1:
+                num_frames = n
+            elif n != num_frames:
+                raise ValueError(f"{video_id}: feature '{name}' has {n} frames, expected {num_frames}")
+            mats.append(mat[:n])
+        q = np.zeros((self.max_frames, sum(self.feature_sizes)), dtype=np.uint8)
+        q[:num_frames] = np.concatenate(mats, axis=1)
+        if dequantize:
+            f = np.zeros(q.shape, dtype=np.float32)
+            f[:num_frames] = utils.Dequantize(q[:num_frames].astype(np.float32), max_quantized_value, min_quantized_value)
+            return video_id, f, labels, num_frames
+        return video_id, q, labels, num_frames
+
+    def batches(self, files: Sequence[str], batch_size: int, drop_remainder: bool = False, verify_crc: bool = False):
+        """Yields (ids, frames uint8 [B, max_frames, F], labels bool [B, V], num_frames int32 [B]) as torch tensors."""
+        ids: List[str] = []
+        q, y, nf = [], [], []
+
+        def flush():
+            out = (list(ids), torch.from_numpy(np.stack(q)), torch.from_numpy(np.stack(y)), torch.tensor(nf, dtype=torch.int32))
+            ids.clear(); q.clear(); y.clear(); nf.clear()
+            return out
+        for path in files:
+            for rec in read_tfrecord(path, verify_crc=verify_crc):
+                vid, frames, labels, n = self.prepare_serialized_examples(rec)
+                ids.append(vid); q.append(frames); y.append(labels); nf.append(n)
+                if len(ids) == batch_size:
+                    yield flush()
+        if ids and not drop_remainder:
+            yield flush()
+
+
+class YT8MAggregatedFeatureReader(_RecordFileReader):
+    """readers.py:68-131: the video-level files, one tf.train.Example of float lists per video.  Same constructor; records come from
+    files instead of a TF filename queue."""
+
+    def __init__(self, num_classes=3862, feature_sizes=(1024, 128), feature_names=("mean_rgb", "mean_audio")):
+        assert len(feature_names) == len(feature_sizes), \
+            "length of feature_names (={}) != length of feature_sizes (={})".format(len(feature_names), len(feature_sizes))
+        assert len(feature_names) > 0, "No feature selected: feature_names is empty!"
+        self.num_classes = num_classes
+        self.feature_sizes = list(feature_sizes)
+        self.feature_names = list(feature_names)
+
+    def _check_device_features(self):
+        if any(int(s) <= 0 for s in self.feature_sizes) or len(self.feature_sizes) > 8 or len(set(self.feature_names)) != len(self.feature_names):
+            raise _capi.LpmError(f"device_batches: at most 8 distinct features of positive sizes (got {self.feature_names}, {self.feature_sizes})")
+
+    def prepare_serialized_examples(self, serialized_example: bytes):
+        """-> (video_id, features float32 [sum(feature_sizes)], labels bool [num_classes], 1): ``tf.parse_example`` as
+        readers.py:104-131 configures it.  Every selected feature is a ``FixedLenFeature``: it has to be there, be a float list and hold
+        exactly its size in values (ValueError, naming the id and the feature); ``labels`` is a ``VarLenFeature``: missing means none.
+        As in YT8MFrameFeatureReader, and unlike a strict ``tf.sparse_to_dense``: label values outside [0, num_classes) are dropped,
+        and a record without an ``id`` has the id "".  The features keep the file's bits."""
+        feats = parse_example(serialized_example)
+        video_id = feats["id"][1][0].decode("utf-8") if "id" in feats else ""
+        labels = np.zeros(self.num_classes, dtype=bool)
+        for v in feats.get("labels", ("int64", []))[1]:
+            if 0 <= v < self.num_classes:
+                labels[v] = True
+        parts = []
+        for name, size in zip(self.feature_names, self.feature_sizes):
+            if feats.get(name) is None:
+                raise ValueError(f"{video_id}: feature '{name}' is missing")
+            kind, vals = feats[name]
+            if kind != "float":
+                raise ValueError(f"{video_id}: feature '{name}' is a {kind} list, not a float list")
+            if len(vals) != size:
+                raise ValueError(f"{video_id}: feature '{name}' has {len(vals)} values, expected {size}")
+            parts.append(vals)
+        return video_id, np.concatenate(parts), labels, 1
+
+    def batches(self, files: Sequence[str], batch_size: int, drop_remainder: bool = False, verify_crc: bool = False):
+        """Yields (ids, features float32 [B, F], labels bool [B, V], num_frames int32 [B] of ones -- the reference returns
+        ``tf.ones([batch])`` in that slot) as torch tensors."""
+        ids: List[str] = []
+        x, y = [], []
+
+        def flush():
+            out = (list(ids), torch.from_numpy(np.stack(x)), torch.from_numpy(np.stack(y)), torch.ones(len(ids), dtype=torch.int32))
+            ids.clear(); x.clear(); y.clear()
+            return out
+        for path in files:
+            records, i = read_tfrecord(path, verify_crc=verify_crc), -1
+            while True:
+                i += 1
+                try:                                            # (errors name the record, as device_batches' do)
+                    rec = next(records, None)
+                    if rec is None:
+                        break
+                    vid, features, labels, _ = self.prepare_serialized_examples(rec)
+                except (IOError, ValueError) as e:
+                    raise type(e)(f"{path}: record {i}: {str(e).replace(path + ': ', '', 1)}") from e
+                ids.append(vid); x.append(features); y.append(labels)
+                if len(ids) == batch_size:
+                    yield flush()
+        if ids and not drop_remainder:
+            yield flush()
 
 
 class ShufflePool:
@@ -578,10 +723,12 @@ class _Slot:
         self.np = self.t.numpy()
         self.mv = memoryview(self.np)
 
-    def reserve(self, nbytes: int):
-        """Room for nbytes (the slot is empty: nothing is kept)."""
+    def reserve(self, nbytes: int, keep: int = 0):
+        """Room for nbytes; the first ``keep`` bytes stay (0: the slot is empty)."""
         if nbytes > self.t.numel():
+            old = self.np
             self._alloc(max(nbytes, 2 * self.t.numel()))
+            self.np[:keep] = old[:keep]
 
     def reserve_meta(self, nbytes: int):
         if nbytes > self.meta.numel():
@@ -600,12 +747,14 @@ def _pread_exact(fd: int, mv, offset: int) -> int:
 
 
 class _DevicePipeline:
-    """The two threads behind YT8MFrameFeatureReader.device_batches: one reads the records of batch k + 1 into a
-    pinned slot while the other indexes batch k, enqueues its copies and kernels and hands it to the consumer."""
+    """The two threads behind the readers' device_batches (DESIGN.md sections 13, 22): one reads the records of batch k + 1 into a
+    pinned slot while the other indexes batch k, enqueues its copies and kernels and hands it to the consumer.  The read side does not
+    know what a record holds; ``_emit`` indexes and gathers frames (SequenceExample) or float lists (Example, ``self.examples``)."""
 
     def __init__(self, reader, files, batch_size, dev, drop_remainder, verify_crc, prefetch, reader_threads, stats):
         self.reader, self.files, self.B, self.dev = reader, files, batch_size, dev
         self.drop_remainder, self.verify_crc, self.nthreads = drop_remainder, verify_crc, reader_threads
+        self.examples = isinstance(reader, YT8MAggregatedFeatureReader)
         self.stats = stats if stats is not None else {}
         self.lock = threading.Lock()
         for k in ("walk_s", "read_s", "index_s", "issue_s", "bytes", "batches", "clips"):
@@ -779,7 +928,8 @@ class _DevicePipeline:
         """Index the slot's records, send slot and tables to the device, gather; False when the consumer has gone."""
         from . import ops
         r, lib = self.reader, _capi.load()
-        n, nfeat, T = len(src), len(r.feature_names), r.max_frames
+        n, nfeat = len(src), len(r.feature_names)
+        T = 1 if self.examples else r.max_frames
         t0 = time.perf_counter()
         buf = slot.np[:nbytes]
         ro, rl = np.empty(n, np.int64), np.empty(n, np.int64)
@@ -792,23 +942,35 @@ class _DevicePipeline:
             raise IOError(f"{src[0][0]}: the slot's framing does not match the records read ({nrec.value} of {n})")
         names, sizes = _feature_arrays(r.feature_names, r.feature_sizes)
         id_off, id_len = np.empty(n, np.int64), np.empty(n, np.int32)
-        n_off = 8 * n * nfeat * T                               # the tables, in one pinned block: offsets | label_start | num_frames | labels
-        n_fixed = n_off + 4 * (n + 1) + 4 * n
+        # the tables, in one pinned block: offsets (examples: offsets int64 | strides int32) | label_start | num_frames | labels
+        n_off = 8 * n * nfeat * T
+        n_tab = n_off + 4 * n * nfeat if self.examples else n_off
+        n_fixed = n_tab + 4 * (n + 1) + 4 * n
         slot.reserve_meta(n_fixed + 4 * (8 * n + 64))
+        what = "lpm_yt8m_locate_examples" if self.examples else "lpm_yt8m_locate"
         while True:
             m = slot.meta.numpy()
-            idx = RecordIndex(m[n_off + 4 * (n + 1):n_fixed].view(np.int32), m[:n_off].view(np.int64),
-                              m[n_off:n_off + 4 * (n + 1)].view(np.int32), m[n_fixed:(m.size // 4) * 4].view(np.int32), id_off, id_len)
-            st, needed, failed = _locate_into(lib, buf, ro, rl, names, sizes, nfeat, T, r.num_classes, 0, idx)
+            label_start, num_frames = m[n_tab:n_tab + 4 * (n + 1)].view(np.int32), m[n_tab + 4 * (n + 1):n_fixed].view(np.int32)
+            label_index = m[n_fixed:(m.size // 4) * 4].view(np.int32)
+            if self.examples:
+                idx = ExampleIndex(m[:n_off].view(np.int64).reshape(n, nfeat), m[n_off:n_tab].view(np.int32).reshape(n, nfeat), label_start,
+                                   label_index, id_off, id_len)
+                st, needed, failed = _locate_examples_into(lib, buf, ro, rl, names, sizes, nfeat, r.num_classes, 0, idx)
+            else:
+                idx = RecordIndex(num_frames, m[:n_off].view(np.int64), label_start, label_index, id_off, id_len)
+                st, needed, failed = _locate_into(lib, buf, ro, rl, names, sizes, nfeat, T, r.num_classes, 0, idx)
             if st == _capi.LPM_ERR_WORKSPACE and n_fixed + 4 * needed > slot.meta.numel():
                 slot.reserve_meta(n_fixed + 4 * needed)
                 continue
             if st != 0:
                 path, i = src[max(failed, 0)]
-                _raise_native(lib, st, "lpm_yt8m_locate", f"{path}: record {i}: ")
+                _raise_native(lib, st, what, f"{path}: record {i}: ")
             break
         nlab = int(idx.label_start[n])
         ids = [bytes(buf[o:o + ln]).decode("utf-8") for o, ln in zip(id_off.tolist(), id_len.tolist())]
+        if self.examples:
+            num_frames[:] = 1
+            nbytes = self._repack(slot, nbytes, ro, rl, idx)
         t1 = time.perf_counter()
         with torch.cuda.stream(self.side):
             ev = None
@@ -822,11 +984,15 @@ class _DevicePipeline:
             meta.copy_(slot.meta[:n_meta], non_blocking=True)
             slot.copied = torch.cuda.Event()
             slot.copied.record(self.side)
-            nf = meta[n_off + 4 * (n + 1):n_fixed].view(torch.int32).clone()      # (its own storage: it goes to the consumer)
+            nf = meta[n_tab + 4 * (n + 1):n_fixed].view(torch.int32).clone()      # (its own storage: it goes to the consumer)
             if ev is not None:
                 ev[1].record(self.side)
-            frames = ops.gather_frames(raw, nbytes, meta[:n_off].view(torch.int64).view(n, nfeat, T), nf, r.feature_sizes, T)
-            labels = ops.labels_dense(meta[n_off:n_off + 4 * (n + 1)].view(torch.int32), meta[n_fixed:n_meta].view(torch.int32),
+            if self.examples:
+                frames = ops.gather_examples(raw, nbytes, meta[:n_off].view(torch.int64).view(n, nfeat),
+                                             meta[n_off:n_tab].view(torch.int32).view(n, nfeat), r.feature_sizes)
+            else:
+                frames = ops.gather_frames(raw, nbytes, meta[:n_off].view(torch.int64).view(n, nfeat, T), nf, r.feature_sizes, T)
+            labels = ops.labels_dense(meta[n_tab:n_tab + 4 * (n + 1)].view(torch.int32), meta[n_fixed:n_meta].view(torch.int32),
                                       r.num_classes)
             if ev is not None:
                 ev[2].record(self.side)
@@ -841,3 +1007,24 @@ class _DevicePipeline:
         st_["batches"] += 1
         st_["clips"] += n
         return self._put((ids, frames, labels, nf, done))
+
+    def _repack(self, slot: _Slot, nbytes: int, ro, rl, idx: ExampleIndex) -> int:
+        """Float lists without a constant stride (stride 0: several runs, a mix of packed and unpacked values, ...): the Python parser
+        reads that record, its values go packed into the slot behind the records and the table points there.  -> the slot's bytes."""
+        rows, cols = np.nonzero(idx.feature_stride == 0)
+        if rows.size == 0:
+            return nbytes
+        sizes = [int(s) for s in self.reader.feature_sizes]
+        pos = (nbytes + 3) & ~3
+        slot.reserve(pos + 4 * sum(sizes[f] for f in cols.tolist()), keep=nbytes)
+        parsed = {}
+        for i, f in zip(rows.tolist(), cols.tolist()):
+            if i not in parsed:
+                parsed[i] = parse_example(bytes(slot.np[ro[i]:ro[i] + rl[i]]))
+            vals = np.ascontiguousarray(parsed[i][self.reader.feature_names[f]][1], dtype="<f4")
+            if vals.size != sizes[f]:
+                raise ValueError(f"feature '{self.reader.feature_names[f]}' has {vals.size} values, expected {sizes[f]}")
+            slot.np[pos:pos + 4 * sizes[f]] = vals.view(np.uint8)
+            idx.feature_offset[i, f], idx.feature_stride[i, f] = pos, 4
+            pos += 4 * sizes[f]
+        return pos

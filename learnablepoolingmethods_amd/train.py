@@ -19,6 +19,7 @@ import torch
 import torch.distributed as dist
 
 from . import FLAGS, layers, losses, ops, utils
+from ._capi import LpmError
 from . import variables as vs
 
 ARENA_ALIGN = 4096   # LPM_ARENA_ALIGN: every variable starts on a chunk boundary of the optimizer kernel
@@ -455,8 +456,17 @@ class BucketGather:
         return {n for b in self.gathered for n in self.bucket_names[b]}
 
 
+def check_input_rank(model, raw):
+    """A [batch, features] input (the video-level reader's) in front of a frame-level model: refused here, by name, rather than by a
+    shape error from deep inside the model."""
+    if raw.dim() == 2 and type(model).__module__.endswith(".frame_level_models"):
+        raise LpmError(f"{type(model).__name__} needs frames, a [batch, max_frames, features] input, and got video-level features "
+                       f"{tuple(raw.shape)}: the models that take those are the ones of video_level_models (MoeModel, ...)")
+
+
 def normalize_input(raw, num_frames=None):
-    """The model input of train.py:262-264: L2-normalised frames (the quantised reader output dequantised and zero-padded first)."""
+    """The model input of train.py:262-264: L2-normalised over the last axis, whatever the rank (``feature_dim = rank - 1``): frames
+    [batch, max_frames, features] (the quantised reader output dequantised and zero-padded first) or video-level features [batch, features]."""
     if raw.dtype == torch.uint8:          # quantised reader output: dequantise + pad + normalise in one pass
         if raw.is_cuda:
             return ops.dequantize_l2_normalize(raw, num_frames)
@@ -465,7 +475,7 @@ def normalize_input(raw, num_frames=None):
         return layers.l2_normalize(x, 2)
     if raw.is_cuda and raw.shape[-1] % 4 == 0 and raw.shape[-1] <= 2048 and not raw.requires_grad:
         return ops.l2_normalize_rows(raw)
-    return layers.l2_normalize(raw, 2)
+    return layers.l2_normalize(raw, raw.dim() - 1)
 
 
 class Trainer:
@@ -543,6 +553,7 @@ class Trainer:
 
     def _model_input(self, raw, num_frames, kw):
         """-> (model input, model keywords): train.py:262-264's normalised fp32 frames, or the uint8 batch itself (_quantised_frames)."""
+        check_input_rank(self.model, raw)
         if self._quantised_frames(raw):
             return raw, {**kw, "quantised_training": True}
         return self._normalize_input(raw, num_frames), kw
@@ -806,12 +817,31 @@ class Trainer:
         else:
             if self.w16 is not None:
                 self.w16.invalidate()          # the generic update writes the master through raw pointers: the copy is rebuilt at its next use
-            self.arena._scratch = ops.clip_adam_step(self.arena.param, self.arena.grad, self.arena.m, self.arena.v,
-                                                     self.arena.offsets, len(self.arena.names), self.clip, lr,
-                                                     self.global_step, scratch=self.arena._scratch, l2=self._l2_fold)  # :332-336
+            if self.device.type != "cuda":
+                self._host_clip_adam(lr)           # a Trainer asked for on the CPU device: the host route, as readers.batches() is
+            else:
+                self.arena._scratch = ops.clip_adam_step(self.arena.param, self.arena.grad, self.arena.m, self.arena.v,
+                                                         self.arena.offsets, len(self.arena.names), self.clip, lr,
+                                                         self.global_step, scratch=self.arena._scratch, l2=self._l2_fold)  # :332-336
         self._join_update_stream()
         return {"loss": label_loss.detach(), "predictions": predictions.detach(), "learning_rate": lr,
                 "global_step": self.global_step}
+
+    @torch.no_grad()
+    def _host_clip_adam(self, lr, beta1=0.9, beta2=0.999, eps=1e-8):
+        """lpm_multi_tensor_clip_adam's arithmetic for a trainer on the CPU device, in PyTorch over the arenas: per-variable clip_by_norm
+        (utils.py:181-188), then tf.train.AdamOptimizer (train.py:332-336).  Never taken with tensors on a GPU."""
+        a, t = self.arena, self.global_step
+        lr_t = lr * math.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
+        for name in a.names:
+            lo, hi = a.segment(name)
+            g = a.grad[lo:hi]
+            if self.clip and self.clip > 0:
+                g = g * (self.clip / torch.clamp(torch.linalg.vector_norm(g), min=self.clip))
+            m, v = a.m[lo:hi], a.v[lo:hi]
+            m.mul_(beta1).add_(g, alpha=1.0 - beta1)
+            v.mul_(beta2).addcmul_(g, g, value=1.0 - beta2)
+            a.param[lo:hi].sub_(lr_t * m / (v.sqrt() + eps))
 
     def calibrate_operand_scales(self, model_input_raw, num_frames, labels, **kw):
         """The fp16 two-product format's scales measured NOW, synchronously, from one forward + backward on this batch in split-bf16
@@ -1106,6 +1136,7 @@ class Trainer:
     def predict(self, model_input_raw, num_frames, **kw):
         """eval.build_graph path: same forward with is_training=False (eval.py:143-150)."""
         self._join_update_stream()        # (hidden1_weights' update of an interrupted step may still be running on its stream)
+        check_input_rank(self.model, model_input_raw)
         x = self._normalize_input(model_input_raw.to(self.device), num_frames.to(self.device))
         result, _ = self._forward(x, num_frames.to(self.device), None, is_training=False, **kw)
         return result["predictions"]

@@ -3,6 +3,8 @@ the input pipeline; :44-112, the flags) around ``train.Trainer.step``:
 
     files -> readers.YT8MFrameFeatureReader.training_batches (shuffled device batches) -> Trainer.step -> log line / checkpoint / summaries
 
+(``--frame_features false``: readers.YT8MAggregatedFeatureReader, the video-level files, in front of a model of video_level_models.)
+
 ``run`` steps until ``max_steps <= global_step`` or the batches end.  On steps with ``global_step % log_every == 0`` it computes
 Hit@1, PERR and GAP of the step's predictions against its labels (``evaluation.batch_metrics``: lpm_eval_rows + the pooled top-20
 average precision on the device, eval_util on the CPU), copies them and the loss to the host ONCE and logs the reference's line byte
@@ -184,7 +186,8 @@ def _flag_value(default):
 
 def _parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m learnablepoolingmethods_amd.training",
-                                 description="Train a frame-level model from YT8M TFRecord files (the reference's train.py flags).")
+                                 description="Train a frame-level or video-level model from YT8M TFRecord files (the reference's train.py "
+                                             "flags).")
     ap.add_argument("--train_data_pattern", default="", help="comma-separated globs of TFRecord files (train.py:51)")
     ap.add_argument("--train_dir", default="/tmp/yt8m_model/", help="checkpoint directory (train.py:48)")
     ap.add_argument("--model", default="NetVladV1", help="a class of frame_level_models (train.py:64)")
@@ -194,10 +197,13 @@ def _parser() -> argparse.ArgumentParser:
     ap.add_argument("--summary_dir", default="", help="write TensorBoard event files here (empty: none; may equal --train_dir)")
     ap.add_argument("--histogram_steps", type=int, default=1000, help="steps between histogram summaries (with --summary_dir)")
     ap.add_argument("--start_new_model", type=_flag_value(False), nargs="?", const=True, default=False, help="train.py:68")
-    ap.add_argument("--feature_names", default="rgb,audio", help="train.py:55 (frame-level default)")
-    ap.add_argument("--feature_sizes", default="1024,128", help="train.py:57")
+    ap.add_argument("--frame_features", type=_flag_value(True), nargs="?", const=True, default=True,
+                    help="true: frame-level files (SequenceExample, uint8 frames); false: video-level files (Example, float features) for a "
+                         "model of video_level_models.  The reference's default is false (train.py:59-62); this command line keeps true")
+    ap.add_argument("--feature_names", default=None, help="train.py:55 (default: rgb,audio; with --frame_features false: mean_rgb,mean_audio)")
+    ap.add_argument("--feature_sizes", default=None, help="train.py:57 (default: 1024,128)")
     ap.add_argument("--num_classes", type=int, default=3862)
-    ap.add_argument("--max_frames", type=int, default=300, help="frames kept per clip (readers.py:134)")
+    ap.add_argument("--max_frames", type=int, default=300, help="frames kept per clip (readers.py:134); ignored with --frame_features false")
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--seed", type=int, default=0, help="variable initialisation and input order")
     ap.add_argument("--log_every", type=int, default=10)
@@ -223,9 +229,13 @@ def main(argv=None) -> Dict[str, object]:
     if not files:
         raise IOError("Unable to find training files. data_pattern='" + args.train_data_pattern + "'.")
     logging.info("Number of training files: %s.", str(len(files)))
-    names = [s.strip() for s in args.feature_names.split(",") if s.strip()]
-    sizes = [int(s) for s in args.feature_sizes.split(",") if s.strip()]
-    reader = readers.YT8MFrameFeatureReader(num_classes=args.num_classes, feature_sizes=sizes, feature_names=names, max_frames=args.max_frames)
+    feature_names = args.feature_names or ("rgb,audio" if args.frame_features else "mean_rgb,mean_audio")
+    names = [s.strip() for s in feature_names.split(",") if s.strip()]
+    sizes = [int(s) for s in (args.feature_sizes or "1024,128").split(",") if s.strip()]
+    if args.frame_features:                                                    # train.py:596-606
+        reader = readers.YT8MFrameFeatureReader(num_classes=args.num_classes, feature_sizes=sizes, feature_names=names, max_frames=args.max_frames)
+    else:
+        reader = readers.YT8MAggregatedFeatureReader(num_classes=args.num_classes, feature_sizes=sizes, feature_names=names)
     device = torch.device(args.device)
     trainer = Trainer(registry.get_model(args.model), vocab_size=args.num_classes, batch_size=FLAGS.batch_size, device=device, seed=args.seed)
     kw = dict(reader_threads=args.reader_threads) if device.type == "cuda" else {}
