@@ -883,6 +883,24 @@ int lpm_moe_ce_bwd(const float* gate_act, const float* expert_act, const float* 
                    lpm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * HingeLoss / SoftmaxLoss of the predictions (losses.py:54-69, :72-96), whichever head made them:
+ *   kind LPM_LABEL_LOSS_HINGE    s = 2 y - 1;  row loss = sum_j max(0, b - s_j p_j);  gradient -s_j / B where b - s_j p_j > 0
+ *                                STRICTLY (a tie takes tf.maximum's zeros), else 0
+ *   kind LPM_LABEL_LOSS_SOFTMAX  cnt = sum_j y_j;  row loss = [cnt > 0] (lse - sum_{y_j} p_j / cnt), lse = log sum_j exp(p_j) with the
+ *                                row maximum taken out;  gradient ([cnt > 0] softmax(p)_j - y_j / cnt) / B.  A row without labels
+ *                                gives exactly 0 both ways.  b is not read.
+ * predictions [B, V] fp32 contiguous; labels [B, V], ONE BYTE per element (bool / uint8; nonzero = positive).  Forward: row_loss [B],
+ * loss (0-d) = the mean of row_loss, and for the softmax kind row_state [B, 3] = (max_j p_j, sum_j exp(p_j - max), cnt) per row -- the
+ * log-sum-exp in its two parts and the number of positives -- which the backward takes back (hinge: row_state may be NULL).  Backward: dpredictions [B, V] = dloss (scalar on the device) * the gradient above.  Any B >= 1 and
+ * V >= 1; all sums are added in a fixed order (no floating-point atomics): the same inputs give the same bits.
+ * ------------------------------------------------------------------------------------------- */
+enum { LPM_LABEL_LOSS_HINGE = 1, LPM_LABEL_LOSS_SOFTMAX = 2 };
+int lpm_label_loss_fwd(int kind, const float* predictions, const uint8_t* labels, int B, int V, float b, float* row_state,
+                       float* row_loss, float* loss, lpm_stream_t stream);
+int lpm_label_loss_bwd(int kind, const float* predictions, const uint8_t* labels, const float* row_state, const float* dloss, int B,
+                       int V, float b, float* dpredictions, lpm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a14 + a15: per-variable clip_by_norm + TF-style Adam over a flat parameter arena
  *   replaces utils.clip_gradient_norms (utils.py:170-189) + tf.train.AdamOptimizer.apply_gradients
  *   (train.py:336).  `offsets` [ntensors+1] (int64, DEVICE) delimits each variable inside the

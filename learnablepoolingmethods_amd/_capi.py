@@ -186,6 +186,8 @@ SIGNATURES = {
     "lpm_moe_ce_nblk": (_i, [_i, _i]),
     "lpm_moe_ce_fwd": (_i, [_f, _f, _f, _i, _i, _i, _fl, _f, _f, _f, _f]),
     "lpm_moe_ce_bwd": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _fl, _f, _f, _f]),
+    "lpm_label_loss_fwd": (_i, [_i, _f, _f, _i, _i, _fl, _f, _f, _f, _f]),
+    "lpm_label_loss_bwd": (_i, [_i, _f, _f, _f, _f, _i, _i, _fl, _f, _f]),
     "lpm_clip_adam_scratch_bytes": (_s, [_l, _i]),
     "lpm_factored_clip_adam_scratch_bytes": (_s, [_i, _i]),
     "lpm_factored_clip_adam_q": (_i, [_f, _f, _f, _l, _f, _i, _i, _i, _f, _f, _f, _fl, _fl, _fl, _fl, _fl, _l, _f, _s, _f]),
@@ -252,6 +254,8 @@ SIGNATURES = {
     "lpm_bn_rows_act_image_fwd_fmt": (_i, [_f, _f, _i, _i, _i, _f, _f, _fl, _fl, _i, _f, _f, _f, _f, _f, _f, _s, _f, _f]),
     "lpm_bn_act_bwd_image_fmt": (_i, [_f, _f, _f, _i, _f, _f, _f, _fl, _i, _i, _f, _f, _f, _f, _f, _s, _f, _f]),
 }
+LPM_LABEL_LOSS_HINGE = 1         # kinds of lpm_label_loss_fwd / _bwd
+LPM_LABEL_LOSS_SOFTMAX = 2
 LPM_ERR_WORKSPACE = -3
 LPM_ERR_IO = -5                  # lpm_tfrecord_frame: a CRC mismatch
 LPM_ERR_DATA = -6                # lpm_yt8m_locate: a malformed example

@@ -188,13 +188,17 @@ class DeviceEvaluationMetrics:
         return {"avg_hit_at_one": out[0], "avg_perr": out[1], "avg_loss": out[2], "aps": out[4:], "gap": out[3], "num_examples": N}
 
 
-def evaluate(model, batches, top_k: int = 20, metrics=None, summary_writer=None, global_step=None) -> Dict[str, object]:
+def evaluate(model, batches, top_k: int = 20, metrics=None, summary_writer=None, global_step=None,
+             label_loss_fn=None) -> Dict[str, object]:
     """eval.py's evaluation_loop for anything with ``.predict(frames, num_frames)`` and ``.vocab_size`` (a Predictor or a Trainer) over
     (ids, frames, labels, num_frames) batches (readers.YT8MFrameFeatureReader.batches; uint8 frames go into predict as they are).
     Predictions on a GPU go into DeviceEvaluationMetrics, CPU predictions into eval_util.EvaluationMetrics with cross_entropy_rows as
     the loss.  ``metrics`` (cleared first) replaces the default.  -> get()'s dict plus map (the mean of aps), num_examples and
     examples_per_second.  With ``summary_writer`` (summaries.SummaryWriter) AND ``global_step`` the epoch's Epoch/Eval_Avg_Hit@1,
-    Epoch/Eval_Avg_Perr, Epoch/Eval_Avg_Loss, Epoch/Eval_MAP and Epoch/Eval_GAP are written at that step (utils.py:123-137)."""
+    Epoch/Eval_Avg_Perr, Epoch/Eval_Avg_Loss, Epoch/Eval_MAP and Epoch/Eval_GAP are written at that step (utils.py:123-137).
+    ``label_loss_fn`` (a losses.BaseLoss: eval.py:316's ``find_class_by_name(FLAGS.label_loss, [losses])()``): its calculate_loss of every
+    batch's predictions and labels is what both kinds of metrics accumulate, so avg_loss and Epoch/Eval_Avg_Loss are that loss weighted
+    by examples; None keeps the cross entropy described above."""
     t0 = time.perf_counter()
     if metrics is not None:
         metrics.clear()
@@ -205,7 +209,10 @@ def evaluate(model, batches, top_k: int = 20, metrics=None, summary_writer=None,
             metrics = (DeviceEvaluationMetrics(int(model.vocab_size), top_k, p.device) if p.is_cuda
                        else eval_util.EvaluationMetrics(int(model.vocab_size), top_k))
         y = labels.to(p.device)
-        if isinstance(metrics, DeviceEvaluationMetrics):
+        if label_loss_fn is not None:
+            with torch.no_grad():
+                metrics.accumulate(p, y, label_loss_fn.calculate_loss(p, y))
+        elif isinstance(metrics, DeviceEvaluationMetrics):
             metrics.accumulate(p, y)
         else:
             metrics.accumulate(p, y, cross_entropy_rows(p, y))

@@ -133,6 +133,13 @@ FLAGS.define("moe_prob_gating", False, ":41")
 FLAGS.define("moe_prob_gating_input", "prob", ":44")
 # train.py
 FLAGS.define("batch_size", 1024, "train.py:78")
+FLAGS.define("label_loss", "CrossEntropyLoss", "train.py:80: the class of losses the run optimises (CrossEntropyLoss, HingeLoss, SoftmaxLoss)")
+FLAGS.define("label_loss_fused", False, "build extension: HingeLoss / SoftmaxLoss of fp32 predictions and bool / uint8 labels on the GPU run as "
+             "ops.label_loss (csrc/label_loss.hip: one row-reduction launch plus the batch mean forward, one element-wise launch backward, "
+             "the labels read as bytes); False: the classes' torch formulation (the CPU path; same results).  Off: "
+             "tools/bench_label_loss.py measured the fused route 1.4 x faster for the softmax kind and 1.5-5 % slower for the hinge kind at "
+             "(1024, 3862) and (80, 3862), and the default is on only if it is not slower for both kinds at both shapes "
+             "(profiles/bench_label_loss.json, DESIGN.md section 23)")
 FLAGS.define("regularization_penalty", 1.0, ":83")
 FLAGS.define("base_learning_rate", 0.01, ":86")
 FLAGS.define("learning_rate_decay", 0.95, ":88")

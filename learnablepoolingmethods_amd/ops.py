@@ -3829,6 +3829,62 @@ def moe_cross_entropy(gate_act, expert_act, labels, num_mixtures, eps=10e-6):
     return _MoeCrossEntropy.apply(gate_act, expert_act, labels, int(num_mixtures), float(eps))
 
 
+LABEL_LOSS_KINDS = {"hinge": _capi.LPM_LABEL_LOSS_HINGE, "softmax": _capi.LPM_LABEL_LOSS_SOFTMAX}
+
+
+class _LabelLoss(torch.autograd.Function):
+    """(predictions, labels) -> loss: HingeLoss / SoftmaxLoss in one row-reduction launch (plus the one-workgroup batch mean) forward
+    and one element-wise launch backward (csrc/label_loss.hip).  The labels are read as the bytes they are."""
+
+    @staticmethod
+    def forward(ctx, predictions, labels, kind, b):
+        lib = _capi.load()
+        p, y = predictions.contiguous(), labels.contiguous()
+        B, V = p.shape
+        row_state = _empty((B, 3), p) if kind == _capi.LPM_LABEL_LOSS_SOFTMAX else None
+        row_loss, loss = _empty((B,), p), _empty((), p)
+        lib.check(lib._lpm_label_loss_fwd(kind, ptr(p), ptr(y), B, V, b, ptr(row_state), ptr(row_loss), ptr(loss), stream_ptr()),
+                  "lpm_label_loss_fwd")
+        ctx.args = (kind, b, B, V)
+        ctx.save_for_backward(p, y, row_state)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dloss):
+        lib = _capi.load()
+        kind, b, B, V = ctx.args
+        p, y, row_state = ctx.saved_tensors
+        dloss = dloss.to(torch.float32).contiguous()
+        dp = torch.empty_like(p)
+        lib.check(lib._lpm_label_loss_bwd(kind, ptr(p), ptr(y), ptr(row_state), ptr(dloss), B, V, b, ptr(dp), stream_ptr()),
+                  "lpm_label_loss_bwd")
+        return dp, None, None, None
+
+
+def label_loss(predictions, labels, kind, b=1.0):
+    """losses.py:54-69 HingeLoss (kind "hinge"; b: the margin) / :72-96 SoftmaxLoss (kind "softmax") of fp32 predictions [B, V] and
+    bool / uint8 labels [B, V] on the GPU -> the 0-d loss, differentiable in the predictions (once; the labels get no gradient).  Hinge
+    ties (b - s p == 0) get gradient 0, a row without labels gives exactly 0 loss and gradient under the softmax kind; the same inputs
+    give the same bits.  Everything is checked before any launch."""
+    if not isinstance(predictions, torch.Tensor) or not isinstance(labels, torch.Tensor):
+        raise LpmError("label_loss: predictions and labels must be tensors")
+    if not isinstance(kind, str) or kind not in LABEL_LOSS_KINDS:
+        raise LpmError(f"label_loss: unknown kind {kind!r}; the kinds are {sorted(LABEL_LOSS_KINDS)}")
+    if not predictions.is_cuda or not labels.is_cuda:
+        raise LpmError("label_loss needs tensors on an MI355X (cuda/hip device); got a CPU tensor.  losses.HingeLoss / SoftmaxLoss "
+                       "carry the torch formulation for other devices.")
+    if predictions.device != labels.device:
+        raise LpmError(f"label_loss: predictions are on {predictions.device}, labels on {labels.device}")
+    _f32(predictions, "label_loss: predictions")
+    if labels.dtype not in (torch.bool, torch.uint8):
+        raise LpmError(f"label_loss: labels must be bool or uint8 (one byte per element), got {labels.dtype}")
+    if predictions.dim() != 2 or predictions.shape != labels.shape or predictions.numel() == 0:
+        raise LpmError(f"label_loss: predictions and labels must be the same non-empty [B, V]; got {tuple(predictions.shape)} and "
+                       f"{tuple(labels.shape)}")
+    return _LabelLoss.apply(predictions, labels, LABEL_LOSS_KINDS[kind], float(b))
+
+
 class ComputeCopy:
     """The bf16 compute copy of a weight beside its fp32 master (SURVEY section 7 hard part 2: "keep master fp32 + bf16 compute copy";
     BASELINE configs[4]).  The owner (train.Trainer) attaches it to the variable as ``W._lpm_w16``; FactoredGradient.clip_adam keeps it

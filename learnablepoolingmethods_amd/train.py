@@ -493,7 +493,7 @@ class Trainer:
                                   else learning_rate_decay_examples)
         self.reg_penalty = FLAGS.regularization_penalty if regularization_penalty is None else regularization_penalty
         self.clip = FLAGS.clip_gradient_norm if clip_gradient_norm is None else clip_gradient_norm
-        self.loss_fn = label_loss_fn or losses.CrossEntropyLoss()
+        self.loss_fn = label_loss_fn or losses.by_name(FLAGS.label_loss)                        # train.py:576
         self.device = torch.device(device)
         self.group = group
         self.store = vs.VariableStore(device=self.device, seed=seed)
