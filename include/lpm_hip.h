@@ -1197,6 +1197,28 @@ int lpm_triangulation_bn_moments_bwd(const float* x, const float* anchors, const
                                      const float* g_t, int B, int T, int D, int K, int affine_grads, int training, float* dx, float* danchors,
                                      float* dgrad, void* workspace, size_t workspace_bytes, lpm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The rows of the inference CSV as text (inference.py:88-96), csrc/csv_rows.hip and csrc/format_pairs.h.  index int32 [B, k] and value
+ * fp32 [B, k] (the outputs of lpm_topk_rows; any int32 is accepted) -> text uint8 [B, stride] with stride = lpm_format_pairs_stride of k
+ * = 25 k rounded up to 16 (a pair is at most 11 + 1 + 12 + 1 bytes), and length int32 [B]: row r is
+ *     "c0 s0 c1 s1 ... c(k-1) s(k-1)\n"      c as "%i", s as Python's "%g" % float(s) of the exactly widened value,
+ * one space between the items, a newline at the end, no id and no comma, in text[r * stride : r * stride + length[r]].  The bytes of a
+ * row's slot behind length[r] are unspecified; nothing outside text[0 : B * stride] and length[0 : B] is written.  %g is exact for every
+ * bit pattern: six significant digits rounded half-even on the binary value, the decimal exponent taken after rounding, trailing zeros
+ * stripped, "inf" / "-inf", and "nan" for every NaN whatever its sign.  Integer arithmetic only; no atomics: the same input gives the
+ * same bytes, and the device and the host entry give the same bytes as each other.  1 <= k <= 64, B >= 1 (the stride of any other k is 0);
+ * index, value and length 4-byte aligned; a 16-byte aligned text leaves as 16-byte stores, any other as bytes.  The _host entry takes host
+ * pointers, needs no device and takes no stream. */
+int lpm_format_pairs_stride(int k);
+int lpm_format_pairs(const int32_t* index, const float* value, int B, int k, unsigned char* text, int32_t* length, lpm_stream_t stream);
+int lpm_format_pairs_host(const int32_t* index, const float* value, int B, int k, unsigned char* text, int32_t* length);
+/* Host: out = "<id>,<row>" for the B rows in order, where id r is the bytes ids[id_begin[r] : id_end[r]] as they are (any UTF-8, may be
+ * empty) and row r is text[r * stride : r * stride + length[r]] (text and length as lpm_format_pairs wrote them, copied to the host);
+ * *out_length their total.  LPM_ERR_WORKSPACE when out_capacity bytes do not hold it (B * (stride + 1) plus the ids' bytes always do);
+ * LPM_ERR_BADARG for a length outside [0, stride] or an id of negative length.  Needs no device and takes no stream. */
+int lpm_csv_join_rows(const void* ids, const int64_t* id_begin, const int64_t* id_end, const unsigned char* text, const int32_t* length,
+                      int B, int stride, unsigned char* out, int64_t out_capacity, int64_t* out_length);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,6 +191,13 @@ FLAGS.define("train_quantised_frames", True, "build extension: Trainer.build / s
              "forms, lpm_frame_bn_bwd*_q8) instead of first writing the dequantised, L2-normalised fp32 frames of all max_frames "
              "(ops.dequantize_l2_normalize) -- the same results bit for bit.  False: the fp32 detour (A/B).  fp32 input, the CPU and other "
              "models are not affected")
+FLAGS.define("csv_rows_fused", True, "build extension: inference.write_csv formats the rows of the CSV with ops.format_pairs (csrc/csv_rows.hip: "
+             "every \"%i %g\" pair of a batch as text on the device, exact for every float) and joins ids and rows in native host code "
+             "(lpm_csv_join_rows), batch n's copy and join under batch n + 1's forward; False: the rows go through format_top_k_lines, "
+             "Python's own formatting (the same bytes).  On: tools/bench_inference.py measured write_csv against write_top_k end to end on an "
+             "MI355X at 31.5 k against 24.7 k rows/s for NetVladV1 at the cfg-2 sizes (B = 80) and 1.73 M against 0.235 M rows/s for MoeModel on "
+             "[1024, 1152] features, and the default is on only if it is not slower at both shapes (profiles/bench_inference.json, DESIGN.md "
+             "section 24)")
 FLAGS.define("gather_frames_fused", False, "build extension: the reader's uint8 frames on the GPU go unnormalised to the five triangulation "
              "models as well (RegularizedTriangulationModel, SoftAttentionTriangulationModel, TriangulationCnnClusterModel, JuhanTestModelV5, "
              "JuhanTestModelV1), which draw SampleRandomFrames' index table and gather, dequantise, L2-normalise and batch-normalise the "

@@ -11,6 +11,7 @@ import os
 import weakref
 from typing import NamedTuple, Optional
 
+import numpy as np
 import torch
 
 from . import _capi
@@ -409,6 +410,86 @@ def topk_rows(p, k):
     if B:
         lib.check(lib._lpm_topk_rows(ptr(p), B, V, k, ptr(index), ptr(value), stream_ptr()), "lpm_topk_rows")
     return index, value
+
+
+FORMAT_PAIRS_MAX_K = 64  # lpm_format_pairs' limit
+
+
+def format_pairs_stride(k) -> int:
+    """Bytes of a row's slot in format_pairs' text: 25 k rounded up to 16 (lpm_format_pairs_stride)."""
+    k = int(k)
+    if not 1 <= k <= FORMAT_PAIRS_MAX_K:
+        raise LpmError(f"format_pairs: need 1 <= k <= {FORMAT_PAIRS_MAX_K}, got {k}")
+    return int(_capi.load()._lpm_format_pairs_stride(k))
+
+
+def format_pairs(classes, scores, out=None):
+    """-> (text uint8 [B, stride], length int32 [B]): row r of the inference CSV without its id, ``"c0 s0 c1 s1 ... \\n"`` with every pair
+    as ``"%i %g" % (c, s)``, in ``text[r, :length[r]]`` (the bytes behind are unspecified).  classes int32 [B, k], scores float32 [B, k]
+    (topk_rows' outputs), 1 <= k <= 64, B >= 1.  CUDA tensors run lpm_format_pairs on the current stream, CPU tensors
+    lpm_format_pairs_host: the same bytes.  ``out``: a contiguous uint8 buffer of at least B * (stride + 4) bytes on the same device whose
+    start is 4-byte aligned; text and length are then views of it, text first and length at byte B * stride (one copy moves both)."""
+    if not (torch.is_tensor(classes) and torch.is_tensor(scores) and classes.dtype == torch.int32 and scores.dtype == torch.float32
+            and classes.dim() == 2 and classes.shape == scores.shape and classes.device == scores.device):
+        raise LpmError("format_pairs: expected classes int32 [batch, k] and scores float32 [batch, k] on one device")
+    B, k = classes.shape
+    if B < 1:
+        raise LpmError("format_pairs: need at least one row")
+    stride = format_pairs_stride(k)
+    nbytes = B * (stride + 4)
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=classes.device)
+    elif not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.dim() == 1 and out.is_contiguous() and out.numel() >= nbytes
+              and out.device == classes.device and out.data_ptr() % 4 == 0):
+        raise LpmError(f"format_pairs: out must be a contiguous 4-byte aligned uint8 buffer of at least {nbytes} bytes on {classes.device}")
+    text = out[:B * stride].view(B, stride)
+    length = out[B * stride:nbytes].view(torch.int32)
+    return format_pairs_into(classes, scores, text, length)
+
+
+def format_pairs_into(classes, scores, text, length):
+    """format_pairs into caller-owned tensors: text uint8 [B, stride] and length int32 [B], both contiguous.  -> (text, length)."""
+    B, k = classes.shape
+    stride = format_pairs_stride(k)
+    if not (text.dtype == torch.uint8 and tuple(text.shape) == (B, stride) and text.is_contiguous() and length.dtype == torch.int32
+            and tuple(length.shape) == (B,) and length.is_contiguous() and text.device == classes.device and length.device == classes.device):
+        raise LpmError(f"format_pairs: need text uint8 [{B}, {stride}] and length int32 [{B}], contiguous, on {classes.device}")
+    lib = _capi.load()
+    classes, scores = classes.contiguous(), scores.contiguous()
+    if classes.is_cuda:
+        lib.check(lib._lpm_format_pairs(ptr(classes), ptr(scores), B, k, ptr(text), ptr(length), stream_ptr()), "lpm_format_pairs")
+    else:
+        lib.check(lib._lpm_format_pairs_host(classes.data_ptr(), scores.data_ptr(), B, k, text.data_ptr(), length.data_ptr()),
+                  "lpm_format_pairs_host")
+    return text, length
+
+
+def csv_join_rows(ids, text, length):
+    """-> the bytes ``"<id>,<row>"`` of every row in order, as a memoryview of a fresh host buffer (lpm_csv_join_rows, host code): ids a
+    sequence of str (or UTF-8 bytes), text / length format_pairs' outputs on the host (pinned memory or not)."""
+    B, stride = text.shape
+    if (text.is_cuda or length.is_cuda or len(ids) != B or B < 1 or text.dtype != torch.uint8 or length.dtype != torch.int32
+            or tuple(length.shape) != (B,) or not text.is_contiguous() or not length.is_contiguous()):
+        raise LpmError("csv_join_rows: need contiguous host tensors text uint8 [B, stride], length int32 [B] and B ids, B >= 1")
+    try:
+        blob = "\0".join(ids).encode("utf-8")                                                     # one join, no loop over the rows
+    except TypeError:                                                                             # (ids as bytes, or mixed)
+        blob = b"\0".join(v if isinstance(v, bytes) else v.encode("utf-8") for v in ids)
+    a = np.frombuffer(blob, dtype=np.uint8)
+    cut = np.flatnonzero(a == 0).astype(np.int64)
+    if cut.size != B - 1:                                                                         # an id that holds a NUL itself
+        sizes = np.array([len(v if isinstance(v, bytes) else v.encode("utf-8")) for v in ids], dtype=np.int64)
+        end = np.cumsum(sizes) + np.arange(B, dtype=np.int64)
+        begin = end - sizes
+    else:
+        begin = np.concatenate([np.zeros(1, np.int64), cut + 1])
+        end = np.concatenate([cut, np.array([a.size], np.int64)])
+    buf = np.empty(B * (stride + 1) + len(blob), dtype=np.uint8)
+    n = C.c_int64(0)
+    lib = _capi.load()
+    lib.check(lib._lpm_csv_join_rows(blob, begin.ctypes.data, end.ctypes.data, text.data_ptr(), length.data_ptr(), B, stride,
+                                     buf.ctypes.data, buf.size, C.byref(n)), "lpm_csv_join_rows")
+    return memoryview(buf)[:n.value]
 
 
 class EvalRows(NamedTuple):

@@ -39,6 +39,7 @@ from __future__ import annotations
 
 import argparse
 import glob
+import json
 import logging
 import os
 import re
@@ -215,8 +216,34 @@ def _parser() -> argparse.ArgumentParser:
     return ap
 
 
+MODEL_FLAGS_FILE = "model_flags.json"
+
+
+def write_model_flags(train_dir: str, model_flags: Dict[str, object], start_new_model: bool = False) -> str:
+    """train.py:390-411: record which model ``train_dir`` holds, for inference.main.  The reference's five keys (model, feature_names,
+    feature_sizes, frame_features, label_loss) must equal those of a file that is already there (ValueError naming both; the reference
+    logs them and exits); ``start_new_model`` removes the old file first.  -> the file's path."""
+    os.makedirs(train_dir, exist_ok=True)
+    path = os.path.join(train_dir, MODEL_FLAGS_FILE)
+    if start_new_model and os.path.exists(path):
+        os.remove(path)
+    if os.path.exists(path):
+        with open(path) as f:
+            existing = json.load(f)
+        five = ("model", "feature_names", "feature_sizes", "frame_features", "label_loss")
+        ran, previously = {k: model_flags.get(k) for k in five}, {k: existing.get(k) for k in five}
+        if ran != previously:
+            raise ValueError(f"Model flags do not match existing file {path}. Please delete the file, change --train_dir, or pass flag "
+                             f"--start_new_model. Ran model with flags: {ran}. Previously ran with flags: {previously}")
+        return path
+    with open(path, "w") as f:
+        f.write(json.dumps(model_flags))
+    return path
+
+
 def main(argv=None) -> Dict[str, object]:
-    """train.py's ``main``: flags -> reader + Trainer + ``run``.  -> run's dict."""
+    """train.py's ``main``: flags -> reader + Trainer + ``run``.  -> run's dict.  With a ``train_dir`` it also records the model in
+    ``train_dir/model_flags.json`` (write_model_flags) once the Trainer stands."""
     from . import readers, registry, summaries
     from .train import Trainer
     args = _parser().parse_args(argv)
@@ -238,6 +265,13 @@ def main(argv=None) -> Dict[str, object]:
         reader = readers.YT8MAggregatedFeatureReader(num_classes=args.num_classes, feature_sizes=sizes, feature_names=names)
     device = torch.device(args.device)
     trainer = Trainer(registry.get_model(args.model), vocab_size=args.num_classes, batch_size=FLAGS.batch_size, device=device, seed=args.seed)
+    if args.train_dir:
+        write_model_flags(args.train_dir, {
+            "model": args.model, "feature_names": ",".join(names), "feature_sizes": ",".join(str(v) for v in sizes),
+            "frame_features": bool(args.frame_features), "label_loss": FLAGS.label_loss,                  # the reference's five
+            "num_classes": int(args.num_classes), "max_frames": int(args.max_frames),
+            "flags": {name: getattr(FLAGS, name) for name, default in FLAGS._defaults.items() if getattr(FLAGS, name) != default},
+        }, start_new_model=args.start_new_model)
     kw = dict(reader_threads=args.reader_threads) if device.type == "cuda" else {}
     batches = reader.training_batches(files, FLAGS.batch_size, device=device, num_epochs=args.num_epochs, seed=args.seed, **kw)
     writer = summaries.SummaryWriter(args.summary_dir) if args.summary_dir else None
