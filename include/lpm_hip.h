@@ -977,6 +977,20 @@ int lpm_topk_rows(const float* p, int B, int V, int k, int32_t* index, float* va
 int lpm_eval_rows(const float* p, const unsigned char* labels, int B, int V, int k, unsigned char* hit1, int32_t* num_labels,
                   int32_t* hits_at_n, double* loss_row, int32_t* top_index, float* top_value, unsigned char* top_label, lpm_stream_t stream);
 
+/* The batch statistics behind lpm_eval_rows, one launch (DeviceEvaluationMetrics.accumulate with FLAGS.eval_stats_fused): from the batch's
+ * hit1 / num_labels / hits_at_n / loss_row [B] as lpm_eval_rows wrote them and its labels uint8 [B, V] (nonzero = positive; row-contiguous,
+ * at ANY byte address) ->
+ *   batch [4] fp64     mean of hit1 | mean over the rows of hits_at_n / num_labels (0 where num_labels == 0) | mean loss | B
+ *   sum_loss [1] fp64  += mean loss * B (the product rounded, then the sum)
+ *   class_pos [V] i64  += the column sums of the labels
+ * The mean loss is the mean of loss_row, or -- loss_row null -- the value at given_loss (device memory: one float, or one double when
+ * given_loss_is_f64), bit for bit; exactly one of the two is given.  The fp64 sums run in a fixed order (no floating-point atomics): the
+ * same inputs give the same bits.  class_pos is added to with integer atomics and is exact at every label density.  The labels are read
+ * once, 16 bytes per load over the aligned part of the range.  B > 0, 1 <= V <= 65536. */
+int lpm_eval_batch_stats(const unsigned char* hit1, const int32_t* num_labels, const int32_t* hits_at_n, const double* loss_row,
+                         const void* given_loss, int given_loss_is_f64, const unsigned char* labels, int B, int V, double* batch,
+                         double* sum_loss, int64_t* class_pos, lpm_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * The frame reader's device path (readers.YT8MFrameFeatureReader.device_batches): the two host entry points below look at the header
  * bytes of a buffer of TFRecord records and never at a frame's payload; the records go to the GPU as they are and the two kernels put

@@ -199,6 +199,7 @@ SIGNATURES = {
     "lpm_dropout_keep_mask": (_i, [_f, _l, _fl, C.c_uint64, _f]),
     "lpm_topk_rows": (_i, [_f, _i, _i, _i, _f, _f, _f]),
     "lpm_eval_rows": (_i, [_f, _f, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f]),
+    "lpm_eval_batch_stats": (_i, [_f, _f, _f, _f, _f, _i, _f, _i, _i, _f, _f, _f, _f]),
     "lpm_tfrecord_frame": (_i, [_f, _l, _i, _i, _l, _f, _f, _f, _f]),               # (host entry points: _f = any caller-owned buffer)
     "lpm_yt8m_locate": (_i, [_f, _l, _f, _f, _i, _l, _f, _f, _i, _i, _i, _f, _f, _f, _f, _l, _f, _f, _f, _f]),
     "lpm_gather_frames": (_i, [_f, _l, _l, _f, _f, _i, _i, _f, _i, _f, _f]),

@@ -198,6 +198,12 @@ FLAGS.define("csv_rows_fused", True, "build extension: inference.write_csv forma
              "MI355X at 31.5 k against 24.7 k rows/s for NetVladV1 at the cfg-2 sizes (B = 80) and 1.73 M against 0.235 M rows/s for MoeModel on "
              "[1024, 1152] features, and the default is on only if it is not slower at both shapes (profiles/bench_inference.json, DESIGN.md "
              "section 24)")
+FLAGS.define("eval_stats_fused", True, "build extension: evaluation.DeviceEvaluationMetrics.accumulate is two launches, lpm_eval_rows and "
+             "lpm_eval_batch_stats (csrc/eval_batch_stats.hip: the batch's Hit@1 / PERR / loss means into one fp64 [4] slot, the loss sum and the "
+             "per-class label counts, the labels read once as 16-byte loads); False: the means and the label counts are about ten small torch "
+             "launches behind lpm_eval_rows (the same values; the fp64 sums in torch's order).  On: tools/bench_eval_stats.py measured accumulate on an MI355X at 50.7 against 122.5 us per batch at (80, 3862), 50.1 "
+             "against 115.9 us at (128, 3862) and 60.4 against 129.5 us at (1024, 3862), and the default is on only if the fused route is not "
+             "slower at all three shapes (profiles/bench_eval_stats.json, DESIGN.md section 25)")
 FLAGS.define("gather_frames_fused", False, "build extension: the reader's uint8 frames on the GPU go unnormalised to the five triangulation "
              "models as well (RegularizedTriangulationModel, SoftAttentionTriangulationModel, TriangulationCnnClusterModel, JuhanTestModelV5, "
              "JuhanTestModelV1), which draw SampleRandomFrames' index table and gather, dequantise, L2-normalise and batch-normalise the "

@@ -10,8 +10,6 @@ the Python route and the drop-in surface."""
 from __future__ import annotations
 
 import argparse
-import glob
-import json
 import logging
 import os
 import time
@@ -20,6 +18,7 @@ from typing import Dict, Iterable, Iterator, Sequence
 import torch
 
 from . import FLAGS
+from .model_flags import MODEL_FLAGS_FILE  # noqa: F401  (this module keeps exporting the name)
 
 CSV_HEADER = "VideoId,LabelConfidencePairs\n"
 
@@ -146,9 +145,6 @@ def write_csv(out_file, predictor, batches: Iterable, top_k: int = 20) -> int:
 
 
 # ---- command line (python -m learnablepoolingmethods_amd.inference) --------------------------------------------------------------
-MODEL_FLAGS_FILE = "model_flags.json"
-
-
 def _parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m learnablepoolingmethods_amd.inference",
                                  description="Write the VideoId,LabelConfidencePairs CSV of a trained model over YT8M TFRecord files (the "
@@ -167,39 +163,24 @@ def _parser() -> argparse.ArgumentParser:
 def main(argv=None) -> Dict[str, object]:
     """inference.py's ``main``: model_flags.json + a checkpoint + files -> the CSV.  -> {num_examples, seconds, examples_per_second,
     output_file}.  Every video appears once, in file order, the last smaller batch included."""
-    from . import readers, registry, training
+    from . import model_flags, registry, training
     from .predictor import Predictor
     args = _parser().parse_args(argv)
-    flags_file = os.path.join(args.train_dir, MODEL_FLAGS_FILE)
-    if not os.path.exists(flags_file):
-        raise IOError("Cannot find %s. Did you run eval.py?" % flags_file)                 # inference.py:221-223
-    with open(flags_file) as f:
-        flags_dict = json.load(f)
+    flags_dict = model_flags.read(args.train_dir, "Cannot find %s. Did you run eval.py?")              # inference.py:221-223
     if not args.output_file:
         raise ValueError("'output_file' was not specified. Unable to continue with inference.")
     if not args.input_data_pattern:
         raise ValueError("'input_data_pattern' was not specified. Unable to continue with inference.")
-    files = []
-    for pattern in args.input_data_pattern.split(","):
-        files.extend(sorted(glob.glob(pattern)) if pattern else [])
+    files = model_flags.matching_files(args.input_data_pattern)
     if not files:
         raise IOError("Unable to find input files. data_pattern='" + args.input_data_pattern + "'")       # inference.py:117-120
     logging.info("number of input files: " + str(len(files)))
     checkpoint = args.checkpoint or training.latest_checkpoint(args.train_dir)
     if not checkpoint or not os.path.exists(checkpoint):
         raise IOError("Cannot find a checkpoint (model.ckpt-<step>.pt) in %s" % args.train_dir)
-    names = [s.strip() for s in flags_dict["feature_names"].split(",") if s.strip()]
-    sizes = [int(s) for s in flags_dict["feature_sizes"].split(",") if s.strip()]
     num_classes = int(flags_dict["num_classes"])
-    saved = {name: getattr(FLAGS, name) for name in FLAGS._defaults}
-    try:
-        for name, value in flags_dict.get("flags", {}).items():
-            setattr(FLAGS, name, value)
-        if flags_dict["frame_features"]:
-            reader = readers.YT8MFrameFeatureReader(num_classes=num_classes, feature_sizes=sizes, feature_names=names,
-                                                    max_frames=int(flags_dict["max_frames"]))
-        else:
-            reader = readers.YT8MAggregatedFeatureReader(num_classes=num_classes, feature_sizes=sizes, feature_names=names)
+    with model_flags.applied(flags_dict):
+        reader = model_flags.build_reader(flags_dict)
         device = torch.device(args.device)
         predictor = Predictor.from_checkpoint(checkpoint, registry.get_model(flags_dict["model"]), vocab_size=num_classes, device=device)
         if device.type == "cuda":
@@ -220,9 +201,6 @@ def main(argv=None) -> Dict[str, object]:
         finally:
             batches.close()
         seconds = time.time() - start
-    finally:
-        for name, value in saved.items():
-            setattr(FLAGS, name, value)
     return {"num_examples": num_examples, "seconds": seconds,
             "examples_per_second": num_examples / seconds if seconds > 0 else float("inf"), "output_file": args.output_file}
 

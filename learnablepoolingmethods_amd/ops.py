@@ -549,6 +549,55 @@ def eval_rows(p, labels, k, with_loss=True, out: Optional[EvalRows] = None) -> E
     return out
 
 
+def eval_batch_stats(rows: EvalRows, labels, batch, sum_loss, class_pos, loss=None):
+    """The batch statistics behind eval_rows in ONE HIP launch (lpm_eval_batch_stats): from ``rows`` (eval_rows' hit1, num_labels,
+    hits_at_n and loss_row of the batch) and its 0 / 1 labels [B, V] (bool or uint8, row-contiguous, at any byte address -- a row slice
+    of a larger matrix is fine) it writes ``batch`` fp64 [4] = (mean of hit1, mean of hits_at_n / num_labels with 0 for a row without
+    labels, mean loss, B) and adds mean loss * B to ``sum_loss`` (fp64, one element) and the labels' column sums to ``class_pos`` (int64
+    [V]).  The mean loss is the mean of rows.loss_row, or ``loss`` itself, bit for bit, when one is given: ONE fp32 or fp64 value on the
+    device (rows.loss_row may then be None).  The fp64 sums run in a fixed order; class_pos is exact at every label density.  No host
+    synchronisation.  Arguments are checked before the launch.  -> batch."""
+    for name, t, dt in (("rows.hit1", rows.hit1, torch.uint8), ("rows.num_labels", rows.num_labels, torch.int32),
+                        ("rows.hits_at_n", rows.hits_at_n, torch.int32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or not t.is_contiguous():
+            raise LpmError(f"eval_batch_stats: {name} must be a contiguous {dt} vector")
+    B = rows.hit1.shape[0]
+    dev = rows.hit1.device
+    if B < 1 or rows.num_labels.shape[0] != B or rows.hits_at_n.shape[0] != B:
+        raise LpmError("eval_batch_stats: need hit1, num_labels and hits_at_n of one batch of at least one row")
+    if not isinstance(labels, torch.Tensor) or labels.dtype not in (torch.uint8, torch.bool) or labels.dim() != 2 or labels.shape[0] != B:
+        raise LpmError(f"eval_batch_stats: expected bool or uint8 labels [{B}, classes]")
+    if not labels.is_contiguous():
+        raise LpmError("eval_batch_stats: the labels must be row-contiguous (any start address)")
+    V = labels.shape[1]
+    if not 1 <= V <= TOPK_MAX_V:
+        raise LpmError(f"eval_batch_stats: need 1 <= classes <= {TOPK_MAX_V} (classes={V})")
+    if loss is None:
+        lr = rows.loss_row
+        if not isinstance(lr, torch.Tensor) or lr.dtype != torch.float64 or tuple(lr.shape) != (B,) or not lr.is_contiguous():
+            raise LpmError(f"eval_batch_stats: without a given loss rows.loss_row must be a contiguous float64 vector of {B} elements")
+    else:
+        lr = None
+        if not isinstance(loss, torch.Tensor) or loss.numel() != 1 or loss.dtype not in (torch.float32, torch.float64):
+            raise LpmError("eval_batch_stats: a given loss must be ONE float32 or float64 value on the device (reduce a longer one first)")
+    for name, t, dt, n in (("batch", batch, torch.float64, 4), ("sum_loss", sum_loss, torch.float64, 1), ("class_pos", class_pos, torch.int64, V)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.numel() != n or not t.is_contiguous():
+            raise LpmError(f"eval_batch_stats: {name} must be a contiguous {dt} tensor of {n} elements")
+    for name, t in (("rows.num_labels", rows.num_labels), ("rows.hits_at_n", rows.hits_at_n), ("rows.loss_row", lr), ("labels", labels),
+                    ("loss", loss), ("batch", batch), ("sum_loss", sum_loss), ("class_pos", class_pos)):
+        if t is not None and (not t.is_cuda or t.device != dev):
+            raise LpmError(f"eval_batch_stats: {name} must be on the GPU device of rows.hit1 ({dev}); eval_util.EvaluationMetrics computes "
+                           "the metrics of CPU tensors")
+    if not dev.type == "cuda":
+        raise LpmError("eval_batch_stats: expected tensors on a GPU device (eval_util.EvaluationMetrics computes the metrics of CPU tensors)")
+    lib = _capi.load()
+    y = labels.view(torch.uint8) if labels.dtype == torch.bool else labels
+    lib.check(lib._lpm_eval_batch_stats(ptr(rows.hit1), ptr(rows.num_labels), ptr(rows.hits_at_n), ptr(lr), ptr(loss),
+                                        int(loss is not None and loss.dtype == torch.float64), ptr(y), B, V, ptr(batch), ptr(sum_loss),
+                                        ptr(class_pos), stream_ptr()), "lpm_eval_batch_stats")
+    return batch
+
+
 HISTOGRAM_MAX_LIMITS = 2048        # lpm_histogram_segments' limits
 HISTOGRAM_MAX_SEGMENTS = 65535
 _DEFAULT_LIMITS = {}               # device -> summaries.default_bucket_limits() as an fp64 tensor there

@@ -8,7 +8,7 @@ the input pipeline; :44-112, the flags) around ``train.Trainer.step``:
 ``run`` steps until ``max_steps <= global_step`` or the batches end.  On steps with ``global_step % log_every == 0`` it computes
 Hit@1, PERR and GAP of the step's predictions against its labels (``evaluation.batch_metrics``: lpm_eval_rows + the pooled top-20
 average precision on the device, eval_util on the CPU), copies them and the loss to the host ONCE and logs the reference's line byte
-for byte.  With ``train_dir`` it saves ``model.ckpt-<step>.pt`` (``Trainer.save``) at the first logged step, at every logged step at
+for byte.  With ``train_dir`` it saves ``model.ckpt-<step>.pt`` (``Trainer.save`` under a temporary name, then ``os.replace``) at the first logged step, at every logged step at
 which ``export_model_steps`` steps have passed since the last save (the reference takes this decision at its logged steps too), and on
 exit; on entry the newest ``model.ckpt-*.pt`` there is restored -- after ``Trainer.build`` on the first batch -- unless
 ``start_new_model``, which removes the old ``model.ckpt-*.pt`` files instead (the reference deletes the whole directory).  The input
@@ -49,6 +49,7 @@ from typing import Callable, Dict, Iterable, List, Optional
 import torch
 
 from . import FLAGS, evaluation
+from .model_flags import MODEL_FLAGS_FILE
 
 _CKPT = re.compile(r"^model\.ckpt-(\d+)\.pt$")
 
@@ -98,7 +99,11 @@ def run(trainer, batches: Iterable, max_steps: Optional[int] = None, log_every: 
     def save(step):
         nonlocal last_export
         path = checkpoint_path(train_dir, step)
-        trainer.save(path)
+        # written under a name _CKPT does not match, then renamed: a polling evaluation.run never opens half a file.  model.ckpt-<step>.tmp,
+        # not ...pt.tmp: torch.save names the records inside the file after the file's name up to its last dot, so this keeps the bytes
+        tmp = path[:-len(".pt")] + ".tmp"
+        trainer.save(tmp)
+        os.replace(tmp, path)
         written.append(path)
         last_export = step
 
@@ -214,9 +219,6 @@ def _parser() -> argparse.ArgumentParser:
     for name, default in FLAGS._defaults.items():
         ap.add_argument("--" + name, type=_flag_value(default), default=None, help=f"FLAGS.{name} (default {default!r})")
     return ap
-
-
-MODEL_FLAGS_FILE = "model_flags.json"
 
 
 def write_model_flags(train_dir: str, model_flags: Dict[str, object], start_new_model: bool = False) -> str:
