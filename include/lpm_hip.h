@@ -922,6 +922,24 @@ int lpm_multi_tensor_clip_adam_l2(float* param, const float* grad, float* m, flo
                                   int ntensors, int64_t total, float clip_norm, float lr, float beta1, float beta2, float eps,
                                   int64_t step, float* scratch, lpm_stream_t stream);
 
+/* a14 + the update rules tf.train offers beside Adam (train.py:106,252,577: --optimizer), over the same arenas and in the same three
+ * stages: per-chunk sums of squares (with the l2coef[t] * param term formed on the fly; l2coef may be NULL), one workgroup per variable
+ * that reduces them in a fixed order to clip / max(||g||, clip) (1 when clip <= 0), and ONE apply kernel templated on the rule.  With
+ * g the clipped gradient, every product and sum rounded on its own, IEEE square roots and divisions, in this order of operations:
+ *   GRADIENT_DESCENT  p -= lr g
+ *   MOMENTUM          a = h0 a + g;                 p -= lr a                        (slot0 = a; h0 = momentum)
+ *   ADAGRAD           a = a + g g;                  p -= lr g / sqrt(a)              (slot0 = a)
+ *   RMSPROP           s = s + (g g - s)(1 - h0);    p -= lr g / sqrt(s + h1)         (slot0 = s; h0 = decay, h1 = epsilon)
+ *   ADADELTA          a = h0 a + (1 - h0) g g;  u = sqrt(d + h1) / sqrt(a + h1) g;  d = h0 d + (1 - h0) u u;  p -= lr u
+ *                                                                                    (slot0 = a, slot1 = d; h0 = rho, h1 = epsilon)
+ * A slot arena the rule does not keep is never loaded, stored or dereferenced: NULL is legal for it.  A NULL slot the rule keeps, an
+ * unknown kind, total % 4 != 0 and arenas that are not 16-byte aligned are refused before anything is launched.  No floating-point
+ * atomics: the same inputs give the same bits.  scratch: lpm_clip_adam_scratch_bytes(total, ntensors). */
+enum { LPM_UPDATE_GRADIENT_DESCENT = 1, LPM_UPDATE_MOMENTUM = 2, LPM_UPDATE_ADAGRAD = 3, LPM_UPDATE_RMSPROP = 4, LPM_UPDATE_ADADELTA = 5 };
+int lpm_multi_tensor_clip_update(int kind, float* param, const float* grad, float* slot0, float* slot1, const int64_t* offsets,
+                                 const float* l2coef, int ntensors, int64_t total, float clip_norm, float lr, float h0, float h1,
+                                 float* scratch, lpm_stream_t stream);
+
 /* a14 + a15 for a variable whose gradient is dW [N1, N2] = X^T DY, X [R, N1], DY [R, N2], R = the batch over ALL towers (the SUM of
  * utils.combine_gradients, utils.py:192-213, is the product over the concatenated rows): the hidden projection's weight
  * (frame_level_models.py:2314-2319), 75 % (cfg-2) ... 94 % (cfg-5) of the model's parameters.  The gradient is never written:

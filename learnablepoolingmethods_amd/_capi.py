@@ -237,6 +237,7 @@ SIGNATURES = {
     "lpm_format_pairs_host": (_i, [_f, _f, _i, _i, _f, _f]),                    # (host entry points, as lpm_tfrecord_frame)
     "lpm_csv_join_rows": (_i, [_f, _f, _f, _f, _f, _i, _i, _f, _l, _f]),
     "lpm_multi_tensor_clip_adam_l2":(_i, [_f, _f, _f, _f, _f, _f, _i, _l, _fl, _fl, _fl, _fl, _fl, _l, _f, _f]),
+    "lpm_multi_tensor_clip_update": (_i, [_i, _f, _f, _f, _f, _f, _f, _i, _l, _fl, _fl, _fl, _fl, _f, _f]),
     "lpm_weight_pack": (_i, [_f, _i, _f]),
     "lpm_sum_splits": (_i, [_f, _i, _i, _i, _f, _f, _f, _i, _f]),          # (jobs: a HOST array of WeightPackJob)
     # round 5: the entry points that take an operand format (LpmOperandFormat*: a HOST struct, NULL = split-bf16 x3)

@@ -145,6 +145,12 @@ FLAGS.define("base_learning_rate", 0.01, ":86")
 FLAGS.define("learning_rate_decay", 0.95, ":88")
 FLAGS.define("learning_rate_decay_examples", 4000000, ":91")
 FLAGS.define("clip_gradient_norm", 1.0, ":108")
+FLAGS.define("optimizer", "AdamOptimizer", "train.py:106: the class of tf.train that applies the gradients (optimizers.SUPPORTED: AdamOptimizer, "
+             "GradientDescentOptimizer, MomentumOptimizer, AdagradOptimizer, RMSPropOptimizer, AdadeltaOptimizer), built from the learning rate "
+             "alone as train.py:252 does.  Any rule but Adam updates every variable, hidden1_weights included, through "
+             "lpm_multi_tensor_clip_update: the factored, early, sharded routes of that variable are Adam's")
+FLAGS.define("optimizer_momentum", None, "build extension: MomentumOptimizer's momentum.  tf.train.MomentumOptimizer has no default for it -- the "
+             "reference's optimizer_class(learning_rate) raises -- so --optimizer MomentumOptimizer is refused without this flag")
 FLAGS.define("hidden1_factored_update", True, "build extension: the GPU trainer consumes hidden1_weights' gradient as the product "
              "descriptors^T . d(activation) it is (lpm_factored_clip_adam): the gradient is never written, the towers all-gather its "
              "two skinny factors instead of all-reducing it.  False: the generic path (gradient written into the arena)")

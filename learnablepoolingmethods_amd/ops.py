@@ -4225,6 +4225,28 @@ def clip_adam_step(param, grad, m, v, offsets, ntensors, clip_norm, lr, step, be
     return scratch
 
 
+def clip_update_step(spec, param, grad, slots, offsets, ntensors, clip_norm, lr, scratch: Optional[torch.Tensor] = None,
+                     l2: Optional[torch.Tensor] = None):
+    """lpm_multi_tensor_clip_update: clip_adam_step's arenas, stages and ``l2`` under one of the other rules of ``--optimizer``
+    (``spec``: optimizers.by_name; ``slots``: the arenas the rule keeps, in the spec's order -- none for GradientDescentOptimizer).  The
+    slots a rule does not keep go in as NULL: the kernel never looks at them."""
+    lib = _capi.load()
+    total = param.numel()
+    slots = tuple(slots)
+    if len(slots) != spec.slots or any(s.dtype != torch.float32 or s.numel() != total or not s.is_contiguous() for s in slots):
+        raise LpmError(f"clip_update_step: {spec.name} keeps {spec.slots} slot arena(s) of the parameter arena's size, contiguous fp32; got {len(slots)}")
+    if scratch is None:
+        scratch = torch.empty(lib._lpm_clip_adam_scratch_bytes(total, ntensors) // 4, dtype=torch.float32, device=param.device)
+    if l2 is not None and (l2.dtype != torch.float32 or l2.numel() != ntensors or not l2.is_contiguous()):
+        raise LpmError("clip_update_step: l2 must be a contiguous fp32 vector with one coefficient per variable")
+    s0, s1 = (slots + (None, None))[:2]
+    with _timed("clip_update", (spec.kind, total, ntensors)):
+        lib.check(lib._lpm_multi_tensor_clip_update(spec.kind, ptr(param), ptr(grad), ptr(s0), ptr(s1), ptr(offsets), ptr(l2), ntensors, total,
+                                                    float(clip_norm), float(lr), float(spec.h0), float(spec.h1), ptr(scratch), stream_ptr()),
+                  "lpm_multi_tensor_clip_update")
+    return scratch
+
+
 # ----------------------------------------------------------------------------------------------
 # triangulation-embedding pooling (csrc/triangulation_pool.hip)
 # ----------------------------------------------------------------------------------------------

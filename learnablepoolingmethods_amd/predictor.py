@@ -18,6 +18,7 @@ import torch
 from . import FLAGS, ops
 from . import variables as vs
 from ._capi import LpmError
+from .optimizers import SLOT_KEYS
 from .train import check_input_rank, normalize_input
 
 # models whose frame-prep op reads uint8 frames in eval mode (ops.frame_sample_bn / frame_sample_bn_split)
@@ -98,10 +99,11 @@ class Predictor:
 
     @classmethod
     def from_checkpoint(cls, path: str, model, vocab_size: int = 3862, model_kwargs=None, device="cuda") -> "Predictor":
-        """From a file written by Trainer.save: its variables and moving statistics (the Adam slots and the step count are dropped)."""
+        """From a file written by Trainer.save: its variables and moving statistics (the optimiser's slots -- Adam's, or those of the
+        ``--optimizer`` the file names -- and the step count are dropped)."""
         state = torch.load(path, map_location="cpu")
-        variables = {n: v for n, v in state.items()
-                     if n not in _NOT_VARIABLES and torch.is_tensor(v) and not n.endswith("/Adam") and not n.endswith("/Adam_1")}
+        slots = tuple("/" + k for k in SLOT_KEYS.get(state.get("optimizer", "AdamOptimizer"), SLOT_KEYS["AdamOptimizer"]))
+        variables = {n: v for n, v in state.items() if n not in _NOT_VARIABLES and torch.is_tensor(v) and not (slots and n.endswith(slots))}
         if not variables:
             raise ValueError(f"{path}: no variables in this checkpoint")
         return cls(model, vocab_size, variables, device, model_kwargs)

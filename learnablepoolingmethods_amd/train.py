@@ -18,7 +18,7 @@ from typing import Dict, List, Optional
 import torch
 import torch.distributed as dist
 
-from . import FLAGS, layers, losses, ops, utils
+from . import FLAGS, layers, losses, ops, optimizers, utils
 from ._capi import LpmError
 from . import variables as vs
 
@@ -41,12 +41,15 @@ def learning_rate(base_learning_rate, global_step, batch_size, num_towers, decay
 
 
 class ParameterArena:
-    """Flat fp32 arenas (param / grad / adam m / adam v) with every trainable variable a view into them."""
+    """Flat fp32 arenas (param / grad / the optimiser's slots: adam m / adam v) with every trainable variable a view into them."""
 
-    def __init__(self, store: vs.VariableStore, first: Optional[List[str]] = None, gather: bool = False, bucket_of=None):
+    def __init__(self, store: vs.VariableStore, first: Optional[List[str]] = None, gather: bool = False, bucket_of=None,
+                 optimizer: Optional[optimizers.OptimizerSpec] = None):
         """gather=False: every variable's .grad IS its slice of the gradient arena (autograd accumulates in place; one tiny
         add kernel per variable per step).  gather=True: .grad stays None during backward (autograd adopts each producer's
-        tensor) and ``collect`` moves all of them into the arena with one multi-tensor copy."""
+        tensor) and ``collect`` moves all of them into the arena with one multi-tensor copy.
+        ``optimizer`` (None: Adam): only the slot arenas its rule keeps are allocated (``slots``), each filled -- alignment padding
+        included -- with the rule's initial value; ``m`` / ``v`` are Adam's two and None under any other rule."""
         self.gather = gather
         tv = store.trainable_variables()
         names = [n for n in (first or []) if n in tv] + [n for n in tv if n not in (first or [])]
@@ -63,8 +66,13 @@ class ParameterArena:
         self.device = dev
         self.param = torch.zeros(cur, dtype=torch.float32, device=dev)
         self.grad = torch.zeros(cur, dtype=torch.float32, device=dev)
-        self.m = torch.zeros(cur, dtype=torch.float32, device=dev)
-        self.v = torch.zeros(cur, dtype=torch.float32, device=dev)
+        if optimizer is None or optimizer.kind == optimizers.ADAM:
+            self.m = torch.zeros(cur, dtype=torch.float32, device=dev)
+            self.v = torch.zeros(cur, dtype=torch.float32, device=dev)
+            self.slots = [self.m, self.v]
+        else:
+            self.m = self.v = None
+            self.slots = [torch.full((cur,), init, dtype=torch.float32, device=dev) for init in optimizer.slot_init]
         self.offsets_host = offs
         self.offsets = torch.tensor(offs, dtype=torch.int64, device=dev)
         self.views: Dict[str, torch.Tensor] = {}
@@ -483,7 +491,7 @@ class Trainer:
 
     def __init__(self, model, vocab_size=3862, batch_size=None, base_learning_rate=None, learning_rate_decay=None,
                  learning_rate_decay_examples=None, regularization_penalty=None, clip_gradient_norm=None,
-                 label_loss_fn=None, device="cuda", group=None, seed=0, model_kwargs=None):
+                 label_loss_fn=None, device="cuda", group=None, seed=0, model_kwargs=None, optimizer=None, optimizer_momentum=None):
         self.model = model
         self.vocab_size = vocab_size
         self.batch_size = batch_size or FLAGS.batch_size
@@ -494,6 +502,8 @@ class Trainer:
         self.reg_penalty = FLAGS.regularization_penalty if regularization_penalty is None else regularization_penalty
         self.clip = FLAGS.clip_gradient_norm if clip_gradient_norm is None else clip_gradient_norm
         self.loss_fn = label_loss_fn or losses.by_name(FLAGS.label_loss)                        # train.py:576
+        self.optimizer = optimizers.by_name(FLAGS.optimizer if optimizer is None else optimizer, optimizer_momentum)   # train.py:577
+        self._adam = self.optimizer.kind == optimizers.ADAM
         self.device = torch.device(device)
         self.group = group
         self.store = vs.VariableStore(device=self.device, seed=seed)
@@ -578,7 +588,8 @@ class Trainer:
                 elif n.endswith("/moving_variance"):
                     v.fill_(1.0)
         gather = self.device.type == "cuda"
-        self.arena = ParameterArena(self.store, first=["tower/hidden1_weights"], gather=gather, bucket_of=dp_bucket_of)
+        self.arena = ParameterArena(self.store, first=["tower/hidden1_weights"], gather=gather, bucket_of=dp_bucket_of,
+                                    optimizer=self.optimizer)
         bucket_names: Dict[int, List[str]] = {}
         for n in self.arena.names:
             bucket_names.setdefault(dp_bucket_of(n), []).append(n)
@@ -599,10 +610,12 @@ class Trainer:
         self.sharded = None
         # beyond hidden1_factored_max_towers (or from hidden1_sharded_min_towers on): route C, the sharded update
         shard_from = FLAGS.hidden1_sharded_min_towers or (FLAGS.hidden1_factored_max_towers + 1)
-        want_sharded = (self.sync.active and FLAGS.hidden1_sharded_update and self.num_towers >= shard_from
+        # (the factored, early, update-stream, fold-dx and sharded routes of hidden1_weights are Adam kernels: under any other rule the
+        # variable's gradient is written into the arena and updated with all the others; towers > 1: route A, the bucket all-reduce)
+        want_sharded = (self._adam and self.sync.active and FLAGS.hidden1_sharded_update and self.num_towers >= shard_from
                         and h1 in self.arena.views and self.arena.names[0] == h1
                         and ShardedVariableUpdate.supported(self.arena, h1, self.num_towers))
-        want_factored = (self.device.type == "cuda" and FLAGS.hidden1_factored_update and not want_sharded
+        want_factored = (self._adam and self.device.type == "cuda" and FLAGS.hidden1_factored_update and not want_sharded
                          and self.num_towers <= FLAGS.hidden1_factored_max_towers
                          and h1 in self.arena.views and self.arena.names[0] == h1
                          and self.arena.views[h1].dim() == 2 and self.arena.views[h1].shape[1] % 32 == 0)
@@ -817,7 +830,14 @@ class Trainer:
         else:
             if self.w16 is not None:
                 self.w16.invalidate()          # the generic update writes the master through raw pointers: the copy is rebuilt at its next use
-            if self.device.type != "cuda":
+            if not self._adam:
+                a = self.arena
+                if self.device.type != "cuda":
+                    optimizers.host_clip_update(self.optimizer, a, self.clip, lr)
+                else:
+                    a._scratch = ops.clip_update_step(self.optimizer, a.param, a.grad, a.slots, a.offsets, len(a.names), self.clip, lr,
+                                                      scratch=a._scratch, l2=self._l2_fold)     # :332-336
+            elif self.device.type != "cuda":
                 self._host_clip_adam(lr)           # a Trainer asked for on the CPU device: the host route, as readers.batches() is
             else:
                 self.arena._scratch = ops.clip_adam_step(self.arena.param, self.arena.grad, self.arena.m, self.arena.v,
@@ -907,7 +927,12 @@ class Trainer:
         a0, _ = self.arena.segment(name)
         g = self.arena.grad[a0:a0 + t.numel()].view(t.shape)
         coef = getattr(self, "_l2_folded", {}).get(name)
-        if coef:
+        if coef and not self._adam:
+            # the L2 penalty's share, coefficient * w, was added inside the clip + update passes from the weight BEFORE the update, which
+            # these rules' slots do not give back: formed here from the weight AFTER it, it is off by coefficient * (the step taken),
+            # a term of second order in the two small numbers
+            g = g + coef * t.detach()
+        elif coef:
             # the L2 penalty's share, coefficient * w, was added inside the clip + Adam passes (FLAGS.fold_l2_into_update) from the weight
             # BEFORE the update: w_old = w + lr_t m / (sqrt(v) + eps) with the moments the update left behind (exact to rounding)
             b1, b2, eps = 0.9, 0.999, 1e-8
@@ -1007,7 +1032,9 @@ class Trainer:
     # -- checkpoint / resume (train.py:501-515,593: Supervisor-saved variables + Adam slots + global_step) ------------------
     def state_dict(self, sync: bool = False) -> Dict[str, object]:
         """Everything a resumed run needs, keyed by the reference's TF variable names (``tower/video_VLAD/cluster_weights``,
-        ``tower/video_attention/q/kernel``, ..., Adam slots as ``<name>/Adam`` and ``<name>/Adam_1``) plus ``global_step``.
+        ``tower/video_attention/q/kernel``, ..., Adam slots as ``<name>/Adam`` and ``<name>/Adam_1``; the slots of another
+        ``--optimizer`` under TF's keys for them, optimizers.by_name: ``<name>/Momentum``, ``/Adagrad``, ``/RMSProp``, ``/Adadelta`` and
+        ``/Adadelta_1``) plus ``global_step`` and ``optimizer``, the rule's name.
 
         No communication by default: a chief-only ``if rank == 0: trainer.save(path)`` (the reference's Supervisor / is_chief
         pattern, train.py:501-515) must not enter a collective the other ranks never reach.  Data-parallel runs call
@@ -1032,9 +1059,10 @@ class Trainer:
             a0, _ = self.arena.segment(n)
             k = self.arena.views[n].numel()
             shape = self.arena.views[n].shape
-            out[n + "/Adam"] = self.arena.m[a0:a0 + k].view(shape).clone().cpu()
-            out[n + "/Adam_1"] = self.arena.v[a0:a0 + k].view(shape).clone().cpu()
+            for key, slot in zip(self.optimizer.slot_keys, self.arena.slots):
+                out[n + "/" + key] = slot[a0:a0 + k].view(shape).clone().cpu()
         out["global_step"] = int(self.global_step)
+        out["optimizer"] = self.optimizer.name
         if self.sync is not None and self.sync.active and not sync:
             # a chief-only save: this rank's own moving statistics (the towers' mean needs sync_moving_statistics() on every rank
             # first) and, on the sharded route, Adam moments of hidden1_weights for this rank's shard only -- recorded, not hidden
@@ -1099,6 +1127,12 @@ class Trainer:
         if self.sharded is not None:
             self.sharded.wait_parameters()
             self.store.pending.pop(self.arena.names[0], None)
+        saved_with = state.get("optimizer", "AdamOptimizer")          # (checkpoints from before --optimizer existed: Adam's)
+        if saved_with != self.optimizer.name:
+            # tf.train.Saver.restore would fail on the slot variables the checkpoint does not hold
+            raise RuntimeError(f"checkpoint was written by a trainer with --optimizer {saved_with} and this trainer runs {self.optimizer.name}: "
+                               f"it holds none of this rule's slot variables ({', '.join(self.optimizer.slot_keys) or 'it keeps none'}); build the "
+                               f"Trainer with optimizer={saved_with!r} to resume from it")
         shard = state.get("hidden1_adam_shard")
         if shard is not None:
             # a chief-only save on the sharded route without prepare_checkpoint() holds real Adam moments of hidden1_weights
@@ -1117,10 +1151,9 @@ class Trainer:
             for n in self.arena.names:
                 a0, _ = self.arena.segment(n)
                 k = self.arena.views[n].numel()
-                if n + "/Adam" in state:
-                    self.arena.m[a0:a0 + k].copy_(torch.as_tensor(state[n + "/Adam"]).reshape(-1))
-                if n + "/Adam_1" in state:
-                    self.arena.v[a0:a0 + k].copy_(torch.as_tensor(state[n + "/Adam_1"]).reshape(-1))
+                for key, slot in zip(self.optimizer.slot_keys, self.arena.slots):
+                    if n + "/" + key in state:
+                        slot[a0:a0 + k].copy_(torch.as_tensor(state[n + "/" + key]).reshape(-1))
         self.global_step = int(state.get("global_step", self.global_step))
         if self.w16 is not None:
             self.w16.invalidate()          # the master was rewritten (store.load copies through views: version counters see it; belt and braces)

@@ -187,6 +187,8 @@ def run(trainer, batches: Iterable, max_steps: Optional[int] = None, log_every: 
 def _flag_value(default):
     if isinstance(default, bool):
         return lambda s: str(s).lower() in ("1", "true", "yes", "y")
+    if default is None:                   # (a flag without a default, optimizer_momentum: a number when given)
+        return float
     return type(default)
 
 
@@ -266,7 +268,9 @@ def main(argv=None) -> Dict[str, object]:
     else:
         reader = readers.YT8MAggregatedFeatureReader(num_classes=args.num_classes, feature_sizes=sizes, feature_names=names)
     device = torch.device(args.device)
-    trainer = Trainer(registry.get_model(args.model), vocab_size=args.num_classes, batch_size=FLAGS.batch_size, device=device, seed=args.seed)
+    # --optimizer / --optimizer_momentum (train.py:106,577) are registered flags: set above, handed on by name here
+    trainer = Trainer(registry.get_model(args.model), vocab_size=args.num_classes, batch_size=FLAGS.batch_size, device=device, seed=args.seed,
+                      optimizer=FLAGS.optimizer, optimizer_momentum=FLAGS.optimizer_momentum)
     if args.train_dir:
         write_model_flags(args.train_dir, {
             "model": args.model, "feature_names": ",".join(names), "feature_sizes": ",".join(str(v) for v in sizes),
