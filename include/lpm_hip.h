@@ -1251,6 +1251,24 @@ int lpm_format_pairs_host(const int32_t* index, const float* value, int B, int k
 int lpm_csv_join_rows(const void* ids, const int64_t* id_begin, const int64_t* id_end, const unsigned char* text, const int32_t* length,
                       int B, int stride, unsigned char* out, int64_t out_capacity, int64_t* out_length);
 
+/* ---- csrc/lstm.hip: one layer of BasicLSTMCell(H, forget_bias) under dynamic_rnn(sequence_length), the recurrent half ----
+ * The caller forms xw = X Wx for all B T rows (a large GEMM) and hands it over as [B, T, 4H]; wh is the recurrent half of the TF kernel,
+ * [H, 4H] with rows ldw floats apart (kernel + In * 4H, ldw = 4H), its base on 16 bytes.  Columns gate-major i | j | f | o.
+ * lpm_lstm_layer_fwd launches ONE kernel per time step t = 0 .. T-1 on the stream: z = xw[:, t] + h_{t-1} wh + bias on exact-fp32 MFMAs,
+ * c' = c sigmoid(f + forget_bias) + sigmoid(i) tanh(j), h' = tanh(c') sigmoid(o); for t >= min(lengths[b], T) the state is copied and
+ * outputs[b, t] = 0.  hs, cs [B, T + 1, H]: the states BEFORE step t at [:, t] -- the caller zeroes [:, 0], the kernels write the rest
+ * (h_last = hs[:, T], c_last = cs[:, T]); gates [B, T, 4H]: sigmoid(i), tanh(j), sigmoid(f + forget_bias), sigmoid(o); outputs [B, T, H].
+ * lpm_lstm_layer_bwd launches one kernel per step s = T-1 .. 0: dh_s = dZ_{s+1} wh^T + dhp + g_out[:, s], step s's gate arithmetic, dZ_s
+ * into dz [B, T, 4H] (zero rows at masked steps).  dhp, dc [B, H]: on entry the gradients of h_last and c_last, overwritten; g_out
+ * [B, T, H] or NULL.  dX, dkernel and dbias are GEMMs / sums over dz of the caller's.  lengths: int32 [B].
+ * lpm_lstm_supported: H a multiple of 128, B, T >= 1; elsewhere LPM_ERR_UNSUPPORTED_SHAPE before any launch.  No atomics, no grid-wide
+ * synchronisation: steps are ordered by the stream; the same inputs give the same bits. */
+int lpm_lstm_supported(int B, int T, int H);
+int lpm_lstm_layer_fwd(const float* xw, const float* wh, int64_t ldw, const float* bias, const int32_t* lengths, int B, int T, int H,
+                       float forget_bias, float* hs, float* cs, float* gates, float* outputs, lpm_stream_t stream);
+int lpm_lstm_layer_bwd(const float* wh, int64_t ldw, const int32_t* lengths, const float* cs, const float* gates, const float* g_out,
+                       float* dhp, float* dc, float* dz, int B, int T, int H, lpm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

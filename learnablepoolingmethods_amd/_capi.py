@@ -232,6 +232,9 @@ SIGNATURES = {
     "lpm_triangulation_bn_moments_pool": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f]),
     "lpm_triangulation_bn_moments_dw": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _f, _f, _f]),
     "lpm_triangulation_bn_moments_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _s, _f]),
+    "lpm_lstm_supported": (_i, [_i, _i, _i]),
+    "lpm_lstm_layer_fwd": (_i, [_f, _f, _l, _f, _f, _i, _i, _i, _fl, _f, _f, _f, _f, _f]),
+    "lpm_lstm_layer_bwd": (_i, [_f, _l, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _f]),
     "lpm_format_pairs_stride": (_i, [_i]),
     "lpm_format_pairs": (_i, [_f, _f, _i, _i, _f, _f, _f]),
     "lpm_format_pairs_host": (_i, [_f, _f, _i, _i, _f, _f]),                    # (host entry points, as lpm_tfrecord_frame)

@@ -122,6 +122,16 @@ FLAGS.define("triangulation_v1_fused", False, "build extension: on the GPU each 
              "the mean and variance over the frames without any [B, T, K*D] tensor); False: TriangulationCnnIndirectAttentionModule.pool "
              "materialises it (the CPU path; same variables, same results).  Off until tools/bench_triangulation_v1.py has shown the fused "
              "path not slower at both model-default shapes (profiles/bench_triangulation_v1.json)")
+FLAGS.define("batch_norm", True, "TriangulationRelationalModel (frame_level_models.py:1503): True iff add batch normalization")
+FLAGS.define("audio_triangulation_anchor_size_v1", 4, "TriangulationRelationalModel (:1505): anchors of the audio stream")
+FLAGS.define("video_triangulation_anchor_size_v1", 16, "TriangulationRelationalModel (:1507): anchors of the video stream")
+FLAGS.define("lstm_fused", True, "build extension: on the GPU every layer of rnn_modules' LSTM stacks whose hidden size is a multiple of 128 "
+             "is ONE ops.lstm_layer call (csrc/lstm.hip: a kernel per time step each way -- the recurrent product on exact-fp32 MFMAs with "
+             "the gate arithmetic, the length mask and the state update in its epilogue -- between three large GEMMs outside the time "
+             "loop); False: rnn_modules._lstm_layer_host runs the layer as a per-step torch formulation (the CPU path; same variables, "
+             "same results).  On: tools/bench_lstm.py measured forward + backward of one layer at 0.93 ms fused against 10.6 ms per step at "
+             "(B, T, In, H) = (16, 30, 512, 512) and 82.3 against 175.3 ms at (16, 30, 16384, 16384), and the default is on only if the "
+             "fused route is not slower at both shapes (profiles/bench_lstm.json, DESIGN.md section 27)")
 FLAGS.define("wtm_projection_l1", 1e-5, "layers.l1_l2_regularizer(1e-5) on dis_projection_2 / temp_projection_2 (frame_level_models.py:1272,1287): "
              "tf.contrib's first positional argument is scale_l1")
 FLAGS.define("wtm_projection_l2", 1.0, "... and its scale_l2 keeps the default 1.0: the penalty is l1 * sum |w| + l2 * sum(w^2) / 2 (SURVEY App. B)")

@@ -1,7 +1,7 @@
 """NetVLAD prototypes behind the reference's model-registry API
 (reference: frame_level_models.py:2193-2513 NetVladV1 / NetVladV2, :2765-2877 NetVLAD / LightVLAD) and the triangulation-embedding
 family's RegularizedTriangulationModel (:1148-1307), SoftAttentionTriangulationModel (:965-1145), TriangulationCnnClusterModel
-(:757-939) and JuhanTestModelV5 (:491-606).
+(:757-939), JuhanTestModelV5 (:491-606), JuhanTestModelV1 (:59-154) and the recurrent TriangulationRelationalModel (:1511-1630).
 
 Same names, ``create_model`` signature, variable names and output contract as the reference; the hot
 ops (frame sampling + input_bn, soft-assignment GEMM, fused softmax/residual aggregation/normalise,
@@ -689,6 +689,86 @@ class JuhanTestModelV1(models.BaseModel):
         aggregated_model = getattr(video_level_models, "ClassLearningFourNnModel")
         return aggregated_model().create_model(model_input=activation, vocab_size=vocab_size, is_training=is_training,
                                                **unused_params)                                              # :147-154
+
+
+class TriangulationRelationalModel(models.BaseModel):
+    """The reference's recurrent model (frame_level_models.py:1511-1630): input batch norm, per stream the triangulation embedding of
+    every sampled frame MATERIALISED as [B, T, D*K] -- the LSTM reads it -- and a one-layer LstmLastHiddenModule of hidden size D*K over it
+    with the raw ``num_frames`` as sequence lengths (up to 300 against 30 sampled frames: a length above T means T), the two last hidden
+    states concatenated, two hidden layers of width 2048 (``lstm_hidden_1`` / ``lstm_hidden_2``: batch norm, leaky_relu(0.2), dropout with
+    keep probability 0.5 in training) and the mixture-of-experts classifier.
+
+    The model does not run as written; the resolutions:
+      * ``t_emb, det_reg = TriangulationEmbedding.forward(...)`` (:1570, :1576) unpacks a single tensor: the tensor is taken and
+        det_reg = 0, the model's own ``else`` branch (:1583-1584);
+      * ``getattr(video_level_models, "WillowMoeModel")`` (:1622) names a class that exists nowhere: MoeModel it is, WILLOW's
+        mixture of experts with probability gating; det_reg goes into its ``**unused_params``;
+      * ``add_batch_norm = add_batch_norm or FLAGS.batch_norm`` (:1524): False cannot switch it off (C23), kept.
+    Frames are sampled (SampleRandomFrames) only when ``sample_random_frames`` or FLAGS.sample_random_frames is set, as written; there is
+    no sampling otherwise and T is the input's max_frames.
+
+    On the GPU with FLAGS.lstm_fused each stream's LSTM is ONE ops.lstm_layer call (csrc/lstm.hip); otherwise rnn_modules runs the
+    per-step torch formulation.  The variables and the results are the same either way.  ``frame_uniform`` [B, iterations] replaces the
+    random draw of SampleRandomFrames, ``dropout_masks`` {"hidden_1", "hidden_2"} (KEEP masks [B, 2048], non-zero = kept) the two
+    dropout draws; ``video_anchor_size`` and ``audio_anchor_size`` override the flags (the reference reads the flags only).  fp32 frames
+    only: a uint8 batch is dequantised before it gets here (train.normalize_input)."""
+
+    HIDDEN = 2048
+    KEEP_PROB = 0.5
+
+    def create_model(self, model_input, vocab_size, num_frames, iterations=None, add_batch_norm=None, sample_random_frames=None,
+                     hidden_size=None, is_training=True, frame_uniform=None, video_anchor_size=None, audio_anchor_size=None,
+                     dropout_masks=None, **unused_params):
+        from . import rnn_modules
+        iterations = iterations or FLAGS.iterations                                                           # :1522
+        random_frames = sample_random_frames or FLAGS.sample_random_frames                                    # :1523
+        add_batch_norm = add_batch_norm or FLAGS.batch_norm                                                   # :1524 (C23)
+        video_anchor_size = int(video_anchor_size or FLAGS.video_triangulation_anchor_size_v1)                # :1525
+        audio_anchor_size = int(audio_anchor_size or FLAGS.audio_triangulation_anchor_size_v1)                # :1526
+        if model_input.dtype == torch.uint8:
+            raise LpmError("TriangulationRelationalModel reads fp32 frames: dequantise a uint8 batch first (train.normalize_input)")
+        if random_frames:                                                                                     # :1528-1531
+            model_input = model_utils.SampleRandomFrames(model_input, num_frames.reshape(-1, 1), iterations, uniform=frame_uniform)
+        max_frames, feature_size = model_input.shape[1], model_input.shape[2]                                 # :1534-1535
+        if feature_size <= 1024:
+            raise ValueError("TriangulationRelationalModel slices a 1024-wide video and a 128-wide audio stream out of its input "
+                             f"(frame_level_models.py:1570,1576); got {feature_size} features")
+        dev = model_input.device
+        masks = dropout_masks or {}
+        reshaped_input = model_input.reshape(-1, feature_size)                                                # :1537
+        streams = (("video_t_emb", 1024, video_anchor_size, slice(0, 1024)),
+                   ("audio_t_emb", feature_size - 1024, audio_anchor_size, slice(1024, None)))
+        t_embs = [video_pooling_modules.TriangulationEmbedding(D, max_frames, K, add_batch_norm, is_training) for _, D, K, _ in streams]
+        lstms = [rnn_modules.LstmLastHiddenModule(lstm_size=D * K, lstm_layers=1, output_dim=D * K, num_frames=num_frames.reshape(-1),
+                                                  scope_id=None) for _, D, K, _ in streams]                   # :1550-1559
+        if add_batch_norm:
+            reshaped_input = layers.batch_norm(reshaped_input, is_training, "input_bn")                       # :1561-1567
+        lstm_outputs = []
+        for (scope, D, K, cols), t_emb, lstm in zip(streams, t_embs, lstms):
+            with vs.variable_scope(scope):                                                                    # :1569-1579
+                emb = t_emb.forward(reshaped_input[:, cols]).reshape(-1, max_frames, D * K)                   # (a single tensor: C36)
+                lstm_outputs.append(lstm.forward(emb))
+        det_reg = 0                                                                                           # :1581-1584 (C36)
+        activation = torch.cat(lstm_outputs, 1)                                                               # :1586
+
+        def hidden(x, name, bn_scope, key):
+            w = vs.get_variable(name, [x.shape[1], self.HIDDEN], vs.random_normal_initializer(1 / math.sqrt(self.HIDDEN)), device=dev)
+            x = x.matmul(w)
+            if add_batch_norm:
+                x = layers.batch_norm(x, is_training, bn_scope)
+            x = torch.nn.functional.leaky_relu(x, 0.2)
+            if is_training:                                          # tf.nn.dropout(keep_prob=0.5) :1604, :1620
+                keep = masks.get(key)
+                if keep is None:
+                    keep = torch.rand(x.shape, device=dev) < self.KEEP_PROB
+                x = x * keep.to(device=dev).ne(0).to(x.dtype) / self.KEEP_PROB
+            return x
+
+        activation = hidden(activation, "lstm_hidden_1", "activation_1_bn", "hidden_1")                       # :1590-1604
+        activation = hidden(activation, "lstm_hidden_2", "activation_2_bn", "hidden_2")                       # :1606-1620
+        aggregated_model = getattr(video_level_models, "MoeModel")                                            # :1622 (C37)
+        return aggregated_model().create_model(model_input=activation, vocab_size=vocab_size, is_training=is_training,
+                                               det_reg=det_reg, **unused_params)                             # :1625-1630
 
 
 class NetVladV2(models.BaseModel):

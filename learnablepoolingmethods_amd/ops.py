@@ -4715,3 +4715,97 @@ def triangulation_bn_moments(x, anchors, gamma_s, beta_s, gamma_t, beta_t, max_f
     pool_s, pool_t, bstats = _TriangulationBnMoments.apply(x, anchors.contiguous(), gamma_s, beta_s, gamma_t, beta_t, T, bool(self_attention),
                                                            bool(batch_norm), stats)
     return pool_s, pool_t, (tuple(bstats.unbind(0)) if batch_norm else None)
+
+
+# ----------------------------------------------------------------------------------------------
+# one LSTM layer: a kernel per time step each way (csrc/lstm.hip)
+# ----------------------------------------------------------------------------------------------
+def lstm_layer_ok(B, T, H) -> bool:
+    """Whether lstm_layer takes these sizes: a hidden size that is a multiple of 128, any batch B >= 1, any T >= 1, any input width."""
+    return bool(_capi.load()._lpm_lstm_supported(int(B), int(T), int(H)))
+
+
+class _LstmLayer(torch.autograd.Function):
+    """lpm_lstm_layer_fwd / _bwd between three GEMMs of torch's: xw = X Wx before the time loop, dX = dZ Wx^T and
+    dkernel = [X ; H_prev]^T dZ after it.  Saved: the inputs, the states hs, cs [B, T + 1, H] and the activated gates [B, T, 4H]."""
+
+    @staticmethod
+    def forward(ctx, x, kernel, bias, lengths, forget_bias):
+        lib = _capi.load()
+        B, T, In = x.shape
+        H = bias.shape[0] // 4
+        wh = kernel[In:]
+        if wh.data_ptr() % 16:              # (a kernel that is a view at an odd offset of a larger buffer: the 16-byte loads need a base)
+            wh = wh.clone()
+        xw = x.reshape(B * T, In).matmul(kernel[:In])
+        hs, cs = _empty((B, T + 1, H), x), _empty((B, T + 1, H), x)
+        hs[:, 0].zero_()
+        cs[:, 0].zero_()
+        gates, outputs = _empty((B, T, 4 * H), x), _empty((B, T, H), x)
+        with _timed("lstm_layer_fwd", (B, T, In, H)):
+            lib.check(lib._lpm_lstm_layer_fwd(ptr(xw), ptr(wh), 4 * H, ptr(bias), ptr(lengths), B, T, H, forget_bias, ptr(hs), ptr(cs),
+                                              ptr(gates), ptr(outputs), stream_ptr()), "lpm_lstm_layer_fwd")
+        ctx.save_for_backward(x, kernel, lengths, hs, cs, gates)
+        ctx.dims = (B, T, In, H)
+        return outputs, hs[:, T].clone(), cs[:, T].clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out, g_h, g_c):
+        lib = _capi.load()
+        x, kernel, lengths, hs, cs, gates = ctx.saved_tensors
+        B, T, In, H = ctx.dims
+        wh = kernel[In:]
+        if wh.data_ptr() % 16:
+            wh = wh.clone()
+        dhp, dc = g_h.to(torch.float32).clone().contiguous(), g_c.to(torch.float32).clone().contiguous()
+        g_out = g_out.to(torch.float32).contiguous()
+        dz = _empty((B, T, 4 * H), x)
+        with _timed("lstm_layer_bwd", (B, T, In, H)):
+            lib.check(lib._lpm_lstm_layer_bwd(ptr(wh), 4 * H, ptr(lengths), ptr(cs), ptr(gates), ptr(g_out), ptr(dhp), ptr(dc), ptr(dz),
+                                              B, T, H, stream_ptr()), "lpm_lstm_layer_bwd")
+        dz2 = dz.reshape(B * T, 4 * H)
+        dx = dz2.matmul(kernel[:In].t()).reshape(B, T, In) if ctx.needs_input_grad[0] else None
+        dkernel = dbias = None
+        if ctx.needs_input_grad[1]:
+            dkernel = torch.empty_like(kernel)
+            torch.mm(x.reshape(B * T, In).t(), dz2, out=dkernel[:In])
+            torch.mm(hs[:, :T].reshape(B * T, H).t(), dz2, out=dkernel[In:])
+        if ctx.needs_input_grad[2]:
+            dbias = dz2.sum(dim=0)
+        return dx, dkernel, dbias, None, None
+
+
+def lstm_layer(x, kernel, bias, lengths, forget_bias=1.0):
+    """One layer of TF1's BasicLSTMCell(H, forget_bias) under tf.nn.dynamic_rnn(sequence_length=lengths) on the GPU:
+    x [B, T, In] fp32, kernel [In + H, 4H] (TF's: the rows of x first, then those of h; columns gate-major i | j | f | o), bias [4H],
+    lengths [B] integers -> (outputs [B, T, H], h_last [B, H], c_last [B, H]).
+        z = [x_t, h] kernel + bias;  c' = c sigmoid(f + forget_bias) + sigmoid(i) tanh(j);  h' = tanh(c') sigmoid(o);  zero initial state.
+    From t = min(lengths[b], T) on the state is copied through and outputs[b, t] = 0: a length of 0 gives zeros everywhere, a length above
+    T means T.  Differentiable (once) in x, kernel and bias, from all three results; dx is exactly zero at masked steps.  One kernel per
+    time step each way (csrc/lstm.hip: the recurrent product on exact-fp32 MFMAs with the gate arithmetic in its epilogue); X Wx, dX and
+    dkernel are three large fp32 GEMMs outside the time loop.  No atomics: the same inputs give the same bits.  GPU only; H a multiple of
+    128 (lstm_layer_ok), any B, T, In >= 1.  rnn_modules._lstm_layer_host is the per-step torch formulation for everything else."""
+    what = "lstm_layer"
+    if not all(torch.is_tensor(t) for t in (x, kernel, bias, lengths)):
+        raise LpmError(f"{what}: x, kernel, bias and lengths must be tensors")
+    if not (x.is_cuda and kernel.is_cuda and bias.is_cuda):
+        raise LpmError(f"{what}: needs tensors on an MI355X (cuda/hip device); got {x.device} / {kernel.device} / {bias.device}.  There "
+                       "is no CPU fallback here: rnn_modules._lstm_layer_host is the host path")
+    if not (x.device == kernel.device == bias.device):
+        raise LpmError(f"{what}: x is on {x.device}, kernel on {kernel.device}, bias on {bias.device}")
+    _f32(x, what + " x"), _f32(kernel, what + " kernel"), _f32(bias, what + " bias")
+    if x.dim() != 3 or kernel.dim() != 2 or bias.dim() != 1 or min(x.shape) < 1:
+        raise LpmError(f"{what}: expected x [B, T, In], kernel [In + H, 4H] and bias [4H], all non-empty (x {tuple(x.shape)}, kernel "
+                       f"{tuple(kernel.shape)}, bias {tuple(bias.shape)})")
+    B, T, In = x.shape
+    H = bias.shape[0] // 4
+    if bias.shape[0] != 4 * H or H < 1 or tuple(kernel.shape) != (In + H, 4 * H):
+        raise LpmError(f"{what}: kernel must be [In + H, 4H] = [{In + H}, {4 * H}] for bias [{bias.shape[0]}] and x {tuple(x.shape)}; "
+                       f"got {tuple(kernel.shape)}")
+    if lengths.dim() != 1 or lengths.shape[0] != B or lengths.is_floating_point() or lengths.dtype == torch.bool:
+        raise LpmError(f"{what}: lengths must be [B] = [{B}] integers (got {tuple(lengths.shape)}, {lengths.dtype})")
+    if not lstm_layer_ok(B, T, H):
+        raise LpmError(f"{what}: the hidden size must be a multiple of 128 (got {H}); rnn_modules._lstm_layer_host takes every other shape")
+    lengths = lengths.to(x.device).clamp(0, T).to(torch.int32).contiguous()
+    return _LstmLayer.apply(x.contiguous(), kernel.contiguous(), bias.contiguous(), lengths, float(forget_bias))
