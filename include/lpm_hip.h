@@ -1230,6 +1230,44 @@ int lpm_triangulation_bn_moments_bwd(const float* x, const float* anchors, const
                                      float* dgrad, void* workspace, size_t workspace_bytes, lpm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Attention-weighted convolution moments of the triangulation embedding (video_pooling_modules.py:1108-1268
+ * TriangulationNsCnnIndirectAttentionModule, the pooling of JuhanTestModelV2): the convolution side in csrc/triangulation_moments.hip, the
+ * chain in csrc/triangulation_bn_moments.hip.  x [B * T, D] (a clip's rows contiguous), anchors [D, K] AS THEY ARE, cnn_s, cnn_t [K, F, D],
+ * J = K * D.  Per row n, with e and g as in the section above (g NOT normalised again, frames t >= 1 only):
+ *     so[n,k,f] = <cnn_s[k,f,:], e[n,k,:]>,  to[n,k,f] = <cnn_t[k,f,:], g[n,k,:]>;   per clip G_s = E E^T, G_t = g g^T over all J,
+ *     w = softmax_t(sum_u relu(G[t,u]));   pool = [(1/T') sum_t w_t out_t | mean_t (out_t - mean_t out)^2]  [B, 2 K F], element k * F + f
+ * The norms come from lpm_triangulation_bn_moments_stats (want_stats = 0) and the Grams from lpm_triangulation_bn_moments_gram with the
+ * identity table aff = (1, 0, 0, 1) x 2; relu, row sums, softmax and their backward are [B, T, T] work of the caller.  Nothing of size
+ * B * T * K * D is written in either direction; no floating-point atomics (the same inputs give the same bits); all products are exact-fp32
+ * MFMAs (the roll's one boundary column per 32-column chunk is a plain loop).
+ *   _conv:     iq = q + B * T * K -> ind [B * T, K] (1 on frames t >= 1, 0 on frame 0: the temporal operand's scale; kept for _dweights),
+ *              so, to [B * T, K * F] (to = 0 on frame 0)
+ *   _pool:     w_s [B, T], w_t [B, T-1] (both null: the plain mean) -> pool_s, pool_t [B, 2 K F], stats [2, 2, B, K F] (per stream the plain
+ *              mean of every column and the mean of the deviations from it: kept for _dout)
+ *   _dout:     g_s, g_t [B, 2 K F] -> dso, dto [B * T, K * F]:  dout[t] = (w_t gm + 2 gv ((out[t] - mean) - c)) / T'  (dto = 0 on frame 0),
+ *              and with weights dw_s [B, T], dw_t [B, T-1]:  dw[b,t] = <gm[b], out_t> / T'
+ *   _dweights: -> dcnn_s, dcnn_t [K, F, D] (overwritten)
+ *   _bwd:      m_s [B, T, T], m_t [B, T-1, T-1]: M[t,u] = [G[t,u] > 0] (dr_t + dr_u) (SYMMETRIC; both null: no attention) ->
+ *              dx [B * T, D], danchors [D, K] (overwritten):  de = cnn_s^T dso + M_s E,  dg = cnn_t^T dto + M_t g, the roll's transpose and
+ *              the clamped normalisation's backward.  workspace: 16-byte aligned, lpm_triangulation_cnn_attention_workspace_bytes(...) bytes.
+ * D in {128, 1024}, 2 <= T <= lpm_triangulation_attention_max_frames(), K >= 1, F >= 1; anything else LPM_ERR_UNSUPPORTED_SHAPE /
+ * LPM_ERR_BADARG before any launch. */
+size_t lpm_triangulation_cnn_attention_workspace_bytes(int B, int T, int D, int K);
+int lpm_triangulation_cnn_attention_conv(const float* x, const float* anchors, const float* cnn_s, const float* cnn_t, const float* iq, int B,
+                                         int T, int D, int K, int F, float* ind, float* so, float* to, lpm_stream_t stream);
+int lpm_triangulation_cnn_attention_pool(const float* so, const float* to, const float* w_s, const float* w_t, int B, int T, int K, int F,
+                                         float* pool_s, float* pool_t, float* stats, lpm_stream_t stream);
+int lpm_triangulation_cnn_attention_dout(const float* so, const float* to, const float* w_s, const float* w_t, const float* stats,
+                                         const float* g_s, const float* g_t, int B, int T, int K, int F, float* dso, float* dto, float* dw_s,
+                                         float* dw_t, lpm_stream_t stream);
+int lpm_triangulation_cnn_attention_dweights(const float* x, const float* anchors, const float* iq, const float* ind, const float* dso,
+                                             const float* dto, int B, int T, int D, int K, int F, float* dcnn_s, float* dcnn_t,
+                                             lpm_stream_t stream);
+int lpm_triangulation_cnn_attention_bwd(const float* x, const float* anchors, const float* q, const float* cnn_s, const float* cnn_t,
+                                        const float* dso, const float* dto, const float* m_s, const float* m_t, int B, int T, int D, int K, int F,
+                                        float* dx, float* danchors, void* workspace, size_t workspace_bytes, lpm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The rows of the inference CSV as text (inference.py:88-96), csrc/csv_rows.hip and csrc/format_pairs.h.  index int32 [B, k] and value
  * fp32 [B, k] (the outputs of lpm_topk_rows; any int32 is accepted) -> text uint8 [B, stride] with stride = lpm_format_pairs_stride of k
  * = 25 k rounded up to 16 (a pair is at most 11 + 1 + 12 + 1 bytes), and length int32 [B]: row r is

@@ -29,6 +29,9 @@
 //   per (frame, column) for the rest.  The temporal tile has a 33rd column (feature j + 32, which may be the next anchor's first): its
 //   M V product is a plain loop.  Sweeps 1 and 2 give a workgroup a (clip, anchor) and walk the chunks; sweep 3 gives it a (clip, chunk)
 //   and walks the anchors, adding onto its own columns of dx in turn.
+// The CONV policy of tb_bwd (triangulation_cnn_attention, JuhanTestModelV2; entry points at the end of the file): V is e / g itself, there
+//   is no batch norm (sweeps 2 and 3 only), and dV = M V + W_k^T dout, the per-anchor convolution's input gradient accumulated behind the
+//   M V product in the same MFMA accumulators (dout [B T, K F] and W [K, F, D] from global memory).
 #include "triangulation_common.h"
 
 // g = e[j] - e[j-1] must be exactly zero where both are equal, and every kernel must form V with the same roundings: no fused products
@@ -286,10 +289,18 @@ struct TbBwdArgs {
     float inv_ns, inv_nt;     // 1 / (B T), 1 / (B (T - 1)) in training mode; 0 with given statistics or without batch norm
     int B, T, K;
     float *dpart, *dot, *dx, *da_part;
+    // CONV (triangulation_cnn_attention's chain): the convolutions' weights [K, F, D] and upstream tensors dso, dto [B T, K F]
+    const float *cnn_s, *cnn_t, *dso, *dto;
+    int F;
 };
 
 // the M V product of one 32-column chunk: tP[t][c] = sum_u M[t,u] tV[u][c], rows by frame index (off = 1: M is over the frames 1 .. T-1)
-__device__ __forceinline__ void tb_mv(const float* __restrict__ m, int T, int Tp, int off, const float (*tV)[TB_LDV], float (*tP)[TB_LDV]) {
+// CONV: m may be null (no attention), and the convolution's input gradient is added in the same accumulators:
+//   tP[t][c] += sum_f dout[t][f] w[f][c],  dout the (clip, anchor)'s [T, F] block (rows KF floats apart), w the anchor's [F, D] block at the chunk
+template <bool CONV>
+__device__ __forceinline__ void tb_mv(const float* __restrict__ m, int T, int Tp, int off, const float (*tV)[TB_LDV], float (*tP)[TB_LDV],
+                                      const float* __restrict__ dout = nullptr, const float* __restrict__ w = nullptr, int64_t KF = 0, int F = 0,
+                                      int ldw = 0) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31;
     const int Tk = T - off;
     for (int job = wave; job < Tp / 32; job += TA_WAVES) {
@@ -298,18 +309,26 @@ __device__ __forceinline__ void tb_mv(const float* __restrict__ m, int T, int Tp
         f32x16 ac;
 #pragma unroll
         for (int r = 0; r < 16; ++r) ac[r] = 0.f;
+        if (!CONV || m)
         for (int s2 = 0; s2 < Tp; s2 += 2) {               // A[t][u] = M[u][t] (symmetric): read along M's rows
             const int srow = s2 + (lane >> 5), sr = srow - off;
             const float mv = (tok && sr >= 0 && sr < Tk) ? m[(int64_t)sr * Tk + tcol] : 0.f;
             ac = mfma32(mv, tV[srow][c], ac);
         }
+        if (CONV)
+            for (int f2 = 0; f2 < F; f2 += 2) {
+                const int f = f2 + (lane >> 5);
+                const bool fok = f < F;
+                const float dv = (tok && fok) ? dout[(int64_t)(t0 + c) * KF + f] : 0.f;
+                ac = mfma32(dv, fok ? w[(int64_t)f * ldw + c] : 0.f, ac);
+            }
 #pragma unroll
         for (int r = 0; r < 16; ++r) tP[t0 + mfma32_row(r, lane)][c] = ac[r];
     }
 }
 
 // one (clip, anchor, chunk) of a sweep; `first`: the first anchor this workgroup adds onto its columns of dx (sweep 3)
-template <int D, int SWEEP>
+template <int D, int SWEEP, bool CONV>
 __device__ __forceinline__ void tb_bwd_chunk(const TbBwdArgs& A, int b, int k, int c0, bool first, int Tp, float (*tV)[TB_LDV],
                                              float (*tP)[TB_LDV], float (*tR)[TA_LD], float* cw_s, float* cw_t, float* dotacc, float* dacc) {
     const int T = A.T, K = A.K, J = K * D, T1 = T - 1;
@@ -319,21 +338,34 @@ __device__ __forceinline__ void tb_bwd_chunk(const TbBwdArgs& A, int b, int k, i
     const float* iqb = A.iq + (int64_t)b * T * K;
     const bool attention = A.m_s != nullptr;
     const float two_s = 2.f / (float)T, two_t = 2.f / (float)T1;
+    // CONV: V is e / g itself (no affine map), and dV = M V + W^T dout comes whole from tb_mv
+    const int64_t KF = (int64_t)K * A.F;
+    const float* dout_s = CONV ? A.dso + ((int64_t)b * T * K + k) * A.F : nullptr;
+    const float* dout_t = CONV ? A.dto + ((int64_t)b * T * K + k) * A.F : nullptr;
     // ---- spatial ----
     {
-        const float sc = A.aff[j], mu = A.aff[J + j], be = A.aff[2 * J + j], istd = A.aff[3 * J + j];
-        const float gm = A.g_s[(int64_t)b * 2 * J + j], gq = A.g_s[(int64_t)b * 2 * J + J + j];
-        const float rb = A.rawbar[(int64_t)b * J + j], cr = A.corr[(int64_t)b * J + j];
+        const float sc = CONV ? 1.f : A.aff[j], mu = CONV ? 0.f : A.aff[J + j], be = CONV ? 0.f : A.aff[2 * J + j];
+        const float istd = CONV ? 1.f : A.aff[3 * J + j];
+        const float gm = CONV ? 0.f : A.g_s[(int64_t)b * 2 * J + j], gq = CONV ? 0.f : A.g_s[(int64_t)b * 2 * J + J + j];
+        const float rb = CONV ? 0.f : A.rawbar[(int64_t)b * J + j], cr = CONV ? 0.f : A.corr[(int64_t)b * J + j];
         float c1 = 0.f, c2 = 0.f;
         if (SWEEP > 1) {
             c1 = A.dgrad[j] * A.inv_ns;
             c2 = A.dgrad[J + j] * A.inv_ns;
         }
-        if (attention) {
+        if (CONV) {
+            if (attention)
+                for (int t = r0; t < Tp; t += 8)
+                    tV[t][c] = t < T ? tb_e(xb + (int64_t)t * D, A.anchors, iqb + (int64_t)t * K, K, k, d) : 0.f;
+            __syncthreads();
+            tb_mv<true>(attention ? A.m_s + (int64_t)b * T * T : nullptr, T, Tp, 0, tV, tP, dout_s, A.cnn_s + ((int64_t)k * A.F) * D + c0, KF, A.F,
+                        D);
+            __syncthreads();
+        } else if (attention) {
             for (int t = r0; t < Tp; t += 8)
                 tV[t][c] = t < T ? tb_affine(tb_e(xb + (int64_t)t * D, A.anchors, iqb + (int64_t)t * K, K, k, d), sc, mu, be) : 0.f;
             __syncthreads();
-            tb_mv(A.m_s + (int64_t)b * T * T, T, Tp, 0, tV, tP);
+            tb_mv<false>(A.m_s + (int64_t)b * T * T, T, Tp, 0, tV, tP);
             __syncthreads();
         }
         float sb = 0.f, sg = 0.f;
@@ -342,12 +374,12 @@ __device__ __forceinline__ void tb_bwd_chunk(const TbBwdArgs& A, int b, int k, i
             if (t < T) {
                 const float raw = tb_e(xb + (int64_t)t * D, A.anchors, iqb + (int64_t)t * K, K, k, d);
                 const float hat = (raw - mu) * istd;
-                const float dV = cw_s[t] * gm + (two_s * (sc * ((raw - rb) - cr))) * gq + (attention ? tP[t][c] : 0.f);
+                const float dV = CONV ? tP[t][c] : cw_s[t] * gm + (two_s * (sc * ((raw - rb) - cr))) * gq + (attention ? tP[t][c] : 0.f);
                 if (SWEEP == 1) {
                     sb += dV;
                     sg = fmaf(dV, hat, sg);
                 } else {
-                    draw = sc * ((dV - c1) - hat * c2);
+                    draw = CONV ? dV : sc * ((dV - c1) - hat * c2);
                 }
             }
             if (SWEEP > 1) tR[t][c] = draw;
@@ -368,12 +400,12 @@ __device__ __forceinline__ void tb_bwd_chunk(const TbBwdArgs& A, int b, int k, i
     __syncthreads();
     // ---- temporal: columns 0 .. 31 are this chunk's; column 32 is feature j0 + 32 (sweeps 2, 3: the roll's other term) ----
     {
-        const float* af = A.aff + (int64_t)4 * J;
+        const float* af = CONV ? nullptr : A.aff + (int64_t)4 * J;
         const int jx = (k * D + c0 + TA_CH) % J, kx = jx / D, dx_ = jx % D;         // the 33rd column
-        const float sc = af[j], mu = af[J + j], be = af[2 * J + j], istd = af[3 * J + j];
-        const float gm = A.g_t[(int64_t)b * 2 * J + j], gq = A.g_t[(int64_t)b * 2 * J + J + j];
-        const float rb = A.rawbar[((int64_t)A.B + b) * J + j], cr = A.corr[((int64_t)A.B + b) * J + j];
-        const float scx = af[jx], mux = af[J + jx], bex = af[2 * J + jx], istdx = af[3 * J + jx];
+        const float sc = CONV ? 1.f : af[j], mu = CONV ? 0.f : af[J + j], be = CONV ? 0.f : af[2 * J + j], istd = CONV ? 1.f : af[3 * J + j];
+        const float gm = CONV ? 0.f : A.g_t[(int64_t)b * 2 * J + j], gq = CONV ? 0.f : A.g_t[(int64_t)b * 2 * J + J + j];
+        const float rb = CONV ? 0.f : A.rawbar[((int64_t)A.B + b) * J + j], cr = CONV ? 0.f : A.corr[((int64_t)A.B + b) * J + j];
+        const float scx = CONV ? 1.f : af[jx], mux = CONV ? 0.f : af[J + jx], bex = CONV ? 0.f : af[2 * J + jx], istdx = CONV ? 1.f : af[3 * J + jx];
         float c1 = 0.f, c2 = 0.f, c1x = 0.f, c2x = 0.f;
         if (SWEEP > 1) {
             c1 = A.dgrad[2 * J + j] * A.inv_nt;
@@ -382,7 +414,28 @@ __device__ __forceinline__ void tb_bwd_chunk(const TbBwdArgs& A, int b, int k, i
             c2x = A.dgrad[3 * J + jx] * A.inv_nt;
         }
         const float* mt = attention ? A.m_t + (int64_t)b * T1 * T1 : nullptr;
-        if (attention) {
+        if (CONV) {
+            if (attention) {
+                for (int t = r0; t < Tp; t += 8)
+                    tV[t][c] = (t >= 1 && t < T) ? tb_g<D>(xb + (int64_t)t * D, A.anchors, iqb + (int64_t)t * K, K, k, d) : 0.f;
+                for (int t = threadIdx.x; t < Tp; t += 64 * TA_WAVES)
+                    tV[t][TA_CH] = (t >= 1 && t < T) ? tb_g<D>(xb + (int64_t)t * D, A.anchors, iqb + (int64_t)t * K, K, kx, dx_) : 0.f;
+            }
+            __syncthreads();
+            tb_mv<true>(mt, T, Tp, 1, tV, tP, dout_t, A.cnn_t + ((int64_t)k * A.F) * D + c0, KF, A.F, D);
+            for (int t = threadIdx.x; t < Tp; t += 64 * TA_WAVES) {             // the 33rd column: plain loops over u and over f
+                float acc = 0.f;
+                if (t >= 1 && t < T) {
+                    if (attention)
+                        for (int u = 1; u < T; ++u) acc = fmaf(mt[(int64_t)(u - 1) * T1 + (t - 1)], tV[u][TA_CH], acc);
+                    const float* dr = A.dto + (((int64_t)b * T + t) * K + kx) * A.F;
+                    const float* wx = A.cnn_t + ((int64_t)kx * A.F) * D + dx_;
+                    for (int f = 0; f < A.F; ++f) acc = fmaf(dr[f], wx[(int64_t)f * D], acc);
+                }
+                tP[t][TA_CH] = acc;
+            }
+            __syncthreads();
+        } else if (attention) {
             for (int t = r0; t < Tp; t += 8)
                 tV[t][c] = (t >= 1 && t < T) ? tb_affine(tb_g<D>(xb + (int64_t)t * D, A.anchors, iqb + (int64_t)t * K, K, k, d), sc, mu, be) : 0.f;
             if (SWEEP > 1)
@@ -390,7 +443,7 @@ __device__ __forceinline__ void tb_bwd_chunk(const TbBwdArgs& A, int b, int k, i
                     tV[t][TA_CH] = (t >= 1 && t < T) ? tb_affine(tb_g<D>(xb + (int64_t)t * D, A.anchors, iqb + (int64_t)t * K, K, kx, dx_), scx, mux, bex)
                                                      : 0.f;
             __syncthreads();
-            tb_mv(mt, T, Tp, 1, tV, tP);
+            tb_mv<false>(mt, T, Tp, 1, tV, tP);
             if (SWEEP > 1)
                 for (int t = threadIdx.x; t < Tp; t += 64 * TA_WAVES) {
                     float acc = 0.f;
@@ -406,12 +459,12 @@ __device__ __forceinline__ void tb_bwd_chunk(const TbBwdArgs& A, int b, int k, i
             if (t >= 1 && t < T) {
                 const float raw = tb_g<D>(xb + (int64_t)t * D, A.anchors, iqb + (int64_t)t * K, K, k, d);
                 const float hat = (raw - mu) * istd;
-                const float dV = cw_t[t] * gm + (two_t * (sc * ((raw - rb) - cr))) * gq + (attention ? tP[t][c] : 0.f);
+                const float dV = CONV ? tP[t][c] : cw_t[t] * gm + (two_t * (sc * ((raw - rb) - cr))) * gq + (attention ? tP[t][c] : 0.f);
                 if (SWEEP == 1) {
                     sb += dV;
                     sg = fmaf(dV, hat, sg);
                 } else {
-                    draw = sc * ((dV - c1) - hat * c2);
+                    draw = CONV ? dV : sc * ((dV - c1) - hat * c2);
                 }
             }
             if (SWEEP > 1) tV[t][c] = draw;                  // (this thread's own element: nothing else reads it before the barrier)
@@ -431,15 +484,15 @@ __device__ __forceinline__ void tb_bwd_chunk(const TbBwdArgs& A, int b, int k, i
             return;
         }
         // the 33rd column's draw
-        const float gmx = A.g_t[(int64_t)b * 2 * J + jx], gqx = A.g_t[(int64_t)b * 2 * J + J + jx];
-        const float rbx = A.rawbar[((int64_t)A.B + b) * J + jx], crx = A.corr[((int64_t)A.B + b) * J + jx];
+        const float gmx = CONV ? 0.f : A.g_t[(int64_t)b * 2 * J + jx], gqx = CONV ? 0.f : A.g_t[(int64_t)b * 2 * J + J + jx];
+        const float rbx = CONV ? 0.f : A.rawbar[((int64_t)A.B + b) * J + jx], crx = CONV ? 0.f : A.corr[((int64_t)A.B + b) * J + jx];
         for (int t = threadIdx.x; t < Tp; t += 64 * TA_WAVES) {
             float draw = 0.f;
             if (t >= 1 && t < T) {
                 const float raw = tb_g<D>(xb + (int64_t)t * D, A.anchors, iqb + (int64_t)t * K, K, kx, dx_);
                 const float hat = (raw - mux) * istdx;
-                const float dV = cw_t[t] * gmx + (two_t * (scx * ((raw - rbx) - crx))) * gqx + (attention ? tP[t][TA_CH] : 0.f);
-                draw = scx * ((dV - c1x) - hat * c2x);
+                const float dV = CONV ? tP[t][TA_CH] : cw_t[t] * gmx + (two_t * (scx * ((raw - rbx) - crx))) * gqx + (attention ? tP[t][TA_CH] : 0.f);
+                draw = CONV ? dV : scx * ((dV - c1x) - hat * c2x);
             }
             tV[t][TA_CH] = draw;
         }
@@ -481,7 +534,7 @@ __device__ __forceinline__ void tb_bwd_chunk(const TbBwdArgs& A, int b, int k, i
     __syncthreads();
 }
 
-template <int D, int SWEEP>
+template <int D, int SWEEP, bool CONV = false>
 __global__ __launch_bounds__(64 * TA_WAVES) void tb_bwd_kernel(const TbBwdArgs A) {
     extern __shared__ __attribute__((aligned(16))) float tb_sh[];
     const int T = A.T, K = A.K, Tp = (T + 31) & ~31;
@@ -494,15 +547,15 @@ __global__ __launch_bounds__(64 * TA_WAVES) void tb_bwd_kernel(const TbBwdArgs A
     const int b = SWEEP == 3 ? blockIdx.x / NCH : blockIdx.x / K;
     const int rest = SWEEP == 3 ? blockIdx.x % NCH : blockIdx.x % K;
     for (int t = threadIdx.x; t < Tp; t += 64 * TA_WAVES) {    // the mean's weight of every frame, by frame index
-        cw_s[t] = t < T ? (A.w_s ? A.w_s[(int64_t)b * T + t] : 1.f) / (float)T : 0.f;
-        cw_t[t] = (t >= 1 && t < T) ? (A.w_t ? A.w_t[(int64_t)b * (T - 1) + t - 1] : 1.f) / (float)(T - 1) : 0.f;
+        cw_s[t] = (!CONV && t < T) ? (A.w_s ? A.w_s[(int64_t)b * T + t] : 1.f) / (float)T : 0.f;
+        cw_t[t] = (!CONV && t >= 1 && t < T) ? (A.w_t ? A.w_t[(int64_t)b * (T - 1) + t - 1] : 1.f) / (float)(T - 1) : 0.f;
         dotacc[t] = 0.f;
     }
     __syncthreads();
     if (SWEEP == 3) {
-        for (int k = 0; k < K; ++k) tb_bwd_chunk<D, SWEEP>(A, b, k, rest * TA_CH, k == 0, Tp, tV, tP, tR, cw_s, cw_t, dotacc, dacc);
+        for (int k = 0; k < K; ++k) tb_bwd_chunk<D, SWEEP, CONV>(A, b, k, rest * TA_CH, k == 0, Tp, tV, tP, tR, cw_s, cw_t, dotacc, dacc);
     } else {
-        for (int c0 = 0; c0 < D; c0 += TA_CH) tb_bwd_chunk<D, SWEEP>(A, b, rest, c0, false, Tp, tV, tP, tR, cw_s, cw_t, dotacc, dacc);
+        for (int c0 = 0; c0 < D; c0 += TA_CH) tb_bwd_chunk<D, SWEEP, CONV>(A, b, rest, c0, false, Tp, tV, tP, tR, cw_s, cw_t, dotacc, dacc);
         if (SWEEP == 2)
             for (int t = threadIdx.x; t < T; t += 64 * TA_WAVES) A.dot[((int64_t)b * T + t) * K + rest] = dotacc[t];
     }
@@ -647,6 +700,7 @@ extern "C" int lpm_triangulation_bn_moments_bwd(const float* x, const float* anc
     A.inv_ns = training ? 1.f / (float)BT : 0.f;
     A.inv_nt = training ? 1.f / (float)(BT - B) : 0.f;
     A.B = B; A.T = T; A.K = K;
+    A.cnn_s = A.cnn_t = A.dso = A.dto = nullptr; A.F = 0;
     A.dpart = (float*)workspace;
     A.dot = A.dpart + (size_t)4 * B * J;
     A.da_part = A.dot + (size_t)BT * K;
@@ -662,6 +716,51 @@ extern "C" int lpm_triangulation_bn_moments_bwd(const float* x, const float* anc
         }
         hipLaunchKernelGGL((tb_bwd_kernel<DD, 2>), grid_k, block, lds, s, A);
         hipLaunchKernelGGL((tb_bwd_kernel<DD, 3>), grid_c, block, lds, s, A);
+    });
+    if (const int rc = ta_reduce_partials(dx, A.da_part, B, T, D, K, 1, TP_SUM_CHUNK, dx, danchors, s, name)) return rc;
+    return check_launch(name);
+}
+
+// ---- the chain of triangulation_cnn_attention (TriangulationNsCnnIndirectAttentionModule, JuhanTestModelV2): tb_bwd's sweeps 2 and 3 under the
+// CONV policy -- V = e / g themselves, dV = M V + W^T dout from one accumulator, no batch norm, hence no sweep 1 ----
+extern "C" size_t lpm_triangulation_cnn_attention_workspace_bytes(int B, int T, int D, int K) {
+    if (B <= 0 || T <= 1 || D <= 0 || K <= 0) return 0;
+    return ((size_t)B * T * K + (size_t)B * K * D) * sizeof(float);                 // the dot products, danchors partials
+}
+
+extern "C" int lpm_triangulation_cnn_attention_bwd(const float* x, const float* anchors, const float* q, const float* cnn_s, const float* cnn_t,
+                                                   const float* dso, const float* dto, const float* m_s, const float* m_t, int B, int T, int D,
+                                                   int K, int F, float* dx, float* danchors, void* workspace, size_t workspace_bytes,
+                                                   lpm_stream_t stream) {
+    using namespace lpm;
+    const char* name = "lpm_triangulation_cnn_attention_bwd";
+    LPM_REQUIRE(x && anchors && q && cnn_s && cnn_t && dso && dto && dx && danchors, LPM_ERR_BADARG, "%s: null pointer", name);
+    LPM_REQUIRE(!m_s == !m_t, LPM_ERR_BADARG, "%s: M of both streams, or none", name);
+    if (const int rc = tb_check(name, B, T, D, K)) return rc;
+    LPM_REQUIRE(F >= 1 && (int64_t)B * T * K * F < (1ll << 31), LPM_ERR_UNSUPPORTED_SHAPE, "%s: need F >= 1 and B * T * K * F < 2^31 (F=%d)", name, F);
+    LPM_REQUIRE(workspace && workspace_bytes >= lpm_triangulation_cnn_attention_workspace_bytes(B, T, D, K), LPM_ERR_WORKSPACE,
+                "%s: workspace too small", name);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t BT = (int64_t)B * T;
+    const size_t lds = tb_bwd_lds(T);
+    if (const int rc = tp_reserve_lds<tb_bwd_kernel<1024, 2, true>, tb_bwd_kernel<1024, 3, true>, tb_bwd_kernel<128, 2, true>,
+                                      tb_bwd_kernel<128, 3, true>>(name, (int)tb_bwd_lds(TA_MAX_FRAMES)))
+        return rc;
+    TbBwdArgs A;
+    A.x = x; A.anchors = anchors; A.q = q; A.iq = q + BT * K; A.aff = nullptr; A.w_s = A.w_t = nullptr; A.m_s = m_s; A.m_t = m_t;
+    A.rawbar = A.corr = A.g_s = A.g_t = A.dgrad = nullptr;
+    A.inv_ns = A.inv_nt = 0.f;
+    A.B = B; A.T = T; A.K = K;
+    A.cnn_s = cnn_s; A.cnn_t = cnn_t; A.dso = dso; A.dto = dto; A.F = F;
+    A.dpart = nullptr;
+    A.dot = (float*)workspace;
+    A.da_part = A.dot + (size_t)BT * K;
+    A.dx = dx;
+    const dim3 block(64 * TA_WAVES), grid_k((unsigned)(B * K)), grid_c((unsigned)(B * (D / TA_CH)));
+    tp_dispatch_d(D, [&](auto d) {
+        constexpr int DD = decltype(d)::value;
+        hipLaunchKernelGGL((tb_bwd_kernel<DD, 2, true>), grid_k, block, lds, s, A);
+        hipLaunchKernelGGL((tb_bwd_kernel<DD, 3, true>), grid_c, block, lds, s, A);
     });
     if (const int rc = ta_reduce_partials(dx, A.da_part, B, T, D, K, 1, TP_SUM_CHUNK, dx, danchors, s, name)) return rc;
     return check_launch(name);

@@ -594,3 +594,153 @@ extern "C" int lpm_triangulation_moments_bwd(const float* x, const float* anchor
     if (const int rc = ta_reduce_partials(dx, da_part, NRT, TV_ROWS, D, K, 1, TP_SUM_CHUNK, dx, danchors, s, name)) return rc;
     return check_launch(name);
 }
+
+// ---- the convolution side of triangulation_cnn_attention (TriangulationNsCnnIndirectAttentionModule :1108-1268, JuhanTestModelV2) ----
+// The temporal operand is g itself, NOT normalised again: tv_conv and tv_dw run as they are with `it` = ind [B T, K], 1 on the frames
+// t >= 1 and 0 on frame 0 of a clip (a product with 1 is exact), so the walks above exist once.  The pools take the softmax weights of
+// the caller's Grams:  pool = [ (1/T') sum_t w_t out_t  |  mean_t (out_t - mean_t out)^2 ]  (the plain mean without weights), and the
+// backward's  dout[t] = (w_t gm + 2 gv ((out[t] - mean) - c)) / T',  dw[t] = <gm, out[t]> / T'.
+namespace lpm {
+
+__global__ __launch_bounds__(256) void tc_ind_kernel(int64_t BTK, int T, int K, float* __restrict__ ind) {
+    const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (m < BTK) ind[m] = (m / K) % T ? 1.f : 0.f;
+}
+
+// a thread per (clip, column), blockIdx.y = stream: pool [B, 2 K F]; stats [2, 2, B, K F] = each stream's plain mean, then the mean of the
+// deviations from it (what the rounded mean is off by); sums over t two-level
+__global__ __launch_bounds__(256) void tc_pool_kernel(const float* __restrict__ so, const float* __restrict__ to, const float* __restrict__ w_s,
+                                                      const float* __restrict__ w_t, int B, int T, int64_t KF, float* __restrict__ pool_s,
+                                                      float* __restrict__ pool_t, float* __restrict__ stats) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= B * KF) return;
+    const int64_t b = i / KF, j = i % KF;
+    const int z = blockIdx.y, Tz = T - z;
+    const float* v = (z ? to : so) + b * T * KF + j;
+    const float* w = z ? w_t : w_s;                          // null: the plain mean
+    if (w) w += b * Tz;
+    const float cnt = (float)Tz;
+    float tot = 0.f, acc = 0.f, wtot = 0.f, wacc = 0.f;
+    for (int t = z; t < T; ++t) {
+        const float val = v[t * KF];
+        acc += val;
+        if (w) wacc = fmaf(w[t - z], val, wacc);
+        if (((t - z) & (TP_SUM_CHUNK - 1)) == TP_SUM_CHUNK - 1) {
+            tot += acc;
+            wtot += wacc;
+            acc = wacc = 0.f;
+        }
+    }
+    const float mean = (tot + acc) / cnt, wsum = wtot + wacc;
+    float dtot = 0.f, dacc = 0.f;
+    tot = acc = 0.f;
+    for (int t = z; t < T; ++t) {
+        const float dev = v[t * KF] - mean;
+        acc = fmaf(dev, dev, acc);
+        dacc += dev;
+        if (((t - z) & (TP_SUM_CHUNK - 1)) == TP_SUM_CHUNK - 1) {
+            tot += acc;
+            dtot += dacc;
+            acc = dacc = 0.f;
+        }
+    }
+    float* pool = (z ? pool_t : pool_s) + b * 2 * KF;
+    pool[j] = w ? wsum / cnt : mean;
+    pool[KF + j] = (tot + acc) / cnt;
+    float* st = stats + (int64_t)z * 2 * B * KF;
+    st[b * KF + j] = mean;
+    st[(B + b) * KF + j] = (dtot + dacc) / cnt;
+}
+
+// a workgroup per (clip, frame), blockIdx.y = stream: dout [B T, K F] (the temporal one zero on frame 0) and dw[b,t] = <gm[b], out_t> / T'
+__global__ __launch_bounds__(256) void tc_dout_kernel(const float* __restrict__ so, const float* __restrict__ to, const float* __restrict__ w_s,
+                                                      const float* __restrict__ w_t, const float* __restrict__ stats, const float* __restrict__ g_s,
+                                                      const float* __restrict__ g_t, int B, int T, int64_t KF, float* __restrict__ dso,
+                                                      float* __restrict__ dto, float* __restrict__ dw_s, float* __restrict__ dw_t) {
+    __shared__ float red[4];
+    const int z = blockIdx.y, b = blockIdx.x / T, t = blockIdx.x % T, Tz = T - z;
+    const int64_t n = (int64_t)b * T + t;
+    float* dout = (z ? dto : dso) + n * KF;
+    if (z && t == 0) {                                     // (uniform over the workgroup)
+        for (int64_t j = threadIdx.x; j < KF; j += 256) dout[j] = 0.f;
+        return;
+    }
+    const float* out = (z ? to : so) + n * KF;
+    const float* g = (z ? g_t : g_s) + (int64_t)b * 2 * KF;
+    const float* st = stats + (int64_t)z * 2 * B * KF;
+    const float *mean = st + (int64_t)b * KF, *corr = st + (int64_t)(B + b) * KF;
+    const float* w = z ? w_t : w_s;
+    const float wt = w ? w[(int64_t)b * Tz + t - z] : 1.f, cnt = (float)Tz;
+    float acc = 0.f;
+    for (int64_t j = threadIdx.x; j < KF; j += 256) {
+        const float v = out[j], gm = g[j];
+        dout[j] = (wt * gm + 2.f * g[KF + j] * ((v - mean[j]) - corr[j])) / cnt;
+        acc = fmaf(gm, v, acc);
+    }
+    acc = wave_sum_dpp(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0 && w) {
+        const float d = ((red[0] + red[1]) + (red[2] + red[3])) / cnt;
+        if (z) dw_t[(int64_t)b * (T - 1) + t - 1] = d; else dw_s[n] = d;
+    }
+}
+
+}  // namespace lpm
+
+extern "C" int lpm_triangulation_cnn_attention_conv(const float* x, const float* anchors, const float* cnn_s, const float* cnn_t, const float* iq,
+                                                    int B, int T, int D, int K, int F, float* ind, float* so, float* to, lpm_stream_t stream) {
+    using namespace lpm;
+    const char* name = "lpm_triangulation_cnn_attention_conv";
+    LPM_REQUIRE(x && anchors && cnn_s && cnn_t && iq && ind && so && to, LPM_ERR_BADARG, "%s: null pointer", name);
+    if (const int rc = tv_check(name, B, T, D, K, F)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t BT = (int64_t)B * T, BTK = BT * K;
+    const int NR = tv_row_tiles(BT), NF = (F + 31) / 32;
+    hipLaunchKernelGGL(tc_ind_kernel, dim3((unsigned)((BTK + 255) / 256)), dim3(256), 0, s, BTK, T, K, ind);
+    tp_dispatch_d(D, [&](auto d) {
+        hipLaunchKernelGGL(tv_conv_kernel<decltype(d)::value>, dim3((unsigned)((int64_t)K * NF * NR)), dim3(64 * TA_WAVES), 0, s, x, anchors, cnn_s,
+                           cnn_t, iq, ind, BT, K, F, NR, so, to);
+    });
+    return check_launch(name);
+}
+
+extern "C" int lpm_triangulation_cnn_attention_pool(const float* so, const float* to, const float* w_s, const float* w_t, int B, int T, int K, int F,
+                                                    float* pool_s, float* pool_t, float* stats, lpm_stream_t stream) {
+    using namespace lpm;
+    const char* name = "lpm_triangulation_cnn_attention_pool";
+    LPM_REQUIRE(so && to && pool_s && pool_t && stats && !w_s == !w_t, LPM_ERR_BADARG, "%s: null pointer", name);
+    if (const int rc = tv_check(name, B, T, 128, K, F)) return rc;
+    const int64_t KF = (int64_t)K * F, cols = B * KF;
+    hipLaunchKernelGGL(tc_pool_kernel, dim3((unsigned)((cols + 255) / 256), 2), dim3(256), 0, (hipStream_t)stream, so, to, w_s, w_t, B, T, KF, pool_s,
+                       pool_t, stats);
+    return check_launch(name);
+}
+
+extern "C" int lpm_triangulation_cnn_attention_dout(const float* so, const float* to, const float* w_s, const float* w_t, const float* stats,
+                                                    const float* g_s, const float* g_t, int B, int T, int K, int F, float* dso, float* dto,
+                                                    float* dw_s, float* dw_t, lpm_stream_t stream) {
+    using namespace lpm;
+    const char* name = "lpm_triangulation_cnn_attention_dout";
+    LPM_REQUIRE(so && to && stats && g_s && g_t && dso && dto && !w_s == !w_t && !w_s == !dw_s && !w_t == !dw_t, LPM_ERR_BADARG,
+                "%s: null pointer (the weights and dw of both streams, or none)", name);
+    if (const int rc = tv_check(name, B, T, 128, K, F)) return rc;
+    hipLaunchKernelGGL(tc_dout_kernel, dim3((unsigned)(B * T), 2), dim3(256), 0, (hipStream_t)stream, so, to, w_s, w_t, stats, g_s, g_t, B, T,
+                       (int64_t)K * F, dso, dto, dw_s, dw_t);
+    return check_launch(name);
+}
+
+extern "C" int lpm_triangulation_cnn_attention_dweights(const float* x, const float* anchors, const float* iq, const float* ind, const float* dso,
+                                                        const float* dto, int B, int T, int D, int K, int F, float* dcnn_s, float* dcnn_t,
+                                                        lpm_stream_t stream) {
+    using namespace lpm;
+    const char* name = "lpm_triangulation_cnn_attention_dweights";
+    LPM_REQUIRE(x && anchors && iq && ind && dso && dto && dcnn_s && dcnn_t, LPM_ERR_BADARG, "%s: null pointer", name);
+    if (const int rc = tv_check(name, B, T, D, K, F)) return rc;
+    const int NF = (F + 31) / 32;
+    tp_dispatch_d(D, [&](auto d) {
+        hipLaunchKernelGGL(tv_dw_kernel<decltype(d)::value>, dim3((unsigned)((int64_t)K * NF * (D / (32 * TA_WAVES)))), dim3(64 * TA_WAVES), 0,
+                           (hipStream_t)stream, x, anchors, iq, ind, dso, dto, (int64_t)B * T, K, F, dcnn_s, dcnn_t);
+    });
+    return check_launch(name);
+}

@@ -122,6 +122,26 @@ FLAGS.define("triangulation_v1_fused", False, "build extension: on the GPU each 
              "the mean and variance over the frames without any [B, T, K*D] tensor); False: TriangulationCnnIndirectAttentionModule.pool "
              "materialises it (the CPU path; same variables, same results).  Off until tools/bench_triangulation_v1.py has shown the fused "
              "path not slower at both model-default shapes (profiles/bench_triangulation_v1.json)")
+FLAGS.define("jtmv2_iteration", 200, "JuhanTestModelV2 (frame_level_models.py:158): sampled frames per clip")
+FLAGS.define("jtmv2_add_batch_norm", True, "JuhanTestModelV2 (:160): batch norm inside each stream's module and on the joined streams")
+FLAGS.define("jtmv2_sample_random_frames", True, "JuhanTestModelV2 (:162): defined and read nowhere, as written")
+FLAGS.define("jtmv2_video_anchor_size", 32, "JuhanTestModelV2 (:164): anchors of the video stream")
+FLAGS.define("jtmv2_audio_anchor_size", 8, "JuhanTestModelV2 (:166): anchors of the audio stream")
+FLAGS.define("jtmv2_video_kernel_size", 64, "JuhanTestModelV2 (:168): filters per anchor of the video stream's two convolutions")
+FLAGS.define("jtmv2_audio_kernel_size", 16, "JuhanTestModelV2 (:170): filters per anchor of the audio stream's two convolutions")
+FLAGS.define("jtmv2_video_hidden", 2048, "JuhanTestModelV2 (:172): width of the video stream's hidden layer")
+FLAGS.define("jtmv2_video_output_dim", 2048, "JuhanTestModelV2 (:174): width of the video stream's fused output")
+FLAGS.define("jtmv2_audio_hidden", 256, "JuhanTestModelV2 (:176): width of the audio stream's hidden layer")
+FLAGS.define("jtmv2_audio_output_dim", 256, "JuhanTestModelV2 (:178): width of the audio stream's fused output")
+FLAGS.define("jtmv2_use_attention", True, "JuhanTestModelV2 (:180): the soft-attention weights on the pooled means")
+FLAGS.define("jtmv2_use_relu", False, "JuhanTestModelV2 (:182): relu behind the hidden and the fusion layer")
+FLAGS.define("triangulation_v2_fused", False, "build extension: on the GPU each stream of JuhanTestModelV2 pools through "
+             "ops.triangulation_cnn_attention_moments (the norms, the Grams, the softmax weights, the per-anchor convolutions of the embedding "
+             "and of its rolled differences and their weighted mean and variance over the frames, without any [B, T, K*D] tensor); False: "
+             "TriangulationNsCnnIndirectAttentionModule.pool materialises it (the CPU path; same variables, same results).  Off: "
+             "tools/bench_triangulation_v2.py measured forward + backward of one stream at 37.3 ms fused against 11.6 ms at (B, T, D, K, F) = "
+             "(16, 200, 1024, 32, 64) and 3.44 against 1.51 ms at (16, 200, 128, 8, 16) (with 148 against 2594 MiB and 19 against 125 MiB "
+             "allocated), and the default is on only if the fused path is not slower at both (profiles/bench_triangulation_v2.json)")
 FLAGS.define("batch_norm", True, "TriangulationRelationalModel (frame_level_models.py:1503): True iff add batch normalization")
 FLAGS.define("audio_triangulation_anchor_size_v1", 4, "TriangulationRelationalModel (:1505): anchors of the audio stream")
 FLAGS.define("video_triangulation_anchor_size_v1", 16, "TriangulationRelationalModel (:1507): anchors of the video stream")

@@ -1,7 +1,7 @@
 """NetVLAD prototypes behind the reference's model-registry API
 (reference: frame_level_models.py:2193-2513 NetVladV1 / NetVladV2, :2765-2877 NetVLAD / LightVLAD) and the triangulation-embedding
 family's RegularizedTriangulationModel (:1148-1307), SoftAttentionTriangulationModel (:965-1145), TriangulationCnnClusterModel
-(:757-939), JuhanTestModelV5 (:491-606), JuhanTestModelV1 (:59-154) and the recurrent TriangulationRelationalModel (:1511-1630).
+(:757-939), JuhanTestModelV5 (:491-606), JuhanTestModelV1 (:59-154), JuhanTestModelV2 (:158-268) and the recurrent TriangulationRelationalModel (:1511-1630).
 
 Same names, ``create_model`` signature, variable names and output contract as the reference; the hot
 ops (frame sampling + input_bn, soft-assignment GEMM, fused softmax/residual aggregation/normalise,
@@ -689,6 +689,61 @@ class JuhanTestModelV1(models.BaseModel):
         aggregated_model = getattr(video_level_models, "ClassLearningFourNnModel")
         return aggregated_model().create_model(model_input=activation, vocab_size=vocab_size, is_training=is_training,
                                                **unused_params)                                              # :147-154
+
+
+class JuhanTestModelV2(models.BaseModel):
+    """One TriangulationNsCnnIndirectAttentionModule per stream (the triangulation embedding against orthogonally initialised anchors and
+    its rolled differences, a convolution per anchor over each, soft-attention weights over the frames from the relu'd Gram of the
+    embedding, the weighted mean and the variance of the convolutions' results, a hidden layer and a fusion layer), a batch norm of the
+    joined streams and the class-learning four-layer classifier (frame_level_models.py:158-268).  No input batch norm.  As written:
+    SURVEY App. C29, C32-C34, C39 (and C23).
+
+    On the GPU with FLAGS.triangulation_v2_fused each stream's pooling goes through ops.triangulation_cnn_attention_moments: no
+    [(B*T), K*D] tensor (419 MB at the video defaults B = 16, T = 200, K = 32, D = 1024) is written; otherwise
+    TriangulationNsCnnIndirectAttentionModule.pool materialises them.  The variables and the results are the same either way.
+    ``frame_uniform`` [B, iterations] replaces the random draw of SampleRandomFrames; ``video_anchor_size``, ``audio_anchor_size``,
+    ``video_kernel_size``, ``audio_kernel_size``, ``video_hidden``, ``audio_hidden``, ``video_output_dim`` and ``audio_output_dim``
+    override the flags (the reference reads the flags only)."""
+
+    def create_model(self, model_input, vocab_size, num_frames, iterations=None, add_batch_norm=None, sample_random_frames=None,
+                     hidden_size=None, is_training=True, frame_uniform=None, video_anchor_size=None, audio_anchor_size=None,
+                     video_kernel_size=None, audio_kernel_size=None, video_hidden=None, audio_hidden=None, video_output_dim=None,
+                     audio_output_dim=None, quantised_training=False, **unused_params):
+        iterations = iterations or FLAGS.jtmv2_iteration                                                      # :197
+        add_batch_norm = add_batch_norm or FLAGS.jtmv2_add_batch_norm                                         # :198 (C23)
+        video_anchor_size = int(video_anchor_size or FLAGS.jtmv2_video_anchor_size)                           # :199-206
+        audio_anchor_size = int(audio_anchor_size or FLAGS.jtmv2_audio_anchor_size)
+        video_hidden = int(video_hidden or FLAGS.jtmv2_video_hidden)
+        audio_hidden = int(audio_hidden or FLAGS.jtmv2_audio_hidden)
+        video_kernel_size = int(video_kernel_size or FLAGS.jtmv2_video_kernel_size)
+        audio_kernel_size = int(audio_kernel_size or FLAGS.jtmv2_audio_kernel_size)
+        video_output_dim = int(video_output_dim or FLAGS.jtmv2_video_output_dim)
+        audio_output_dim = int(audio_output_dim or FLAGS.jtmv2_audio_output_dim)
+        use_attention, use_relu = FLAGS.jtmv2_use_attention, FLAGS.jtmv2_use_relu                             # :207-208
+        # sample_random_frames and hidden_size are accepted and read nowhere, as written
+        quantised, model_input, max_frames, feature_size = _random_frames(model_input, num_frames, iterations, frame_uniform)  # :210-216
+        if feature_size <= 1024:
+            raise ValueError("JuhanTestModelV2 slices a 1024-wide video and a 128-wide audio stream out of its input "
+                             f"(frame_level_models.py:245-249); got {feature_size} features")
+        streams = (("video", 1024, video_anchor_size, video_kernel_size, video_hidden, video_output_dim, slice(0, 1024)),
+                   ("audio", feature_size - 1024, audio_anchor_size, audio_kernel_size, audio_hidden, audio_output_dim, slice(1024, None)))
+        features = _stream_features(quantised, model_input, num_frames, iterations, frame_uniform, False, is_training,
+                                    quantised_training)                                                       # (no input batch norm)
+        v2_modules = [video_pooling_modules.TriangulationNsCnnIndirectAttentionModule(
+            feature_size=D, max_frames=max_frames, anchor_size=K, self_attention=use_attention, hidden_layer_size=H, kernel_size=F,
+            output_dim=O, add_relu=use_relu, batch_norm=add_batch_norm, is_training=is_training, scope_id=None)
+            for _, D, K, F, H, O, _ in streams]                                                               # :218-242
+        fused = bool(FLAGS.triangulation_v2_fused and model_input.is_cuda and max_frames >= 2)
+        acts = []
+        for (name, *_), x, module in zip(streams, features, v2_modules):
+            with vs.variable_scope(name + "_triangulation_embedding"):                                        # :244-250
+                acts.append(module.head(*module.fused_pool(x.contiguous())) if fused else module.forward(x))
+        activation = torch.cat(acts, 1)                                                                       # :252
+        if add_batch_norm:
+            activation = layers.batch_norm(activation, is_training, "final_activation_bn")                    # :254-260
+        aggregated_model = getattr(video_level_models, "ClassLearningFourNnModel")
+        return aggregated_model().create_model(model_input=activation, vocab_size=vocab_size, is_training=is_training,
+                                               **unused_params)                                              # :262-268
 
 
 class TriangulationRelationalModel(models.BaseModel):

@@ -4718,6 +4718,114 @@ def triangulation_bn_moments(x, anchors, gamma_s, beta_s, gamma_t, beta_t, max_f
 
 
 # ----------------------------------------------------------------------------------------------
+# attention-weighted convolution moments of the triangulation embedding: TriangulationNsCnnIndirectAttentionModule's pooling
+# (csrc/triangulation_moments.hip: the convolutions and their moments; csrc/triangulation_bn_moments.hip: the norms, the Grams, the chain)
+# ----------------------------------------------------------------------------------------------
+class _TriangulationCnnAttentionMoments(torch.autograd.Function):
+    """The saved state is the inputs, the norms q [2, B*T, K], the temporal indicator ind [B*T, K], the convolutions' results so, to
+    [B*T, K*F], the per-clip means and their corrections stats [2, 2, B, K*F] and, with attention, the two Grams and weight vectors; e and
+    g are recomputed in the backward, whose workspaces (dso, dto [B*T, K*F] among them) live for that call only."""
+
+    @staticmethod
+    def forward(ctx, x, anchors, cnn_s, cnn_t, T, attention):
+        lib = _capi.load()
+        D, K = anchors.shape
+        F = cnn_s.shape[1]
+        B, J = x.shape[0] // T, K * D
+        dims = (B, T, D, K, F)
+        q = _empty((2, B * T, K), x)
+        with _timed("triangulation_cnn_attention_norms", dims):
+            lib.check(lib._lpm_triangulation_bn_moments_stats(ptr(x), ptr(anchors), B, T, D, K, 0, ptr(q), None, None, 0, stream_ptr()),
+                      "lpm_triangulation_bn_moments_stats")
+        iq = q[1]
+        gram_s = gram_t = w_s = w_t = None
+        if attention:
+            aff = _empty((8, J), x)                   # the Gram kernel's affine table: the identity (a product with 1 and a sum with 0 are exact)
+            aff.copy_(torch.tensor([1.0, 0.0, 0.0, 1.0] * 2, device=x.device).unsqueeze(1).expand(8, J))
+            gram_s, gram_t = _empty((B, T, T), x), _empty((B, T - 1, T - 1), x)
+            wsb = int(lib._lpm_triangulation_bn_moments_workspace_bytes(1, B, T, D, K))
+            ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+            with _timed("triangulation_cnn_attention_gram", dims):
+                lib.check(lib._lpm_triangulation_bn_moments_gram(ptr(x), ptr(anchors), ptr(iq), ptr(aff), B, T, D, K, ptr(gram_s), ptr(gram_t),
+                                                                 ptr(ws) if wsb else None, wsb, stream_ptr()), "lpm_triangulation_bn_moments_gram")
+            del aff, ws
+            with _timed("triangulation_cnn_attention_softmax", dims):
+                w_s, w_t = _attention_weights(gram_s), _attention_weights(gram_t)
+        ind = _empty((B * T, K), x)
+        so, to = _empty((B * T, K * F), x), _empty((B * T, K * F), x)
+        with _timed("triangulation_cnn_attention_conv", dims):
+            lib.check(lib._lpm_triangulation_cnn_attention_conv(ptr(x), ptr(anchors), ptr(cnn_s), ptr(cnn_t), ptr(iq), B, T, D, K, F, ptr(ind),
+                                                                ptr(so), ptr(to), stream_ptr()), "lpm_triangulation_cnn_attention_conv")
+        pool_s, pool_t = _empty((B, 2 * K * F), x), _empty((B, 2 * K * F), x)
+        stats = _empty((2, 2, B, K * F), x)
+        with _timed("triangulation_cnn_attention_pool", dims):
+            lib.check(lib._lpm_triangulation_cnn_attention_pool(ptr(so), ptr(to), ptr(w_s) if attention else None,
+                                                                ptr(w_t) if attention else None, B, T, K, F, ptr(pool_s), ptr(pool_t), ptr(stats),
+                                                                stream_ptr()), "lpm_triangulation_cnn_attention_pool")
+        ctx.save_for_backward(x, anchors, cnn_s, cnn_t, q, ind, so, to, stats, *((gram_s, gram_t, w_s, w_t) if attention else ()))
+        ctx.dims = (B, T, D, K, F, attention)
+        return pool_s, pool_t
+
+    @staticmethod
+    def backward(ctx, g_s, g_t):
+        lib = _capi.load()
+        x, anchors, cnn_s, cnn_t, q, ind, so, to, stats, *att = ctx.saved_tensors
+        B, T, D, K, F, attention = ctx.dims
+        dims = (B, T, D, K, F)
+        g_s, g_t = g_s.contiguous(), g_t.contiguous()
+        dso, dto = torch.empty_like(so), torch.empty_like(to)
+        w_s = w_t = dw_s = dw_t = m_s = m_t = None
+        if attention:
+            gram_s, gram_t, w_s, w_t = att
+            dw_s, dw_t = _empty((B, T), x), _empty((B, T - 1), x)
+        opt = (lambda t: ptr(t)) if attention else (lambda t: None)
+        with _timed("triangulation_cnn_attention_dout", dims):
+            lib.check(lib._lpm_triangulation_cnn_attention_dout(ptr(so), ptr(to), opt(w_s), opt(w_t), ptr(stats), ptr(g_s), ptr(g_t), B, T, K, F,
+                                                                ptr(dso), ptr(dto), opt(dw_s), opt(dw_t), stream_ptr()),
+                      "lpm_triangulation_cnn_attention_dout")
+        if attention:
+            with _timed("triangulation_cnn_attention_softmax_bwd", dims):
+                m_s, m_t = _attention_weights_bwd(gram_s, w_s, dw_s), _attention_weights_bwd(gram_t, w_t, dw_t)
+        dx, danchors, dcnn_s, dcnn_t = torch.empty_like(x), torch.empty_like(anchors), torch.empty_like(cnn_s), torch.empty_like(cnn_t)
+        with _timed("triangulation_cnn_attention_dweights", dims):
+            lib.check(lib._lpm_triangulation_cnn_attention_dweights(ptr(x), ptr(anchors), ptr(q[1]), ptr(ind), ptr(dso), ptr(dto), B, T, D, K, F,
+                                                                    ptr(dcnn_s), ptr(dcnn_t), stream_ptr()),
+                      "lpm_triangulation_cnn_attention_dweights")
+        wsb = int(lib._lpm_triangulation_cnn_attention_workspace_bytes(B, T, D, K))
+        ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+        with _timed("triangulation_cnn_attention_bwd", dims):
+            lib.check(lib._lpm_triangulation_cnn_attention_bwd(ptr(x), ptr(anchors), ptr(q), ptr(cnn_s), ptr(cnn_t), ptr(dso), ptr(dto), opt(m_s),
+                                                               opt(m_t), B, T, D, K, F, ptr(dx), ptr(danchors), ptr(ws), wsb, stream_ptr()),
+                      "lpm_triangulation_cnn_attention_bwd")
+        return dx, danchors, dcnn_s, dcnn_t, None, None
+
+
+def triangulation_cnn_attention_moments(x, anchors, cnn_s, cnn_t, max_frames, self_attention=True):
+    """One stream of TriangulationNsCnnIndirectAttentionModule's pooling (video_pooling_modules.py:1108-1268, JuhanTestModelV2): x
+    [B * max_frames, D] (a clip's rows contiguous), anchors [D, K] as they are (NOT normalised), ``cnn_s``, ``cnn_t`` [K, F, D] as the
+    variables are stored -> (spatial_pool, temporal_pool), each [B, 2 K*F] = [mean | variance], element k * F + f:
+        e = l2_normalize(x - a_k);  g = e - roll(e, 1) over the FEATURE axis of the flattened [K*D] row, frame 0 dropped, not normalised again;
+        so = <cnn_s[k,f], e_k>, to = <cnn_t[k,f], g_k>;  per clip G = V V^T over all K*D (V = e or g), w = softmax_t(sum_u relu(G[t,u]));
+        mean = (1/T') sum_t w_t out_t (the plain mean without ``self_attention``), var = the mean of squared deviations from the
+        unweighted mean.
+    Differentiable in all four tensors; where a squared norm does not exceed 1e-12, e takes the clamped value.  Nothing of size
+    B * T * K * D is written.  GPU only; D in TRIANGULATION_FEATURES, 2 <= max_frames <= 320, contiguous fp32 input; the same inputs give
+    the same bits."""
+    what = "triangulation_cnn_attention_moments"
+    T = _attention_args(what, x, anchors, max_frames)
+    D, K = anchors.shape
+    for name, cnn in (("cnn_s", cnn_s), ("cnn_t", cnn_t)):
+        if not torch.is_tensor(cnn) or cnn.dim() != 3 or cnn.shape[0] != K or cnn.shape[2] != D or cnn.shape[1] < 1:
+            raise LpmError(f"{what}: {name} must be [K, F, D] = [{K}, F, {D}] (got {tuple(cnn.shape) if torch.is_tensor(cnn) else type(cnn)})")
+        _f32(cnn, f"{what} {name}")
+        if cnn.device != x.device:
+            raise LpmError(f"{what}: {name} is on {cnn.device}, x on {x.device}")
+    if cnn_s.shape != cnn_t.shape:
+        raise LpmError(f"{what}: cnn_s {tuple(cnn_s.shape)} and cnn_t {tuple(cnn_t.shape)} must have one shape")
+    return _TriangulationCnnAttentionMoments.apply(x, anchors.contiguous(), cnn_s.contiguous(), cnn_t.contiguous(), T, bool(self_attention))
+
+
+# ----------------------------------------------------------------------------------------------
 # one LSTM layer: a kernel per time step each way (csrc/lstm.hip)
 # ----------------------------------------------------------------------------------------------
 def lstm_layer_ok(B, T, H) -> bool:

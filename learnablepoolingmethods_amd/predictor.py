@@ -26,6 +26,8 @@ FUSED_Q8_MODELS = ("NetVladV1", "NetVladV2")
 # models that gather SampleRandomFrames' frames from the uint8 batch themselves (ops.frame_gather_bn_split), FLAGS.gather_frames_fused
 GATHER_Q8_MODELS = ("RegularizedTriangulationModel", "SoftAttentionTriangulationModel", "TriangulationCnnClusterModel", "JuhanTestModelV5",
                     "JuhanTestModelV1")
+# likewise, added after the five above (whose tuple the frame-gather tests pin by value)
+GATHER_Q8_LATER_MODELS = ("JuhanTestModelV2",)
 
 
 def takes_quantised_frames(model, frames) -> bool:
@@ -36,7 +38,7 @@ def takes_quantised_frames(model, frames) -> bool:
         return False
     if name in FUSED_Q8_MODELS:
         return True
-    return bool(name in GATHER_Q8_MODELS and FLAGS.gather_frames_fused and frames.shape[2] % 4 == 0 and frames.shape[2] <= 2048)
+    return bool(name in GATHER_Q8_MODELS + GATHER_Q8_LATER_MODELS and FLAGS.gather_frames_fused and frames.shape[2] % 4 == 0 and frames.shape[2] <= 2048)
 # checkpoint entries that are not variables (train.Trainer.state_dict)
 _NOT_VARIABLES = ("global_step", "bn_statistics_synced", "hidden1_adam_shard")
 _H1 = "tower/hidden1_weights"

@@ -149,6 +149,24 @@ def glorot_uniform_initializer():
     return init
 
 
+def orthogonal_initializer(gain: float = 1.0):
+    """tf.orthogonal_initializer: the leading dimensions flattened to rows, QR of a standard-normal draw (of the transposed shape when
+    there are fewer rows than columns), the signs fixed by diag(R), the result scaled by ``gain``: orthonormal columns for rows >= columns,
+    orthonormal rows otherwise."""
+    def init(shape, dev, gen):
+        if len(shape) < 2:
+            raise ValueError("orthogonal_initializer: the variable needs at least two dimensions")
+        rows, cols = math.prod(shape[:-1]), shape[-1]
+        flat = (max(rows, cols), min(rows, cols))
+        a = torch.randn(flat, device=dev, generator=gen)
+        q, r = torch.linalg.qr(a.double().cpu(), mode="reduced")                 # (on the host: a one-off, and the same on every device)
+        q = q * torch.sign(torch.diagonal(r)).unsqueeze(0)
+        if rows < cols:
+            q = q.t()
+        return (gain * q).reshape(shape).to(device=dev, dtype=torch.float32)
+    return init
+
+
 # -- default store (TF's default graph) -----------------------------------------------------------
 _default = VariableStore()
 

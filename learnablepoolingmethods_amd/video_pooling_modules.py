@@ -1,6 +1,6 @@
 """NetVladOrthoReg and NetVladAttenCluster (reference: video_pooling_modules.py:1499-1586, 1589-1663) and the triangulation
 embeddings (TriangulationEmbedding :376-428, WeightedTriangulationEmbedding :1395-1459, TriangulationTemporalEmbedding :1462-1497,
-TriangulationV5Module :142-373, TriangulationCnnIndirectAttentionModule :431-631)."""
+TriangulationV5Module :142-373, TriangulationCnnIndirectAttentionModule :431-631, TriangulationNsCnnIndirectAttentionModule :1108-1342)."""
 from __future__ import annotations
 
 import math
@@ -371,6 +371,95 @@ class TriangulationCnnIndirectAttentionModule(modules.BaseModule):
         spatial_temporal_concat = torch.cat([spatial_activation, temporal_activation], 1)                                 # :610
         sp_weights = weights("spa_temp_fusion", spatial_temporal_concat.shape[1], self.output_dim)                        # :612-616
         return act(bn(spatial_temporal_concat.matmul(sp_weights), "activation_bn"))                                       # :617-628
+
+    def forward(self, inputs, **unused_params):
+        """inputs [(B*max_frames), D] -> [B, output_dim]."""
+        return self.head(*self.pool(inputs))
+
+
+class TriangulationNsCnnIndirectAttentionModule(modules.BaseModule):
+    """:1108-1342 (JuhanTestModelV2's module): the triangulation embedding of every frame against the anchors AS THEY ARE
+    (tf.orthogonal_initializer, not normalised), its difference with itself rolled by one along the FEATURE axis (:1185; SURVEY App. C29;
+    frame 0 dropped, not normalised again: C34), a 1x1 convolution per anchor over each (``spatial_cnn_weights``, ``temporal_cnn_weights``
+    [K, F, D], not shared between anchors), soft-attention weights over the frames of a clip from the relu'd Gram matrix of the [T, K*D]
+    rows (C39: as written the Gram is taken per frame and the model raises), the weighted mean of the convolutions' results divided by the
+    frame count once more (C32) and their UNWEIGHTED reduce_var (C33); then per stream a batch norm, a hidden layer, batch norm and an
+    optional relu, and the fusion layer.  ``pool`` MATERIALISES [(B*T), K*D] several times: the drop-in surface and the CPU path;
+    ``variables`` + ops.triangulation_cnn_attention_moments + ``head`` is the fused one (``fused_pool``)."""
+
+    def __init__(self, feature_size, max_frames, anchor_size, self_attention, hidden_layer_size, kernel_size, output_dim, add_relu,
+                 batch_norm, is_training, scope_id=None):
+        self.feature_size = feature_size
+        self.max_frames = max_frames
+        self.anchor_size = int(anchor_size)
+        self.self_attention = self_attention
+        self.hidden_layer_size = int(hidden_layer_size)
+        self.kernel_size = int(kernel_size)
+        self.output_dim = int(output_dim)
+        self.add_relu = add_relu
+        self.batch_norm = batch_norm
+        self.is_training = is_training
+        self.scope_id = scope_id
+
+    def variables(self, device):
+        """(anchor_weights [D, K], spatial_cnn_weights, temporal_cnn_weights [K, F, D]) without a forward, created in the reference's
+        order (:1156-1161, :1222-1235): what the fused path needs."""
+        sid = "" if self.scope_id is None else str(self.scope_id)
+        D, K, F = self.feature_size, self.anchor_size, self.kernel_size
+        anchor_weights = vs.get_variable("anchor_weights" + sid, [D, K], vs.orthogonal_initializer(), device=device)
+        vs.summary("anchor_weights" + sid, anchor_weights)
+        init = vs.random_normal_initializer(1 / math.sqrt(F * D))
+        spatial_cnn_weights = vs.get_variable("spatial_cnn_weights" + sid, [K, F, D], init, device=device)
+        temporal_cnn_weights = vs.get_variable("temporal_cnn_weights" + sid, [K, F, D], init, device=device)
+        return anchor_weights, spatial_cnn_weights, temporal_cnn_weights
+
+    def pool(self, inputs):
+        """inputs [(B*max_frames), D] -> (spatial_pool, temporal_pool), each [B, 2 K*F] (:1156-1268)."""
+        D, K, F, T = self.feature_size, self.anchor_size, self.kernel_size, self.max_frames
+        anchor_weights, spatial_cnn_weights, temporal_cnn_weights = self.variables(inputs.device)
+        spatial = inputs.unsqueeze(1) - anchor_weights.t().unsqueeze(0)                                # :1164-1173 -> [M, K, D]
+        spatial = layers.l2_normalize(spatial, 2).reshape(-1, K * D)                                   # :1175-1176
+        temporal = spatial - torch.roll(spatial, shifts=1, dims=1)                                     # :1185-1186: the feature axis (C29)
+        temporal = temporal.reshape(-1, T, K * D)[:, 1:].reshape(-1, K * D)                            # :1187-1192
+        pools = []
+        for v, cnn, Tz in ((spatial, spatial_cnn_weights, T), (temporal, temporal_cnn_weights, T - 1)):
+            out = v.reshape(-1, K, D).transpose(0, 1).matmul(cnn.transpose(1, 2)).transpose(0, 1).reshape(-1, Tz, K * F)   # :1237-1254
+            if self.self_attention:
+                v = v.reshape(-1, Tz, K * D)                                                           # (C39: the frames of a clip)
+                weight = torch.softmax(torch.relu(v.matmul(v.transpose(1, 2))).sum(dim=2), dim=1)      # :1201-1216
+                mean = (out * weight.unsqueeze(2)).mean(dim=1)                                         # :1258-1259 (C32)
+            else:
+                mean = out.mean(dim=1)                                                                 # :1261-1262
+            pools.append(torch.cat([mean, module_utils.reduce_var(out, 1)], 1))                        # :1264-1268 (C33)
+        return pools[0], pools[1]
+
+    def fused_pool(self, inputs):
+        """``pool`` through ops.triangulation_cnn_attention_moments: the same variables in the same order."""
+        anchor_weights, spatial_cnn_weights, temporal_cnn_weights = self.variables(inputs.device)
+        return ops.triangulation_cnn_attention_moments(inputs, anchor_weights, spatial_cnn_weights, temporal_cnn_weights, self.max_frames,
+                                                       self_attention=bool(self.self_attention))
+
+    def head(self, spatial_pool, temporal_pool):
+        """The two pools -> [B, output_dim] (:1270-1342)."""
+        dev, H = spatial_pool.device, self.hidden_layer_size
+
+        def bn(x, scope):
+            return layers.batch_norm(x, self.is_training, scope) if self.batch_norm else x
+
+        def act(x):
+            return torch.relu(x) if self.add_relu else x
+
+        def weights(name, rows, units, fan):
+            return vs.get_variable(name, [rows, units], vs.random_normal_initializer(1 / math.sqrt(fan)), device=dev)
+        spatial_pool, temporal_pool = bn(spatial_pool, "spatial_pool_bn"), bn(temporal_pool, "temporal_pool_bn")            # :1270-1282
+        spatial_weights = weights("spatial_hidden", spatial_pool.shape[1], H, H)                                         # :1284-1294
+        temporal_weights = weights("temporal_hidden", temporal_pool.shape[1], H, H)
+        spatial_activation, temporal_activation = spatial_pool.matmul(spatial_weights), temporal_pool.matmul(temporal_weights)
+        spatial_activation = act(bn(spatial_activation, "spatial_activation_bn"))                                        # :1299-1316
+        temporal_activation = act(bn(temporal_activation, "temporal_activation_bn"))
+        spatial_temporal_concat = torch.cat([spatial_activation, temporal_activation], 1)                                 # :1321
+        sp_weights = weights("spa_temp_fusion", spatial_temporal_concat.shape[1], self.output_dim, self.output_dim)       # :1323-1328
+        return act(bn(spatial_temporal_concat.matmul(sp_weights), "activation_bn"))                                       # :1330-1339
 
     def forward(self, inputs, **unused_params):
         """inputs [(B*max_frames), D] -> [B, output_dim]."""
