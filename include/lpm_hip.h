@@ -67,6 +67,9 @@ enum {
 
 int lpm_version(void);
 const char* lpm_last_error(void);
+/* 1 when the library was built with -DLPM_MEASURE, 0 otherwise.  Only such a build holds the measurement instantiations (kernels that skip
+ * part of their work, so that what they write is garbage) and reads the variables that select them: docs/switches.md. */
+int lpm_measure_build(void);
 
 /* Kernel timing for bench.py: while enabled, the K1 (video stream, tag 1) and K2 (tag 2) forward launches are issued with
  * hipExtLaunchKernelGGL and a start/stop HIP event pair on their own stream, i.e. the elapsed time is the kernel's duration

@@ -112,6 +112,7 @@ SIGNATURES = {
     "lpm_split_weight_tiles_bf16": (_i, [_f, _i, _i, _i, _f, _f]),
     "lpm_split_frames_bf16": (_i, [_f, _l, _i, _i, _i, _f, _f]),
     "lpm_assign_gemm_tiles_fwd_bf16": (_i, [_f, _f, _i, _i, _i, _i, _f, _f, _f]),
+    "lpm_measure_build": (_i, []),
     "lpm_k1_forms_disable": (_i, [_i]),
     "lpm_mha_bwd_set_terms": (_i, [_i]),
     "lpm_assign_gemm_tiles_bwd_dw_bf16": (_i, [_f, _f, _i, _i, _i, _i, _f, _f, _s, _f]),
@@ -330,6 +331,20 @@ def load() -> _Lib:
     if _LIB is None:
         _LIB = _Lib(os.environ.get("LPM_HIP_LIBRARY") or LIB_PATH)      # (the override: A/B of two builds of the library, tools/)
     return _LIB
+
+
+# read by liblpm_hip.so only when it was built with -DLPM_MEASURE (docs/switches.md)
+MEASURE_VARIABLES = ("LPM_VB_DBG", "LPM_VB_DELAY", "LPM_VC_DBG", "LPM_VK_DBG", "LPM_TG_DBG", "LPM_FA_DBG", "LPM_FA_FOLD_DBG", "LPM_K1_WIDE_DBG",
+                     "LPM_K2_EXTRA_LDS", "LPM_TG_AP", "LPM_TG_WIDE_NS", "LPM_TG_WIDE4_NS")
+
+
+def require_measure_build():
+    """For the timing tools under tools/: with a measurement variable set, a library that is no measurement build ignores it -- exit
+    rather than time a kernel the variable does not affect."""
+    names = [v for v in MEASURE_VARIABLES if v in os.environ]
+    if names and not load()._lpm_measure_build():
+        raise SystemExit(f"{', '.join(names)} set, but {load().path} is not a measurement build: "
+                         f"rebuild with LPM_EXTRA_HIPCC_FLAGS=-DLPM_MEASURE")
 
 
 def ptr(t: Optional[torch.Tensor]):

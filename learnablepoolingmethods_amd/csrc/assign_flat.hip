@@ -355,7 +355,7 @@ static_assert(AW_KB % AW_DB == 0 && AW_TAIL >= AW_DB, "B register sets by step w
 static_assert(aw_wait(-800) == (AW_DB - 1) * 2 + AW_DMA && aw_wait(-800 + AW_KB - 1) == (AW_DB - 1) * 2 &&
               aw_wait(0) == (AW_DB - 1) * 2 + AW_DMA && aw_wait(AW_TAIL - 1) == 0, "steady-state and tail waits");
 
-// DBG (timing experiments, -DLPM_K1_WIDE_EXPERIMENTS builds only, LPM_K1_WIDE_DBG=n; results are garbage): 1 no epilogue, 2 no B fragment
+// DBG (timing experiments, -DLPM_MEASURE builds only, LPM_K1_WIDE_DBG=n; results are garbage): 1 no epilogue, 2 no B fragment
 // loads, 4 no DMA, 8 no MFMAs, 16 no fragment reads, 64 no logits stores, 128 non-temporal logits stores
 template <int DBG>
 __global__ __launch_bounds__(512, 1) void assign_wide_kernel(const AssignFlatArgs a) {
@@ -585,7 +585,7 @@ __global__ __launch_bounds__(512, 1) void assign_wide_kernel(const AssignFlatArg
 
 // LPM_K1_WIDE=0: the flat 96-row plain form (A/B)
 bool assign_wide_ok(int B, int T, int MT, int D, int K, int nblk) {
-    static const int on = [] { const char* e = getenv("LPM_K1_WIDE"); return (e && e[0] == '0') ? 0 : 1; }();
+    static const int on = env_first_is("LPM_K1_WIDE", '0') ? 0 : 1;
     const int DS = D / 32;
     const int64_t M = (int64_t)B * T;
     return on && !(g_k1_forms_off.load(std::memory_order_relaxed) & 2) && D % 128 == 0 && DS / 4 >= 3 && K % 512 == 0 && K > 0 && M < ((int64_t)1 << 31) && (M + AW_ROWS - 1) / AW_ROWS <= nblk &&
@@ -605,8 +605,8 @@ int assign_wide_launch(const void* xr, const void* wt, int B, int T, int MT, int
     const dim3 grid((unsigned)nwg, (unsigned)(K / 512));
     const size_t lds = (size_t)AW_NS * AW_STAGE;
     void (*kern)(const AssignFlatArgs) = assign_wide_kernel<0>;
-#ifdef LPM_K1_WIDE_EXPERIMENTS                                     // tools/k1_bf16_loop.py: build with LPM_EXTRA_HIPCC_FLAGS=-DLPM_K1_WIDE_EXPERIMENTS
-    static const int dbg = [] { const char* e = getenv("LPM_K1_WIDE_DBG"); return e ? atoi(e) : 0; }();
+#ifdef LPM_MEASURE                                                 // tools/k1_bf16_loop.py: build with LPM_EXTRA_HIPCC_FLAGS=-DLPM_MEASURE
+    static const int dbg = env_measure_mode("LPM_K1_WIDE_DBG");
     switch (dbg) {
         case 1: kern = assign_wide_kernel<1>; break;
         case 2: kern = assign_wide_kernel<2>; break;
@@ -632,20 +632,17 @@ int assign_wide_launch(const void* xr, const void* wt, int B, int T, int MT, int
 }
 
 static int af_enabled() {
-    static const int on = [] {
-        const char* e = getenv("LPM_K1_FLAT");         // 0: the 128-row tile GEMM form (A/B switch)
-        return (e && e[0] == '0') ? 0 : 1;
-    }();
+    static const int on = env_first_is("LPM_K1_FLAT", '0') ? 0 : 1;         // 0: the 128-row tile GEMM form (A/B switch)
     return on && !(g_k1_forms_off.load(std::memory_order_relaxed) & 1);
 }
 
 // steps per stage (LPM_K1_KB = 1, 2, 4) and steps of B fragments in flight (LPM_K1_DB = 4; 8 with four steps per stage): A/B switches
 static int af_kb() {
-    static const int kb = [] { const char* e = getenv("LPM_K1_KB"); const int v = e ? atoi(e) : 0; return (v == 1 || v == 2 || v == 4) ? v : 2; }();
+    static const int kb = [] { const int v = env_int("LPM_K1_KB", 0); return (v == 1 || v == 2 || v == 4) ? v : 2; }();
     return kb;
 }
 static int af_db() {
-    static const int db = [] { const char* e = getenv("LPM_K1_DB"); const int v = e ? atoi(e) : 0; return (v == 8 && af_kb() == 4) ? 8 : 4; }();
+    static const int db = [] { const int v = env_int("LPM_K1_DB", 0); return (v == 8 && af_kb() == 4) ? 8 : 4; }();
     return db;
 }
 
@@ -655,7 +652,7 @@ bool assign_flat_ok(int B, int T, int D, int K) {
 }
 // plain bf16 tiles: double steps of 32 reduction elements (LPM_K1_FLAT_BF16=0: the 128-row tile GEMM form, A/B)
 bool assign_flat_plain_ok(int B, int T, int D, int K) {
-    static const int on = [] { const char* e = getenv("LPM_K1_FLAT_BF16"); return (e && e[0] == '0') ? 0 : 1; }();
+    static const int on = env_first_is("LPM_K1_FLAT_BF16", '0') ? 0 : 1;
     const int DS = D / 32, tail = af_tail(2, 4);
     return on && af_enabled() && D % 32 == 0 && DS % 4 == 0 && DS >= tail + 4 && K % 256 == 0 && K > 0 && (int64_t)B * T < (int64_t)1 << 31;
 }
@@ -681,7 +678,7 @@ int assign_flat_launch(const void* xr, const void* wt, int B, int T, int MT, int
         if (timed) hipExtLaunchKernelGGL((assign_flat_kernel<KB, DB, LUMP>), grid, dim3(512), lds, stream, e0, e1, 0, a); \
         else hipLaunchKernelGGL((assign_flat_kernel<KB, DB, LUMP>), grid, dim3(512), lds, stream, a);      \
     } while (0)
-    static const int lump = [] { const char* e = getenv("LPM_K1_LUMP"); return (e && e[0] == '1') ? 1 : 0; }();
+    static const int lump = env_first_is("LPM_K1_LUMP", '1') ? 1 : 0;
     if (planes == 1) {
         const size_t lds1 = (size_t)af_ns(2) * 2 * AF_KSTEP;
         if (timed) hipExtLaunchKernelGGL((assign_flat_kernel<2, 4, false, true>), grid, dim3(512), lds1, stream, e0, e1, 0, a);

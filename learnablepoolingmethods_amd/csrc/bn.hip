@@ -59,7 +59,7 @@ constexpr int BNB_ROWS = 64;
 // column chunks (gridDim.y) of the two statistics passes: one per 256 float4 column groups, at most 8; the per-block partial sums of a
 // column are the same numbers whichever workgroup forms them
 static inline unsigned bn_col_chunks(int C) {
-    static const int cap = [] { const char* e = getenv("LPM_BN_COL_CHUNKS"); return e ? atoi(e) : 8; }();      // 1: one chunk, the round-5 launch (A/B)
+    static const int cap = env_int("LPM_BN_COL_CHUNKS", 8);      // 1: one chunk, the round-5 launch (A/B)
     const int c = (C / 4 + 255) / 256;
     return (unsigned)(c < 1 ? 1 : (c > cap ? (cap < 1 ? 1 : cap) : c));
 }

@@ -94,7 +94,7 @@ static int clip_adam_impl(float* param, const float* grad, float* m, float* v, c
     float* chunk_ss = scratch;
     float* factor = scratch + nchunk;
     const double lr_t = (double)lr * sqrt(1.0 - pow((double)beta2, (double)step)) / (1.0 - pow((double)beta1, (double)step));
-    static const int adam_nt = [] { const char* e = getenv("LPM_ADAM_NT"); return (e && e[0] == '0') ? 0 : 1; }();
+    static const int adam_nt = env_first_is("LPM_ADAM_NT", '0') ? 0 : 1;
     hipLaunchKernelGGL(ca_chunk_sumsq_kernel, dim3((unsigned)nchunk), dim3(256), 0, s, grad, total, chunk_ss, (const float*)param, offsets, ntensors,
                        l2coef);
     hipLaunchKernelGGL(ca_tensor_factor_kernel, dim3(ntensors), dim3(1024), 0, s, chunk_ss, offsets, clip_norm, factor);

@@ -495,14 +495,18 @@ static int factored_clip_adam_impl(const void* xt, const void* dyt, const float*
     g.out = param; g.ldo = N2; g.rows_valid = N1; g.cols_valid = N2;
     g.cols_inner = 1;                     // the column blocks of a row block as neighbours: X tiles from HBM once
     // measurement switches (tools/time_factored.py): 1 = no reduction steps in either pass (the streams alone), 2 = no norm pass
-    static const int dbg = [] { const char* e = getenv("LPM_FA_DBG"); return e ? atoi(e) : 0; }();
+#ifdef LPM_MEASURE
+    static const int dbg = env_measure_mode("LPM_FA_DBG");
+#else
+    constexpr int dbg = 0;
+#endif
     if (dbg & 1) g.steps_per_split = g.total_steps = 0;
     int rc = LPM_OK;
     int64_t npart = nwg;
     if (gdt) {
         const int MT = 2 * ((R + 63) / 64);
         const size_t lds = (size_t)MT * (R / 16) * 2048;
-        static const int from_tiles = [] { const char* e = getenv("LPM_FQ_TILES"); return (e && e[0] == '0') ? 0 : 1; }();   // 0: X from the fp32 matrix (A/B)
+        static const int from_tiles = env_first_is("LPM_FQ_TILES", '0') ? 0 : 1;   // 0: X from the fp32 matrix (A/B)
         auto kern = (from_tiles && R <= 128) ? fa_quadform_kernel<true> : fa_quadform_kernel<false>;
         if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
             (void)hipGetLastError();
@@ -520,7 +524,7 @@ static int factored_clip_adam_impl(const void* xt, const void* dyt, const float*
     const double lr_t = (double)lr * sqrt(1.0 - pow((double)beta2, (double)step)) / (1.0 - pow((double)beta1, (double)step));
     g.sumsq = nullptr;
     // whole-row form of the update pass (fa_update_rows_kernel): N2 a multiple of 64, at most 1024; LPM_FA_ROWS=0: the tile-GEMM form (A/B)
-    static const int rows_form = [] { const char* e = getenv("LPM_FA_ROWS"); return (e && e[0] == '0') ? 0 : 1; }();
+    static const int rows_form = env_first_is("LPM_FA_ROWS", '0') ? 0 : 1;
     // Measured (tools/time_factored.py, whole update incl. the ~75 us norm pass): cfg-2 one tower (R = 80, N2 = 512) 693 us against 728;
     // cfg-5 (R = 128, N2 = 1024) 2741 against 2418 and eight towers of cfg-2 (R = 640) 1855 against 1749 -- every wave fetching its own
     // fragments from L2 costs 80 + 160 KB of L2 -> CU traffic per 192 KB of HBM stream at R = 80, but 256 + 512 KB per 384 KB at R = 128:
@@ -532,7 +536,7 @@ static int factored_clip_adam_impl(const void* xt, const void* dyt, const float*
     }
     // the row-block form (fa_update_fold_kernel): always when the projection's input gradient rides along; without it only on request
     // (LPM_FA_FOLD=2: A/B of the two streaming patterns; 0: never -- then a dx request is an error)
-    static const int fold = [] { const char* e = getenv("LPM_FA_FOLD"); return e ? atoi(e) : 1; }();
+    static const int fold = env_int("LPM_FA_FOLD", 1);
     const bool fold_ok = param_bf16 && lpm_factored_fold_supported(R, N1, N2) && fold != 0;
     if (dx && !fold_ok) {
         set_error("lpm_factored_clip_adam_copy_dx: needs the compute copy, N1 %% 64 == 0, N2 %% 128 == 0, R %% 16 == 0 and R <= 128 (R=%d N1=%d N2=%d)", R, N1, N2);
@@ -540,7 +544,11 @@ static int factored_clip_adam_impl(const void* xt, const void* dyt, const float*
     }
     if (fold_ok && (dx || fold == 2)) {
         const int RS = R / 16;
-        static const int fdbg = [] { const char* e = getenv("LPM_FA_FOLD_DBG"); return e ? atoi(e) : 0; }();
+#ifdef LPM_MEASURE
+        static const int fdbg = env_measure_mode("LPM_FA_FOLD_DBG");
+#else
+        constexpr int fdbg = 0;
+#endif
         const size_t lds = (size_t)RS * 4096 + (size_t)64 * FF_ES * sizeof(float);
         auto kern = dx ? fa_update_fold_kernel<true> : fa_update_fold_kernel<false>;
         if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {

@@ -56,6 +56,11 @@ extern "C" int lpm_kernel_timing_read(int tag, float* ms, int max) {
 
 extern "C" int lpm_version(void) { return LPM_VERSION; }
 extern "C" const char* lpm_last_error(void) { return lpm::g_err; }
+#ifdef LPM_MEASURE
+extern "C" int lpm_measure_build(void) { return 1; }
+#else
+extern "C" int lpm_measure_build(void) { return 0; }
+#endif
 
 // ---- measurement: the shader clock over time ---------------------------------------------------------------------------------------------
 // One wave that does nothing but sample: every `period_ticks` ticks of the constant 100 MHz counter (s_memrealtime) it stores the pair

@@ -7,6 +7,7 @@
 #include <stdarg.h>
 
 #include "../../include/lpm_hip.h"
+#include "lpm_env.h"
 
 namespace lpm {
 

@@ -585,7 +585,7 @@ extern "C" int lpm_mha_logit_stats(const float* q, const float* k, int64_t ld, i
     LPM_REQUIRE(q && k && partial, LPM_ERR_BADARG, "lpm_mha_logit_stats: null pointer");
     LPM_MHA_CHECK("lpm_mha_logit_stats");
     hipStream_t s = (hipStream_t)stream;
-    static const int quad = [] { const char* e = getenv("LPM_MHA_STATS_QUAD"); return (e && e[0] == '0') ? 0 : 1; }();   // 0: through the logits (A/B)
+    static const int quad = env_first_is("LPM_MHA_STATS_QUAD", '0') ? 0 : 1;   // 0: through the logits (A/B)
     if (quad && (((uintptr_t)q | (uintptr_t)k) & 15) == 0 && d % 4 == 0) {
         hipLaunchKernelGGL(mha_logit_stats_quad_kernel, dim3((B * h + 3) / 4), dim3(256), 0, s, q, k, ld, L, h, d, B * h, partial,
                            (float*)nullptr);

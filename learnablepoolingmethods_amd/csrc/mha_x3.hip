@@ -1216,10 +1216,7 @@ static int mx_reserve(KernT kern, size_t bytes, const char* what) {
 // on two fp16 terms (round 6: built, measured, NOT the default -- 6 % of the backward at L = 256, 2 % at L = 300 with logits_bn, 0.3 % of a
 // cfg-2 step, for gradients 2-3e-4 from the three-term form's: see the kernels' header).  LPM_MHA_BWD_TERMS=2 opts in;
 // lpm_mha_bwd_set_terms switches at run time (tests, A/B) and returns the old value.
-static std::atomic<int> g_mha_bwd_terms{[] {
-    const char* e = getenv("LPM_MHA_BWD_TERMS");
-    return (e && e[0] == '2') ? 2 : 3;
-}()};
+static std::atomic<int> g_mha_bwd_terms{lpm::env_first_is("LPM_MHA_BWD_TERMS", '2') ? 2 : 3};
 extern "C" int lpm_mha_bwd_set_terms(int terms) {
     if (terms != 2 && terms != 3) return g_mha_bwd_terms.load();
     return g_mha_bwd_terms.exchange(terms);
@@ -1315,7 +1312,7 @@ static int mx_bwd_launch(const float* q, const float* k, const float* v, int64_t
     dim3 grid(B * h);
     // two fp16 terms: only where dS is linear in dO (no correction vectors: see the kernels' header)
     const bool h16 = g_mha_bwd_terms.load(std::memory_order_relaxed) == 2 && !corr_a;
-    static const int tpw = [] { const char* e = getenv("LPM_MHA_BWD_TPW"); return (e && e[0] == '2') ? 2 : 1; }();   // tiles per wave (A/B)
+    static const int tpw = env_first_is("LPM_MHA_BWD_TPW", '2') ? 2 : 1;   // tiles per wave (A/B)
 #define LPM_MX_BWDH_Q(N, AFF, DD, RG, TP)                                                                              \
     do {                                                                                                               \
         auto kq = mha_bwd_dq_h_kernel<N, AFF, DD, RG, TP>;                                                             \

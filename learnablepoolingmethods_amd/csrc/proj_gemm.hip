@@ -829,7 +829,7 @@ extern "C" int lpm_proj_dx(const void* dyt, const float* W, int M, int64_t Kd, i
     dim3 grid((unsigned)((Kd + 255) / 256));
     hipStream_t s = (hipStream_t)stream;
     // second form (whole 128-byte lines of W per stage): N a multiple of 32; LPM_PROJ_DX_FORM=1 selects the first form (A/B)
-    static const int form = [] { const char* e = getenv("LPM_PROJ_DX_FORM"); return (e && e[0] == '1') ? 1 : 2; }();
+    static const int form = env_first_is("LPM_PROJ_DX_FORM", '1') ? 1 : 2;
     if (form == 2 && N % 32 == 0 && N >= 64) {
 #define LPM_PE(MTV)                                                                                                          \
     do {                                                                                                                     \

@@ -646,10 +646,7 @@ __global__ __launch_bounds__(256 * MW, (MW == 2 && NS == 3 && FORM == 0) ? 4 : 2
 int tg_ntw(int cols) { const int nt = (cols + 31) / 32; return nt <= 4 ? 1 : (nt <= 8 ? 2 : (nt <= 16 ? 4 : 2)); }
 
 static int tg_wide_enabled() {
-    static const int on = [] {
-        const char* e = getenv("LPM_TILE_GEMM_WIDE");      // 0: never use the 128-row form (A/B switch)
-        return (e && e[0] == '0') ? 0 : 1;
-    }();
+    static const int on = env_first_is("LPM_TILE_GEMM_WIDE", '0') ? 0 : 1;      // 0: never use the 128-row form (A/B switch)
     return on;
 }
 
@@ -665,7 +662,6 @@ static bool tg_wide_ok(const TileGemmArgs& g, int nbatch, int splits, int ntw, i
 // allow_wide: 0 = 64-row form, 1 = 128-row form (one workgroup per CU, software-pipelined, 4-stage ring) where the shape allows,
 // 2 = 128-row form with a 3-stage ring and two workgroups per CU, 3 = 256-row form (four row tiles per wave; no statistics)
 constexpr int TG_WIDE_NS_DEFAULT = 4;
-constexpr int TG_AP_DEFAULT = 0;
 // the fp16 forms (PL == 3: two terms, B hi-plane tiles; PL == 4: three terms): 256-row workgroups with the image epilogue only
 static int tg_launch_f16_image(const TileGemmArgs& g, hipStream_t stream, const char* what, int planes) {
     if (!tg_wide_ok(g, 1, 1, 2, 3, 8)) {
@@ -691,6 +687,10 @@ static int tg_launch_f16_image(const TileGemmArgs& g, hipStream_t stream, const 
     return check_launch(what);
 }
 
+#ifdef LPM_MEASURE
+// LPM_TG_DBG (measurement, pipelined forms only): 1 no main loop, 2 no stores, 4 no DMA inside the loop, 8 no MFMAs
+static int tg_dbg_env() { static const int v = env_measure_mode("LPM_TG_DBG"); return v; }
+#endif
 template <int EPI, int PL>
 static int tg_launch_pl(const TileGemmArgs& g, int nbatch, int splits, hipStream_t stream, const char* what, int ntw_override,
                         int timing_tag, int allow_wide) {
@@ -718,9 +718,12 @@ static int tg_launch_pl(const TileGemmArgs& g, int nbatch, int splits, hipStream
     dim3 grid((unsigned)(wide ? nbatch * g.a_tiles / (wide4 ? 8 : 4) : nbatch * g.rb_per_batch), (unsigned)((nt + 4 * ntw - 1) / (4 * ntw)),
               (unsigned)splits);
     TileGemmArgs gl = g;
-    // LPM_TG_DBG (measurement, pipelined forms only): 1 no main loop, 2 no stores, 4 no DMA inside the loop, 8 no MFMAs
-    static const int dbg_env = [] { const char* e = getenv("LPM_TG_DBG"); return e ? atoi(e) : 0; }();
+#ifdef LPM_MEASURE
+    const int dbg_env = tg_dbg_env();
     gl.dbg = dbg_env;
+#else
+    gl.dbg = 0;
+#endif
     if (!wide && g.cols_inner) {
         if (g.stats) { set_error("%s: cols_inner and the statistics epilogue index workgroups differently", what); return LPM_ERR_BADARG; }
         gl.cols_inner = (int)grid.y;
@@ -732,13 +735,20 @@ static int tg_launch_pl(const TileGemmArgs& g, int nbatch, int splits, hipStream
     // ring depth of the pipelined forms (LPM_TG_WIDE_NS / LPM_TG_WIDE4_NS = 4, 5: A/B; NS - 2 steps of LDS-DMA stay in flight).
     // Round 4, one box: K1 47.6 / 48.8 / 49.8 us at 4 / 5 / 6 stages; the 256-row dense form 3-10 % slower at 5 -- the loop is not
     // waiting for data in flight.
-    static const int wide_ns = [] { const char* e = getenv("LPM_TG_WIDE_NS"); const int v = e ? atoi(e) : 0; return (v >= 4 && v <= 5) ? v : TG_WIDE_NS_DEFAULT; }();
-    static const int wide4_ns = [] { const char* e = getenv("LPM_TG_WIDE4_NS"); const int v = e ? atoi(e) : 0; return (v >= 4 && v <= 5) ? v : 4; }();
+    // Measurement builds only: the five-stage instantiations exist for this A/B alone.
+#ifdef LPM_MEASURE
+    static const int wide_ns = [] { const int v = env_int("LPM_TG_WIDE_NS", 0); return (v >= 4 && v <= 5) ? v : TG_WIDE_NS_DEFAULT; }();
+    static const int wide4_ns = [] { const int v = env_int("LPM_TG_WIDE4_NS", 0); return (v >= 4 && v <= 5) ? v : 4; }();
+#else
+    constexpr int wide_ns = TG_WIDE_NS_DEFAULT, wide4_ns = 4;
+#endif
     // LPM_TG_AP (0 / 1): the anti-phase form of the 128- / 256-row workgroups (FORM 1) instead of the pipelined one.  Built and measured in
     // round 4, NOT faster (one box: K1 59.9 vs 51.2 us, qkv fwd 432 vs 406 us, ffn1 fwd 459 vs 448 us): a LOAD phase (3-4 LDS-DMA
     // issues + 8-12 fragment reads + two barrier episodes) is longer than a 12- / 24-MFMA COMPUTE phase, and a step costs twice the
-    // longer of the two.  Kept for the A/B.
-    static const int ap = [] { const char* e = getenv("LPM_TG_AP"); return e ? atoi(e) : TG_AP_DEFAULT; }();
+    // longer of the two.  Kept for the A/B, in measurement builds only.
+#ifdef LPM_MEASURE
+    static const int ap = env_int("LPM_TG_AP", 0);
+#endif
     const bool wide2 = wide && allow_wide == 2;
     const size_t lds = wide4 ? (size_t)wide4_ns * (16 + 8 * ntw) * 1024
                              : (wide ? (size_t)(wide2 ? 3 : wide_ns) * (8 + 8 * ntw) * 1024 : tg_lds_bytes(ntw, EPI));
@@ -760,14 +770,17 @@ static int tg_launch_pl(const TileGemmArgs& g, int nbatch, int splits, hipStream
     if constexpr (EPI == TG_EPI_ADAM) {
         LPM_TG_LAUNCH(1);
     } else {
+#ifdef LPM_MEASURE
         if (wide4 && ap) LPM_TG_LAUNCH_K((tile_gemm_kernel<2, TG_EPI_STORE, 2, 4, PL, 4, 1>), 512);
         else if (wide && !wide2 && ap) LPM_TG_LAUNCH_K((tile_gemm_kernel<2, TG_EPI_STORE, 2, 4, PL, 2, 1>), 512);
         else if (wide4 && wide4_ns == 5) LPM_TG_LAUNCH_K((tile_gemm_kernel<2, TG_EPI_STORE, 2, 5, PL, 4>), 512);
         else if (wide4 && dbg_env) LPM_TG_LAUNCH_K((tile_gemm_kernel<2, TG_EPI_STORE, 2, 4, PL, 4, 0, 1>), 512);
-        else if (wide4) LPM_TG_LAUNCH_K((tile_gemm_kernel<2, TG_EPI_STORE, 2, 4, PL, 4>), 512);
+        else if (wide && !wide4 && !wide2 && wide_ns == 5) LPM_TG_LAUNCH_K((tile_gemm_kernel<2, TG_EPI_STORE, 2, 5, PL>), 512);
+        else if (wide && !wide4 && !wide2 && dbg_env) LPM_TG_LAUNCH_K((tile_gemm_kernel<2, TG_EPI_STORE, 2, 4, PL, 2, 0, 1>), 512);
+        else
+#endif
+        if (wide4) LPM_TG_LAUNCH_K((tile_gemm_kernel<2, TG_EPI_STORE, 2, 4, PL, 4>), 512);
         else if (wide2) LPM_TG_LAUNCH_K((tile_gemm_kernel<2, TG_EPI_STORE, 2, 3, PL>), 512);
-        else if (wide && wide_ns == 5) LPM_TG_LAUNCH_K((tile_gemm_kernel<2, TG_EPI_STORE, 2, 5, PL>), 512);
-        else if (wide && dbg_env) LPM_TG_LAUNCH_K((tile_gemm_kernel<2, TG_EPI_STORE, 2, 4, PL, 2, 0, 1>), 512);
         else if (wide) LPM_TG_LAUNCH_K((tile_gemm_kernel<2, TG_EPI_STORE, 2, 4, PL>), 512);
         else if (ntw == 1) LPM_TG_LAUNCH(1);
         else if (ntw == 2) LPM_TG_LAUNCH(2);
@@ -817,20 +830,16 @@ int tile_gemm_image(const TileGemmArgs& g, hipStream_t stream, const char* what,
     gl.ldo = 4; gl.out_batch = 0; gl.out_split = 0;
     if (gl.img_planes != 2) gl.img_planes = 3;
     if (gl.mask_planes != 2) gl.mask_planes = 3;
-    if (planes >= 3) {
-        static const int nt3 = [] { const char* e = getenv("LPM_DENSE_IMG_NT"); return (e && e[0] == '0') ? 0 : 1; }();
-        gl.nt_store = nt3;
-        return tg_launch_f16_image(gl, stream, what, planes);
-    }
     // non-temporal stores: the 0.5 GB image is read back by the next GEMM long after it has left the caches (-6 us of 520 measured;
     // LPM_DENSE_IMG_NT=0: plain stores, A/B)
-    static const int nt = [] { const char* e = getenv("LPM_DENSE_IMG_NT"); return (e && e[0] == '0') ? 0 : 1; }();
+    static const int nt = env_first_is("LPM_DENSE_IMG_NT", '0') ? 0 : 1;
     gl.nt_store = nt;
+    if (planes >= 3) return tg_launch_f16_image(gl, stream, what, planes);
     return tg_launch_pl<TG_EPI_STORE, 2>(gl, 1, 1, stream, what, 2, 0, tile_gemm_image_form() == 3 ? 2 : 3);
 }
 // 4 (default): 256-row workgroups, one per CU; 3: 128-row workgroups, two per CU (their epilogues overlap the neighbour's main loop)
 int tile_gemm_image_form() {
-    static const int form = [] { const char* e = getenv("LPM_DENSE_IMG_FORM"); return (e && e[0] == '3') ? 3 : 4; }();
+    static const int form = env_first_is("LPM_DENSE_IMG_FORM", '3') ? 3 : 4;
     return form;
 }
 int tile_gemm_image_row_groups(int M) { return tile_gemm_image_form() == 3 ? M / 64 : M / 128; }
@@ -1152,7 +1161,7 @@ extern "C" int lpm_split_weight_tiles_parts(const void* x1, int64_t ld1, int64_t
                 (long long)n1a, ks);
     const int64_t total = (int64_t)(R / 16) * ((N + 31) / 32) * 64;
     // four columns per thread where every row piece is an aligned vector (LPM_SWT_PARTS4=0: the one-column form, A/B)
-    static const int four = [] { const char* e = getenv("LPM_SWT_PARTS4"); return (e && e[0] == '0') ? 0 : 1; }();
+    static const int four = env_first_is("LPM_SWT_PARTS4", '0') ? 0 : 1;
     const bool al1 = ld1 % 4 == 0 && ((uintptr_t)x1 & (x1_bf16 ? 7 : 15)) == 0 && ks % 4 == 0 && ((uintptr_t)scale & 15) == 0;
     const bool al2 = n1a == N || (ld2 % 4 == 0 && ((uintptr_t)x2 & 15) == 0);
     if (four && n1a % 4 == 0 && N % 4 == 0 && al1 && al2) {
@@ -1419,11 +1428,11 @@ extern "C" int lpm_skinny_weight_grad_tiles(const void* xt, const void* dyt, int
     g.b = (const uint4*)dyt; g.b_tile = 128; g.b_step = (int64_t)NT2 * 128; g.b_batch = 0; g.b_tiles = NT2;
     g.rb_per_batch = (N1 + 63) / 64; g.steps_per_split = R / 16; g.total_steps = R / 16;
     g.out = dW; g.ldo = N2; g.rows_valid = N1; g.cols_valid = N2;
-    static const int nt = [] { const char* e = getenv("LPM_DW_NT_STORE"); return (e && e[0] == '0') ? 0 : 1; }();      // 0: plain stores (A/B)
+    static const int nt = env_first_is("LPM_DW_NT_STORE", '0') ? 0 : 1;      // 0: plain stores (A/B)
     g.nt_store = nt;
     // the 4 (cfg-2) / 8 (cfg-5) column blocks of a row block as neighbours on one XCD: the activation tiles (86 MB at cfg-2, 277 MB at
     // cfg-5: more than the infinity cache) are fetched from HBM once instead of once per column block (LPM_DW_COLS_INNER=0: A/B)
-    static const int inner = [] { const char* e = getenv("LPM_DW_COLS_INNER"); return (e && e[0] == '0') ? 0 : 1; }();
+    static const int inner = env_first_is("LPM_DW_COLS_INNER", '0') ? 0 : 1;
     g.cols_inner = inner;
     // 5 reduction steps and a 554 MB store: narrow column blocks (36 KB of LDS, 4 workgroups per CU) so that one workgroup's
     // store overlaps its neighbours' loads (measured at cfg-2: 145 us with 128-column blocks, 215 us with 512)

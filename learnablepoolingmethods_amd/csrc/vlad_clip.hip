@@ -355,14 +355,17 @@ static int vlad_clip_impl(const void* at, const void* xt, const float* centres, 
     g.at = (const uint4*)at; g.xt = (const uint4*)xt; g.centres = centres;
     g.T = T; g.D = D; g.S = (T + 15) / 16; g.P = P; g.residual = residual;
     g.out = raw_kmajor; g.asum = asum; g.colsq_part = colsq_part; g.dmajor = dmajor;
-    static const int dbg = [] { const char* e = getenv("LPM_VC_DBG"); return e ? atoi(e) : 0; }();
+#ifdef LPM_MEASURE
+    static const int dbg = env_measure_mode("LPM_VC_DBG");
     g.dbg = dbg;
-    static const int ns = [] { const char* e = getenv("LPM_VC_NS"); return (e && e[0] == '3') ? 3 : 4; }();
-    static const int nt = [] { const char* e = getenv("LPM_VC_NT"); return (e && e[0] == '0') ? 0 : 1; }();
+#endif
+    static const int ns = env_first_is("LPM_VC_NS", '3') ? 3 : 4;
+    static const int nt = env_first_is("LPM_VC_NT", '0') ? 0 : 1;
     const size_t lds = (size_t)ns * VC_STAGE;
-    void (*kern)(const VCArgs);
+    void (*kern)(const VCArgs) = ns == 4 ? (nt ? vlad_clip_kernel<4, 2, 0> : vlad_clip_kernel<4, 0, 0>) : (nt ? vlad_clip_kernel<3, 2, 0> : vlad_clip_kernel<3, 0, 0>);
+#ifdef LPM_MEASURE
     if (dbg) kern = ns == 4 ? (nt ? vlad_clip_kernel<4, 2, 1> : vlad_clip_kernel<4, 0, 1>) : (nt ? vlad_clip_kernel<3, 2, 1> : vlad_clip_kernel<3, 0, 1>);
-    else kern = ns == 4 ? (nt ? vlad_clip_kernel<4, 2, 0> : vlad_clip_kernel<4, 0, 0>) : (nt ? vlad_clip_kernel<3, 2, 0> : vlad_clip_kernel<3, 0, 0>);
+#endif
     if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
         (void)hipGetLastError();
         set_error("lpm_vlad_aggregate_clip_kmajor_fwd: cannot reserve %zu bytes of LDS", lds);

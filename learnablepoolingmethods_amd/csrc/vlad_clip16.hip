@@ -362,16 +362,22 @@ extern "C" int lpm_vlad_aggregate_clip_fwd_bf16(const void* at, const void* xt, 
     g.at = (const uint4*)at; g.xt = (const uint4*)xt; g.centres = centres;
     g.D = D; g.K = K; g.S = 4 * ((T + 63) / 64); g.P = P; g.KH = K / 256; g.residual = residual;
     g.out = (unsigned short*)nrm_bf16; g.asum = asum; g.colsq_part = colsq_part;
-    static const int dbg = [] { const char* e = getenv("LPM_VB_DBG"); return e ? atoi(e) : 0; }();
+#ifdef LPM_MEASURE
+    static const int dbg = env_measure_mode("LPM_VB_DBG");
+    static const int delay = env_int("LPM_VB_DELAY", 8);
+#else
+    constexpr int dbg = 0, delay = 8;
+#endif
     g.dbg = dbg;
-    static const int delay = [] { const char* e = getenv("LPM_VB_DELAY"); return e ? atoi(e) : 8; }();
     g.delay_us = delay;
     constexpr int NS = 4;
     const size_t ring = (size_t)NS * VB_STAGE, epi = (size_t)VB_EPI + VB_TAIL;
     const size_t lds = ring > epi ? ring : epi;
-    static const int nt = [] { const char* e = getenv("LPM_VB_NT"); return (e && e[0] == '0') ? 0 : 1; }();
-    void (*kern)(const VBArgs) = dbg ? (nt ? vlad_clip16_kernel<NS, 1, 2> : vlad_clip16_kernel<NS, 1, 0>)
-                                     : (nt ? vlad_clip16_kernel<NS, 0, 2> : vlad_clip16_kernel<NS, 0, 0>);
+    static const int nt = env_first_is("LPM_VB_NT", '0') ? 0 : 1;
+    void (*kern)(const VBArgs) = nt ? vlad_clip16_kernel<NS, 0, 2> : vlad_clip16_kernel<NS, 0, 0>;
+#ifdef LPM_MEASURE
+    if (dbg) kern = nt ? vlad_clip16_kernel<NS, 1, 2> : vlad_clip16_kernel<NS, 1, 0>;
+#endif
     if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
         (void)hipGetLastError();
         set_error("lpm_vlad_aggregate_clip_fwd_bf16: cannot reserve %zu bytes of LDS", lds);

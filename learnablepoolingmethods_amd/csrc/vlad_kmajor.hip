@@ -318,7 +318,7 @@ __global__ __launch_bounds__(512, 4) void vlad_kmajor_kernel(const VKArgs g) {
 
 // clips that run as wide items: whole rounds of 2 x 256 workgroup slots (64 clips at D = 1024), the rest as 128 x 128 items in the tail
 static int vk_large_clips(int B, int D, int K, int flags) {
-    static const int env_mode = [] { const char* e = getenv("LPM_K2_WIDE"); return e ? atoi(e) : 1; }();      // 0: none, 1: rounds, 2: all
+    static const int env_mode = env_int("LPM_K2_WIDE", 1);      // 0: none, 1: rounds, 2: all
     const int mode = (flags & LPM_VLAD_WIDE_ALL) ? 2 : ((flags & LPM_VLAD_WIDE_NONE) ? 0 : env_mode);
     if (K != 256 || mode == 0) return 0;
     if (mode == 2) return B;
@@ -358,8 +358,10 @@ extern "C" int lpm_vlad_aggregate_kmajor_scaled_fwd(const void* at, const void* 
     g.out = raw_kmajor; g.asum = asum; g.colsq_part = (float*)workspace;
     g.scale = scale; g.colsq = colsq; g.csq = csq; g.gsq = gsq;
     g.arrive = (unsigned*)(g.colsq_part + (size_t)B * P * K);
-    static const int dbg = [] { const char* e = getenv("LPM_VK_DBG"); return e ? atoi(e) : 0; }();
+#ifdef LPM_MEASURE
+    static const int dbg = env_measure_mode("LPM_VK_DBG");
     g.dbg = dbg;
+#endif
     if (hipMemsetAsync(g.arrive, 0, (size_t)B * sizeof(unsigned), s) != hipSuccess) {        // the arrival counters: zero at every launch
         (void)hipGetLastError();
         set_error("lpm_vlad_aggregate_kmajor_scaled_fwd: cannot clear the arrival counters");

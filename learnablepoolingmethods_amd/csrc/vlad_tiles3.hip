@@ -770,7 +770,8 @@ __global__ __launch_bounds__(256) void vlad_finalize2_kmajor4_kernel(float* __re
 namespace lpm {
 // LDS-DMA cache policy of the aggregation kernel's two streams (bit 0: assignment tiles, bit 1: frame tiles non-temporal)
 static int t3_nt() {
-    static const int v = [] { const char* e = getenv("LPM_T3_NT"); return e ? (atoi(e) & 3) : T3_NT_DEFAULT; }();
+    static_assert((T3_NT_DEFAULT & 3) == T3_NT_DEFAULT, "the default is a value of the two-bit mask");
+    static const int v = env_int("LPM_T3_NT", T3_NT_DEFAULT) & 3;
     return v << 1;
 }
 }  // namespace lpm
@@ -866,8 +867,12 @@ extern "C" int lpm_vlad_aggregate_raw_kmajor_fwd(const void* at, const void* xt,
     const int S = (T + 15) / 16, KT = K / 32;
     T3Fused fz{};
     fz.out = raw_kmajor; fz.raw_kmajor = 1;
-    // LPM_K2_EXTRA_LDS (measurement): bytes of unused LDS added to the launch -- 27000 leaves two workgroups per CU instead of three
-    static const int extra_lds = [] { const char* e = getenv("LPM_K2_EXTRA_LDS"); return e ? atoi(e) : 0; }();
+    // LPM_K2_EXTRA_LDS (measurement builds): bytes of unused LDS added to the launch -- 27000 leaves two workgroups per CU instead of three
+#ifdef LPM_MEASURE
+    static const int extra_lds = env_int("LPM_K2_EXTRA_LDS", 0);
+#else
+    constexpr int extra_lds = 0;
+#endif
     const size_t lds = (size_t)T3_NS * T3_STAGE + (4 * 128 + 128 + 16) * sizeof(float) + (size_t)extra_lds;
     auto kern = vlad_aggregate_tiles3_kernel<true, 2>;
     if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
@@ -1039,7 +1044,7 @@ static int vlad_finalize2_impl(float* nrm, const float* colsq_part, int P, int B
                 "lpm_vlad_finalize2_fwd: bf16 storage is implemented for the reference's d-major layout only");
     LPM_REQUIRE(!nrm_bf16 || keep_u, LPM_ERR_BADARG, "lpm_vlad_finalize2_fwd: LPM_VLAD_NRM_BF16 goes with LPM_VLAD_NRM_RAW");
     const size_t lds = (size_t)(K + 32 * 33 + 4) * sizeof(float);
-    static const int wide = [] { const char* e = getenv("LPM_FINALIZE_KMAJOR4"); return e ? atoi(e) : 32; }();   // 0: scalar form (A/B)
+    static const int wide = env_int("LPM_FINALIZE_KMAJOR4", 32);   // 0: scalar form (A/B)
     if ((flags & LPM_VLAD_OUT_KMAJOR) && wide && K <= 512 && (((uintptr_t)nrm | (uintptr_t)out) & 15) == 0) {
         const int R = (wide == 64 && D % 64 == 0) ? 64 : 32;
         const size_t lds4 = (size_t)(K + 4 + R * (K + 2)) * sizeof(float);

@@ -16,13 +16,13 @@ PACKED = re.compile(r"\bv_pk_(fma|mul|add)_f32\b")
 SRC = os.path.join(_build.CSRC, "clip_adam.hip")
 
 
-def _device_asm(flags, tmp_path, name):
+def _device_asm(flags, tmp_path, name, src=SRC):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
     out = tmp_path / name
     dev = [f for f in flags if f not in ("-fPIC",)]
-    r = subprocess.run([hipcc, *dev, "--cuda-device-only", "-S", SRC, "-o", str(out)], capture_output=True, text=True, cwd=str(tmp_path))
+    r = subprocess.run([hipcc, *dev, "--cuda-device-only", "-S", src, "-o", str(out)], capture_output=True, text=True, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-2000:]
     return out.read_text()
 
@@ -45,13 +45,7 @@ def test_clip_wide_aggregation_loop_carries_its_fragments_in_place(tmp_path):
     registers at both ends of the back edge: a register copy behind the request reads bits that have not arrived yet (the round-4
     determinism failure: a v_mov of the next assignment fragment, stale whenever LDS was slower than the copy).  The main loop of every
     production instantiation must hold no vector register copy and no scratch access."""
-    global SRC
-    keep = SRC
-    try:
-        SRC = os.path.join(_build.CSRC, "vlad_clip.hip")
-        asm = _device_asm(_build.FLAGS, tmp_path, "vlad_clip.s")
-    finally:
-        SRC = keep
+    asm = _device_asm(_build.FLAGS, tmp_path, "vlad_clip.s", os.path.join(_build.CSRC, "vlad_clip.hip"))
     kernels = re.findall(r"^(_ZN3lpm16vlad_clip_kernelILi\dELi\dELi0EEEvNS_6VCArgsE):[^\n]*\n(.*?)s_endpgm", asm, flags=re.S | re.M)
     assert len(kernels) >= 2, "production instantiations of vlad_clip_kernel not found in the device assembly"
     for name, body in kernels:
@@ -74,13 +68,7 @@ def test_bf16_clip_wide_aggregation_loop_carries_its_fragments_in_place(tmp_path
     (the loop holds two steps).  The same condition holds: in the main loop of the production instantiations no vector register copy and
     no scratch access, the 24 MFMAs of two steps, and no s_waitcnt vmcnt(0) other than the ones the source places at the end of the
     frame loop (the compiler must not drain the LDS-DMA ring on its own)."""
-    global SRC
-    keep = SRC
-    try:
-        SRC = os.path.join(_build.CSRC, "vlad_clip16.hip")
-        asm = _device_asm(_build.FLAGS, tmp_path, "vlad_clip16.s")
-    finally:
-        SRC = keep
+    asm = _device_asm(_build.FLAGS, tmp_path, "vlad_clip16.s", os.path.join(_build.CSRC, "vlad_clip16.hip"))
     kernels = re.findall(r"^(_ZN3lpm18vlad_clip16_kernelILi\dELi0ELi\dEEEvNS_6VBArgsE):[^\n]*\n(.*?)s_endpgm", asm, flags=re.S | re.M)
     assert len(kernels) >= 2, "production instantiations of vlad_clip16_kernel not found in the device assembly"
     for name, body in kernels:
@@ -138,9 +126,7 @@ def test_flat_k1_loop_keeps_loads_in_flight_and_copies_no_registers():
     src = os.path.join(_build.CSRC, "assign_flat.hip")
     rep = scan.scan(src)
     assert sum("assign_flat_kernel" in n for n, _ in rep) >= 3
-    for name, waits in rep:
-        if re.search(r"assign_wide_kernel<[1-9]\d*>", name):
-            continue                                            # timing-experiment instantiations (-DLPM_K1_WIDE_EXPERIMENTS builds only)
+    for name, waits in rep:                                     # (the timing-experiment instantiations exist in -DLPM_MEASURE builds only)
         assert not waits, f"{name}: compiler-inserted vmcnt waits inside the LDS-DMA loop: {waits[:4]}"
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, "k.s")
@@ -224,3 +210,51 @@ def _check_async_loop(asm, mangled, mfma_counts):
     assert len(seen) >= 48, f"{mangled}: the scan found only {len(seen)} registers written by asynchronous loads"
     assert not copies, f"{mangled}: copies of registers that asynchronous loads write: {copies[:6]}"
     return {"loop": loop, "lines": lines}
+
+
+# The measurement modes (docs/switches.md): the variable the host reads in a -DLPM_MEASURE build, and the mangled names of the instantiations
+# only such a build holds (None: the mode is a run-time argument of the production kernel, which a default build passes as 0).
+MEASURE_ONLY = {
+    "vlad_clip16.hip": (("LPM_VB_DBG", "LPM_VB_DELAY"), r"_ZN3lpm18vlad_clip16_kernelILi\d+ELi1ELi\d+EEE"),
+    "vlad_clip.hip": (("LPM_VC_DBG",), r"_ZN3lpm16vlad_clip_kernelILi\d+ELi\d+ELi1EEE"),
+    "assign_flat.hip": (("LPM_K1_WIDE_DBG",), r"_ZN3lpm18assign_wide_kernelILi[1-9]\d*EEE"),
+    "tile_gemm.hip": (("LPM_TG_DBG", "LPM_TG_AP", "LPM_TG_WIDE_NS", "LPM_TG_WIDE4_NS"), None),       # (checked parameter by parameter below)
+    "vlad_kmajor.hip": (("LPM_VK_DBG",), None),
+    "factored_adam.hip": (("LPM_FA_DBG", "LPM_FA_FOLD_DBG"), None),
+    "vlad_tiles3.hip": (("LPM_K2_EXTRA_LDS",), None),
+}
+
+
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize("name", sorted(MEASURE_ONLY))
+def test_measurement_modes_exist_only_under_the_build_macro(name, tmp_path):
+    """A default build must not be able to produce garbage on request: the host code of the launchers holds the names of the measurement
+    variables only when compiled with -DLPM_MEASURE (the control: it does hold them then), and the device code of a default build holds no
+    DBG = 1 / ablation instantiation -- for tile_gemm.hip no anti-phase (FORM 1) and no five-stage (NS = 5) instantiation either."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not available")
+    variables, gated = MEASURE_ONLY[name]
+    src = os.path.join(_build.CSRC, name)
+    flags = [f for f in _build.FLAGS if f != "-DLPM_MEASURE"] + _build.EXTRA_FLAGS.get(name, [])
+    for macro in ([], ["-DLPM_MEASURE"]):
+        obj = tmp_path / ("host_measure.o" if macro else "host_default.o")
+        r = subprocess.run([hipcc, *flags, *macro, "--cuda-host-only", "-c", src, "-o", str(obj)], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-2000:]
+        data = obj.read_bytes()
+        for v in variables:
+            assert (v.encode() + b"\0" in data) == bool(macro), f"{name}: {v} in the host code of a build {'with' if macro else 'without'} -DLPM_MEASURE"
+    if name in ("vlad_kmajor.hip", "factored_adam.hip", "vlad_tiles3.hip"):
+        return                                                  # no instantiation to look for: the mode is an argument
+    asm = _device_asm(flags, tmp_path, "device.s", src)
+    if gated is not None:
+        family = gated[:gated.index("I")]
+        assert re.search(r"^" + family + r"I\w+:", asm, flags=re.M), f"{name}: no instantiation of the kernel family found at all"
+        assert not re.search(gated, asm), f"{name}: a measurement instantiation in the device code of a default build"
+        return
+    # tile_gemm_kernel<NTW, EPI, MW, NS, PL, RTW, FORM, DBG>
+    inst = re.findall(r"^_ZN3lpm16tile_gemm_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)EEEvNS_12TileGemmArgsE:", asm, flags=re.M)
+    assert len(inst) >= 10, f"only {len(inst)} instantiations of tile_gemm_kernel found"
+    assert any(i[2] == "2" and i[3] == "4" for i in inst) and any(i[2] == "2" and i[3] == "3" for i in inst), "the 128-row forms are missing"
+    bad = [i for i in inst if i[7] != "0" or i[6] != "0" or i[3] == "5"]
+    assert not bad, f"measurement-only instantiations (DBG = 1, FORM 1 or NS = 5) in the device code of a default build: {bad}"

@@ -1751,6 +1751,73 @@ def test_assign_gemm_row_forms_bit_identical(tmp_path):
     assert float(outs[0]["logits"].abs().max()) > 0
 
 
+_MEASURE_SCRIPT = r"""
+import sys, torch
+from learnablepoolingmethods_amd import _capi
+from learnablepoolingmethods_amd._capi import ptr, stream_ptr
+lib = _capi.load()
+dev = torch.device("cuda:0")
+st = stream_ptr()
+ints = lambda nbytes: torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+g = torch.Generator().manual_seed(17)
+# K2 for bf16 storage on clip-wide items (vlad_clip16.hip): the smallest shape with lpm_vlad_clip16_slabs > 0
+B, T, D, K = 2, 64, 384, 256
+P = lib._lpm_vlad_clip16_slabs(D, K)
+assert P > 0
+x = torch.randn(B * T, D, generator=g).to(dev)
+a = torch.rand(B * T, K, generator=g).to(torch.bfloat16).to(dev)
+cen = (torch.randn(D, K, generator=g) / D ** 0.5).to(dev)
+xt = ints(lib._lpm_frame_tiles_bf16_bytes(B, T, D))
+lib.check(lib._lpm_split_frames_bf16(ptr(x), D, B, T, D, ptr(xt), st), "lpm_split_frames_bf16")
+at = ints(B * (K // 32) * lib._lpm_frame_steps_bf16(T) * 1024)
+lib.check(lib._lpm_assign_tiles_bf16(ptr(a), None, None, B, T, K, 0, ptr(at), st), "lpm_assign_tiles_bf16")
+nrm = torch.zeros((B, D, K), dtype=torch.bfloat16, device=dev)
+asum, part = torch.zeros((B, K), device=dev), torch.zeros((B, P, K), device=dev)
+lib.check(lib._lpm_vlad_aggregate_clip_fwd_bf16(ptr(at), ptr(xt), ptr(cen), B, T, D, K, _capi.LPM_VLAD_RESIDUAL, ptr(nrm), ptr(asum), ptr(part),
+                                                st), "lpm_vlad_aggregate_clip_fwd_bf16")
+# one 128-row tile GEMM store (tile_gemm.hip): four row tiles, 16 reduction steps, one 256-column block
+M, Kd, N = 128, 256, 256
+xd = torch.randn(M, Kd, generator=g).to(dev)
+W = (torch.randn(Kd, N, generator=g) / Kd ** 0.5).to(dev)
+xr, wt = ints(lib._lpm_row_tiles_bytes(1, M, Kd)), ints(lib._lpm_weight_tiles_bytes(Kd, N))
+lib.check(lib._lpm_split_rows_tiles(ptr(xd), Kd, 1, M, Kd, ptr(xr), st), "lpm_split_rows_tiles")
+lib.check(lib._lpm_split_weight_tiles(ptr(W), Kd, N, 0, ptr(wt), st), "lpm_split_weight_tiles")
+y = torch.zeros(M, N, device=dev)
+lib.check(lib._lpm_dense_tiles_fwd(ptr(xr), ptr(wt), M, Kd, N, ptr(y), N, 2, st), "lpm_dense_tiles_fwd")
+torch.cuda.synchronize()
+torch.save({"measure_build": lib._lpm_measure_build(), "nrm": nrm.cpu(), "asum": asum.cpu(), "part": part.cpu(), "y": y.cpu(),
+            "y_ref": (xd.double() @ W.double()).cpu()}, sys.argv[1])
+"""
+
+
+@pytest.mark.gpu
+def test_measurement_variables_are_ignored_by_the_default_build(tmp_path):
+    """The measurement instantiations (kernels that skip their main loop, their stores, their MFMAs: garbage by design) and the reads of the
+    variables that select them exist only in -DLPM_MEASURE builds (docs/switches.md).  The bf16 clip-wide K2 and a 128-row tile GEMM store,
+    once in a clean environment and once with LPM_VB_DBG=1 (no main loop) LPM_TG_DBG=2 (no stores) LPM_VC_DBG=1 LPM_FA_FOLD_DBG=16 set
+    (read once per process: hence two child processes): the default build writes the same bits, and they are the right ones."""
+    import os, subprocess, sys
+    from learnablepoolingmethods_amd import _capi
+    if _capi.load()._lpm_measure_build():
+        pytest.skip("a measurement build honours these variables")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    names = ("LPM_VB_DBG", "LPM_VB_DELAY", "LPM_TG_DBG", "LPM_VC_DBG", "LPM_VK_DBG", "LPM_FA_DBG", "LPM_FA_FOLD_DBG", "LPM_K1_WIDE_DBG")
+    clean = {k: v for k, v in os.environ.items() if k not in names}
+    clean["PYTHONPATH"] = root + os.pathsep + os.environ.get("PYTHONPATH", "")
+    outs = []
+    for extra in ({}, {"LPM_VB_DBG": "1", "LPM_TG_DBG": "2", "LPM_VC_DBG": "1", "LPM_FA_FOLD_DBG": "16"}):
+        out = tmp_path / f"measure_{len(outs)}.pt"
+        r = subprocess.run([sys.executable, "-c", _MEASURE_SCRIPT, str(out)], env=dict(clean, **extra), capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]                 # (a failed first child ends the test: the second never starts)
+        assert "measurement mode" not in r.stderr, r.stderr[-2000:]
+        outs.append(torch.load(out))
+    assert outs[0]["measure_build"] == 0 and outs[1]["measure_build"] == 0
+    for k in ("nrm", "asum", "part", "y"):
+        assert torch.equal(outs[0][k], outs[1][k]), k
+    assert float(outs[0]["nrm"].float().abs().max()) > 0 and float(outs[0]["asum"].abs().max()) > 0
+    assert_close(outs[0]["y"], outs[0]["y_ref"], tol=2e-5, what="128-row tile GEMM store")
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("kmajor", [False, True])
 def test_netvlad_raw_nrm_matches_normalised_nrm(kmajor, monkeypatch):

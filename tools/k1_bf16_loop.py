@@ -1,5 +1,5 @@
 """K1 on plain bf16 tiles alone at BASELINE configs[4]'s video shape (128 x 300 frames, 1024 -> 512): HIP-event time per launch.
-usage: python tools/k1_bf16_loop.py [launches]   (LPM_K1_WIDE=0: the flat 96-row form; LPM_K1_WIDE_DBG=n: timing experiments)"""
+usage: python tools/k1_bf16_loop.py [launches]   (LPM_K1_WIDE=0: the flat 96-row form; LPM_K1_WIDE_DBG=n: timing experiments, -DLPM_MEASURE builds only)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -7,6 +7,7 @@ from learnablepoolingmethods_amd import _capi, ops
 from learnablepoolingmethods_amd._capi import ptr, stream_ptr
 
 lib = _capi.load()
+_capi.require_measure_build()
 dev = torch.device("cuda:0")
 B, T, D, K = 128, 300, 1024, 512
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 50

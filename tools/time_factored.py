@@ -3,7 +3,8 @@
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from learnablepoolingmethods_amd import ops
+from learnablepoolingmethods_amd import _capi, ops
+_capi.require_measure_build()
 dev = torch.device("cuda:0")
 a = [int(v) for v in sys.argv[1:]]
 R, N1, N2 = a[:3] if len(a) >= 3 else (80, 270336, 512)

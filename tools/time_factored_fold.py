@@ -6,6 +6,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from learnablepoolingmethods_amd import _capi, ops
 from learnablepoolingmethods_amd._capi import ptr, stream_ptr
+_capi.require_measure_build()
 dev = torch.device("cuda:0")
 mode = sys.argv[1] if len(sys.argv) > 1 else "dx"
 a = [int(v) for v in sys.argv[2:]]

@@ -8,6 +8,7 @@ import torch
 from learnablepoolingmethods_amd import _capi, ops
 
 lib = _capi.load()
+_capi.require_measure_build()
 dev = torch.device("cuda:0")
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 15
 B, T, D, K = 128, 300, 1024, 512

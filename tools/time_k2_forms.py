@@ -12,6 +12,7 @@ from learnablepoolingmethods_amd.ops import ptr, stream_ptr
 
 dev = torch.device("cuda:0")
 lib = _capi.load()
+_capi.require_measure_build()
 B, T, D, K = (int(a) for a in sys.argv[1:5]) if len(sys.argv) >= 5 else (80, 300, 1024, 256)
 g = torch.Generator(device=dev).manual_seed(0)
 x = torch.randn(B * T, D, device=dev, generator=g)

@@ -11,6 +11,7 @@ W = torch.randn(D, K, device=dev, generator=g) / 32
 W2 = torch.randn(1, D, K, device=dev, generator=g) / 32
 bn = (torch.ones(K, device=dev), torch.zeros(K, device=dev), torch.zeros(K, device=dev), torch.ones(K, device=dev))
 lib = _capi.load()
+_capi.require_measure_build()
 with torch.no_grad():
     for _ in range(3):
         ops.netvlad(x[:, :D], W, W2, T, bn=bn, kmajor=True)
