@@ -715,6 +715,9 @@ int lpm_bias_act_bwd(const float* dy, const float* y, int relu, int64_t M, int C
  * one mean/variance per example over all L*F non-batch elements, gamma/beta [F], eps inside the sqrt.
  *   fwd: z = a + r (r may be NULL: then z is not written and a plays its role); y = (z-mean)*rstd*gamma + beta;
  *        stats [B,2] = (mean, rstd).   bwd: dz (gradient w.r.t. z, i.e. w.r.t. both a and r), dgamma, dbeta.
+ *        The moments: mean = s/n, var = q/n - mean^2 from the sums of z and z^2 where mean^2 <= var; elsewhere from sums shifted by a
+ *        per-example pivot K = the example's first z (mean = K + s/n, var = q/n - (s/n)^2 with s, q the sums of z - K and (z - K)^2):
+ *        no cancellation of mean^2 against the mean square at any offset.
  * a, r, y, z, dy, dz: [B, L, F] contiguous.  workspace: lpm_layer_norm_workspace_bytes(B, F).
  * ------------------------------------------------------------------------------------------- */
 size_t lpm_layer_norm_workspace_bytes(int B, int F);

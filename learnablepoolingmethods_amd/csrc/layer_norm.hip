@@ -34,7 +34,14 @@ __device__ __forceinline__ float block_sum(float v, float* sh) {   // 256 thread
     return (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
-// pass 1: z = a + r (written when r != NULL), partial[b][chunk] = (sum z, sum z^2)
+// pass 1: z = a + r (written when r != NULL), partial[b][chunk] = (sum z, sum z^2) and shifted[b][chunk] = (sum (z - K), sum (z - K)^2)
+// with the example's pivot K = its first z, pivot[b] (behind the B * LN_NB pairs of ``shifted``).
+// Two pairs of sums: var = q/n - (s/n)^2 from the RAW sums loses eps32 (mean/std)^2 of the variance (measured at mean/std = 30: y up to 14
+// times, the gradients up to 90 times further from fp64 than a two-pass fp32 evaluation, tests/test_gpu_layer_norm_bounds.py); from the
+// sums SHIFTED by a pivot that lies within the data the same fold loses eps32 ((mean - K)/std)^2, a few eps32, at any offset -- and more
+// than the raw sums where the mean is small against the spread (measured at |mean|/std <= 0.2, the benched step: the mean 4e-8 std off
+// instead of 2e-9).  The fold (ln_moments) takes the raw sums where mean^2 <= var and the shifted ones elsewhere.  Every workgroup forms K
+// itself from the example's element 0: no pass, no launch, no exchange between workgroups.
 // MASK (NetVladV2's encoder: tf.layers.dropout between the dense layer and the layer norm, transformer_utils.py:450): the keep mask
 // [B, L, F] (one byte per element) and its scale 1 / keep_probability apply to act(a + bias), BEFORE the residual is added.
 template <bool MASK>
@@ -42,15 +49,23 @@ __global__ __launch_bounds__(256) void ln_fwd_stats_kernel(const float* __restri
                                                            const float* __restrict__ bias, int relu, int F,
                                                            int64_t n_per, float* __restrict__ z,
                                                            float* __restrict__ partial, const float* __restrict__ r_scale,
-                                                           const unsigned char* __restrict__ mask, float mscale) {
+                                                           const unsigned char* __restrict__ mask, float mscale,
+                                                           float* __restrict__ shifted) {
     __shared__ float sh[4];
     const int b = blockIdx.x, ch = blockIdx.y;
     const int64_t n4 = n_per / 4;
     const float4* ap = reinterpret_cast<const float4*>(a + (int64_t)b * n_per);
     const float4* rp = r ? reinterpret_cast<const float4*>(r + (int64_t)b * n_per) : nullptr;
     float4* zp = reinterpret_cast<float4*>(z + (int64_t)b * n_per);
-    float s = 0.f, q = 0.f;
+    float s = 0.f, q = 0.f, ss = 0.f, sq = 0.f;
     const int F4 = F / 4;
+    float K = ap[0].x;                         // the pivot: element 0 of the example, by the operations of the loop below
+    if (bias) {
+        K += bias[0];
+        if (relu) K = fmaxf(K, 0.f);
+    }
+    if (MASK) K = mask[(int64_t)b * n_per] ? K * mscale : 0.f;
+    if (rp) K += r_scale ? rp[0].x * r_scale[(int64_t)b * (n_per / F)] : rp[0].x;
     // chunk ch takes the 256-float4 pieces ch, ch + LN_NB, ...: at any moment the LN_NB workgroups of an example read
     // LN_NB consecutive 4 KB pieces (contiguous chunks put every workgroup of the grid at the same offset of its own
     // 64 KB-aligned range at the same time: the same few HBM channels for everyone, ~3 TB/s)
@@ -76,40 +91,69 @@ __global__ __launch_bounds__(256) void ln_fwd_stats_kernel(const float* __restri
             v.x += w.x; v.y += w.y; v.z += w.z; v.w += w.w;
         }
         if (rp || bias || MASK) zp[i] = v;
-        s += (v.x + v.y) + (v.z + v.w);
+        const float t = (v.x + v.y) + (v.z + v.w);
+        s += t;
         q = fmaf(v.x, v.x, q); q = fmaf(v.y, v.y, q); q = fmaf(v.z, v.z, q); q = fmaf(v.w, v.w, q);
+        ss += fmaf(-4.f, K, t);                // (the four's sum less 4 K: its rounding, eps32 |t|, averages out over the n / 4 of them)
+        v.x -= K; v.y -= K; v.z -= K; v.w -= K;
+        sq = fmaf(v.x, v.x, sq); sq = fmaf(v.y, v.y, sq); sq = fmaf(v.z, v.z, sq); sq = fmaf(v.w, v.w, sq);
     }
     s = block_sum(s, sh);
     q = block_sum(q, sh);
+    ss = block_sum(ss, sh);
+    sq = block_sum(sq, sh);
     if (threadIdx.x == 0) {
         partial[((int64_t)b * LN_NB + ch) * 2] = s;
         partial[((int64_t)b * LN_NB + ch) * 2 + 1] = q;
+        shifted[((int64_t)b * LN_NB + ch) * 2] = ss;
+        shifted[((int64_t)b * LN_NB + ch) * 2 + 1] = sq;
+        if (ch == 0) shifted[(int64_t)gridDim.x * LN_NB * 2 + b] = K;
     }
 }
 
-// pass 2: y = (z - mean) * rstd * gamma + beta.  r2 != NULL (layer-norm pair): what leaves is y + r2 -- the NEXT layer norm's
-// residual sum -- together with its per-chunk (sum, sum of squares) in partial_next, so the next layer norm needs no statistics
-// pass of its own.
+// The fold of an example's LN_NB chunk sums, in fp64 and in chunk order -> (mean, variance).  Both forms are evaluated; the shifted one
+// (accurate at any offset) decides: where mean^2 <= var the raw sums are at least as accurate and are taken, elsewhere the shifted ones.
+// Every workgroup of the example folds the same numbers, so all of them take the same form.
+__device__ __forceinline__ void ln_moments(const float* __restrict__ partial, const float* __restrict__ shifted, int b, int B, int64_t n_per,
+                                           double& mu, double& var) {
+    double s = 0.0, q = 0.0, ss = 0.0, sq = 0.0;
+#pragma unroll
+    for (int i = 0; i < LN_NB; ++i) {
+        s += (double)partial[((int64_t)b * LN_NB + i) * 2];
+        q += (double)partial[((int64_t)b * LN_NB + i) * 2 + 1];
+        ss += (double)shifted[((int64_t)b * LN_NB + i) * 2];
+        sq += (double)shifted[((int64_t)b * LN_NB + i) * 2 + 1];
+    }
+    const double dm = ss / (double)n_per, mu_s = (double)shifted[(int64_t)B * LN_NB * 2 + b] + dm;
+    double var_s = sq / (double)n_per - dm * dm;
+    if (var_s < 0.0) var_s = 0.0;
+    mu = s / (double)n_per;
+    var = q / (double)n_per - mu * mu;
+    if (var < 0.0) var = 0.0;
+    if (mu_s * mu_s > var_s) {
+        mu = mu_s;
+        var = var_s;
+    }
+}
+
+// pass 2: (mean, var) = ln_moments; y = (z - mean) * rstd * gamma + beta.
+// r2 != NULL (layer-norm pair): what leaves is y + r2 -- the NEXT layer norm's residual sum -- together with its per-chunk raw and
+// shifted (sum, sum of squares) in partial_next / shifted_next, so the next layer norm needs no statistics pass of its own.  Their pivot
+// is the next sum's element 0, which every workgroup forms itself.
 __global__ __launch_bounds__(256) void ln_fwd_apply_kernel(const float* __restrict__ z, const float* __restrict__ partial,
                                                            const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, int64_t n_per, int F,
                                                            float eps, float* __restrict__ y, int64_t y_batch,
                                                            float* __restrict__ stats, const float* __restrict__ r2,
                                                            float* __restrict__ partial_next, unsigned short* __restrict__ y3,
-                                                           const OperandFmt fmt) {
+                                                           const OperandFmt fmt, const float* __restrict__ shifted,
+                                                           float* __restrict__ shifted_next) {
     // y3 != NULL: y ALSO leaves as the split-bf16 activation image [rows][3 F] = [hi | lo | hi] of the dense layer that reads it next
     // (split_gemm.hip's format): the separate split pass over y (read 4 B, write 6 B per element) is not run
     __shared__ float sh[4];
     const int b = blockIdx.x, ch = blockIdx.y;
-    double s = 0.0, q = 0.0;
-#pragma unroll
-    for (int i = 0; i < LN_NB; ++i) {
-        s += (double)partial[((int64_t)b * LN_NB + i) * 2];
-        q += (double)partial[((int64_t)b * LN_NB + i) * 2 + 1];
-    }
-    const double mu = s / (double)n_per;
-    double var = q / (double)n_per - mu * mu;
-    if (var < 0.0) var = 0.0;
+    double mu, var;
+    ln_moments(partial, shifted, b, gridDim.x, n_per, mu, var);
     const float mean = (float)mu, rstd = (float)(1.0 / sqrt(var + (double)eps));
     if (ch == 0 && threadIdx.x == 0) {
         stats[2 * b] = mean;
@@ -120,7 +164,8 @@ __global__ __launch_bounds__(256) void ln_fwd_apply_kernel(const float* __restri
     const float4* zp = reinterpret_cast<const float4*>(z + (int64_t)b * n_per);
     const float4* rp = r2 ? reinterpret_cast<const float4*>(r2 + (int64_t)b * n_per) : nullptr;
     float4* yp = reinterpret_cast<float4*>(y + (int64_t)b * y_batch);
-    float ns = 0.f, nq = 0.f, vmax = 0.f;
+    float ns = 0.f, nq = 0.f, nss = 0.f, nsq = 0.f, vmax = 0.f;
+    const float K2 = rp ? fmaf((zp[0].x - mean) * rstd, gamma[0], beta[0]) + rp[0].x : 0.f;     // the next sum's pivot: its element 0
     for (int64_t i = (int64_t)ch * 256 + threadIdx.x; i < n4; i += (int64_t)LN_NB * 256) {      // interleaved pieces, as in pass 1
         const int c = (int)(i % F4) * 4;
         const float4 v = zp[i];
@@ -133,8 +178,12 @@ __global__ __launch_bounds__(256) void ln_fwd_apply_kernel(const float* __restri
         if (rp) {
             const float4 w = rp[i];
             o.x += w.x; o.y += w.y; o.z += w.z; o.w += w.w;
-            ns += (o.x + o.y) + (o.z + o.w);
+            const float t = (o.x + o.y) + (o.z + o.w);
+            ns += t;
             nq = fmaf(o.x, o.x, nq); nq = fmaf(o.y, o.y, nq); nq = fmaf(o.z, o.z, nq); nq = fmaf(o.w, o.w, nq);
+            nss += fmaf(-4.f, K2, t);
+            const float dx = o.x - K2, dy = o.y - K2, dz = o.z - K2, dw = o.w - K2;
+            nsq = fmaf(dx, dx, nsq); nsq = fmaf(dy, dy, nsq); nsq = fmaf(dz, dz, nsq); nsq = fmaf(dw, dw, nsq);
         }
         yp[i] = o;
         if (y3 && fmt.f16) {       // the fp16 two-product format (operand_format.h): [hi | lo] planes of y * scale
@@ -156,9 +205,14 @@ __global__ __launch_bounds__(256) void ln_fwd_apply_kernel(const float* __restri
     if (rp) {
         ns = block_sum(ns, sh);
         nq = block_sum(nq, sh);
+        nss = block_sum(nss, sh);
+        nsq = block_sum(nsq, sh);
         if (threadIdx.x == 0) {
             partial_next[((int64_t)b * LN_NB + ch) * 2] = ns;
             partial_next[((int64_t)b * LN_NB + ch) * 2 + 1] = nq;
+            shifted_next[((int64_t)b * LN_NB + ch) * 2] = nss;
+            shifted_next[((int64_t)b * LN_NB + ch) * 2 + 1] = nsq;
+            if (ch == 0) shifted_next[(int64_t)gridDim.x * LN_NB * 2 + b] = K2;
         }
     }
     if (y3) of_amax_commit(fmt.amax, vmax);
@@ -405,18 +459,20 @@ static int layer_norm_act_fwd_impl(const float* a, const float* bias, int relu, 
     LPM_LN_CHECK("lpm_layer_norm_act_fwd");
     hipStream_t s = (hipStream_t)stream;
     float* partial = (float*)workspace;
+    float* shifted = partial + (size_t)B * LN_NB * 4;        // (in the backward's column-partial region, free in the forward; see the pair)
     const int64_t n_per = (int64_t)L * F;
     const int64_t yb = y_batch_stride ? y_batch_stride : n_per;
     LPM_REQUIRE(yb >= n_per && yb % 4 == 0 && ((uintptr_t)y & 15) == 0, LPM_ERR_BADARG,
                 "lpm_layer_norm_act_fwd: y_batch_stride must be >= L*F and a multiple of 4, y 16-byte aligned");
     dim3 grid(B, LN_NB);
     if (mask)
-        hipLaunchKernelGGL(ln_fwd_stats_kernel<true>, grid, dim3(256), 0, s, a, r, bias, relu, F, n_per, z, partial, r_scale, mask, mask_scale);
+        hipLaunchKernelGGL(ln_fwd_stats_kernel<true>, grid, dim3(256), 0, s, a, r, bias, relu, F, n_per, z, partial, r_scale, mask, mask_scale,
+                           shifted);
     else
         hipLaunchKernelGGL(ln_fwd_stats_kernel<false>, grid, dim3(256), 0, s, a, r, bias, relu, F, n_per, z, partial, r_scale,
-                           (const unsigned char*)nullptr, 1.f);
+                           (const unsigned char*)nullptr, 1.f, shifted);
     hipLaunchKernelGGL(ln_fwd_apply_kernel, grid, dim3(256), 0, s, (r || bias || mask) ? z : a, partial, gamma, beta, n_per, F, eps, y, yb, stats,
-                       (const float*)nullptr, (float*)nullptr, (unsigned short*)y3, operand_fmt(fmt));
+                       (const float*)nullptr, (float*)nullptr, (unsigned short*)y3, operand_fmt(fmt), (const float*)shifted, (float*)nullptr);
     return check_launch("lpm_layer_norm_act_fwd");
 }
 // ... with tf.layers.dropout between the dense layer and the layer norm (NetVladV2's TransformerEncoderMod, transformer_utils.py:450-454):
@@ -490,18 +546,23 @@ extern "C" int lpm_layer_norm_pair_fwd(const float* a, const float* bias, int re
     LPM_LN_CHECK("lpm_layer_norm_pair_fwd");
     hipStream_t s = (hipStream_t)stream;
     float* partial1 = (float*)workspace;
-    float* partial2 = partial1 + (size_t)B * LN_NB * 2;       // (the backward's column-partial region: free in the forward)
+    // (the backward's column-partial region, B * LN_NB * 2 * F floats, is free in the forward: the second norm's raw sums, then each norm's
+    // shifted sums with their B pivots behind them -- 130 B floats in all)
+    float* partial2 = partial1 + (size_t)B * LN_NB * 2;
+    float* shifted1 = partial1 + (size_t)B * LN_NB * 4;
+    float* shifted2 = shifted1 + (size_t)B * LN_NB * 2 + B;
     const int64_t n_per = (int64_t)L * F;
     const int64_t yb = y_batch_stride ? y_batch_stride : n_per;
     LPM_REQUIRE(yb >= n_per && yb % 4 == 0 && ((uintptr_t)y & 15) == 0, LPM_ERR_BADARG,
                 "lpm_layer_norm_pair_fwd: y_batch_stride must be >= L*F and a multiple of 4, y 16-byte aligned");
     dim3 grid(B, LN_NB);
     hipLaunchKernelGGL(ln_fwd_stats_kernel<false>, grid, dim3(256), 0, s, a, r, bias, relu, F, n_per, z1, partial1, (const float*)nullptr,
-                       (const unsigned char*)nullptr, 1.f);
+                       (const unsigned char*)nullptr, 1.f, shifted1);
     hipLaunchKernelGGL(ln_fwd_apply_kernel, grid, dim3(256), 0, s, (const float*)z1, (const float*)partial1, gamma1, beta1, n_per, F, eps,
-                       z2, n_per, stats1, r, partial2, (unsigned short*)nullptr, OperandFmt{0, 3, 1.f, nullptr});
+                       z2, n_per, stats1, r, partial2, (unsigned short*)nullptr, OperandFmt{0, 3, 1.f, nullptr}, (const float*)shifted1, shifted2);
     hipLaunchKernelGGL(ln_fwd_apply_kernel, grid, dim3(256), 0, s, (const float*)z2, (const float*)partial2, gamma2, beta2, n_per, F, eps,
-                       y, yb, stats2, (const float*)nullptr, (float*)nullptr, (unsigned short*)nullptr, OperandFmt{0, 3, 1.f, nullptr});
+                       y, yb, stats2, (const float*)nullptr, (float*)nullptr, (unsigned short*)nullptr, OperandFmt{0, 3, 1.f, nullptr},
+                       (const float*)shifted2, (float*)nullptr);
     return check_launch("lpm_layer_norm_pair_fwd");
 }
 
