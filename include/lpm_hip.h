@@ -524,7 +524,9 @@ int lpm_vlad_aggregate_bwd_tiles_dx(const void* workspace, size_t workspace_byte
 /* Channel-last training batch norm of a [M, C] matrix (slim.batch_norm on the V2 encoder's [B, L, C] tensors,
  * transformer_utils.py:666,747,760, seen as M = B*L rows): y = (x - mean) * rsqrt(var + eps) * gamma + beta with the batch
  * statistics written to mean / var and folded into the moving averages (biased_moving_variance != 0: TF's non-fused path,
- * which rank-3 inputs take; 0: the fused path's unbiased estimate).  The backward is lpm_bn_bwd with logits := x. */
+ * which rank-3 inputs take; 0: the fused path's unbiased estimate).  The backward is lpm_bn_bwd with logits := x.
+ * The moments come from raw and pivot-shifted column sums of one statistics pass (csrc/bn.hip, bn_fold_kernel): per column the raw form
+ * where mean^2 <= var, the shifted one elsewhere.  Both partial arrays live in the workspace: size it with lpm_bn_rows_workspace_bytes. */
 size_t lpm_bn_rows_workspace_bytes(int M, int C);
 int lpm_bn_rows_fwd(const float* x, int M, int C, const float* gamma, const float* beta, float eps, float decay,
                     int biased_moving_variance, float* y, float* mean, float* var, float* moving_mean, float* moving_var,

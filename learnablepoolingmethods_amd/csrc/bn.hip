@@ -7,20 +7,41 @@
 namespace lpm {
 
 // partial [nblk, 2, C] -> mean/var/scale/shift (+ moving averages); 1024 threads per 16 columns (partial_colsums16)
+// var = q/n - mu^2 from the RAW fp32 sums loses eps32 (mean/std)^2 of the variance (measured at mean/std = 30 on lpm_bn_rows_*: batch_var
+// 25 .. 220 times, dx up to 19 times, y up to 16 times the bound of tests/test_gpu_bn_bounds.py).  shifted != NULL (the lpm_bn_rows_* path,
+// bn_rows_stats_kernel): a second partial array of the same layout holds the sums of (x - K) and (x - K)^2 with the per-column pivot
+// K = pivot[c], the mean of the matrix's first BN_PIVOT_ROWS rows; from them the same fold loses eps32 (1 + ((mean - K)/std)^2), under
+// 3 eps32 at any offset -- and more than the raw sums where the mean is small against the spread.  Both forms are evaluated; the shifted one decides: where mean^2 <= var the raw sums
+// are taken (there the results are bit for bit what they were before the shifted sums existed), elsewhere the shifted ones (as ln_moments,
+// layer_norm.hip).  shifted == NULL (lpm_bn_fold: K1's epilogue, frame_prep.hip, the attention's logit statistics): the raw sums alone.
 template <int CW>
 __global__ __launch_bounds__(1024) void bn_fold_kernel(const float* __restrict__ partial, int nblk, int C,
                                                        double inv_rows, double unbias,
                                                        const float* __restrict__ gamma,
                                                        const float* __restrict__ beta, float eps, float decay,
                                                        float* mean, float* var, float* scale, float* shift,
-                                                       float* moving_mean, float* moving_var) {
-    double s, q;
+                                                       float* moving_mean, float* moving_var,
+                                                       const float* __restrict__ shifted, const float* __restrict__ pivot) {
+    double s, q, ss = 0.0, sq = 0.0;
     int c;
     partial_colsums<CW>(partial, nblk, 2 * (int64_t)C, C, C, s, q, c);
+    if (shifted) {                                  // (the same for every thread of the grid)
+        __syncthreads();                            // partial_colsums' LDS is read by the first call's last step
+        partial_colsums<CW>(shifted, nblk, 2 * (int64_t)C, C, C, ss, sq, c);
+    }
     if (threadIdx.x < CW && c < C) {
-        const double mu = s * inv_rows;
+        double mu = s * inv_rows;
         double vr = q * inv_rows - mu * mu;
         if (vr < 0.0) vr = 0.0;
+        if (shifted) {
+            const double dm = ss * inv_rows, mu_s = (double)pivot[c] + dm;
+            double vr_s = sq * inv_rows - dm * dm;
+            if (vr_s < 0.0) vr_s = 0.0;
+            if (mu_s * mu_s > vr_s) {
+                mu = mu_s;
+                vr = vr_s;
+            }
+        }
         const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
         const float sc = g * (float)(1.0 / sqrt(vr + (double)eps));
         if (mean) mean[c] = (float)mu;
@@ -54,7 +75,12 @@ __device__ __forceinline__ float4 bn_load4(const float* __restrict__ base, int64
     return make_float4(__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u), __uint_as_float(w.y << 16), __uint_as_float(w.y & 0xffff0000u));
 }
 
-// pass 1 of the BN backward: per-block column partials of dlt and dlt*Lhat.
+// pass 1 of the BN backward: per-block column partials of dlt, dlt*Lhat and (L - mean) -> partial [nblk][3][K].
+// The third sum: ``mean`` arrives rounded to fp32, up to eps32/2 |mean| off the column's mean -- 1e-6 std at mean/std = 30 -- so Lhat does
+// not sum to zero over the rows and neither does dl: measured there, the bias gradient of a column no ReLU clips (zero but for rounding)
+// stood at 8.5 .. 8.7 times the two-pass fp32 evaluation's, 1.06 .. 1.09 of its bound in tests/test_gpu_bn_bounds.py.  bn_bwd_reduce_kernel
+// turns the sum into the correction dmu = mean_r(L - mean) for the columns with mean^2 > var (elsewhere 0: there nothing changes, bit for
+// bit), bn_bwd_apply_kernel centres with it.
 constexpr int BNB_ROWS = 64;
 // column chunks (gridDim.y) of the two statistics passes: one per 256 float4 column groups, at most 8; the per-block partial sums of a
 // column are the same numbers whichever workgroup forms them
@@ -72,7 +98,7 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const float* __rest
                                                              const float* __restrict__ var, float eps, int M,
                                                              int K, float* __restrict__ partial, const float* __restrict__ pb, int relu,
                                                              int lbf16) {
-    __shared__ float4 red[2][256];
+    __shared__ float4 red[3][256];
     const int r0 = blockIdx.x * BNB_ROWS;
     const int r1 = min(M, r0 + BNB_ROWS);
     const int tid = threadIdx.x, K4 = K >> 2;
@@ -84,12 +110,14 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const float* __rest
         const float4 mu = *reinterpret_cast<const float4*>(mean + 4 * c4);
         const float4 vr = *reinterpret_cast<const float4*>(var + 4 * c4);
         const float4 rs = make_float4(rsqrtf(vr.x + eps), rsqrtf(vr.y + eps), rsqrtf(vr.z + eps), rsqrtf(vr.w + eps));
-        float4 s = make_float4(0.f, 0.f, 0.f, 0.f), q = s;
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f), q = s, t = s;
         auto add = [&](const float4 d, float4 l) {
             l = bn_preact(l, pb, 4 * c4, relu);
             s.x += d.x; s.y += d.y; s.z += d.z; s.w += d.w;
-            q.x += d.x * ((l.x - mu.x) * rs.x); q.y += d.y * ((l.y - mu.y) * rs.y);
-            q.z += d.z * ((l.z - mu.z) * rs.z); q.w += d.w * ((l.w - mu.w) * rs.w);
+            l.x -= mu.x; l.y -= mu.y; l.z -= mu.z; l.w -= mu.w;
+            q.x += d.x * (l.x * rs.x); q.y += d.y * (l.y * rs.y);
+            q.z += d.z * (l.z * rs.z); q.w += d.w * (l.w * rs.w);
+            t.x += l.x; t.y += l.y; t.z += l.z; t.w += l.w;
         };
         const float4* dp = reinterpret_cast<const float4*>(dlt) + c4;
         int r = r0 + rg;
@@ -107,31 +135,41 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const float* __rest
         if (RG > 1) {
             red[0][tid] = s;
             red[1][tid] = q;
+            red[2][tid] = t;
             __syncthreads();
             if (rg == 0)
                 for (int i = 1; i < RG; ++i) {
-                    const float4 a = red[0][i * K4 + c4], b = red[1][i * K4 + c4];
+                    const float4 a = red[0][i * K4 + c4], b = red[1][i * K4 + c4], e = red[2][i * K4 + c4];
                     s.x += a.x; s.y += a.y; s.z += a.z; s.w += a.w;
                     q.x += b.x; q.y += b.y; q.z += b.z; q.w += b.w;
+                    t.x += e.x; t.y += e.y; t.z += e.z; t.w += e.w;
                 }
         }
         if (rg == 0) {
-            float* p = partial + (int64_t)blockIdx.x * 2 * K;
+            float* p = partial + (int64_t)blockIdx.x * 3 * K;
             *reinterpret_cast<float4*>(p + 4 * c4) = s;
             *reinterpret_cast<float4*>(p + K + 4 * c4) = q;
+            *reinterpret_cast<float4*>(p + 2 * (int64_t)K + 4 * c4) = t;
         }
     }
 }
 
-// pass 2: reduce partials -> dbeta (sum dlt), dgamma (sum dlt*Lhat)
+// pass 2: reduce partials -> dbeta (sum dlt), dgamma (sum dlt*Lhat) and dmu, the part of the column's mean that ``mean`` lost to fp32:
+// mean_r(L - mean) where mean^2 > var, else 0.  With it Lhat is (L - mean - dmu) rstd, so dgamma = sum dlt Lhat = q - dmu rstd s.
 __global__ __launch_bounds__(1024) void bn_bwd_reduce_kernel(const float* __restrict__ partial, int nblk, int K,
-                                                             float* dgamma, float* dbeta) {
-    double s, q;
+                                                             float* dgamma, float* dbeta, const float* __restrict__ mean,
+                                                             const float* __restrict__ var, float eps, double inv_rows, float* __restrict__ dmu) {
+    double s, q, t, unused;
     int c;
-    partial_colsums16(partial, nblk, 2 * (int64_t)K, K, K, s, q, c);
+    partial_colsums16(partial, nblk, 3 * (int64_t)K, K, K, s, q, c);
+    __syncthreads();                                // partial_colsums' LDS is read by the first call's last step
+    partial_colsums16(partial + 2 * (int64_t)K, nblk, 3 * (int64_t)K, 0, K, t, unused, c);
     if (threadIdx.x < 16 && c < K) {
+        const float m = mean[c], v = var[c];
+        const double dm = m * m > v ? t * inv_rows : 0.0;
         dbeta[c] = (float)s;
-        dgamma[c] = (float)q;
+        dgamma[c] = (float)(q - dm * (double)rsqrtf(v + eps) * s);
+        dmu[c] = (float)dm;
     }
 }
 
@@ -232,23 +270,25 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
                                                            const float* __restrict__ dbeta, float eps, int M, int K,
                                                            float* __restrict__ dl, const float* __restrict__ pb, int relu,
                                                            float* __restrict__ dbpart, unsigned short* __restrict__ dl3, const OperandFmt fmt,
-                                                           int lbf16) {
+                                                           int lbf16, const float* __restrict__ dmu) {
     float vmax = 0.f;
     // dl3 != null: the result leaves as the GRADIENT image [M][3K] = [hi | hi | lo] of the dense layer in front instead of as fp32
     // pb / relu: the normalised tensor was act(logits + pb); dl is then the gradient of the RAW logits (masked where the ReLU was off)
     // and dbpart [stride / (K/4)][K] receives this thread's column sums of it (the bias gradient; needs the fixed-column arrangement)
     // dl = A d + Bq (l - mean) + Cq per column, A = gamma rstd, Bq = -gamma rstd^2 dgamma / M, Cq = -gamma rstd dbeta / M.  When the
     // grid stride is a multiple of the row length a thread keeps its four columns and the coefficients are formed once (the
-    // launcher arranges that); otherwise once per element group.  (l - mean) is formed first: columns with |mean| >> sigma.
+    // launcher arranges that); otherwise once per element group.  (l - mean) is formed first: columns with |mean| >> sigma; dmu (see
+    // bn_bwd_reduce_kernel) comes off it afterwards, 0 wherever mean^2 <= var.
     const int64_t total4 = (int64_t)M * K / 4;
     const float invM = 1.f / (float)M;
     const int K4 = K / 4;
     const int64_t stride = (int64_t)gridDim.x * 256;
     const bool fixed = (stride % K4) == 0;
-    float4 A, Bq, Cq, mu;
+    float4 A, Bq, Cq, mu, dm;
     auto coeffs = [&](int c) {
         const float4 vr = *reinterpret_cast<const float4*>(var + c);
         mu = *reinterpret_cast<const float4*>(mean + c);
+        dm = *reinterpret_cast<const float4*>(dmu + c);
         const float4 dg = *reinterpret_cast<const float4*>(dgamma + c), db = *reinterpret_cast<const float4*>(dbeta + c);
         const float4 g = gamma ? *reinterpret_cast<const float4*>(gamma + c) : make_float4(1.f, 1.f, 1.f, 1.f);
         const float rx = rsqrtf(vr.x + eps), ry = rsqrtf(vr.y + eps), rz = rsqrtf(vr.z + eps), rw = rsqrtf(vr.w + eps);
@@ -263,10 +303,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
         if (!fixed) coeffs((int)(i % K4) * 4);
         l = bn_preact(l, pb, (int)(i % K4) * 4, relu);
         float4 o;
-        o.x = fmaf(A.x, d.x, fmaf(Bq.x, l.x - mu.x, Cq.x));
-        o.y = fmaf(A.y, d.y, fmaf(Bq.y, l.y - mu.y, Cq.y));
-        o.z = fmaf(A.z, d.z, fmaf(Bq.z, l.z - mu.z, Cq.z));
-        o.w = fmaf(A.w, d.w, fmaf(Bq.w, l.w - mu.w, Cq.w));
+        o.x = fmaf(A.x, d.x, fmaf(Bq.x, (l.x - mu.x) - dm.x, Cq.x));
+        o.y = fmaf(A.y, d.y, fmaf(Bq.y, (l.y - mu.y) - dm.y, Cq.y));
+        o.z = fmaf(A.z, d.z, fmaf(Bq.z, (l.z - mu.z) - dm.z, Cq.z));
+        o.w = fmaf(A.w, d.w, fmaf(Bq.w, (l.w - mu.w) - dm.w, Cq.w));
         if (pb && relu) {                  // l = relu(.): zero exactly where the unit was off
             o.x = l.x > 0.f ? o.x : 0.f; o.y = l.y > 0.f ? o.y : 0.f; o.z = l.z > 0.f ? o.z : 0.f; o.w = l.w > 0.f ? o.w : 0.f;
         }
@@ -293,22 +333,47 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
 }
 
 // ---- channel-last batch norm of a [M, C] matrix (the V2 encoder's [B, L, C] tensors seen as rows) -----------------------------
-// statistics: per 64-row block column (sum, sum of squares) -> partial [nblk][2][C]  (then bn_fold_kernel)
+// statistics: per 64-row block column (sum, sum of squares) -> partial [nblk][2][C], and beside them the same two sums of the values less
+// the column's pivot K -> shifted [nblk][2][C], pivot [C]  (then bn_fold_kernel, which says why).  K = the mean of act(x + bias) over the
+// first BN_PIVOT_ROWS rows of the matrix, summed in row order: every workgroup forms it itself from those rows (32 C bytes, in L2 after
+// the first workgroup) and gets the same bits -- no pass, no launch, no exchange between workgroups; the four extra VALU operations per
+// element ride behind the eight rows' loads.  (Row 0 alone as the pivot, the layer norms' choice for ONE pivot per example, is up to 4 std
+// off the mean in some of 1024 columns: batch_var at 0.9 .. 1.3 of its bound at mean/std = 3; eight rows put every column within ~1.2 std.)
+constexpr int BN_PIVOT_ROWS = 8;
 __global__ __launch_bounds__(256) void bn_rows_stats_kernel(const float* __restrict__ x, int M, int C, float* __restrict__ partial,
-                                                            const float* __restrict__ pb, int relu) {
-    __shared__ float4 red[2][256];
+                                                            const float* __restrict__ pb, int relu, float* __restrict__ shifted,
+                                                            float* __restrict__ pivot) {
+    __shared__ float4 red[4][256];
     const int r0 = blockIdx.x * BNB_ROWS, r1 = min(M, r0 + BNB_ROWS);
     const int tid = threadIdx.x, C4 = C / 4;
     const int RG = (C4 < 256 && 256 % C4 == 0) ? 256 / C4 : 1;      // thread layout as in bn_bwd_partial_kernel
     const int rg = RG > 1 ? tid / C4 : 0;
     for (int c4 = RG > 1 ? tid % C4 : tid + 256 * (int)blockIdx.y; c4 < C4; c4 += (RG > 1 ? C4 : 256 * (int)gridDim.y)) {     // (column chunks: see bn_bwd_partial_kernel)
-        float4 s = make_float4(0.f, 0.f, 0.f, 0.f), q = s;
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f), q = s, ss = s, sq = s;
+        const float4* xp = reinterpret_cast<const float4*>(x) + c4;
+        float4 K = make_float4(0.f, 0.f, 0.f, 0.f);
+        {
+            const int pr = min(M, BN_PIVOT_ROWS);
+            float4 w[BN_PIVOT_ROWS];
+#pragma unroll
+            for (int u = 0; u < BN_PIVOT_ROWS; ++u) w[u] = xp[(int64_t)min(u, pr - 1) * C4];
+#pragma unroll
+            for (int u = 0; u < BN_PIVOT_ROWS; ++u)
+                if (u < pr) {
+                    const float4 a = bn_preact(w[u], pb, 4 * c4, relu);
+                    K.x += a.x; K.y += a.y; K.z += a.z; K.w += a.w;
+                }
+            const float inv = 1.f / (float)pr;
+            K.x *= inv; K.y *= inv; K.z *= inv; K.w *= inv;
+        }
         auto add = [&](float4 v) {
             v = bn_preact(v, pb, 4 * c4, relu);
             s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
             q.x = fmaf(v.x, v.x, q.x); q.y = fmaf(v.y, v.y, q.y); q.z = fmaf(v.z, v.z, q.z); q.w = fmaf(v.w, v.w, q.w);
+            v.x -= K.x; v.y -= K.y; v.z -= K.z; v.w -= K.w;
+            ss.x += v.x; ss.y += v.y; ss.z += v.z; ss.w += v.w;
+            sq.x = fmaf(v.x, v.x, sq.x); sq.y = fmaf(v.y, v.y, sq.y); sq.z = fmaf(v.z, v.z, sq.z); sq.w = fmaf(v.w, v.w, sq.w);
         };
-        const float4* xp = reinterpret_cast<const float4*>(x) + c4;
         int r = r0 + rg;
         for (; r + 7 * RG < r1; r += 8 * RG) {              // eight rows' loads together (round 4: four left a 375-workgroup grid at
             float4 v[8];                                    // 3.6 TB/s on the [24000, 4096] tensor of cfg-3), rows consumed in order
@@ -328,18 +393,26 @@ __global__ __launch_bounds__(256) void bn_rows_stats_kernel(const float* __restr
         if (RG > 1) {
             red[0][tid] = s;
             red[1][tid] = q;
+            red[2][tid] = ss;
+            red[3][tid] = sq;
             __syncthreads();
             if (rg == 0)
                 for (int i = 1; i < RG; ++i) {
-                    const float4 a = red[0][i * C4 + c4], b = red[1][i * C4 + c4];
+                    const float4 a = red[0][i * C4 + c4], b = red[1][i * C4 + c4], d = red[2][i * C4 + c4], e = red[3][i * C4 + c4];
                     s.x += a.x; s.y += a.y; s.z += a.z; s.w += a.w;
                     q.x += b.x; q.y += b.y; q.z += b.z; q.w += b.w;
+                    ss.x += d.x; ss.y += d.y; ss.z += d.z; ss.w += d.w;
+                    sq.x += e.x; sq.y += e.y; sq.z += e.z; sq.w += e.w;
                 }
         }
         if (rg == 0) {
             float* p = partial + (int64_t)blockIdx.x * 2 * C + 4 * c4;
             *reinterpret_cast<float4*>(p) = s;
             *reinterpret_cast<float4*>(p + C) = q;
+            float* ps = shifted + (int64_t)blockIdx.x * 2 * C + 4 * c4;
+            *reinterpret_cast<float4*>(ps) = ss;
+            *reinterpret_cast<float4*>(ps + C) = sq;
+            if (blockIdx.x == 0) *reinterpret_cast<float4*>(pivot + 4 * c4) = K;
         }
     }
 }
@@ -365,7 +438,7 @@ __global__ __launch_bounds__(256) void bn_rows_apply_kernel(const float* __restr
 
 extern "C" size_t lpm_bn_rows_workspace_bytes(int M, int C) {
     const int nblk = (M + lpm::BNB_ROWS - 1) / lpm::BNB_ROWS;
-    return ((size_t)nblk * 2 * C + 2 * (size_t)C) * sizeof(float);
+    return ((size_t)nblk * 4 * C + 3 * (size_t)C) * sizeof(float);      // raw and shifted partials [nblk][2][C] each, scale, shift, pivot [C]
 }
 
 static int bn_rows_fwd_impl(const float* x, const float* pre_bias, int pre_relu, int M, int C, const float* gamma, const float* beta,
@@ -424,10 +497,12 @@ static int bn_rows_fwd_impl(const float* x, const float* pre_bias, int pre_relu,
     float* partial = (float*)workspace;
     float* scale = partial + (size_t)nblk * 2 * C;
     float* shift = scale + C;
-    hipLaunchKernelGGL(bn_rows_stats_kernel, dim3(nblk, bn_col_chunks(C)), dim3(256), 0, s, x, M, C, partial, pre_bias, pre_relu);
+    float* shifted = shift + C;
+    float* pivot = shifted + (size_t)nblk * 2 * C;
+    hipLaunchKernelGGL(bn_rows_stats_kernel, dim3(nblk, bn_col_chunks(C)), dim3(256), 0, s, x, M, C, partial, pre_bias, pre_relu, shifted, pivot);
     const double unbias = (biased_moving_variance || M <= 1) ? 1.0 : (double)M / (double)(M - 1);
     hipLaunchKernelGGL(bn_fold_kernel<16>, dim3((C + 15) / 16), dim3(1024), 0, s, partial, nblk, C, 1.0 / (double)M, unbias, gamma, beta, eps,
-                       decay, mean, var, scale, shift, moving_mean, moving_var);
+                       decay, mean, var, scale, shift, moving_mean, moving_var, (const float*)shifted, (const float*)pivot);
     const int64_t total4 = (int64_t)M * C / 4;
     const int64_t want = (total4 + 255) / 256;
     hipLaunchKernelGGL(bn_rows_apply_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, s, x, scale, shift, total4, C / 4, y, pre_bias,
@@ -577,16 +652,18 @@ extern "C" int lpm_bn_fold(const float* partial, int nblk, int C, int64_t rows, 
     const double unbias = rows > 1 ? (double)rows / (double)(rows - 1) : 1.0;
     if (partial_colsums_cw(nblk) == 4)
         hipLaunchKernelGGL(bn_fold_kernel<4>, dim3((C + 3) / 4), dim3(1024), 0, (hipStream_t)stream, partial, nblk, C,
-                           1.0 / (double)rows, unbias, gamma, beta, eps, decay, mean, var, scale, shift, moving_mean, moving_var);
+                           1.0 / (double)rows, unbias, gamma, beta, eps, decay, mean, var, scale, shift, moving_mean, moving_var, (const float*)nullptr,
+                           (const float*)nullptr);
     else
         hipLaunchKernelGGL(bn_fold_kernel<16>, dim3((C + 15) / 16), dim3(1024), 0, (hipStream_t)stream, partial, nblk, C,
-                           1.0 / (double)rows, unbias, gamma, beta, eps, decay, mean, var, scale, shift, moving_mean, moving_var);
+                           1.0 / (double)rows, unbias, gamma, beta, eps, decay, mean, var, scale, shift, moving_mean, moving_var, (const float*)nullptr,
+                           (const float*)nullptr);
     return check_launch("lpm_bn_fold");
 }
 
 extern "C" size_t lpm_bn_bwd_workspace_bytes(int M, int K) {
     const int nblk = (M + lpm::BNB_ROWS - 1) / lpm::BNB_ROWS;
-    return (size_t)nblk * 2 * K * sizeof(float);
+    return ((size_t)nblk * 3 * K + (size_t)K) * sizeof(float);          // partial [nblk][3][K], dmu [K]
 }
 
 namespace lpm {
@@ -626,7 +703,7 @@ extern "C" int lpm_bn_act_bwd_supported(int M, int K) {
 extern "C" size_t lpm_bn_act_bwd_workspace_bytes(int M, int K) {
     const int nblk = (M + lpm::BNB_ROWS - 1) / lpm::BNB_ROWS;
     const size_t rows = (size_t)lpm::bn_bwd_grid(M, K) * 256 / (size_t)(K / 4);
-    return ((size_t)nblk * 2 * K + rows * K + (size_t)lpm::BN_CS_SLICES * K) * sizeof(float);
+    return ((size_t)nblk * 3 * K + (size_t)K + rows * K + (size_t)lpm::BN_CS_SLICES * K) * sizeof(float);
 }
 extern "C" int lpm_bn_act_bwd(const float* dlt, const float* x, const float* pre_bias, int pre_relu, const float* mean, const float* var,
                               const float* gamma, float eps, int M, int K, float* dl, float* dgamma, float* dbeta, float* dbias,
@@ -676,11 +753,12 @@ static int bn_bwd_impl(const float* dlt, const float* logits, const float* pre_b
     float* partial = (float*)workspace;
     hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(nblk, bn_col_chunks(K)), dim3(256), 0, s, dlt, logits, mean, var, eps, M, K, partial, pre_bias, pre_relu,
                        logits_bf16);
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3((K + 15) / 16), dim3(1024), 0, s, partial, nblk, K, dgamma, dbeta);
+    float* dmu = partial + (size_t)nblk * 3 * K;
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3((K + 15) / 16), dim3(1024), 0, s, partial, nblk, K, dgamma, dbeta, mean, var, eps, 1.0 / (double)M, dmu);
     const int grid = bn_bwd_grid(M, K);
-    float* dbpart = dbias ? partial + (size_t)nblk * 2 * K : nullptr;
+    float* dbpart = dbias ? dmu + K : nullptr;
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid), dim3(256), 0, s, dlt, logits, mean, var, gamma, dgamma, dbeta,
-                       eps, M, K, dl, pre_bias, pre_relu, dbpart, (unsigned short*)dl3, operand_fmt(fmt), logits_bf16);
+                       eps, M, K, dl, pre_bias, pre_relu, dbpart, (unsigned short*)dl3, operand_fmt(fmt), logits_bf16, (const float*)dmu);
     if (dbias) {
         const int rows = (int)((int64_t)grid * 256 / (K / 4));
         if (rows > 4 * BN_CS_SLICES) {
