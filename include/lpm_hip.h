@@ -329,7 +329,7 @@ int lpm_vlad_finalize2_fwd_ld(float* nrm, const float* colsq_part, int P, int B,
  * -- plus asum and the partial norms colsq_part [B, D/128, K]; lpm_vlad_row_scales turns those into scale [B, K] = 1 / (n_k sqrt(g))
  * and colsq, csq [B, K], gsq [B], so that descriptor[b, k, :] = raw[b, k, :] * scale[b, k] (frame_level_models.py:2819-2822 as one
  * factor per row).  No finalize pass: the [B, D, K]-sized tensor is written once and never re-read by the pooling.  Consumers:
- * lpm_split_rows_scaled (operand image of the q/k/v GEMM), lpm_layer_norm_act_fwd_rs (the encoder's residual); the backward is
+ * lpm_split_rows_fmt with row_scale (operand image of the q/k/v GEMM), lpm_layer_norm_act_fwd_rs (the encoder's residual); the backward is
  * lpm_vlad_aggregate_bwd_tiles with LPM_VLAD_RAW_KMAJOR (dout and the sums both k-major: no transposes). */
 int lpm_vlad_aggregate_raw_kmajor_fwd(const void* at, const void* xt, const float* centres, int B, int T, int D, int K, int flags,
                                       float* raw_kmajor, float* asum, float* colsq_part, lpm_stream_t stream);
@@ -364,7 +364,6 @@ int lpm_vlad_smx_supported(int T, int D, int K);
 int lpm_vlad_aggregate_raw_kmajor_smx_fwd(const float* logits, const float* scale, const float* shift, const void* xt,
                                           const float* centres, int B, int T, int D, int K, int flags, float* raw_kmajor,
                                           float* asum, float* colsq_part, float* stats, lpm_stream_t stream);
-int lpm_split_rows_scaled(const float* x, int64_t ldx, int64_t M, int K, const float* row_scale, void* out3, lpm_stream_t stream);
 int lpm_layer_norm_act_fwd_rs(const float* a, const float* bias, int relu, const float* r, const float* r_scale, const float* gamma,
                               const float* beta, int B, int L, int F, float eps, float* y, int64_t y_batch_stride, float* z,
                               float* stats, void* workspace, size_t workspace_bytes, lpm_stream_t stream);
@@ -614,7 +613,7 @@ typedef struct LpmOperandFormat {
     float scale;    /* > 0, a power of two; 1 for LPM_OPERAND_BF16X3 */
     float* amax;    /* device, may be NULL: LPM_OPERAND_AMAX_SUB * LPM_OPERAND_AMAX_STRIDE floats */
 } LpmOperandFormat;
-/* lpm_split_rows / lpm_split_rows_scaled in either format: x [M,K] (row stride ldx), optionally * row_scale[m], + bias, ReLU ->
+/* lpm_split_rows in either format: x [M,K] (row stride ldx), optionally * row_scale[m], + bias, ReLU ->
  * image [M, planes K] (bf16x3: `order` 0 = [hi|lo|hi], 1 = [hi|hi|lo]; fp16x2: [hi|lo]). */
 int lpm_split_rows_fmt(const float* x, int64_t ldx, int64_t M, int K, const float* bias, int relu, int order, const float* row_scale,
                        void* out, const LpmOperandFormat* fmt, lpm_stream_t stream);
@@ -723,16 +722,10 @@ int lpm_bias_act_bwd(const float* dy, const float* y, int relu, int64_t M, int C
  * a, r, y, z, dy, dz: [B, L, F] contiguous.  workspace: lpm_layer_norm_workspace_bytes(B, F).
  * ------------------------------------------------------------------------------------------- */
 size_t lpm_layer_norm_workspace_bytes(int B, int F);
-int lpm_layer_norm_fwd(const float* a, const float* r, const float* gamma, const float* beta, int B, int L, int F,
-                       float eps, float* y, float* z, float* stats, void* workspace, size_t workspace_bytes,
-                       lpm_stream_t stream);
-int lpm_layer_norm_bwd(const float* dy, const float* z, const float* stats, const float* gamma, int B, int L, int F,
-                       float* dz, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
-                       lpm_stream_t stream);
-/* The same with the producing dense layer's bias add (and ReLU) fused: z = act(a + bias) (+ r), act = relu when `relu`
+/* With the producing dense layer's bias add (and ReLU) fused: z = act(a + bias) (+ r), act = relu when `relu`
  * (tf.layers.dense(use_bias=True[, activation=relu]) at transformer_utils.py:583, :708-711 followed by the residual
  * layer_norm).  Backward: dz as above (= the residual's gradient), da = dz * [a + bias > 0] (written to `da` only when
- * relu; otherwise da = dz), dbias = column sums of da.  bias == NULL reduces to lpm_layer_norm_fwd / _bwd.
+ * relu; otherwise da = dz), dbias = column sums of da.  bias == NULL: the plain residual layer norm.
  * dr_extra (optional, [B,L,F]): added to the residual's gradient on its way out (dz = dz + dr_extra; da is then written
  * separately, `da` required) -- a second consumer's gradient of the residual tensor, folded in without an add pass.
  * da_image (optional, [B*L, 3F] bf16): da written as the split-bf16 gradient image [hi | hi | lo] the next GEMMs read
@@ -856,7 +849,6 @@ int lpm_mha_bwd_x3_image(const float* q, const float* k, const float* v, int64_t
  * rebuilds o = hi + lo for D_q = <dO_q, O_q>); with o_is_image = 0 `o` is the fp32 [B, L, ldo] tensor (ldo shared with dout). */
 int lpm_mha_fwd_x3_image(const float* q, const float* k, const float* v, int64_t ld, int B, int L, int h, int d, float scale,
                          void* o3, float* lse, lpm_stream_t stream);
-size_t lpm_mha_logit_stats_workspace_bytes(int B, int L, int h);
 int lpm_mha_logit_stats(const float* q, const float* k, int64_t ld, int B, int L, int h, int d, float* partial,
                         lpm_stream_t stream);
 /* slim.batch_norm (training mode) of a SMALL [M, C] matrix, M <= 256 rows, with what follows it, in ONE launch each way -- the clip-level

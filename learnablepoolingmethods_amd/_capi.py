@@ -130,7 +130,6 @@ SIGNATURES = {
     "lpm_vlad_aggregate_clip_dmajor_fwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _f]),
     "lpm_vlad_kmajor_workspace_bytes": (_s, [_i, _i, _i]),
     "lpm_vlad_aggregate_kmajor_scaled_fwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _s, _f]),
-    "lpm_split_rows_scaled": (_i, [_f, _l, _l, _i, _f, _f, _f]),
     "lpm_layer_norm_act_fwd_rs": (_i, [_f, _f, _i, _f, _f, _f, _f, _i, _i, _i, _fl, _f, _l, _f, _f, _f, _s, _f]),
     "lpm_layer_norm_act_image_fwd": (_i, [_f, _f, _i, _f, _f, _f, _f, _i, _i, _i, _fl, _f, _l, _f, _f, _f, _f, _s, _f]),
     "lpm_vlad_fused_supported": (_i, [_i, _i]),
@@ -166,8 +165,6 @@ SIGNATURES = {
     "lpm_bias_act_bwd": (_i, [_f, _f, _i, _l, _i, _f, _f, _f, _s, _f]),
     "lpm_split_rows_relu_bwd": (_i, [_f, _l, _i, _f, _f, _f, _f, _s, _f]),
     "lpm_layer_norm_workspace_bytes": (_s, [_i, _i]),
-    "lpm_layer_norm_fwd": (_i, [_f, _f, _f, _f, _i, _i, _i, _fl, _f, _f, _f, _f, _s, _f]),
-    "lpm_layer_norm_bwd": (_i, [_f, _f, _f, _f, _i, _i, _i, _f, _f, _f, _f, _s, _f]),
     "lpm_layer_norm_act_fwd": (_i, [_f, _f, _i, _f, _f, _f, _i, _i, _i, _fl, _f, _l, _f, _f, _f, _s, _f]),
     "lpm_layer_norm_pair_fwd": (_i, [_f, _f, _i, _f, _f, _f, _f, _f, _i, _i, _i, _fl, _f, _l, _f, _f, _f, _f, _f, _s, _f]),
     "lpm_layer_norm_act_bwd": (_i, [_f, _l, _f, _f, _f, _f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _s, _f]),
@@ -182,7 +179,6 @@ SIGNATURES = {
     "lpm_mha_bwd_x3": (_i, [_f, _f, _f, _l, _f, _f, _l, _f, _i, _i, _i, _i, _fl, _f, _f, _f, _f, _f, _l, _f, _f, _f, _f]),
     "lpm_mha_bwd_x3_image": (_i, [_f, _f, _f, _l, _f, _i, _f, _l, _f, _i, _i, _i, _i, _fl, _f, _f]),
     "lpm_mha_fwd_x3_image": (_i, [_f, _f, _f, _l, _i, _i, _i, _i, _fl, _f, _f, _f]),
-    "lpm_mha_logit_stats_workspace_bytes": (_s, [_i, _i, _i]),
     "lpm_mha_logit_stats": (_i, [_f, _f, _l, _i, _i, _i, _i, _f, _f]),
     "lpm_moe_ce_nblk": (_i, [_i, _i]),
     "lpm_moe_ce_fwd": (_i, [_f, _f, _f, _i, _i, _i, _fl, _f, _f, _f, _f]),

@@ -631,10 +631,7 @@ int assign_wide_launch(const void* xr, const void* wt, int B, int T, int MT, int
     return check_launch(what);
 }
 
-static int af_enabled() {
-    static const int on = env_first_is("LPM_K1_FLAT", '0') ? 0 : 1;         // 0: the 128-row tile GEMM form (A/B switch)
-    return on && !(g_k1_forms_off.load(std::memory_order_relaxed) & 1);
-}
+static int af_enabled() { return !(g_k1_forms_off.load(std::memory_order_relaxed) & 1); }      // (lpm_k1_forms_disable: the 128-row tile GEMM form)
 
 // steps per stage (LPM_K1_KB = 1, 2, 4) and steps of B fragments in flight (LPM_K1_DB = 4; 8 with four steps per stage): A/B switches
 static int af_kb() {
@@ -650,11 +647,10 @@ bool assign_flat_ok(int B, int T, int D, int K) {
     const int DS = D / 16, db = af_db(), tail = af_tail(af_kb(), db);
     return af_enabled() && D % 16 == 0 && DS % db == 0 && DS >= tail + db && K % 256 == 0 && K > 0 && (int64_t)B * T < (int64_t)1 << 31;
 }
-// plain bf16 tiles: double steps of 32 reduction elements (LPM_K1_FLAT_BF16=0: the 128-row tile GEMM form, A/B)
+// plain bf16 tiles: double steps of 32 reduction elements
 bool assign_flat_plain_ok(int B, int T, int D, int K) {
-    static const int on = env_first_is("LPM_K1_FLAT_BF16", '0') ? 0 : 1;
     const int DS = D / 32, tail = af_tail(2, 4);
-    return on && af_enabled() && D % 32 == 0 && DS % 4 == 0 && DS >= tail + 4 && K % 256 == 0 && K > 0 && (int64_t)B * T < (int64_t)1 << 31;
+    return af_enabled() && D % 32 == 0 && DS % 4 == 0 && DS >= tail + 4 && K % 256 == 0 && K > 0 && (int64_t)B * T < (int64_t)1 << 31;
 }
 
 int assign_flat_launch(const void* xr, const void* wt, int B, int T, int MT, int D, int K, float* logits, float* stats, int nblk,

@@ -506,8 +506,7 @@ static int factored_clip_adam_impl(const void* xt, const void* dyt, const float*
     if (gdt) {
         const int MT = 2 * ((R + 63) / 64);
         const size_t lds = (size_t)MT * (R / 16) * 2048;
-        static const int from_tiles = env_first_is("LPM_FQ_TILES", '0') ? 0 : 1;   // 0: X from the fp32 matrix (A/B)
-        auto kern = (from_tiles && R <= 128) ? fa_quadform_kernel<true> : fa_quadform_kernel<false>;
+        auto kern = R <= 128 ? fa_quadform_kernel<true> : fa_quadform_kernel<false>;      // X from its tiles / from the fp32 matrix
         if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
             (void)hipGetLastError();
             set_error("lpm_factored_clip_adam_q: cannot reserve %zu bytes of LDS", lds);
@@ -523,13 +522,12 @@ static int factored_clip_adam_impl(const void* xt, const void* dyt, const float*
     hipLaunchKernelGGL(fa_factor_kernel, dim3(1), dim3(1024), 0, s, (const float*)partial, npart, clip_norm, factor);
     const double lr_t = (double)lr * sqrt(1.0 - pow((double)beta2, (double)step)) / (1.0 - pow((double)beta1, (double)step));
     g.sumsq = nullptr;
-    // whole-row form of the update pass (fa_update_rows_kernel): N2 a multiple of 64, at most 1024; LPM_FA_ROWS=0: the tile-GEMM form (A/B)
-    static const int rows_form = env_first_is("LPM_FA_ROWS", '0') ? 0 : 1;
+    // whole-row form of the update pass (fa_update_rows_kernel): N2 a multiple of 64, at most 1024; the tile-GEMM form otherwise.
     // Measured (tools/time_factored.py, whole update incl. the ~75 us norm pass): cfg-2 one tower (R = 80, N2 = 512) 693 us against 728;
     // cfg-5 (R = 128, N2 = 1024) 2741 against 2418 and eight towers of cfg-2 (R = 640) 1855 against 1749 -- every wave fetching its own
     // fragments from L2 costs 80 + 160 KB of L2 -> CU traffic per 192 KB of HBM stream at R = 80, but 256 + 512 KB per 384 KB at R = 128:
     // the whole-row form only where the reduction is short
-    if (rows_form && !param_bf16 && N2 % 256 == 0 && N1 % 32 == 0 && (int64_t)g.total_steps * N2 <= 5 * 512 && (int64_t)NT1 * (N2 / 256) < ((int64_t)1 << 31)) {
+    if (!param_bf16 && N2 % 256 == 0 && N1 % 32 == 0 && (int64_t)g.total_steps * N2 <= 5 * 512 && (int64_t)NT1 * (N2 / 256) < ((int64_t)1 << 31)) {
         hipLaunchKernelGGL(fa_update_rows_kernel, dim3((unsigned)(NT1 * (N2 / 256))), dim3(256), 0, s, (const uint4*)xt, (const uint4*)dyt,
                            g.total_steps, N1, N2, NT1, NT2, N2 / 256, param, m, v, (const float*)factor, (float)lr_t, beta1, beta2, eps);
         return check_launch("lpm_factored_clip_adam (update pass, rows)");

@@ -566,12 +566,6 @@ extern "C" int lpm_layer_norm_pair_fwd(const float* a, const float* bias, int re
     return check_launch("lpm_layer_norm_pair_fwd");
 }
 
-extern "C" int lpm_layer_norm_fwd(const float* a, const float* r, const float* gamma, const float* beta, int B, int L, int F,
-                                  float eps, float* y, float* z, float* stats, void* workspace, size_t workspace_bytes,
-                                  lpm_stream_t stream) {
-    return lpm_layer_norm_act_fwd(a, nullptr, 0, r, gamma, beta, B, L, F, eps, y, 0, z, stats, workspace, workspace_bytes, stream);
-}
-
 static int layer_norm_act_bwd_impl(const float* dy, int64_t dy_batch_stride, const float* z, const float* stats,
                                       const float* gamma, const float* a,
                                       const float* bias, int relu, int B, int L, int F, float* dz, float* da, float* dgamma,
@@ -648,11 +642,4 @@ extern "C" int lpm_layer_norm_act_mask_bwd_fmt(const float* dy, int64_t dy_batch
     LPM_REQUIRE(mask, LPM_ERR_BADARG, "lpm_layer_norm_act_mask_bwd: null keep mask");
     return layer_norm_act_bwd_impl(dy, dy_batch_stride, z, stats, gamma, a, bias, relu, B, L, F, dz, da, dgamma, dbeta, dbias, dr_extra,
                                    da_image, workspace, workspace_bytes, stream, mask, mask_scale, fmt);
-}
-
-extern "C" int lpm_layer_norm_bwd(const float* dy, const float* z, const float* stats, const float* gamma, int B, int L, int F,
-                                  float* dz, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
-                                  lpm_stream_t stream) {
-    return lpm_layer_norm_act_bwd(dy, 0, z, stats, gamma, nullptr, nullptr, 0, B, L, F, dz, nullptr, dgamma, dbeta, nullptr, nullptr, nullptr,
-                                  workspace, workspace_bytes, stream);
 }

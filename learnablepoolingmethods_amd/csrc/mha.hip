@@ -577,16 +577,14 @@ extern "C" int lpm_mha_fwd(const float* q, const float* k, const float* v, int64
     return check_launch("lpm_mha_fwd");
 }
 
-extern "C" size_t lpm_mha_logit_stats_workspace_bytes(int B, int L, int h) { return (size_t)B * h * 2 * L * sizeof(float); }
-
 extern "C" int lpm_mha_logit_stats(const float* q, const float* k, int64_t ld, int B, int L, int h, int d, float* partial,
                                    lpm_stream_t stream) {
     using namespace lpm;
     LPM_REQUIRE(q && k && partial, LPM_ERR_BADARG, "lpm_mha_logit_stats: null pointer");
     LPM_MHA_CHECK("lpm_mha_logit_stats");
     hipStream_t s = (hipStream_t)stream;
-    static const int quad = env_first_is("LPM_MHA_STATS_QUAD", '0') ? 0 : 1;   // 0: through the logits (A/B)
-    if (quad && (((uintptr_t)q | (uintptr_t)k) & 15) == 0 && d % 4 == 0) {
+    // the quadratic form where q and k are aligned vectors; through the logits otherwise
+    if ((((uintptr_t)q | (uintptr_t)k) & 15) == 0 && d % 4 == 0) {
         hipLaunchKernelGGL(mha_logit_stats_quad_kernel, dim3((B * h + 3) / 4), dim3(256), 0, s, q, k, ld, L, h, d, B * h, partial,
                            (float*)nullptr);
         return check_launch("lpm_mha_logit_stats");

@@ -691,21 +691,17 @@ __global__ __launch_bounds__(mx_dkv_nt(NKT)) void mha_bwd_dkv_x3_kernel(const fl
 // Measured (tools/time_mha_bwd.py, rocprofv3, profiles/r06_k4_backward_terms.md; B = 80, h = 64, d = 16), whole backward: L = 256
 // 543 -> 512 us (-6 %), L = 300 with logits_bn (dkv only: the dq pass carries corrections) 1037 -> 1016 us (-2 %); a cfg-2 step 6.72 ->
 // 6.70 ms.  With dP on one fp16 MFMA as well (V rounded once) it was 557 -> 508 us -- and 8e-4 off where attention is peaked.
-// 18-27 % of the MFMAs and 25-38 % of the VALU operations per score buy 2-6 %: the sweeps are bound by neither count.  TPW = 2 (a wave
+// 18-27 % of the MFMAs and 25-38 % of the VALU operations per score buy 2-6 %: the sweeps are bound by neither count.  Two tiles per wave (a wave
 // runs two tiles side by side through ONE stream of fragment reads: half the LDS traffic per score, twice the independent work per
 // wave, but 140 registers = half the waves) measured dkv 290 us against 234, dq 196 against 207 at L = 256 and dq 401 us against 335
 // at L = 300 -- what the kernels live on is the number of waves a SIMD can switch between while one waits for its MFMA -> exp2 ->
 // convert -> MFMA chain, and that is capped at four by the 66 KB of staged operands per (batch, head).  The same measurement answers
-// the merged dq + dkv sweep (DESIGN: ~174 registers, two waves per SIMD): it would run at TPW = 2's occupancy.  NOT the default
+// the merged dq + dkv sweep (DESIGN: ~174 registers, two waves per SIMD): it would run at that form's occupancy.  NOT the default
 // (lpm_mha_bwd_set_terms): 0.3 % of a step does not pay for gradients 2-3e-4 away from the three-term form's (1e-5 from fp64), and
-// tests/test_gpu_attention_modules.py holds its module to 2e-4.  TPW = 2 is reachable for L = 256, d = 16 only (LPM_MHA_BWD_TPW=2).
-// threads per workgroup: one tile per wave -- as the three-term kernels (dq 512; dkv 512, 1024 from NKT = 20 on); two -- one wave per task
-template <int NKT, int TPW, bool DKV> __host__ __device__ constexpr int mx_h_nt() {
-    constexpr int w = (NKT + TPW - 1) / TPW;
-    return TPW == 1 ? (DKV ? mx_dkv_nt(NKT) : MX_DQ_NT) : (w <= 4 ? 256 : (w >= 16 ? 1024 : 64 * w));
-}
-template <int NKT, bool AFFINE, int D, bool RAGGED, int TPW>
-__global__ __launch_bounds__((mx_h_nt<NKT, TPW, false>())) void mha_bwd_dq_h_kernel(const float* __restrict__ q, const float* __restrict__ k,
+// tests/test_gpu_attention_modules.py holds its module to 2e-4.
+// threads per workgroup: as the three-term kernels (dq 512; dkv 512, 1024 from NKT = 20 on)
+template <int NKT, bool AFFINE, int D, bool RAGGED>
+__global__ __launch_bounds__(MX_DQ_NT) void mha_bwd_dq_h_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                             const float* __restrict__ v, int64_t ld, const float* __restrict__ o,
                                                             const float* __restrict__ dout, int64_t ldo,
                                                             const float* __restrict__ lse, int L, int h, float scale,
@@ -715,7 +711,7 @@ __global__ __launch_bounds__((mx_h_nt<NKT, TPW, false>())) void mha_bwd_dq_h_ker
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float vmax = 0.f;
     constexpr int LP = NKT * 16;
-    constexpr int NT = mx_h_nt<NKT, TPW, false>();
+    constexpr int NT = MX_DQ_NT;
     const int nkt = (L + 15) >> 4;
     const float qmul = AFFINE ? scale : scale * MX_LOG2E;      // scores in log2 units (AFFINE: z is converted instead)
     unsigned char* Kp = smem;                                  // K rows, split-bf16 (hi, lo): the scores stay exact
@@ -751,51 +747,48 @@ __global__ __launch_bounds__((mx_h_nt<NKT, TPW, false>())) void mha_bwd_dq_h_ker
 
     const mx_u32x4 z4 = {0u, 0u, 0u, 0u};
 #pragma unroll 1
-    for (int t0 = wave * TPW; t0 < nkt; t0 += (NT / 64) * TPW) {
-        mx_u32x4 qb1[TPW], qb2[TPW], gb1[TPW], gb2[TPW];
-        float dqv[TPW], lq[TPW], sq[TPW], sqinv[TPW];
-        f32x4 dqa[TPW], dqb[TPW];
-#pragma unroll
-        for (int u = 0; u < TPW; ++u) {
-            const int qrow = (t0 + u) * 16 + l15;
-            const bool qok = qrow < L;
-            mx_u32x4 qh = z4, ql = z4, gh = z4, gl = z4;
-            float dpart = 0.f, gmax = 0.f;
-            float gv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            if (qok) {
-                const int c0 = hh * D + ((D == 16) ? 8 * (g & 1) : 0);
-                const float* qp = q + ((int64_t)b * L + qrow) * ld + c0;
-                const float4 a = *reinterpret_cast<const float4*>(qp), c = *reinterpret_cast<const float4*>(qp + 4);
-                const float qv[8] = {a.x * qmul, a.y * qmul, a.z * qmul, a.w * qmul, c.x * qmul, c.y * qmul, c.z * qmul, c.w * qmul};
-                mx_split8(qv, qh, ql);
-                const int64_t off = ((int64_t)b * L + qrow) * ldo + c0;
-                const float4 ga = *reinterpret_cast<const float4*>(dout + off), gc = *reinterpret_cast<const float4*>(dout + off + 4);
-                float4 oa, oc;
-                mx_load_o8(o, (int64_t)b * L + qrow, ldo, c0, oimg, oa, oc, im);
-                gv[0] = ga.x; gv[1] = ga.y; gv[2] = ga.z; gv[3] = ga.w; gv[4] = gc.x; gv[5] = gc.y; gv[6] = gc.z; gv[7] = gc.w;
-                gmax = of_amax8(0.f, gv);
-                dpart = ga.x * oa.x + ga.y * oa.y + ga.z * oa.z + ga.w * oa.w + gc.x * oc.x + gc.y * oc.y + gc.z * oc.z + gc.w * oc.w;
-            }
-            if (D == 16) {                                         // the two 8-column halves live in lane groups g and g^1
-                dpart += __shfl_xor(dpart, 16, 64);
-                gmax = fmaxf(gmax, __shfl_xor(gmax, 16, 64));
-            }
-            // this query's power-of-two scale s_q (max |dO_q| s_q in [16, 32)).  A lane owns one query COLUMN of every product below, so
-            // dP, D_q, dS and dQ of the query all carry s_q and the store takes it out again.
-            mx_pow2_scale(gmax, sq[u], sqinv[u]);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) gv[e] *= sq[u];            // (a power of two: exact; bf16 has fp32's range)
-            mx_split8(gv, gh, gl);
-            dqv[u] = dpart * sq[u];                                // D_q = <dO_q, O_q>
-            lq[u] = qok ? lse[((int64_t)b * h + hh) * L + qrow] * MX_LOG2E : INFINITY;
-            mx_col_frags<D>(qh, ql, g, qb1[u], qb2[u]);
-            mx_col_frags<D>(gh, gl, g, gb1[u], gb2[u]);
-            dqa[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-            dqb[u] = dqa[u];
+    for (int t0 = wave; t0 < nkt; t0 += NT / 64) {
+        mx_u32x4 qb1, qb2, gb1, gb2;
+        float dqv, lq, sq, sqinv;
+        f32x4 dqa, dqb;
+        const int qrow = t0 * 16 + l15;
+        const bool qok = qrow < L;
+        mx_u32x4 qh = z4, ql = z4, gh = z4, gl = z4;
+        float dpart = 0.f, gmax = 0.f;
+        float gv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (qok) {
+            const int c0 = hh * D + ((D == 16) ? 8 * (g & 1) : 0);
+            const float* qp = q + ((int64_t)b * L + qrow) * ld + c0;
+            const float4 a = *reinterpret_cast<const float4*>(qp), c = *reinterpret_cast<const float4*>(qp + 4);
+            const float qv[8] = {a.x * qmul, a.y * qmul, a.z * qmul, a.w * qmul, c.x * qmul, c.y * qmul, c.z * qmul, c.w * qmul};
+            mx_split8(qv, qh, ql);
+            const int64_t off = ((int64_t)b * L + qrow) * ldo + c0;
+            const float4 ga = *reinterpret_cast<const float4*>(dout + off), gc = *reinterpret_cast<const float4*>(dout + off + 4);
+            float4 oa, oc;
+            mx_load_o8(o, (int64_t)b * L + qrow, ldo, c0, oimg, oa, oc, im);
+            gv[0] = ga.x; gv[1] = ga.y; gv[2] = ga.z; gv[3] = ga.w; gv[4] = gc.x; gv[5] = gc.y; gv[6] = gc.z; gv[7] = gc.w;
+            gmax = of_amax8(0.f, gv);
+            dpart = ga.x * oa.x + ga.y * oa.y + ga.z * oa.z + ga.w * oa.w + gc.x * oc.x + gc.y * oc.y + gc.z * oc.z + gc.w * oc.w;
         }
+        if (D == 16) {                                         // the two 8-column halves live in lane groups g and g^1
+            dpart += __shfl_xor(dpart, 16, 64);
+            gmax = fmaxf(gmax, __shfl_xor(gmax, 16, 64));
+        }
+        // this query's power-of-two scale s_q (max |dO_q| s_q in [16, 32)).  A lane owns one query COLUMN of every product below, so
+        // dP, D_q, dS and dQ of the query all carry s_q and the store takes it out again.
+        mx_pow2_scale(gmax, sq, sqinv);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) gv[e] *= sq;            // (a power of two: exact; bf16 has fp32's range)
+        mx_split8(gv, gh, gl);
+        dqv = dpart * sq;                                // D_q = <dO_q, O_q>
+        lq = qok ? lse[((int64_t)b * h + hh) * L + qrow] * MX_LOG2E : INFINITY;
+        mx_col_frags<D>(qh, ql, g, qb1, qb2);
+        mx_col_frags<D>(gh, gl, g, gb1, gb2);
+        dqa = f32x4{0.f, 0.f, 0.f, 0.f};
+        dqb = dqa;
 #pragma unroll 2
         for (int j = 0; j < NKT / 2; ++j) {
-            float ds8[TPW][8];
+            float ds8[8];
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 const int kt = 2 * j + t;
@@ -808,50 +801,40 @@ __global__ __launch_bounds__((mx_h_nt<NKT, TPW, false>())) void mha_bwd_dq_h_ker
                     sc4[0] = a.x; sc4[1] = a.y; sc4[2] = a.z; sc4[3] = a.w; sh4[0] = c.x; sh4[1] = c.y; sh4[2] = c.z; sh4[3] = c.w;
                     ca4[0] = e.x; ca4[1] = e.y; ca4[2] = e.z; ca4[3] = e.w; cb4[0] = f.x; cb4[1] = f.y; cb4[2] = f.z; cb4[3] = f.w;
                 }
+                f32x4 st = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+                st = mx_mfma(ka, qb1, st);
+                dp = mx_mfma(va, gb1, dp);                  // dP^T s_q = V (dO s_q)^T: three terms, as the scores
+                if (D == 16) {
+                    st = mx_mfma(ka, qb2, st);
+                    dp = mx_mfma(va, gb2, dp);
+                }
 #pragma unroll
-                for (int u = 0; u < TPW; ++u) {
-                    f32x4 st = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-                    st = mx_mfma(ka, qb1[u], st);
-                    dp = mx_mfma(va, gb1[u], dp);                  // dP^T s_q = V (dO s_q)^T: three terms, as the scores
-                    if (D == 16) {
-                        st = mx_mfma(ka, qb2[u], st);
-                        dp = mx_mfma(va, gb2[u], dp);
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        float z = st[r];
-                        if (AFFINE) z = fmaf(st[r], sc4[r], sh4[r]) * MX_LOG2E;
-                        if (RAGGED && kt * 16 + 4 * g + r >= L) z = -INFINITY;
-                        const float pr = __builtin_amdgcn_exp2f(z - lq[u]);
-                        float dsv = pr * (dp[r] - dqv[u]);
-                        if (AFFINE) dsv = fmaf(dsv, sc4[r], -sq[u] * fmaf(st[r], cb4[r], ca4[r]));
-                        ds8[u][4 * t + r] = dsv;
-                    }
+                for (int r = 0; r < 4; ++r) {
+                    float z = st[r];
+                    if (AFFINE) z = fmaf(st[r], sc4[r], sh4[r]) * MX_LOG2E;
+                    if (RAGGED && kt * 16 + 4 * g + r >= L) z = -INFINITY;
+                    const float pr = __builtin_amdgcn_exp2f(z - lq);
+                    float dsv = pr * (dp[r] - dqv);
+                    if (AFFINE) dsv = fmaf(dsv, sc4[r], -sq * fmaf(st[r], cb4[r], ca4[r]));
+                    ds8[4 * t + r] = dsv;
                 }
             }
             const unsigned char* kc = Kt + l15 * TS + (32 * j + 8 * g) * 2;
             const mx_u32x4 kh = *reinterpret_cast<const mx_u32x4*>(kc), kl = *reinterpret_cast<const mx_u32x4*>(kc + 16 * TS);
-#pragma unroll
-            for (int u = 0; u < TPW; ++u) {
-                const mx_u32x4 dh = mx_round8_h(ds8[u]);           // dS rounded once; K^T exact: two products, two accumulators
-                dqa[u] = mx_mfma_h(kh, dh, dqa[u]);                // dQ^T[dd, q] += K^T[dd, keys] dS^T[keys, q]
-                dqb[u] = mx_mfma_h(kl, dh, dqb[u]);
-            }
+            const mx_u32x4 dh = mx_round8_h(ds8);           // dS rounded once; K^T exact: two products, two accumulators
+            dqa = mx_mfma_h(kh, dh, dqa);                // dQ^T[dd, q] += K^T[dd, keys] dS^T[keys, q]
+            dqb = mx_mfma_h(kl, dh, dqb);
         }
-#pragma unroll
-        for (int u = 0; u < TPW; ++u) {
-            const int qrow = (t0 + u) * 16 + l15;
-            const float omul = scale * sqinv[u];
-            if (qrow < L && 4 * g < D)
-                mx_store_grad4(dq, ((int64_t)b * L + qrow) * ldd + hh * D + 4 * g, img, (dqa[u][0] + dqb[u][0]) * omul, (dqa[u][1] + dqb[u][1]) * omul,
-                               (dqa[u][2] + dqb[u][2]) * omul, (dqa[u][3] + dqb[u][3]) * omul, im, vmax);
-        }
+        const float omul = scale * sqinv;
+        if (qrow < L && 4 * g < D)
+            mx_store_grad4(dq, ((int64_t)b * L + qrow) * ldd + hh * D + 4 * g, img, (dqa[0] + dqb[0]) * omul, (dqa[1] + dqb[1]) * omul,
+                           (dqa[2] + dqb[2]) * omul, (dqa[3] + dqb[3]) * omul, im, vmax);
     }
     if (img) of_amax_commit(im.gamax, vmax);
 }
 
-template <int NKT, bool AFFINE, int D, bool CORR, int TPW>
-__global__ __launch_bounds__((mx_h_nt<NKT, TPW, true>())) void mha_bwd_dkv_h_kernel(const float* __restrict__ q, const float* __restrict__ k,
+template <int NKT, bool AFFINE, int D, bool CORR>
+__global__ __launch_bounds__(mx_dkv_nt(NKT)) void mha_bwd_dkv_h_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                              const float* __restrict__ v, int64_t ld, const float* __restrict__ o,
                                                              const float* __restrict__ dout, int64_t ldo,
                                                              const float* __restrict__ lse, int L, int h, float scale,
@@ -862,7 +845,7 @@ __global__ __launch_bounds__((mx_h_nt<NKT, TPW, true>())) void mha_bwd_dkv_h_ker
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float vmax = 0.f;
     constexpr int LP = NKT * 16;
-    constexpr int NT = mx_h_nt<NKT, TPW, true>();
+    constexpr int NT = mx_dkv_nt(NKT);
     constexpr int NH = D / 8;
     const int nkt = (L + 15) >> 4;
     const float qmul = AFFINE ? scale : scale * MX_LOG2E;       // scores in log2 units (AFFINE: z is converted instead)
@@ -951,39 +934,35 @@ __global__ __launch_bounds__((mx_h_nt<NKT, TPW, true>())) void mha_bwd_dkv_h_ker
 
     const mx_u32x4 z4 = {0u, 0u, 0u, 0u};
 #pragma unroll 1
-    for (int t0 = wave * TPW; t0 < nkt; t0 += (NT / 64) * TPW) {
-        mx_u32x4 kb1[TPW], kb2[TPW], vb1[TPW], vb2[TPW];
-        float sck[TPW], shk[TPW], cak[TPW], cbk[TPW], zs[TPW], zq[TPW];
-        bool kok[TPW];
-        f32x4 dka[TPW], dkb[TPW], dva[TPW], dvb[TPW];
-#pragma unroll
-        for (int u = 0; u < TPW; ++u) {
-            const int krow = (t0 + u) * 16 + l15;
-            kok[u] = krow < L;
-            mx_u32x4 kh = z4, kl = z4, vh = z4, vl = z4;
-            if (kok[u]) {
-                const int64_t off = ((int64_t)b * L + krow) * ld + hh * D + ((D == 16) ? 8 * (g & 1) : 0);
-                const float4 ka = *reinterpret_cast<const float4*>(k + off), kc = *reinterpret_cast<const float4*>(k + off + 4);
-                const float4 va = *reinterpret_cast<const float4*>(v + off), vc = *reinterpret_cast<const float4*>(v + off + 4);
-                const float kv[8] = {ka.x, ka.y, ka.z, ka.w, kc.x, kc.y, kc.z, kc.w};
-                const float vv[8] = {va.x, va.y, va.z, va.w, vc.x, vc.y, vc.z, vc.w};
-                mx_split8(kv, kh, kl);
-                mx_split8(vv, vh, vl);
-            }
-            mx_col_frags<D>(kh, kl, g, kb1[u], kb2[u]);
-            mx_col_frags<D>(vh, vl, g, vb1[u], vb2[u]);
-            sck[u] = (key_scale && kok[u]) ? key_scale[krow] : 1.f;
-            shk[u] = (key_shift && kok[u]) ? key_shift[krow] : 0.f;
-            cak[u] = ((corr_a && kok[u]) ? corr_a[krow] : 0.f) * gs;
-            cbk[u] = ((corr_b && kok[u]) ? corr_b[krow] : 0.f) * gs;
-            zs[u] = zq[u] = 0.f;
-            dka[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-            dkb[u] = dva[u] = dvb[u] = dka[u];
+    for (int t0 = wave; t0 < nkt; t0 += NT / 64) {
+        mx_u32x4 kb1, kb2, vb1, vb2;
+        float sck, shk, cak, cbk, zs, zq;
+        bool kok;
+        f32x4 dka, dkb, dva, dvb;
+        const int krow = t0 * 16 + l15;
+        kok = krow < L;
+        mx_u32x4 kh = z4, kl = z4, vh = z4, vl = z4;
+        if (kok) {
+            const int64_t off = ((int64_t)b * L + krow) * ld + hh * D + ((D == 16) ? 8 * (g & 1) : 0);
+            const float4 ka = *reinterpret_cast<const float4*>(k + off), kc = *reinterpret_cast<const float4*>(k + off + 4);
+            const float4 va = *reinterpret_cast<const float4*>(v + off), vc = *reinterpret_cast<const float4*>(v + off + 4);
+            const float kv[8] = {ka.x, ka.y, ka.z, ka.w, kc.x, kc.y, kc.z, kc.w};
+            const float vv[8] = {va.x, va.y, va.z, va.w, vc.x, vc.y, vc.z, vc.w};
+            mx_split8(kv, kh, kl);
+            mx_split8(vv, vh, vl);
         }
-        constexpr int UNR = (AFFINE && TPW == 2) ? 1 : 2;       // (the logits_bn form with two key tiles: 180-215 registers unrolled by two)
-#pragma unroll UNR
+        mx_col_frags<D>(kh, kl, g, kb1, kb2);
+        mx_col_frags<D>(vh, vl, g, vb1, vb2);
+        sck = (key_scale && kok) ? key_scale[krow] : 1.f;
+        shk = (key_shift && kok) ? key_shift[krow] : 0.f;
+        cak = ((corr_a && kok) ? corr_a[krow] : 0.f) * gs;
+        cbk = ((corr_b && kok) ? corr_b[krow] : 0.f) * gs;
+        zs = zq = 0.f;
+        dka = f32x4{0.f, 0.f, 0.f, 0.f};
+        dkb = dva = dvb = dka;
+#pragma unroll 2
         for (int j = 0; j < NKT / 2; ++j) {
-            float p8[TPW][8], ds8[TPW][8];
+            float p8[8], ds8[8];
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 const int qt = 2 * j + t;
@@ -991,75 +970,65 @@ __global__ __launch_bounds__((mx_h_nt<NKT, TPW, true>())) void mha_bwd_dkv_h_ker
                 const float4 lq4v = *reinterpret_cast<const float4*>(lses + qt * 16 + 4 * g);
                 const float4 dq4v = *reinterpret_cast<const float4*>(Dq + qt * 16 + 4 * g);
                 const float lq4[4] = {lq4v.x, lq4v.y, lq4v.z, lq4v.w}, dq4[4] = {dq4v.x, dq4v.y, dq4v.z, dq4v.w};
+                f32x4 st = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+                st = mx_mfma(qa, kb1, st);              // S[q, key] (scale folded into Q)
+                dp = mx_mfma(ga, vb1, dp);              // dP[q, key] s = (dO s) V^T: three terms, as the scores
+                if (D == 16) {
+                    st = mx_mfma(qa, kb2, st);
+                    dp = mx_mfma(ga, vb2, dp);
+                }
 #pragma unroll
-                for (int u = 0; u < TPW; ++u) {
-                    f32x4 st = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-                    st = mx_mfma(qa, kb1[u], st);              // S[q, key] (scale folded into Q)
-                    dp = mx_mfma(ga, vb1[u], dp);              // dP[q, key] s = (dO s) V^T: three terms, as the scores
-                    if (D == 16) {
-                        st = mx_mfma(qa, kb2[u], st);
-                        dp = mx_mfma(ga, vb2[u], dp);
+                for (int r = 0; r < 4; ++r) {
+                    const float sraw = st[r];
+                    float z = sraw;
+                    if (AFFINE) z = fmaf(sraw, sck, shk) * MX_LOG2E;
+                    if (!kok) z = -INFINITY;
+                    const float pr = __builtin_amdgcn_exp2f(z - lq4[r]);
+                    const float dz = pr * (dp[r] - dq4[r]);
+                    float dsv = dz;
+                    if (AFFINE) {
+                        zs += dz;
+                        zq = fmaf(dz, sraw, zq);
+                        const bool qin = qt * 16 + 4 * g + r < L;
+                        if constexpr (CORR) dsv = qin ? dz * sck - cak - sraw * cbk : 0.f;
+                        else dsv = qin ? dz * sck : 0.f;
                     }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float sraw = st[r];
-                        float z = sraw;
-                        if (AFFINE) z = fmaf(sraw, sck[u], shk[u]) * MX_LOG2E;
-                        if (!kok[u]) z = -INFINITY;
-                        const float pr = __builtin_amdgcn_exp2f(z - lq4[r]);
-                        const float dz = pr * (dp[r] - dq4[r]);
-                        float dsv = dz;
-                        if (AFFINE) {
-                            zs[u] += dz;
-                            zq[u] = fmaf(dz, sraw, zq[u]);
-                            const bool qin = qt * 16 + 4 * g + r < L;
-                            if constexpr (CORR) dsv = qin ? dz * sck[u] - cak[u] - sraw * cbk[u] : 0.f;
-                            else dsv = qin ? dz * sck[u] : 0.f;
-                        }
-                        p8[u][4 * t + r] = pr;
-                        ds8[u][4 * t + r] = dsv;
-                    }
+                    p8[4 * t + r] = pr;
+                    ds8[4 * t + r] = dsv;
                 }
             }
             if (!stats_only) {
                 const int offt = l15 * TS + (32 * j + 8 * g) * 2;
                 const mx_u32x4 gth = *reinterpret_cast<const mx_u32x4*>(Gt + offt), gtl = *reinterpret_cast<const mx_u32x4*>(Gt + 16 * TS + offt);
                 const mx_u32x4 qth = *reinterpret_cast<const mx_u32x4*>(Qt + offt), qtl = *reinterpret_cast<const mx_u32x4*>(Qt + 16 * TS + offt);
-#pragma unroll
-                for (int u = 0; u < TPW; ++u) {
-                    // P in [0, 1] needs no clamp; dS is clamped to fp16's range (mx_round8_h)
-                    const mx_u32x4 ph = {__builtin_bit_cast(unsigned, __builtin_convertvector(of_f2{p8[u][0], p8[u][1]}, of_h2)),
-                                         __builtin_bit_cast(unsigned, __builtin_convertvector(of_f2{p8[u][2], p8[u][3]}, of_h2)),
-                                         __builtin_bit_cast(unsigned, __builtin_convertvector(of_f2{p8[u][4], p8[u][5]}, of_h2)),
-                                         __builtin_bit_cast(unsigned, __builtin_convertvector(of_f2{p8[u][6], p8[u][7]}, of_h2))};
-                    const mx_u32x4 dh = mx_round8_h(ds8[u]);
-                    dva[u] = mx_mfma_h(gth, ph, dva[u]);       // dV^T[dd, key] += (dO s)^T[dd, q] P[q, key]
-                    dvb[u] = mx_mfma_h(gtl, ph, dvb[u]);
-                    dka[u] = mx_mfma_h(qth, dh, dka[u]);       // dK^T[dd, key] += (scale Q)^T[dd, q] dS[q, key]
-                    dkb[u] = mx_mfma_h(qtl, dh, dkb[u]);
-                }
+                // P in [0, 1] needs no clamp; dS is clamped to fp16's range (mx_round8_h)
+                const mx_u32x4 ph = {__builtin_bit_cast(unsigned, __builtin_convertvector(of_f2{p8[0], p8[1]}, of_h2)),
+                                     __builtin_bit_cast(unsigned, __builtin_convertvector(of_f2{p8[2], p8[3]}, of_h2)),
+                                     __builtin_bit_cast(unsigned, __builtin_convertvector(of_f2{p8[4], p8[5]}, of_h2)),
+                                     __builtin_bit_cast(unsigned, __builtin_convertvector(of_f2{p8[6], p8[7]}, of_h2))};
+                const mx_u32x4 dh = mx_round8_h(ds8);
+                dva = mx_mfma_h(gth, ph, dva);       // dV^T[dd, key] += (dO s)^T[dd, q] P[q, key]
+                dvb = mx_mfma_h(gtl, ph, dvb);
+                dka = mx_mfma_h(qth, dh, dka);       // dK^T[dd, key] += (scale Q)^T[dd, q] dS[q, key]
+                dkb = mx_mfma_h(qtl, dh, dkb);
             }
         }
-#pragma unroll
-        for (int u = 0; u < TPW; ++u) {
-            const int krow = (t0 + u) * 16 + l15;
-            if (!stats_only && kok[u] && 4 * g < D) {
-                const int64_t off = ((int64_t)b * L + krow) * ldd + hh * D + 4 * g;
-                const float kmul = (AFFINE ? 1.f : MX_LN2) * gsinv;      // the staged Q carried log2(e)
-                mx_store_dk4(dk, (int64_t)b * L + krow, ldd, hh * D + 4 * g, img, (dka[u][0] + dkb[u][0]) * kmul, (dka[u][1] + dkb[u][1]) * kmul,
-                             (dka[u][2] + dkb[u][2]) * kmul, (dka[u][3] + dkb[u][3]) * kmul, im, vmax);
-                mx_store_grad4(dv, off, img, (dva[u][0] + dvb[u][0]) * gsinv, (dva[u][1] + dvb[u][1]) * gsinv, (dva[u][2] + dvb[u][2]) * gsinv,
-                               (dva[u][3] + dvb[u][3]) * gsinv, im, vmax);
-            }
-            if (dz_partial) {
-                float a = zs[u], c = zq[u];
-                a += __shfl_xor(a, 16, 64); a += __shfl_xor(a, 32, 64);
-                c += __shfl_xor(c, 16, 64); c += __shfl_xor(c, 32, 64);
-                if (g == 0 && kok[u]) {
-                    float* out = dz_partial + ((int64_t)b * h + hh) * 2 * L;
-                    out[krow] = a * gsinv;
-                    out[L + krow] = c * gsinv;
-                }
+        if (!stats_only && kok && 4 * g < D) {
+            const int64_t off = ((int64_t)b * L + krow) * ldd + hh * D + 4 * g;
+            const float kmul = (AFFINE ? 1.f : MX_LN2) * gsinv;      // the staged Q carried log2(e)
+            mx_store_dk4(dk, (int64_t)b * L + krow, ldd, hh * D + 4 * g, img, (dka[0] + dkb[0]) * kmul, (dka[1] + dkb[1]) * kmul,
+                         (dka[2] + dkb[2]) * kmul, (dka[3] + dkb[3]) * kmul, im, vmax);
+            mx_store_grad4(dv, off, img, (dva[0] + dvb[0]) * gsinv, (dva[1] + dvb[1]) * gsinv, (dva[2] + dvb[2]) * gsinv,
+                           (dva[3] + dvb[3]) * gsinv, im, vmax);
+        }
+        if (dz_partial) {
+            float a = zs, c = zq;
+            a += __shfl_xor(a, 16, 64); a += __shfl_xor(a, 32, 64);
+            c += __shfl_xor(c, 16, 64); c += __shfl_xor(c, 32, 64);
+            if (g == 0 && kok) {
+                float* out = dz_partial + ((int64_t)b * h + hh) * 2 * L;
+                out[krow] = a * gsinv;
+                out[L + krow] = c * gsinv;
             }
         }
     }
@@ -1312,33 +1281,27 @@ static int mx_bwd_launch(const float* q, const float* k, const float* v, int64_t
     dim3 grid(B * h);
     // two fp16 terms: only where dS is linear in dO (no correction vectors: see the kernels' header)
     const bool h16 = g_mha_bwd_terms.load(std::memory_order_relaxed) == 2 && !corr_a;
-    static const int tpw = env_first_is("LPM_MHA_BWD_TPW", '2') ? 2 : 1;   // tiles per wave (A/B)
-#define LPM_MX_BWDH_Q(N, AFF, DD, RG, TP)                                                                              \
+#define LPM_MX_BWDH_Q(N, AFF, DD, RG)                                                                                  \
     do {                                                                                                               \
-        auto kq = mha_bwd_dq_h_kernel<N, AFF, DD, RG, TP>;                                                             \
+        auto kq = mha_bwd_dq_h_kernel<N, AFF, DD, RG>;                                                                 \
         const size_t lq = mx_bwd_dq_lds(N * 16, DD);                                                                   \
         if (int rc = mx_reserve(kq, lq, what)) return rc;                                                              \
-        hipLaunchKernelGGL(kq, grid, dim3(mx_h_nt<N, TP, false>()), lq, s, q, k, v, ld, o, dout, ldo, lse, L, h, scale, key_scale, key_shift, \
+        hipLaunchKernelGGL(kq, grid, dim3(MX_DQ_NT), lq, s, q, k, v, ld, o, dout, ldo, lse, L, h, scale, key_scale, key_shift, \
                            dq, ldd, corr_a, corr_b, img, oimg, im);                                                    \
     } while (0)
-#define LPM_MX_BWDH_KV(N, AFF, DD, TP)                                                                                 \
+#define LPM_MX_BWDH_KV(N, AFF, DD)                                                                                     \
     do {                                                                                                               \
-        auto kk = mha_bwd_dkv_h_kernel<N, AFF, DD, false, TP>;                                                         \
+        auto kk = mha_bwd_dkv_h_kernel<N, AFF, DD, false>;                                                             \
         const size_t lk = mx_bwd_dkv_lds(N * 16, DD);                                                                  \
         if (int rc = mx_reserve(kk, lk, what)) return rc;                                                              \
-        hipLaunchKernelGGL(kk, grid, dim3(mx_h_nt<N, TP, true>()), lk, s, q, k, v, ld, o, dout, ldo, lse, L, h, scale, key_scale, key_shift, \
+        hipLaunchKernelGGL(kk, grid, dim3(mx_dkv_nt(N)), lk, s, q, k, v, ld, o, dout, ldo, lse, L, h, scale, key_scale, key_shift, \
                            dk, dv, ldd, corr_a, corr_b, dz_partial, img, oimg, im);                                    \
     } while (0)
-    if (h16 && tpw == 2 && L == 256 && d == 16 && !key_scale) {         // the measured two-tiles-per-wave form (not the default)
-        if (dq) LPM_MX_BWDH_Q(16, false, 16, false, 2);
-        if (dk || dz_partial) LPM_MX_BWDH_KV(16, false, 16, 2);
-        return check_launch(what);
-    }
 #define LPM_MX_BWD3(N, AFF, DD, RG)                                                                                    \
     do {                                                                                                               \
         if (h16) {                                                                                                     \
-            if (dq) LPM_MX_BWDH_Q(N, AFF, DD, RG, 1);                                                                  \
-            if (dk || dz_partial) LPM_MX_BWDH_KV(N, AFF, DD, 1);                                                       \
+            if (dq) LPM_MX_BWDH_Q(N, AFF, DD, RG);                                                                     \
+            if (dk || dz_partial) LPM_MX_BWDH_KV(N, AFF, DD);                                                          \
             break;                                                                                                     \
         }                                                                                                              \
         if (dq) {                                                                                                      \

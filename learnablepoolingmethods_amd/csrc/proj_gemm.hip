@@ -828,9 +828,8 @@ extern "C" int lpm_proj_dx(const void* dyt, const float* W, int M, int64_t Kd, i
     const int MT = (M + 31) / 32;
     dim3 grid((unsigned)((Kd + 255) / 256));
     hipStream_t s = (hipStream_t)stream;
-    // second form (whole 128-byte lines of W per stage): N a multiple of 32; LPM_PROJ_DX_FORM=1 selects the first form (A/B)
-    static const int form = env_first_is("LPM_PROJ_DX_FORM", '1') ? 1 : 2;
-    if (form == 2 && N % 32 == 0 && N >= 64) {
+    // second form (whole 128-byte lines of W per stage): N a multiple of 32, at least 64; the first form serves the other N
+    if (N % 32 == 0 && N >= 64) {
 #define LPM_PE(MTV)                                                                                                          \
     do {                                                                                                                     \
         auto kern = proj_dx2_kernel<MTV>;                                                                                    \

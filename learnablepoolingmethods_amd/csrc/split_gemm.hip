@@ -206,17 +206,6 @@ extern "C" int lpm_split_rows(const float* x, int64_t ldx, int64_t M, int K, con
     return lpm_split_rows_fmt(x, ldx, M, K, bias, relu, order, nullptr, out3, nullptr, stream);
 }
 
-// x[m, :] * row_scale[m] -> activation image [hi | lo | hi]: the operand of the q/k/v GEMM when x is the pooled descriptor in its
-// lazily normalised form (lpm_vlad_aggregate_raw_kmajor_fwd + lpm_vlad_row_scales)
-extern "C" int lpm_split_rows_scaled(const float* x, int64_t ldx, int64_t M, int K, const float* row_scale, void* out3, lpm_stream_t stream) {
-    using namespace lpm;
-    LPM_REQUIRE(x && out3 && row_scale, LPM_ERR_BADARG, "lpm_split_rows_scaled: null pointer");
-    LPM_REQUIRE(M > 0 && K > 0 && ldx >= K, LPM_ERR_BADARG, "lpm_split_rows_scaled: bad sizes");
-    LPM_REQUIRE(K % 8 == 0 && ldx % 4 == 0 && (((uintptr_t)x | (uintptr_t)out3) & 15) == 0, LPM_ERR_UNSUPPORTED_SHAPE,
-                "lpm_split_rows_scaled: need K %% 8 == 0, ldx %% 4 == 0, 16-byte aligned pointers (K=%d)", K);
-    return lpm_split_rows_fmt(x, ldx, M, K, nullptr, 0, 0, row_scale, out3, nullptr, stream);
-}
-
 namespace lpm {
 // ---- bias (+ ReLU) of a dense layer whose output goes to something other than the next GEMM's operand split (tf.layers.dense with
 // use_bias / activation=relu, e.g. FeedForwardNetworkMod's layers in front of their batch norms, transformer_utils.py:741-760) ----------

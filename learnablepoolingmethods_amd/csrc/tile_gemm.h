@@ -142,7 +142,6 @@ int tile_gemm_softmax_bwd(const TileGemmArgs& g, int nbatch, hipStream_t stream,
 int tile_gemm_ntw(int cols);
 // 256-row form with an image epilogue (g.img, g.img_kind, ...): one batch, one split, columns a multiple of 256, row tiles a multiple of 8
 int tile_gemm_image(const TileGemmArgs& g, hipStream_t stream, const char* what, int planes = 2);   // planes 3: the fp16 two-product form
-int tile_gemm_image_form();
 int tile_gemm_image_row_groups(int M);
 
 // K1's forward on flat 96-row workgroups (assign_flat.hip): the per-clip row tiles gathered per lane, B fragments straight into registers.

@@ -830,19 +830,12 @@ int tile_gemm_image(const TileGemmArgs& g, hipStream_t stream, const char* what,
     gl.ldo = 4; gl.out_batch = 0; gl.out_split = 0;
     if (gl.img_planes != 2) gl.img_planes = 3;
     if (gl.mask_planes != 2) gl.mask_planes = 3;
-    // non-temporal stores: the 0.5 GB image is read back by the next GEMM long after it has left the caches (-6 us of 520 measured;
-    // LPM_DENSE_IMG_NT=0: plain stores, A/B)
-    static const int nt = env_first_is("LPM_DENSE_IMG_NT", '0') ? 0 : 1;
-    gl.nt_store = nt;
+    // non-temporal stores: the 0.5 GB image is read back by the next GEMM long after it has left the caches (-6 us of 520 measured)
+    gl.nt_store = 1;
     if (planes >= 3) return tg_launch_f16_image(gl, stream, what, planes);
-    return tg_launch_pl<TG_EPI_STORE, 2>(gl, 1, 1, stream, what, 2, 0, tile_gemm_image_form() == 3 ? 2 : 3);
+    return tg_launch_pl<TG_EPI_STORE, 2>(gl, 1, 1, stream, what, 2, 0, 3);      // 256-row workgroups, one per CU
 }
-// 4 (default): 256-row workgroups, one per CU; 3: 128-row workgroups, two per CU (their epilogues overlap the neighbour's main loop)
-int tile_gemm_image_form() {
-    static const int form = env_first_is("LPM_DENSE_IMG_FORM", '3') ? 3 : 4;
-    return form;
-}
-int tile_gemm_image_row_groups(int M) { return tile_gemm_image_form() == 3 ? M / 64 : M / 128; }
+int tile_gemm_image_row_groups(int M) { return M / 128; }
 
 // [B*T, C] fp32 (row stride ldx) -> row tiles [b][mt][cs][plane][lane]; mt < 2*ceil(T/64), rows >= T are zero.
 __global__ __launch_bounds__(256) void split_rows_tiles_kernel(const float* __restrict__ x, int64_t ldx, int B, int T, int C, int MT,
@@ -1160,11 +1153,10 @@ extern "C" int lpm_split_weight_tiles_parts(const void* x1, int64_t ld1, int64_t
                 "lpm_split_weight_tiles_parts: need R %% 16 == 0, the scaled block a multiple of 32 columns and of ks (R=%d n1a=%lld ks=%d)", R,
                 (long long)n1a, ks);
     const int64_t total = (int64_t)(R / 16) * ((N + 31) / 32) * 64;
-    // four columns per thread where every row piece is an aligned vector (LPM_SWT_PARTS4=0: the one-column form, A/B)
-    static const int four = env_first_is("LPM_SWT_PARTS4", '0') ? 0 : 1;
+    // four columns per thread where every row piece is an aligned vector; the one-column form otherwise
     const bool al1 = ld1 % 4 == 0 && ((uintptr_t)x1 & (x1_bf16 ? 7 : 15)) == 0 && ks % 4 == 0 && ((uintptr_t)scale & 15) == 0;
     const bool al2 = n1a == N || (ld2 % 4 == 0 && ((uintptr_t)x2 & 15) == 0);
-    if (four && n1a % 4 == 0 && N % 4 == 0 && al1 && al2) {
+    if (n1a % 4 == 0 && N % 4 == 0 && al1 && al2) {
         const int64_t want4 = (total / 4 + 255) / 256;
         hipLaunchKernelGGL(split_weight_tiles_parts4_kernel, dim3((unsigned)(want4 < 65536 ? want4 : 65536)), dim3(256), 0, (hipStream_t)stream,
                            (const float*)x1, ld1, n1a, x1_bf16 ? 1 : 0, scale, ks, x2, ld2, R, N, (uint4*)wt);
@@ -1193,7 +1185,7 @@ static int assign_gemm_tiles_fwd_impl(const void* xr, const void* wt, int B, int
     LPM_REQUIRE(B > 0 && lpm_assign_gemm_tiles_supported(T, D, K), LPM_ERR_UNSUPPORTED_SHAPE,
                 "lpm_assign_gemm_tiles_fwd: need D %% 32 == 0, K %% 32 == 0, K <= 512 (D=%d K=%d)", D, K);
     const int MT = row_tiles_per_clip(T), DS = D / 16, NT = K / 32;
-    // fp32 storage, K a multiple of 256, D a multiple of 64: flat 96-row workgroups (assign_flat.hip; LPM_K1_FLAT=0: the forms below)
+    // fp32 storage, K a multiple of 256, D a multiple of 64: flat 96-row workgroups (assign_flat.hip; lpm_k1_forms_disable: the forms below)
     if (planes == 2 && assign_flat_ok(B, T, D, K))
         return assign_flat_launch(xr, wt, B, T, MT, D, K, (float*)logits, partial, lpm_assign_gemm_tiles_nblk(B, T),
                                   D >= 1024 ? LPM_TIMING_K1 : 0, (hipStream_t)stream, "lpm_assign_gemm_tiles_fwd");
@@ -1428,8 +1420,7 @@ extern "C" int lpm_skinny_weight_grad_tiles(const void* xt, const void* dyt, int
     g.b = (const uint4*)dyt; g.b_tile = 128; g.b_step = (int64_t)NT2 * 128; g.b_batch = 0; g.b_tiles = NT2;
     g.rb_per_batch = (N1 + 63) / 64; g.steps_per_split = R / 16; g.total_steps = R / 16;
     g.out = dW; g.ldo = N2; g.rows_valid = N1; g.cols_valid = N2;
-    static const int nt = env_first_is("LPM_DW_NT_STORE", '0') ? 0 : 1;      // 0: plain stores (A/B)
-    g.nt_store = nt;
+    g.nt_store = 1;
     // the 4 (cfg-2) / 8 (cfg-5) column blocks of a row block as neighbours on one XCD: the activation tiles (86 MB at cfg-2, 277 MB at
     // cfg-5: more than the infinity cache) are fetched from HBM once instead of once per column block (LPM_DW_COLS_INNER=0: A/B)
     static const int inner = env_first_is("LPM_DW_COLS_INNER", '0') ? 0 : 1;

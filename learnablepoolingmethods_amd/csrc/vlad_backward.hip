@@ -1026,10 +1026,9 @@ static int vlad_aggregate_bwd_tiles_impl(const float* dout, int64_t dob, const f
     g.logits = assign; g.logits_bf16 = planes == 1 ? 1 : 0; g.scale = scale; g.shift = shift; g.ctil = ctil; g.softmax = sm ? 1 : 0;
     // K = 512 (cfg-5's video stream): the fused epilogue needs all K columns of a row in one workgroup -- 64 x 512 tiles, 131 KB of
     // LDS, one workgroup per CU: 367 us.  Two launches instead: the GEMM on 64 x 256 tiles with the plain store (two per CU), then the
-    // row-wise softmax backward in place (LPM_DA_SPLIT=0: the fused form, A/B)
-    static const int da_split = env_first_is("LPM_DA_SPLIT", '0') ? 0 : 1;
+    // row-wise softmax backward in place
     int rc;
-    if (da_split && K == 512) {
+    if (K == 512) {
         g.ldo = K; g.out_batch = (int64_t)T * K; g.out_split = 0; g.accumulate = 0;
         rc = tile_gemm_store(g, B, 1, s, "lpm_vlad_aggregate_bwd_tiles", 2, planes);
         if (rc == LPM_OK) {

@@ -318,8 +318,7 @@ __global__ __launch_bounds__(512, 4) void vlad_kmajor_kernel(const VKArgs g) {
 
 // clips that run as wide items: whole rounds of 2 x 256 workgroup slots (64 clips at D = 1024), the rest as 128 x 128 items in the tail
 static int vk_large_clips(int B, int D, int K, int flags) {
-    static const int env_mode = env_int("LPM_K2_WIDE", 1);      // 0: none, 1: rounds, 2: all
-    const int mode = (flags & LPM_VLAD_WIDE_ALL) ? 2 : ((flags & LPM_VLAD_WIDE_NONE) ? 0 : env_mode);
+    const int mode = (flags & LPM_VLAD_WIDE_ALL) ? 2 : ((flags & LPM_VLAD_WIDE_NONE) ? 0 : 1);      // 0: none, 1: rounds, 2: all
     if (K != 256 || mode == 0) return 0;
     if (mode == 2) return B;
     const int P = D / 128;

@@ -316,12 +316,9 @@ static bool launch_assign_tiles2(const void* assign, const float* scale, const f
                                  void* at, hipStream_t stream, int timing_tag) {
     if (K != 64 && K != 128 && K != 256 && K != 512) return false;
     if ((((uintptr_t)assign | (uintptr_t)at) & 15) != 0) return false;
-    static const int on = env_first_is("LPM_ASSIGN_TILES2", '0') ? 0 : 1;     // 0: first form (A/B)
-    if (!on) return false;
     hipEvent_t e0, e1;
     const bool timed = timing_tag && timing_request(timing_tag, &e0, &e1);
-    static const int two = env_first_is("LPM_ASSIGN_TILES_NSTEP", '1') ? 0 : 1;     // "1": one step per workgroup (A/B)
-    if (BF16IN && K == 512 && S % 2 == 0 && two) {
+    if (BF16IN && K == 512 && S % 2 == 0) {      // two steps per workgroup
         auto kern = softmax ? assign_tiles2_kernel<true, BF16IN, 8, 2> : assign_tiles2_kernel<false, BF16IN, 8, 2>;
         if (timed)
             hipExtLaunchKernelGGL(kern, dim3(B * S / 2), dim3(256), 0, stream, e0, e1, 0, (const float*)assign, scale, shift, T, S, (uint4*)at);

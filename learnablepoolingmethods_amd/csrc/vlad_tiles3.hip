@@ -30,7 +30,6 @@ __device__ __forceinline__ f32x16 t3_mfma(t3_u32x4 a, t3_u32x4 b, f32x16 c) {
 __device__ __forceinline__ float t3_bf(unsigned h) { return __uint_as_float(h << 16); }
 
 constexpr int T3_NS = 3;                  // ring stages (48 KB: three workgroups per CU)
-constexpr int T3_NT_DEFAULT = 0;          // see t3_nt()
 constexpr int T3_STAGE = 16 * 1024;       // bytes per stage: 4 A tiles + 4 x tiles, 2 planes, 1 KB each
 constexpr int T3_WS = 36;                 // epilogue per-wave tile row stride (floats): 144 B, 16-B aligned
 constexpr int T3_EPI = 8 * 32 * T3_WS * 4;  // epilogue bytes (8 waves x [32 d][32 k + pad]), overlays the ring
@@ -164,7 +163,7 @@ __device__ __forceinline__ void t3_split2(float a, float b, unsigned& hi, unsign
 template <bool FUSED, int PL, bool SMX = false>
 __global__ __launch_bounds__(512, SMX ? 4 : 6) void vlad_aggregate_tiles3_kernel(
     const uint4* __restrict__ at, const uint4* __restrict__ xt, const float* __restrict__ centres, int T, int D, int K,
-    int S, int KT, int resflags, float* __restrict__ nrm, float* __restrict__ asum, float* __restrict__ colsq_part, const T3Fused fz,
+    int S, int KT, int residual, float* __restrict__ nrm, float* __restrict__ asum, float* __restrict__ colsq_part, const T3Fused fz,
     const T3Softmax sm) {
     static_assert(!SMX || PL == 2, "the in-kernel softmax writes split-bf16 fragments");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // the ONLY LDS object (guide 5, trap (a))
@@ -186,27 +185,16 @@ __global__ __launch_bounds__(512, SMX ? 4 : 6) void vlad_aggregate_tiles3_kernel
                                 : xt + (((int64_t)b * S + pplane) * DT + ds * 4 + ptile) * 64 + lane;
     const int adst = (ptile * 2 + pplane) * 1024, xdst = 8192 + (ptile * 2 + pplane) * 1024;
     const int NST = PL == 2 ? S : S / 2;           // ring stages
-    const int residual = resflags & 1;             // bit 0: subtract (sum_t a) * centres; bits 1, 2: LDS-DMA cache policy, see issue()
     const int k0s = kb * 128;                      // first cluster of this workgroup's slab
 
     auto issue = [&](int s) {                 // the pieces of step min(s, NST - 1) into stage s % NS
         unsigned char* st = smem + (s % T3_NS) * T3_STAGE;
         const int sc = SMX ? min(s, NST - 1) : s;
-        // resflags bit 1 / bit 2 (LPM_T3_NT = 1 / 2 / 3): non-temporal policy for the assignment / frame pieces
-        if (!SMX) {
-            if (resflags & 2)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(asrc + (int64_t)sc * 128),
-                                                 (__attribute__((address_space(3))) void*)(st + adst), 16, 0, 2);
-            else
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(asrc + (int64_t)sc * 128),
-                                                 (__attribute__((address_space(3))) void*)(st + adst), 16, 0, 0);
-        }
-        if (resflags & 4)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(xsrc + (int64_t)sc * DT * 128),
-                                             (__attribute__((address_space(3))) void*)(st + xdst), 16, 0, 2);
-        else
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(xsrc + (int64_t)sc * DT * 128),
-                                             (__attribute__((address_space(3))) void*)(st + xdst), 16, 0, 0);
+        if (!SMX)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(asrc + (int64_t)sc * 128),
+                                             (__attribute__((address_space(3))) void*)(st + adst), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(xsrc + (int64_t)sc * DT * 128),
+                                         (__attribute__((address_space(3))) void*)(st + xdst), 16, 0, 0);
     };
 
     f32x16 acc[2];
@@ -713,11 +701,12 @@ __global__ __launch_bounds__(256) void vlad_finalize2_kernel(float* __restrict__
 // back in place (d-major, what the backward reads) and staged, times 1/sqrt(g), in an LDS tile whose row stride K + 2 makes
 // the transposed read conflict-free (bank = 8 dq + 2 j + k over the 64 lanes of a wave); the tile leaves as float4 pieces
 // along d: 4 R contiguous bytes per cluster row.   grid (D/R, B).
-template <int R>
+constexpr int FK4_R = 32;
 __global__ __launch_bounds__(256) void vlad_finalize2_kmajor4_kernel(float* __restrict__ nrm, const float* __restrict__ colsq_part,
                                                                      int P, int D, int K, float* __restrict__ out,
                                                                      float* __restrict__ colsq, float* __restrict__ csq,
                                                                      float* __restrict__ gsq, int keep_u) {
+    constexpr int R = FK4_R;
     extern __shared__ float fs[];            // [K] inv_n, [4] partial sums, [R][K + 2] tile
     float* invn = fs;
     float* wg = fs + K;
@@ -767,14 +756,6 @@ __global__ __launch_bounds__(256) void vlad_finalize2_kmajor4_kernel(float* __re
 
 }  // namespace lpm
 
-namespace lpm {
-// LDS-DMA cache policy of the aggregation kernel's two streams (bit 0: assignment tiles, bit 1: frame tiles non-temporal)
-static int t3_nt() {
-    static_assert((T3_NT_DEFAULT & 3) == T3_NT_DEFAULT, "the default is a value of the two-bit mask");
-    static const int v = env_int("LPM_T3_NT", T3_NT_DEFAULT) & 3;
-    return v << 1;
-}
-}  // namespace lpm
 extern "C" int lpm_vlad_tiles3_supported(int D, int K) { return (D % 128 == 0 && K % 128 == 0 && D >= 128 && K >= 128) ? 1 : 0; }
 
 static int vlad_aggregate_tiles3_impl(const void* at, const void* xt, const float* centres, int B, int T, int D, int K, int flags,
@@ -813,10 +794,10 @@ static int vlad_aggregate_tiles3_impl(const void* at, const void* xt, const floa
     hipEvent_t e0, e1;
     if (D >= 1024 && timing_request(LPM_TIMING_K2, &e0, &e1))      // (the video stream's launches only: lpm_common.h)
         hipExtLaunchKernelGGL(kern, grid, dim3(512), lds, (hipStream_t)stream, e0, e1, 0, (const uint4*)at, (const uint4*)xt, centres, T,
-                              D, K, S, KT, residual | t3_nt(), nrm, asum, colsq_part, fz, T3Softmax{});
+                              D, K, S, KT, residual, nrm, asum, colsq_part, fz, T3Softmax{});
     else
         hipLaunchKernelGGL(kern, grid, dim3(512), lds, (hipStream_t)stream, (const uint4*)at, (const uint4*)xt, centres, T, D, K, S, KT,
-                           residual | t3_nt(), nrm, asum, colsq_part, fz, T3Softmax{});
+                           residual, nrm, asum, colsq_part, fz, T3Softmax{});
     return check_launch("lpm_vlad_aggregate_tiles3_fwd");
 }
 
@@ -884,10 +865,10 @@ extern "C" int lpm_vlad_aggregate_raw_kmajor_fwd(const void* at, const void* xt,
     hipEvent_t e0, e1;
     if (D >= 1024 && timing_request(LPM_TIMING_K2, &e0, &e1))      // (the video stream's launches only: lpm_common.h)
         hipExtLaunchKernelGGL(kern, grid, dim3(512), lds, (hipStream_t)stream, e0, e1, 0, (const uint4*)at, (const uint4*)xt, centres, T, D, K,
-                              S, KT, residual | t3_nt(), (float*)nullptr, asum, colsq_part, fz, T3Softmax{});
+                              S, KT, residual, (float*)nullptr, asum, colsq_part, fz, T3Softmax{});
     else
         hipLaunchKernelGGL(kern, grid, dim3(512), lds, (hipStream_t)stream, (const uint4*)at, (const uint4*)xt, centres, T, D, K, S, KT,
-                           residual | t3_nt(), (float*)nullptr, asum, colsq_part, fz, T3Softmax{});
+                           residual, (float*)nullptr, asum, colsq_part, fz, T3Softmax{});
     return check_launch("lpm_vlad_aggregate_raw_kmajor_fwd");
 }
 
@@ -935,9 +916,9 @@ extern "C" int lpm_vlad_aggregate_raw_kmajor_smx_fwd(const float* logits, const 
     dim3 grid(B * (K / 128) * (D / 128));
     if (D >= 1024 && timing_request(LPM_TIMING_K2, &e0, &e1))      // (the video stream's launches only: lpm_common.h)
         hipExtLaunchKernelGGL(kern, grid, dim3(512), lds, s, e0, e1, 0, (const uint4*)nullptr, (const uint4*)xt, centres, T, D, K, S, KT,
-                              residual | t3_nt(), (float*)nullptr, asum, colsq_part, fz, sm);
+                              residual, (float*)nullptr, asum, colsq_part, fz, sm);
     else
-        hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, (const uint4*)nullptr, (const uint4*)xt, centres, T, D, K, S, KT, residual | t3_nt(),
+        hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, (const uint4*)nullptr, (const uint4*)xt, centres, T, D, K, S, KT, residual,
                            (float*)nullptr, asum, colsq_part, fz, sm);
     return check_launch("lpm_vlad_aggregate_raw_kmajor_smx_fwd");
 }
@@ -1004,9 +985,9 @@ extern "C" int lpm_vlad_aggregate_fused_fwd(const void* at, const void* xt, cons
     hipEvent_t e0, e1;
     if (D >= 1024 && timing_request(LPM_TIMING_K2, &e0, &e1))      // (the video stream's launches only: lpm_common.h)
         hipExtLaunchKernelGGL(kern, grid, dim3(512), lds, s, e0, e1, 0, (const uint4*)at, (const uint4*)xt, centres, T, D, K, S, KT,
-                              residual | t3_nt(), nrm, asum, part, fz, T3Softmax{});
+                              residual, nrm, asum, part, fz, T3Softmax{});
     else
-        hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, (const uint4*)at, (const uint4*)xt, centres, T, D, K, S, KT, residual | t3_nt(), nrm, asum,
+        hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, (const uint4*)at, (const uint4*)xt, centres, T, D, K, S, KT, residual, nrm, asum,
                            part, fz, T3Softmax{});
     // follow-up for tiles whose workgroup gave up waiting for its clip (fail flag set; none in practice)
     hipLaunchKernelGGL(vlad_fused_fixup_kernel, grid, dim3(256), 0, s, nrm, part, fail, D, K, fz);
@@ -1044,9 +1025,8 @@ static int vlad_finalize2_impl(float* nrm, const float* colsq_part, int P, int B
                 "lpm_vlad_finalize2_fwd: bf16 storage is implemented for the reference's d-major layout only");
     LPM_REQUIRE(!nrm_bf16 || keep_u, LPM_ERR_BADARG, "lpm_vlad_finalize2_fwd: LPM_VLAD_NRM_BF16 goes with LPM_VLAD_NRM_RAW");
     const size_t lds = (size_t)(K + 32 * 33 + 4) * sizeof(float);
-    static const int wide = env_int("LPM_FINALIZE_KMAJOR4", 32);   // 0: scalar form (A/B)
-    if ((flags & LPM_VLAD_OUT_KMAJOR) && wide && K <= 512 && (((uintptr_t)nrm | (uintptr_t)out) & 15) == 0) {
-        const int R = (wide == 64 && D % 64 == 0) ? 64 : 32;
+    if ((flags & LPM_VLAD_OUT_KMAJOR) && K <= 512 && (((uintptr_t)nrm | (uintptr_t)out) & 15) == 0) {
+        constexpr int R = FK4_R;
         const size_t lds4 = (size_t)(K + 4 + R * (K + 2)) * sizeof(float);
         dim3 grid4(D / R, B);
         auto launch = [&](auto kern) -> int {
@@ -1063,7 +1043,7 @@ static int vlad_finalize2_impl(float* nrm, const float* colsq_part, int P, int B
                 hipLaunchKernelGGL(kern, grid4, dim3(256), lds4, (hipStream_t)stream, nrm, colsq_part, P, D, K, out, colsq, csq, gsq, keep_u);
             return check_launch("lpm_vlad_finalize2_fwd");
         };
-        return R == 64 ? launch(vlad_finalize2_kmajor4_kernel<64>) : launch(vlad_finalize2_kmajor4_kernel<32>);
+        return launch(vlad_finalize2_kmajor4_kernel);
     }
     if (flags & LPM_VLAD_OUT_KMAJOR)
         hipLaunchKernelGGL(vlad_finalize2_kernel<true>, grid, dim3(256), lds, (hipStream_t)stream, nrm, colsq_part, P, D, K, out, colsq,

@@ -250,7 +250,7 @@ class NetVladV1(models.BaseModel):
         if shortcut:
             with torch.no_grad():
                 rgb, audio = reshaped_input[:, 0:1024], reshaped_input[:, 1024:]
-            if ops.SPLIT_VECTOR and g_in.is_cuda and g_in.dim() == 1 and g_in.shape[0] > 1024:
+            if g_in.is_cuda and g_in.dim() == 1 and g_in.shape[0] > 1024:
                 (gv, ga), (bv, ba) = ops.split_vector(g_in, 1024), ops.split_vector(b_in, 1024)
                 aff_v, aff_a = (gv, bv), (ga, ba)
             else:
@@ -859,7 +859,7 @@ class NetVladV2(models.BaseModel):
                                                                   is_training, "netvlad_audio_scope")
         if split is not None:
             rgb, audio = split
-        elif has_audio and reshaped_input.is_cuda and ops.V2_SPLIT_COLUMNS:
+        elif has_audio and reshaped_input.is_cuda:
             # one contiguous copy per stream (the encoder and the aggregation both want whole rows); their gradients come back as ONE
             # concatenation instead of two zero-filled [M, 1152] buffers, two slice copies and an add
             # (the copies do not carry the views' shared-gradient slot -- ops._SplitColumns.backward then concatenates the two

@@ -39,7 +39,7 @@ def batch_norm(x: torch.Tensor, is_training: bool, scope: str, pre_bias: torch.T
     if pre_bias is not None:
         if is_training and x.dim() == 3 and ops.batch_norm_rows_act_ok(x, pre_bias):
             return ops.batch_norm_rows_act(x, pre_bias, pre_relu, gamma, beta, mm, mv, biased_moving_variance=True)
-        if ops.BIAS_ACT_FUSED and x.is_contiguous() and ops.bias_act_ok(x, pre_bias):
+        if x.is_contiguous() and ops.bias_act_ok(x, pre_bias):
             x = ops.bias_act(x * 1.0 if x._base is not None else x, pre_bias, pre_relu)      # (a view of the GEMM's output: not in place on it)
         else:
             x = x + pre_bias
@@ -138,7 +138,7 @@ def dense(x: torch.Tensor, units: int, use_bias: bool, name: str, activation=Non
     y = ops.dense_x3(x.reshape(rows, x.shape[-1]), kernel) if split else x.matmul(kernel)
     if defer_bias:
         return y.reshape(*x.shape[:-1], units), bias
-    if use_bias and activation in (None, torch.relu) and ops.BIAS_ACT_FUSED and ops.bias_act_ok(y, bias):
+    if use_bias and activation in (None, torch.relu) and ops.bias_act_ok(y, bias):
         # one in-place pass over the GEMM's fresh output (one pass in the backward as well) instead of add + relu (threshold + reduce)
         return ops.bias_act(y, bias, activation is torch.relu).reshape(*x.shape[:-1], units)
     y = y.reshape(*x.shape[:-1], units)

@@ -40,10 +40,6 @@ PROJ_STREAM = os.environ.get("LPM_PROJ_STREAM", "1") != "0"
 # vmcnt(0): forward 107 + 22 us vs the library's 202 us at cfg-2, 480 vs 1060 us at cfg-5; dx 135 vs 212 us at cfg-2's N = 512, 455 vs 1000 us
 # at cfg-5's N = 1024.  Rounds 1-3, every stage waiting a full memory round trip: forward 145 / 600, dx 267 -- the library stayed -- / 634)
 PROJ_DX_STREAM_MIN_N = int(os.environ.get("LPM_PROJ_DX_STREAM_MIN_N", "512"))
-# ... and inside the channel-last batch norm that follows it (ops.batch_norm_rows_act: FeedForwardNetworkMod); "0": ops.bias_act + plain BN
-BN_ACT_FUSED = os.environ.get("LPM_BN_ACT_FUSED", "1") != "0"
-# tf.layers.dense's bias add + ReLU as one in-place pass (ops.bias_act) where the output does not feed the next GEMM's split directly; "0": A/B
-BIAS_ACT_FUSED = os.environ.get("LPM_BIAS_ACT_FUSED", "1") != "0"
 # K5 of hidden1_weights: the gradient's norm from quadratic forms (lpm_factored_clip_adam_q) instead of a tile-GEMM pass; "0": A/B
 FACTORED_NORM_QUADFORM = os.environ.get("LPM_FACTORED_NORM_QUADFORM", "1") != "0"
 # a5 with the softmax inside the aggregation kernel (lpm_vlad_aggregate_raw_kmajor_smx_fwd; the lazily normalised k-major descriptor
@@ -77,9 +73,6 @@ FFN_TILES = os.environ.get("LPM_FFN_TILES", "1") != "0"
 # Run-time switch of the direct weight-gradient writes (ops._dw_x3 -> the trainer's arena slots, FLAGS.direct_weight_gradients): False
 # returns every gradient through autograd (A/B inside one process: tools/ab_flags.py ops.DIRECT_WGRAD).
 DIRECT_WGRAD = True
-# FeedForwardNetworkMod (NetVladV2's frame encoders) as one node whose batch norm writes the second dense layer's operand image and
-# whose backward writes the first layer's gradient image (ops.ffn_mod_x3); 0: dense / batch_norm / dense as separate nodes (A/B).
-FFN_MOD_FUSED = os.environ.get("LPM_FFN_MOD_FUSED", "1") != "0"
 # Matrix-core arithmetic of the soft-assignment GEMM K1: "bf16x3" (split-bf16 tiles on the bf16 pipe, default where
 # D %% 16 == 0 and K <= 512) or "f32" (exact fp32 MFMA).
 ASSIGN_PRECISION = os.environ.get("LPM_ASSIGN_PRECISION", "bf16x3")
@@ -95,21 +88,16 @@ MHA_PRECISION = os.environ.get("LPM_MHA_PRECISION", "bf16x3")
 # attention_bn over columns whose variance is at rounding level -- still 1e-2 with a split-bf16 forward, debug_v2_grad.py).  At the
 # benchmark's sizes (300 keys, cfg-3) a split-bf16 forward changes nothing measurable: worst whole-model gradient against the fp64 oracle
 # 4.8e-5 (bf16x3 forward) vs 5.1e-5 (fp32 forward) at 80 clips (tests/test_gpu_benched_shapes.py), the whole GPU tier green either way,
-# and the step is 0.2 ms shorter.  "auto" for the forward pass = exact fp32 below MHA_BN_X3_MIN_KEYS keys, split-bf16 from there.
+# and the step is 0.2 ms shorter.  "auto" for the forward pass = exact fp32 below 128 keys, split-bf16 from there.
 MHA_BN_PRECISION = os.environ.get("LPM_MHA_BN_PRECISION", "mixed")
 # "mixed": arithmetic per pass (forward, backward statistics pass, backward main pass)
 MHA_BN_MIXED = os.environ.get("LPM_MHA_BN_MIXED", "auto,bf16x3,bf16x3")
-MHA_BN_X3_MIN_KEYS = int(os.environ.get("LPM_MHA_BN_X3_MIN_KEYS", "128"))
 
 # Split-bf16 tile copies of the most recent frame_sample_bn output (produced by the same kernel that writes the fp32
 # frames): {"base": weakref to y, "F": F, "Dv": .., "video": tensor, "audio": tensor|None}.  ops.netvlad / vlad_aggregate
 # look a column-slice view of y up here instead of re-reading it through lpm_split_frames.
 _XT_CACHE = {}
-MHA_BN_MOMENTS = os.environ.get("LPM_MHA_BN_MOMENTS", "1") != "0"      # ... statistics by lpm_mha_logit_stats_moments, moments kept for the backward
-MHA_BN_ONEPASS = os.environ.get("LPM_MHA_BN_ONEPASS", "1") != "0"      # logits_bn backward without the separate statistics pass (A/B switch)
 LN_IMAGE = os.environ.get("LPM_LN_IMAGE", "1") != "0"              # the attention block's layer norm also writes the operand image of the feed-forward block behind it (A/B switch)
-SPLIT_VECTOR = True          # NetVladV1: input_bn's gamma / beta halves with ONE concatenated gradient each (A/B switch)
-V2_SPLIT_COLUMNS = True      # NetVladV2: the two streams' inputs as contiguous copies with ONE concatenated gradient (A/B switch)
 DEBUG_TAP = None      # tools/determinism_check.py: a dict that the video stream's pooling backward fills with copies of its intermediates
 
 # bench.py sets this to a list to collect (name, dims, start_event, end_event) around hot-kernel launches
@@ -202,11 +190,9 @@ class _BNSmall(torch.autograd.Function):
         return dx, dgamma, dbeta, None, None, None, dmul
 
 
-BN_SMALL = True              # the clip-level batch norms (hidden1_bn + relu6, gating_bn + gate) as one launch each way (A/B switch)
-
-
 def bn_small_ok(x, mul=None):
-    return (BN_SMALL and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and 1 < x.shape[0] <= 256
+    """the clip-level batch norms (hidden1_bn + relu6, gating_bn + gate) as one launch each way"""
+    return (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and 1 < x.shape[0] <= 256
             and (mul is None or (mul.shape == x.shape and mul.dtype == torch.float32)))
 
 
@@ -954,13 +940,10 @@ class _FrameSampleBNSplit(torch.autograd.Function):
         return None, None, dgamma, dbeta, None, None, None, None, None
 
 
-FRAME_SPLIT = os.environ.get("LPM_FRAME_SPLIT", "1") != "0"      # "0": NetVladV2 slices one [B S, F] matrix (A/B)
-
-
 def frame_sample_bn_split_ok(raw, Dv, is_training=True, quantised_training=False):
     """uint8 frames (the reader's quantised batch) qualify in eval mode, and in training mode with ``quantised_training``."""
     dtype_ok = raw.dtype == torch.float32 or (raw.dtype == torch.uint8 and (not is_training or quantised_training))
-    return bool(FRAME_SPLIT and raw.is_cuda and raw.dim() == 3 and dtype_ok and VLAD_PRECISION == "bf16x3"
+    return bool(raw.is_cuda and raw.dim() == 3 and dtype_ok and VLAD_PRECISION == "bf16x3"
                 and 0 < Dv < raw.shape[2] and Dv % 32 == 0 and (raw.shape[2] - Dv) % 32 == 0)
 
 
@@ -1443,7 +1426,7 @@ class _NetVLAD(torch.autograd.Function):
             # NOT from the step's weight pack: K1 streams its 1 MB of weight tiles once per workgroup, a fresh 16 KB per step that all
             # workgroups of an XCD want at the same moment -- its loop is bound by the latency of that first touch.  Written right here
             # the tiles are still in the memory-side cache when K1 starts (42.9 us); written at the top of the step, 700 MB of frame
-            # preparation earlier, they come from HBM (54.8 us; measured in one process, LPM_WEIGHT_PACK A/B, round 4).  (Reading them into every XCD's L2 with
+            # preparation earlier, they come from HBM (54.8 us; measured in one process, round 4).  (Reading them into every XCD's L2 with
             # a small launch in front of K1 on top of that: no effect, 43.5-45.2 vs 43.9-44.6 us.)
             wt = _weight_tiles(W, D, K, False, x, pack=False)
             _k1_selfcheck(lib, 2, x.device)
@@ -2136,7 +2119,7 @@ class WeightPack:
     def begin_step(self):
         self.ready = {}
         self.armed = True
-        if not self.plan or not WEIGHT_PACK:
+        if not self.plan:
             return
         lib = _capi.load()
         jobs, keep = [], []
@@ -2208,11 +2191,7 @@ class WeightPack:
         return {f: got[f] for f in forms}
 
 
-# the split-K partial sums of the encoders' weight-gradient GEMMs added into their arena slots by lpm_sum_splits; "0": torch.sum per slot (A/B)
-SUM_SPLITS = os.environ.get("LPM_SUM_SPLITS", "1") != "0"
 _ACTIVE_PACK = None      # the WeightPack of the trainer whose step is running (train.Trainer.step), else None
-# "0": every consumer derives its own operand forms, one launch each (A/B)
-WEIGHT_PACK = os.environ.get("LPM_WEIGHT_PACK", "1") != "0"
 
 
 _LIBRARY_SELECTION = None       # None: not attempted; True / False: recorded solutions active / not (mismatching validators, switched off, ...)
@@ -2451,11 +2430,10 @@ def _dw_x3(x3, dy3, K, N, outs=None, sa=None, sg=None, terms=None):
     return res
 
 
-# "1": FeedForwardNetwork's tile GEMMs read their data operand straight from its operand image (per-lane LDS-DMA gather of 32-byte row
-# pieces) instead of from a row-tile copy made by a pass of its own (lpm_split_rows_tiles / lpm_image_row_tiles: 96 + 38 us per cfg-2
-# step).  Built and measured in round 5, one box, alternating: 6.57 / 6.50 ms with the gather against 6.46 ms with the copies -- the
-# gathered loads cost the two GEMMs what the passes cost; off by default, kept for the A/B
-TILE_GEMM_FROM_IMAGE = os.environ.get("LPM_TILE_GEMM_FROM_IMAGE", "0") == "1"
+# FeedForwardNetwork's tile GEMMs read their data operand from a row-tile copy made by a pass of its own (lpm_split_rows_tiles /
+# lpm_image_row_tiles: 96 + 38 us per cfg-2 step), not straight from its operand image (per-lane LDS-DMA gather of 32-byte row pieces).
+# Measured in round 5, one box, alternating: 6.57 / 6.50 ms with the gather against 6.46 ms with the copies -- the gathered loads cost
+# the two GEMMs what the passes cost.
 # terms of the fp16 weight-gradient product: 2 = xh^T [dyh | dyl] (the gradient exact, the activation rounded once: 1.4e-4 per GEMM);
 # 1 = xh^T dyh (both rounded once: 2e-4 per GEMM -- an error that stays in THIS weight's gradient and is not carried further down the
 # backward, unlike an input gradient's).  LPM_DW_TERMS, A/B; measured in tests/test_gpu_fp16x2.py
@@ -2464,9 +2442,6 @@ DW_TERMS = int(os.environ.get("LPM_DW_TERMS", "1"))
 # north-star's 1e-3 at the untouched initialisation (1.0e-3 with two terms everywhere in round 4, 1.15e-3 with one).
 # Measured in round 6 (tests/test_gpu_models.py::test_untouched_reference_initialisation[cfg2] prints it per setting)
 DW_TERMS_FFN1 = int(os.environ.get("LPM_DW_TERMS_FFN1", str(DW_TERMS)))
-
-
-DW_SLICES = int(os.environ.get("LPM_DW_SLICES", "0"))        # 0: the policy below; n: that many slices of the token reduction (A/B)
 
 
 def _dw_x2(x2, dy2, K, N, outs, alpha, terms=None):
@@ -2479,7 +2454,7 @@ def _dw_x2(x2, dy2, K, N, outs, alpha, terms=None):
     terms = DW_TERMS if terms is None else terms
     lib = _capi.load()
     M = x2.shape[0]
-    S = DW_SLICES if DW_SLICES else (8 if K * N <= (1 << 20) else 4)     # (in-step at cfg-2, 2 -> 4 slices: 171 / 174 / 155 -> 146 / 151 / 116 us)
+    S = 8 if K * N <= (1 << 20) else 4     # (in-step at cfg-2, 2 -> 4 slices: 171 / 174 / 155 -> 146 / 151 / 116 us)
     while S > 1 and (M % S or M // S < 512):
         S //= 2
     xh = x2.view(S, M // S, x2.shape[1])[:, :, :K]
@@ -2529,7 +2504,7 @@ def _dw_x3_impl(x3, dy3, K, N, outs):
     if outs is None:
         return full if full is not None else part.sum(0)
     slots = [_grad_slot(W) for W, _, _ in outs]
-    if (SUM_SPLITS and part is not None and all(sl is not None and sl.is_contiguous() for sl in slots) and len(outs) <= 3
+    if (part is not None and all(sl is not None and sl.is_contiguous() for sl in slots) and len(outs) <= 3
             and all(nc == N // len(outs) and c0 == i * (N // len(outs)) for i, (_, c0, nc) in enumerate(outs)) and (N // len(outs)) % 4 == 0):
         # every destination is a free arena slot and the column blocks tile the product evenly: ONE launch adds the split-K partial sums
         # into all of them (lpm_sum_splits) instead of one strided torch reduction per destination
@@ -2586,16 +2561,12 @@ class _FFNX3(torch.autograd.Function):
             # the first dense layer on the hand-written 256-row tile GEMM with the bias + ReLU + operand split in its epilogue: the
             # [M, 4F] pre-activation never exists in fp32 (335 MB written + read at cfg-2), no separate split pass
             st = stream_ptr()
-            akind = _capi.LPM_OPERAND_FP16X3 if f16 else _capi.LPM_OPERAND_BF16X3
-            if TILE_GEMM_FROM_IMAGE:     # the kernel gathers its A fragments from the image y3 row by row: no row-tile copy of y
-                yr, ykind = y3, akind
-            else:
-                yr, ykind = _tile_buffer(lib._lpm_row_tiles_bytes(1, M, F), y2d), -1
-                lib.check(lib._lpm_split_rows_tiles_fmt(ptr(y2d), y2d.stride(0), 1, M, F, ptr(yr), s1.fmt if s1 is not None else None, st),
-                          "lpm_split_rows_tiles")
+            yr =_tile_buffer(lib._lpm_row_tiles_bytes(1, M, F), y2d)
+            lib.check(lib._lpm_split_rows_tiles_fmt(ptr(y2d), y2d.stride(0), 1, M, F, ptr(yr), s1.fmt if s1 is not None else None, st),
+                      "lpm_split_rows_tiles")
             w1t = _weight_tiles(W1, F, H, False, y2d, f16=f16)
             f3 = torch.empty((M, 3 * H), dtype=dt, device=y2d.device)
-            lib.check(lib._lpm_dense_tiles_act_image_fwd_fmt(ptr(yr), ykind, ptr(w1t), ptr(b1.contiguous()), M, F, H, a1, ptr(f3),
+            lib.check(lib._lpm_dense_tiles_act_image_fwd_fmt(ptr(yr), -1, ptr(w1t), ptr(b1.contiguous()), M, F, H, a1, ptr(f3),
                                                              s2.fmt if s2 is not None else None, st), "lpm_dense_tiles_act_image_fwd")
             w23n, _ = _split_weight(W2, need_t=False, f16=f16)
             ctx.save_for_backward(y3, f3, w13k, W2)
@@ -2633,15 +2604,12 @@ class _FFNX3(torch.autograd.Function):
             # split of the result in its epilogue: df never exists in fp32
             st = stream_ptr()
             W2 = w23k                                                     # (saved in its place: the fp32 weight [H, N])
-            if TILE_GEMM_FROM_IMAGE:
-                dor, dkind = do3, gkind
-            else:
-                dor, dkind = _tile_buffer(lib._lpm_row_tiles_bytes(1, M, N), f3), -1
-                lib.check(lib._lpm_image_row_tiles_fmt(ptr(do3), M, N, 1, ptr(dor), gkind, st), "lpm_image_row_tiles")
+            dor = _tile_buffer(lib._lpm_row_tiles_bytes(1, M, N), f3)
+            lib.check(lib._lpm_image_row_tiles_fmt(ptr(do3), M, N, 1, ptr(dor), gkind, st), "lpm_image_row_tiles")
             w2tt = _weight_tiles(W2, N, H, True, f3, f16=f16)
             wsb = lib._lpm_dense_tiles_relu_bwd_workspace_bytes(M, H)
             ws = torch.empty(wsb // 4, dtype=torch.float32, device=f3.device)
-            lib.check(lib._lpm_dense_tiles_relu_bwd_image_fmt(ptr(dor), dkind, ptr(w2tt), ptr(f3), akind, M, N, H, a2, ptr(dp3), ptr(db1), ptr(ws), wsb,
+            lib.check(lib._lpm_dense_tiles_relu_bwd_image_fmt(ptr(dor), -1, ptr(w2tt), ptr(f3), akind, M, N, H, a2, ptr(dp3), ptr(db1), ptr(ws), wsb,
                                                               g1.fmt if g1 is not None else None, st), "lpm_dense_tiles_relu_bwd_image")
         else:
             df = _mm3(do3, w23k)                                          # [M, H]  (un-scaled: alpha rides in the split pass below)
@@ -2835,7 +2803,7 @@ class _ProjectionParts(torch.autograd.Function):
         wsb = lib._lpm_proj_fwd_workspace_bytes(M, Kd, N)
         ws = torch.empty(wsb // 4, dtype=torch.float32, device=x1.device)
         # bf16 storage with a compute copy of the weight attached (ops.ComputeCopy): both passes read the copy
-        cc = getattr(W, "_lpm_w16", None) if PROJ_W16 else None
+        cc = getattr(W, "_lpm_w16", None)
         ctx.w16 = cc.tensor(W) if (cc is not None and x1.dtype == torch.bfloat16) else None
         with _timed("proj_fwd", (M, Kd, N)):
             if ctx.w16 is not None:
@@ -3146,13 +3114,9 @@ class _BNDenseX3(torch.autograd.Function):
         return dx, dgamma, dbeta, None, None, dW
 
 
-# "0": layers.batch_norm + layers.dense as two nodes with an operand-split pass in between (A/B)
-BN_DENSE_FUSED = os.environ.get("LPM_BN_DENSE_FUSED", "1") != "0"
-
-
 def bn_dense_x3_ok(x, units):
     rows = x.numel() // x.shape[-1]
-    return (BN_DENSE_FUSED and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[-1] % 8 == 0 and units % 8 == 0 and rows >= 1024)
+    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[-1] % 8 == 0 and units % 8 == 0 and rows >= 1024)
 
 
 def bn_dense_x3(x, gamma, beta, moving_mean, moving_var, W, bias=None):
@@ -3161,13 +3125,13 @@ def bn_dense_x3(x, gamma, beta, moving_mean, moving_var, W, bias=None):
     rows = x.numel() // x.shape[-1]
     out = _BNDenseX3.apply(x.reshape(rows, x.shape[-1]), gamma, beta, moving_mean, moving_var, W)
     if bias is not None:
-        out = bias_act(out, bias, False) if (BIAS_ACT_FUSED and bias_act_ok(out, bias)) else out + bias
+        out = bias_act(out, bias, False) if bias_act_ok(out, bias) else out + bias
     return out.reshape(*x.shape[:-1], W.shape[1])
 
 
 def ffn_mod_x3_ok(x, filter_size, final_size):
     rows = x.numel() // x.shape[-1]
-    return (FFN_MOD_FUSED and BN_ACT_FUSED and x.is_cuda and x.dtype == torch.float32 and x.shape[-1] % 8 == 0 and filter_size % 8 == 0
+    return (x.is_cuda and x.dtype == torch.float32 and x.shape[-1] % 8 == 0 and filter_size % 8 == 0
             and final_size % 8 == 0 and rows >= 1024 and bool(_capi.load()._lpm_bn_act_bwd_supported(rows, filter_size)))
 
 
@@ -3196,7 +3160,7 @@ def _take_image(y, rows):
 
 def batch_norm_rows_act_ok(x, bias):
     C = x.shape[-1]
-    return (BN_ACT_FUSED and x.is_cuda and x.dtype == torch.float32 and bias is not None and C % 4 == 0
+    return (x.is_cuda and x.dtype == torch.float32 and bias is not None and C % 4 == 0
             and bool(_capi.load()._lpm_bn_act_bwd_supported(x.numel() // C, C)))
 
 
@@ -3334,10 +3298,6 @@ def residual_layer_norm(a, r, gamma, beta, bias=None, relu=False, image=False, m
     return _ResidualLayerNorm.apply(a, r, gamma, beta, bias, bool(relu), None, None, bool(image) and LN_IMAGE, mask, float(mask_scale), site)
 
 
-# NetVladV2: tf.layers.dropout between output_transform and the layer norm rides in the layer norm's passes; "0": separate passes (A/B)
-LN_DROPOUT_FUSED = os.environ.get("LPM_LN_DROPOUT_FUSED", "1") != "0"
-
-
 # ----------------------------------------------------------------------------------------------
 # K4: attention core
 # ----------------------------------------------------------------------------------------------
@@ -3351,14 +3311,14 @@ def _mha_dims(q, num_heads):
 
 
 def _bn_pass_precision(which, L=None):
-    """MHA_BN_PRECISION = "mixed": per-pass arithmetic of the logits_bn attention, as 'fwd,stats,main' in MHA_BN_MIXED ("auto": by the
-    number of keys L, see MHA_BN_X3_MIN_KEYS)."""
+    """MHA_BN_PRECISION = "mixed": per-pass arithmetic of the logits_bn attention, as 'fwd,stats,main' in MHA_BN_MIXED ("auto": split-bf16
+    from 128 keys L on, exact fp32 below)."""
     if MHA_BN_PRECISION != "mixed":
         return MHA_BN_PRECISION
     fwd, stats, main = MHA_BN_MIXED.split(",")
     prec = {"fwd": fwd, "stats": stats, "main": main}[which]
     if prec == "auto":
-        prec = "bf16x3" if (L is not None and L >= MHA_BN_X3_MIN_KEYS) else "f32"
+        prec = "bf16x3" if (L is not None and L >= 128) else "f32"
     return prec
 
 
@@ -3682,7 +3642,7 @@ class _MHACoreBN(torch.autograd.Function):
         if is_training:
             partial = _empty((B * h, 2, L), q)
             # (lpm_mha_logit_stats_moments reads q and k as float4: 16-byte aligned views only; anything else takes the general kernel)
-            if MHA_BN_MOMENTS and d in (8, 16) and q.data_ptr() % 16 == 0 and k.data_ptr() % 16 == 0 and (q.stride(1) * 4) % 16 == 0:
+            if d in (8, 16) and q.data_ptr() % 16 == 0 and k.data_ptr() % 16 == 0 and (q.stride(1) * 4) % 16 == 0:
                 # the statistics from the d x d moments of q, which the backward's repair of dk needs again (kept: 272 floats per head)
                 moments = _empty((B * h, d * d + d), q)
                 lib.check(lib._lpm_mha_logit_stats_moments(ptr(q), ptr(k), q.stride(1), B, L, h, d, ptr(partial), ptr(moments), stream_ptr()),
@@ -3715,7 +3675,7 @@ class _MHACoreBN(torch.autograd.Function):
         q, k, v, o, lse, kscale, kshift, mean, var, gamma = ctx.saved_tensors
         do = do.contiguous()
         st = stream_ptr()
-        onepass = (MHA_BN_ONEPASS and is_training and d in (8, 16) and _bn_pass_precision("stats", L) == "bf16x3"
+        onepass = (is_training and d in (8, 16) and _bn_pass_precision("stats", L) == "bf16x3"
                    and _bn_pass_precision("main", L) == "bf16x3")
         if onepass and image:
             N = h * d
@@ -3812,9 +3772,6 @@ class _QKVAttnBNX3(torch.autograd.Function):
         return (dx.view(B, L, F) if dx is not None else None), dWq, dWk, dWv, dgamma, dbeta, None, None, None
 
 
-DROPOUT_MASK_KERNEL = os.environ.get("LPM_DROPOUT_MASK_KERNEL", "1") != "0"       # "0": torch's bernoulli_ draws the keep masks (A/B)
-
-
 def dropout_keep_mask(shape, keep_prob, device):
     """uint8 keep mask of tf.layers.dropout (1 = kept, probability keep_prob) for the layer norm that applies it (transformer_utils.py:450).
     On the GPU one store-stream launch (lpm_dropout_keep_mask) seeded from torch's CPU generator -- torch.manual_seed makes runs repeatable;
@@ -3822,7 +3779,7 @@ def dropout_keep_mask(shape, keep_prob, device):
     n = 1
     for d in shape:
         n *= int(d)
-    if DROPOUT_MASK_KERNEL and device.type == "cuda" and n % 16 == 0 and 0.0 < keep_prob <= 1.0:
+    if device.type == "cuda" and n % 16 == 0 and 0.0 < keep_prob <= 1.0:
         seed = int(torch.empty((), dtype=torch.int64).random_().item()) & ((1 << 63) - 1)
         mask = torch.empty(tuple(shape), dtype=torch.uint8, device=device)
         lib = _capi.load()
@@ -3833,7 +3790,6 @@ def dropout_keep_mask(shape, keep_prob, device):
 
 # LPM_ATTN_BLOCK_BN=0: MultiHeadAttentionBN + the encoder's first layer norm as separate autograd nodes (A/B)
 ATTN_BLOCK_BN = os.environ.get("LPM_ATTN_BLOCK_BN", "1") != "0"
-ATTN_BLOCK_BN_LN_IMAGE = os.environ.get("LPM_ATTN_BLOCK_LN_IMAGE", "1") != "0"      # "0": the masked gradient in fp32 + an operand-split pass (A/B)
 
 
 class _AttnBlockBNX3(torch.autograd.Function):
@@ -3872,13 +3828,9 @@ class _AttnBlockBNX3(torch.autograd.Function):
         extra = ctx.join.take() if ctx.join is not None else None        # the aggregation's gradient of the same frames (ops.GradJoin)
         if extra is not None:
             extra = extra.reshape(B, L, F).contiguous()
-        if ATTN_BLOCK_BN_LN_IMAGE:
-            # the gradient of att through the dropout mask leaves the layer norm as the operand image of the output transform's GEMMs
-            img, dz, dgamma, dbeta, dbo = _ResidualLayerNorm.backward(cl, dy, dr_extra=extra, da_image=True, site=_site("g", co.wrefs[0]))[:5]
-            do, dg2, db2, _, _, dWo = _BNDenseX3.backward(co, None, do3=img)
-        else:
-            first, dz, dgamma, dbeta, dbo = _ResidualLayerNorm.backward(cl, dy, dr_extra=extra)[:5]
-            do, dg2, db2, _, _, dWo = _BNDenseX3.backward(co, first.view(B * L, -1))
+        # the gradient of att through the dropout mask leaves the layer norm as the operand image of the output transform's GEMMs
+        img, dz, dgamma, dbeta, dbo = _ResidualLayerNorm.backward(cl, dy, dr_extra=extra, da_image=True, site=_site("g", co.wrefs[0]))[:5]
+        do, dg2, db2, _, _, dWo = _BNDenseX3.backward(co, None, do3=img)
         got = _MHACoreBN.backward(cm, do.view(B, L, N), image=True, site=_site("g", ctx.wq))
         acc = dz.view(B * L, F) if cq.needs_input_grad[0] else None
         if got[1] is None:
@@ -3900,7 +3852,7 @@ def attention_block_bn_x3(x, Wq, Wk, Wv, logits_bn, attention_bn, Wo, bo, gamma,
 
 def qkv_attention_bn_ok(x, hidden, num_heads):
     """Whether MultiHeadAttentionBN's self-attention front runs as ops.qkv_attention_bn_x3 for this [B, L, F] input (training only)."""
-    return bool(MHA_BN_GRAD_IMAGE and MHA_BN_ONEPASS and x.is_cuda and x.dim() == 3 and hidden % num_heads == 0 and hidden // num_heads in (8, 16)
+    return bool(MHA_BN_GRAD_IMAGE and x.is_cuda and x.dim() == 3 and hidden % num_heads == 0 and hidden // num_heads in (8, 16)
                 and x.shape[1] <= 512 and _bn_pass_precision("stats", x.shape[1]) == "bf16x3" and _bn_pass_precision("main", x.shape[1]) == "bf16x3")
 
 
@@ -4051,9 +4003,6 @@ class ComputeCopy:
         return None if (self.stale or self.version != self._versions(W)) else self.buf
 
 
-PROJ_W16 = os.environ.get("LPM_PROJ_W16", "1") != "0"       # "0": the projection ignores an attached compute copy (A/B)
-
-
 class FactoredGradient:
     """The gradient of the hidden projection's weight as the product it is: dW = X^T DY with X [R, N1] the projection's input and
     DY [R, N2] the gradient of its output (R = clips).  ``put`` (called by _Projection.backward while ``armed``) keeps the two
@@ -4143,10 +4092,10 @@ class FactoredGradient:
             quad = (FACTORED_NORM_QUADFORM and self.x is not None and self.x.shape[0] == self.R and self.R <= 128 and self.x.stride(1) == 1
                     and self.x.dtype == torch.float32)
             tiles_only = (FACTORED_NORM_QUADFORM and self.x is None and self.x_in_tiles and self.dy is not None and self.dy.shape[0] == self.R
-                          and self.R <= 128 and os.environ.get("LPM_FQ_TILES", "1") != "0")
+                          and self.R <= 128)
             if tiles_only:
                 # X lives in its tiles only (put_tiles): the quadratic forms read it from there (fa_quadform_kernel<true>; the fp32
-                # pointer is the A/B form's operand and is not dereferenced)
+                # pointer is not dereferenced)
                 G = torch.mm(self.dy, self.dy.t())
                 gdt = _tile_buffer(lib._lpm_row_tiles_bytes(1, self.R, self.R), G)
                 lib.check(lib._lpm_split_rows_tiles(ptr(G), self.R, 1, self.R, self.R, ptr(gdt), stream_ptr()), "lpm_split_rows_tiles")
@@ -4179,7 +4128,7 @@ def _factored_clip_adam_copy(self, lib, param, m, v, param_bf16, clip_norm, lr, 
         quad = (FACTORED_NORM_QUADFORM and self.x is not None and self.x.shape[0] == self.R and self.R <= 128 and self.x.stride(1) == 1
                 and self.x.dtype == torch.float32)
         tiles_only = (FACTORED_NORM_QUADFORM and self.x is None and self.x_in_tiles and self.dy is not None and self.dy.shape[0] == self.R
-                      and self.R <= 128 and os.environ.get("LPM_FQ_TILES", "1") != "0")
+                      and self.R <= 128)
         if tiles_only or quad:
             G = torch.mm(self.dy, self.dy.t())
             gdt = _tile_buffer(lib._lpm_row_tiles_bytes(1, self.R, self.R), G)

