@@ -1268,6 +1268,49 @@ int lpm_triangulation_cnn_attention_bwd(const float* x, const float* anchors, co
                                         float* dx, float* danchors, void* workspace, size_t workspace_bytes, lpm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Rectified attention moments of the twice-normalised triangulation embedding (video_pooling_modules.py:634-888
+ * TriangulationMagnitudeNsCnnIndirectAttentionModule, the pooling of JuhanTestModelV3): the convolution side in csrc/triangulation_moments.hip,
+ * the Grams and the chain in csrc/triangulation_bn_moments.hip.  x [B * T, D] (a clip's rows contiguous), anchors [D, K] AS THEY ARE, cnn_s,
+ * cnn_t [K, F, D].  Per row n and anchor k:
+ *     q = |x - a_k|^2, n = sqrt(q), e = (x - a_k) / sqrt(max(q, 1e-12));  g = e - roll(e, 1) over the flattened [K D] row (frames t >= 1),
+ *     p = |g_k|^2, tau = sqrt(p), h = g / sqrt(max(p, 1e-12));  so = relu(<cnn_s[k,f,:], e_k>), to = relu(<cnn_t[k,f,:], h_k>);
+ *     per clip G_s = E E^T, G_t = H H^T over all K D, w = softmax_t(sum_u relu(G[t,u]));  out_s = [so | n], out_t = [to | tau], W = K F + K
+ *     (W = K F without add_norm);  pool = [(1/T') sum_t w_t out_t | mean_t (out_t - mean_t out)^2]  [B, 2 W]
+ * relu, row sums, softmax and their backward are [B, T, T] work of the caller.  Nothing of size B * T * K * D is written in either direction;
+ * no floating-point atomics (the same inputs give the same bits); all products are exact-fp32 MFMAs (the roll's one boundary column per
+ * 32-column chunk is a plain loop).  Each reciprocal norm is taken once, by _norms, and every other entry scales by those bits.
+ *   _norms:    -> q, p [2, B * T, K]: the squared norms (p = -1 on frame 0 of a clip), then 1 / sqrt(max(., 1e-12)) (0 on frame 0 for p)
+ *   _gram:     aff [8, K D] the identity table (1, 0, 0, 1) x 2 -> gram_s [B, T, T], gram_t [B, T-1, T-1]; workspace:
+ *              lpm_triangulation_bn_moments_workspace_bytes(1, ...) bytes
+ *   _conv:     -> so, to [B * T, K * F], rectified (to = 0 on frame 0)
+ *   _pool:     w_s [B, T], w_t [B, T-1] (both null: the plain mean) -> pool_s, pool_t [B, 2 W], stats [2, 2, B, W] (per stream the plain mean
+ *              of every column and the mean of the deviations from it: kept for _dout)
+ *   _dout:     g_s, g_t [B, 2 W] -> dso, dto [B * T, K * F]:  dout[t] = [out[t] > 0] (w_t gm + 2 gv ((out[t] - mean) - c)) / T'; dng, dtg
+ *              [B * T, K]: the same of the norm columns times [squared norm > 1e-12] (zero without add_norm, and dtg on frame 0); with
+ *              weights dw_s [B, T], dw_t [B, T-1]:  dw[b,t] = <gm[b], out_t> / T' over all W columns
+ *   (dcnn_s, dcnn_t: lpm_triangulation_cnn_attention_dweights with iq = q + B T K and ind = p + B T K)
+ *   _bwd:      m_s, m_t as lpm_triangulation_cnn_attention_bwd takes them -> dx [B * T, D], danchors [D, K] (overwritten):
+ *              ge = cnn_s^T dso + M_s E, gh = cnn_t^T dto + M_t H, both normalisations' backward with dn = dng, dtau = dtg, the roll's
+ *              transpose.  workspace: 16-byte aligned, lpm_triangulation_magnitude_workspace_bytes(...) bytes.
+ * D in {128, 1024}, 2 <= T <= lpm_triangulation_attention_max_frames(), K >= 1, F >= 1; anything else LPM_ERR_UNSUPPORTED_SHAPE /
+ * LPM_ERR_BADARG before any launch. */
+size_t lpm_triangulation_magnitude_workspace_bytes(int B, int T, int D, int K);
+int lpm_triangulation_magnitude_norms(const float* x, const float* anchors, int B, int T, int D, int K, float* q, float* p, lpm_stream_t stream);
+int lpm_triangulation_magnitude_gram(const float* x, const float* anchors, const float* q, const float* p, const float* aff, int B, int T, int D,
+                                     int K, float* gram_s, float* gram_t, void* workspace, size_t workspace_bytes, lpm_stream_t stream);
+int lpm_triangulation_magnitude_conv(const float* x, const float* anchors, const float* cnn_s, const float* cnn_t, const float* q, const float* p,
+                                     int B, int T, int D, int K, int F, float* so, float* to, lpm_stream_t stream);
+int lpm_triangulation_magnitude_pool(const float* so, const float* to, const float* q, const float* p, const float* w_s, const float* w_t, int B,
+                                     int T, int K, int F, int add_norm, float* pool_s, float* pool_t, float* stats, lpm_stream_t stream);
+int lpm_triangulation_magnitude_dout(const float* so, const float* to, const float* q, const float* p, const float* w_s, const float* w_t,
+                                     const float* stats, const float* g_s, const float* g_t, int B, int T, int K, int F, int add_norm, float* dso,
+                                     float* dto, float* dng, float* dtg, float* dw_s, float* dw_t, lpm_stream_t stream);
+int lpm_triangulation_magnitude_bwd(const float* x, const float* anchors, const float* q, const float* p, const float* cnn_s, const float* cnn_t,
+                                    const float* dso, const float* dto, const float* dng, const float* dtg, const float* m_s, const float* m_t,
+                                    int B, int T, int D, int K, int F, float* dx, float* danchors, void* workspace, size_t workspace_bytes,
+                                    lpm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The rows of the inference CSV as text (inference.py:88-96), csrc/csv_rows.hip and csrc/format_pairs.h.  index int32 [B, k] and value
  * fp32 [B, k] (the outputs of lpm_topk_rows; any int32 is accepted) -> text uint8 [B, stride] with stride = lpm_format_pairs_stride of k
  * = 25 k rounded up to 16 (a pair is at most 11 + 1 + 12 + 1 bytes), and length int32 [B]: row r is

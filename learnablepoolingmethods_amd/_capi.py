@@ -235,6 +235,13 @@ SIGNATURES = {
     "lpm_triangulation_cnn_attention_dout": (_i, [_f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f]),
     "lpm_triangulation_cnn_attention_dweights": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f]),
     "lpm_triangulation_cnn_attention_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _s, _f]),
+    "lpm_triangulation_magnitude_workspace_bytes": (_s, [_i, _i, _i, _i]),
+    "lpm_triangulation_magnitude_norms": (_i, [_f, _f, _i, _i, _i, _i, _f, _f, _f]),
+    "lpm_triangulation_magnitude_gram": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _i, _f, _f, _f, _s, _f]),
+    "lpm_triangulation_magnitude_conv": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f]),
+    "lpm_triangulation_magnitude_pool": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _f]),
+    "lpm_triangulation_magnitude_dout": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f]),
+    "lpm_triangulation_magnitude_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _s, _f]),
     "lpm_lstm_supported": (_i, [_i, _i, _i]),
     "lpm_lstm_layer_fwd": (_i, [_f, _f, _l, _f, _f, _i, _i, _i, _fl, _f, _f, _f, _f, _f]),
     "lpm_lstm_layer_bwd": (_i, [_f, _l, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _f]),

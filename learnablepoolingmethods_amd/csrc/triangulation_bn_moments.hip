@@ -32,6 +32,11 @@
 // The CONV policy of tb_bwd (triangulation_cnn_attention, JuhanTestModelV2; entry points at the end of the file): V is e / g itself, there
 //   is no batch norm (sweeps 2 and 3 only), and dV = M V + W_k^T dout, the per-anchor convolution's input gradient accumulated behind the
 //   M V product in the same MFMA accumulators (dout [B T, K F] and W [K, F, D] from global memory).
+// The MAG policy on top of CONV (triangulation_magnitude, JuhanTestModelV3; entry points at the end of the file): the temporal operand is
+//   h = g it, it = 1 / sqrt(max(|g_k|^2, 1e-12)) per (row, anchor) from tv_norms, in the Gram and in the chain alike, and both norms are
+//   outputs.  gh = M_t H + W_t^T dto is no longer the gradient of g:  gg = it (gh - h (h . gh) [p > eps]) + dtau [p > eps] h.  The dot
+//   product (h . gh) holds a per-anchor block of the Gram, which the saved G_t (summed over the anchors) does not contain, so it takes a
+//   sweep of its own in front of the other two (tb_mag_s1); sweep 3 adds dn [q > eps] e.
 #include "triangulation_common.h"
 
 // g = e[j] - e[j-1] must be exactly zero where both are equal, and every kernel must form V with the same roundings: no fused products
@@ -132,9 +137,11 @@ __global__ __launch_bounds__(256) void tb_colsum_kernel(const float* __restrict_
 }
 
 // triangulation_attention.hip's Gram kernel on V_s (frames 0 .. T-1) and V_t (frames 1 .. T-1; row 0 of the tile is zero)
-template <int D>
+// MAG: V_t = h = g it, it [B T, K] the reciprocal norm of the rolled difference (triangulation_magnitude)
+template <int D, bool MAG = false>
 __global__ __launch_bounds__(64 * TA_WAVES) void tb_gram_kernel(const float* __restrict__ x, const float* __restrict__ anchors,
-                                                                const float* __restrict__ iq, const float* __restrict__ aff, int T, int K, int S,
+                                                                const float* __restrict__ iq, const float* __restrict__ it,
+                                                                const float* __restrict__ aff, int T, int K, int S,
                                                                 int NT, float* __restrict__ part_s, float* __restrict__ part_t) {
     __shared__ float tile[2][2][64][TA_LD];                // [tile I / J][V_s / V_t]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -147,6 +154,7 @@ __global__ __launch_bounds__(64 * TA_WAVES) void tb_gram_kernel(const float* __r
     const int nside = diag ? 1 : 2;
     const float* xb = x + (int64_t)b * T * D;
     const float* iqb = iq + (int64_t)b * T * K;
+    const float* itb = MAG ? it + (int64_t)b * T * K : nullptr;
     const int c = threadIdx.x & 31, r0 = threadIdx.x >> 5;
     const int qi = wave >> 1, qj = wave & 1;
     const float (*tI)[64][TA_LD] = tile[0];
@@ -172,7 +180,10 @@ __global__ __launch_bounds__(64 * TA_WAVES) void tb_gram_kernel(const float* __r
                         const float* xr = xb + (int64_t)t * D;
                         const float* iqr = iqb + (int64_t)t * K;
                         vs = tb_affine(tb_e(xr, anchors, iqr, K, k, d), sc_s, mu_s, be_s);
-                        if (t >= 1) vt = tb_affine(tb_g<D>(xr, anchors, iqr, K, k, d), sc_t, mu_t, be_t);
+                        if (t >= 1) {
+                            const float g = tb_g<D>(xr, anchors, iqr, K, k, d);
+                            vt = tb_affine(MAG ? g * itb[(int64_t)t * K + k] : g, sc_t, mu_t, be_t);
+                        }
                     }
                     tile[side][0][r][c] = vs;
                     tile[side][1][r][c] = vt;
@@ -292,7 +303,20 @@ struct TbBwdArgs {
     // CONV (triangulation_cnn_attention's chain): the convolutions' weights [K, F, D] and upstream tensors dso, dto [B T, K F]
     const float *cnn_s, *cnn_t, *dso, *dto;
     int F;
+    // MAG (triangulation_magnitude's chain), all [B T, K]: it = 1 / sqrt(max(p, eps)) (0 on frame 0 of a clip), s1g = (h . gh) [p > eps]
+    // (written by tb_mag_s1, read by the sweeps), dtg = dtau [p > eps], dng = dn [q > eps]
+    const float *it, *dtg, *dng;
+    float* s1g;
+    const float* p;
 };
+
+// the temporal operand of a chain: g itself, or (MAG) h = g it
+template <int D, bool MAG>
+__device__ __forceinline__ float tb_gh(const float* __restrict__ xr, const float* __restrict__ anchors, const float* __restrict__ iqr,
+                                       const float* __restrict__ itr, int K, int k, int d) {
+    const float g = tb_g<D>(xr, anchors, iqr, K, k, d);
+    return MAG ? g * itr[k] : g;
+}
 
 // the M V product of one 32-column chunk: tP[t][c] = sum_u M[t,u] tV[u][c], rows by frame index (off = 1: M is over the frames 1 .. T-1)
 // CONV: m may be null (no attention), and the convolution's input gradient is added in the same accumulators:
@@ -328,7 +352,7 @@ __device__ __forceinline__ void tb_mv(const float* __restrict__ m, int T, int Tp
 }
 
 // one (clip, anchor, chunk) of a sweep; `first`: the first anchor this workgroup adds onto its columns of dx (sweep 3)
-template <int D, int SWEEP, bool CONV>
+template <int D, int SWEEP, bool CONV, bool MAG>
 __device__ __forceinline__ void tb_bwd_chunk(const TbBwdArgs& A, int b, int k, int c0, bool first, int Tp, float (*tV)[TB_LDV],
                                              float (*tP)[TB_LDV], float (*tR)[TA_LD], float* cw_s, float* cw_t, float* dotacc, float* dacc) {
     const int T = A.T, K = A.K, J = K * D, T1 = T - 1;
@@ -336,6 +360,7 @@ __device__ __forceinline__ void tb_bwd_chunk(const TbBwdArgs& A, int b, int k, i
     const int d = c0 + c, j = k * D + d;
     const float* xb = A.x + (int64_t)b * T * D;
     const float* iqb = A.iq + (int64_t)b * T * K;
+    const float* itb = MAG ? A.it + (int64_t)b * T * K : iqb;       // (read under MAG only)
     const bool attention = A.m_s != nullptr;
     const float two_s = 2.f / (float)T, two_t = 2.f / (float)T1;
     // CONV: V is e / g itself (no affine map), and dV = M V + W^T dout comes whole from tb_mv
@@ -417,9 +442,10 @@ __device__ __forceinline__ void tb_bwd_chunk(const TbBwdArgs& A, int b, int k, i
         if (CONV) {
             if (attention) {
                 for (int t = r0; t < Tp; t += 8)
-                    tV[t][c] = (t >= 1 && t < T) ? tb_g<D>(xb + (int64_t)t * D, A.anchors, iqb + (int64_t)t * K, K, k, d) : 0.f;
+                    tV[t][c] = (t >= 1 && t < T) ? tb_gh<D, MAG>(xb + (int64_t)t * D, A.anchors, iqb + (int64_t)t * K, itb + (int64_t)t * K, K, k, d) : 0.f;
                 for (int t = threadIdx.x; t < Tp; t += 64 * TA_WAVES)
-                    tV[t][TA_CH] = (t >= 1 && t < T) ? tb_g<D>(xb + (int64_t)t * D, A.anchors, iqb + (int64_t)t * K, K, kx, dx_) : 0.f;
+                    tV[t][TA_CH] =
+                        (t >= 1 && t < T) ? tb_gh<D, MAG>(xb + (int64_t)t * D, A.anchors, iqb + (int64_t)t * K, itb + (int64_t)t * K, K, kx, dx_) : 0.f;
             }
             __syncthreads();
             tb_mv<true>(mt, T, Tp, 1, tV, tP, dout_t, A.cnn_t + ((int64_t)k * A.F) * D + c0, KF, A.F, D);
@@ -463,11 +489,15 @@ __device__ __forceinline__ void tb_bwd_chunk(const TbBwdArgs& A, int b, int k, i
                 if (SWEEP == 1) {
                     sb += dV;
                     sg = fmaf(dV, hat, sg);
+                } else if (MAG) {                          // gg from gh = dV: the second normalisation's backward and tau's own gradient
+                    const int64_t m = ((int64_t)b * T + t) * K + k;
+                    const float itau = A.it[m], h = raw * itau;
+                    draw = itau * (dV - h * A.s1g[m]) + A.dtg[m] * h;
                 } else {
                     draw = CONV ? dV : sc * ((dV - c1) - hat * c2);
                 }
             }
-            if (SWEEP > 1) tV[t][c] = draw;                  // (this thread's own element: nothing else reads it before the barrier)
+            if (SWEEP > 1) tV[t][c] = draw;                 // (this thread's own element: nothing else reads it before the barrier)
         }
         if (SWEEP == 1) {
             __syncthreads();
@@ -492,7 +522,13 @@ __device__ __forceinline__ void tb_bwd_chunk(const TbBwdArgs& A, int b, int k, i
                 const float raw = tb_g<D>(xb + (int64_t)t * D, A.anchors, iqb + (int64_t)t * K, K, kx, dx_);
                 const float hat = (raw - mux) * istdx;
                 const float dV = CONV ? tP[t][TA_CH] : cw_t[t] * gmx + (two_t * (scx * ((raw - rbx) - crx))) * gqx + (attention ? tP[t][TA_CH] : 0.f);
-                draw = CONV ? dV : scx * ((dV - c1x) - hat * c2x);
+                if (MAG) {
+                    const int64_t m = ((int64_t)b * T + t) * K + kx;
+                    const float itau = A.it[m], h = raw * itau;
+                    draw = itau * (dV - h * A.s1g[m]) + A.dtg[m] * h;
+                } else {
+                    draw = CONV ? dV : scx * ((dV - c1x) - hat * c2x);
+                }
             }
             tV[t][TA_CH] = draw;
         }
@@ -511,7 +547,8 @@ __device__ __forceinline__ void tb_bwd_chunk(const TbBwdArgs& A, int b, int k, i
                 v = eh * de;
             } else {
                 const float qg = A.q[n * K + k] > kL2Eps ? 1.f : 0.f;
-                const float gr = A.iq[n * K + k] * (de - eh * (A.dot[n * K + k] * qg));
+                float gr = A.iq[n * K + k] * (de - eh * (A.dot[n * K + k] * qg));
+                if (MAG) gr = gr + A.dng[n * K + k] * eh;  // n = |x - a_k| is an output
                 float* po = A.dx + n * D + d;
                 *po = first ? gr : *po + gr;               // (an earlier anchor of this workgroup: this thread wrote it)
                 da += gr;
@@ -534,7 +571,48 @@ __device__ __forceinline__ void tb_bwd_chunk(const TbBwdArgs& A, int b, int k, i
     __syncthreads();
 }
 
-template <int D, int SWEEP, bool CONV = false>
+// MAG's sweep in front of the other two, one (clip, anchor, chunk): dotacc[t] += sum_c h[t][c] gh[t][c],  gh = M_t H + W_t^T dto
+template <int D>
+__device__ __forceinline__ void tb_mag_s1_chunk(const TbBwdArgs& A, int b, int k, int c0, int Tp, float (*tV)[TB_LDV], float (*tP)[TB_LDV],
+                                                float* dotacc) {
+    const int T = A.T, K = A.K, T1 = T - 1;
+    const int c = threadIdx.x & 31, r0 = threadIdx.x >> 5;
+    const int d = c0 + c;
+    const float* xb = A.x + (int64_t)b * T * D;
+    const float* iqb = A.iq + (int64_t)b * T * K;
+    const float* itb = A.it + (int64_t)b * T * K;
+    for (int t = r0; t < Tp; t += 8)
+        tV[t][c] = (t >= 1 && t < T) ? tb_gh<D, true>(xb + (int64_t)t * D, A.anchors, iqb + (int64_t)t * K, itb + (int64_t)t * K, K, k, d) : 0.f;
+    __syncthreads();
+    tb_mv<true>(A.m_t ? A.m_t + (int64_t)b * T1 * T1 : nullptr, T, Tp, 1, tV, tP, A.dto + ((int64_t)b * T * K + k) * A.F,
+                A.cnn_t + ((int64_t)k * A.F) * D + c0, (int64_t)K * A.F, A.F, D);
+    __syncthreads();
+    for (int t = r0; t < Tp; t += 8) {
+        const float v = half_sum(tV[t][c] * tP[t][c]);     // the 32 columns of the chunk: one half-wave per frame
+        if (c == 0 && t < T) dotacc[t] += v;
+    }
+    __syncthreads();
+}
+
+// a workgroup per (clip, anchor): s1g[n,k] = (h . gh) [p > eps]
+template <int D>
+__global__ __launch_bounds__(64 * TA_WAVES) void tb_mag_s1_kernel(const TbBwdArgs A) {
+    extern __shared__ __attribute__((aligned(16))) float tb_sh[];
+    const int T = A.T, K = A.K, Tp = (T + 31) & ~31;
+    float (*tV)[TB_LDV] = reinterpret_cast<float (*)[TB_LDV]>(tb_sh);
+    float (*tP)[TB_LDV] = tV + Tp;
+    float* dotacc = tb_sh + 2 * Tp * TB_LDV;
+    const int b = blockIdx.x / K, k = blockIdx.x % K;
+    for (int t = threadIdx.x; t < Tp; t += 64 * TA_WAVES) dotacc[t] = 0.f;
+    __syncthreads();
+    for (int c0 = 0; c0 < D; c0 += TA_CH) tb_mag_s1_chunk<D>(A, b, k, c0, Tp, tV, tP, dotacc);
+    for (int t = threadIdx.x; t < T; t += 64 * TA_WAVES) {
+        const int64_t m = ((int64_t)b * T + t) * K + k;
+        A.s1g[m] = A.p[m] > kL2Eps ? dotacc[t] : 0.f;      // (frame 0 of a clip: p = -1)
+    }
+}
+
+template <int D, int SWEEP, bool CONV = false, bool MAG = false>
 __global__ __launch_bounds__(64 * TA_WAVES) void tb_bwd_kernel(const TbBwdArgs A) {
     extern __shared__ __attribute__((aligned(16))) float tb_sh[];
     const int T = A.T, K = A.K, Tp = (T + 31) & ~31;
@@ -553,9 +631,9 @@ __global__ __launch_bounds__(64 * TA_WAVES) void tb_bwd_kernel(const TbBwdArgs A
     }
     __syncthreads();
     if (SWEEP == 3) {
-        for (int k = 0; k < K; ++k) tb_bwd_chunk<D, SWEEP, CONV>(A, b, k, rest * TA_CH, k == 0, Tp, tV, tP, tR, cw_s, cw_t, dotacc, dacc);
+        for (int k = 0; k < K; ++k) tb_bwd_chunk<D, SWEEP, CONV, MAG>(A, b, k, rest * TA_CH, k == 0, Tp, tV, tP, tR, cw_s, cw_t, dotacc, dacc);
     } else {
-        for (int c0 = 0; c0 < D; c0 += TA_CH) tb_bwd_chunk<D, SWEEP, CONV>(A, b, rest, c0, false, Tp, tV, tP, tR, cw_s, cw_t, dotacc, dacc);
+        for (int c0 = 0; c0 < D; c0 += TA_CH) tb_bwd_chunk<D, SWEEP, CONV, MAG>(A, b, rest, c0, false, Tp, tV, tP, tR, cw_s, cw_t, dotacc, dacc);
         if (SWEEP == 2)
             for (int t = threadIdx.x; t < T; t += 64 * TA_WAVES) A.dot[((int64_t)b * T + t) * K + rest] = dotacc[t];
     }
@@ -636,7 +714,8 @@ extern "C" int lpm_triangulation_bn_moments_gram(const float* x, const float* an
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)(B * S * NT * NT)), block(64 * TA_WAVES);
     tp_dispatch_d(D, [&](auto d) {
-        hipLaunchKernelGGL(tb_gram_kernel<decltype(d)::value>, grid, block, 0, s, x, anchors, iq, aff, T, K, S, NT, part_s, part_t);
+        hipLaunchKernelGGL(tb_gram_kernel<decltype(d)::value>, grid, block, 0, s, x, anchors, iq, (const float*)nullptr, aff, T, K, S, NT, part_s,
+                           part_t);
     });
     if (S > 1) {
         if (const int rc = ta_sum_slices(part_s, B, (int64_t)T * T, S, gram_s, s, name)) return rc;
@@ -701,6 +780,7 @@ extern "C" int lpm_triangulation_bn_moments_bwd(const float* x, const float* anc
     A.inv_nt = training ? 1.f / (float)(BT - B) : 0.f;
     A.B = B; A.T = T; A.K = K;
     A.cnn_s = A.cnn_t = A.dso = A.dto = nullptr; A.F = 0;
+    A.it = A.dtg = A.dng = A.p = nullptr; A.s1g = nullptr;
     A.dpart = (float*)workspace;
     A.dot = A.dpart + (size_t)4 * B * J;
     A.da_part = A.dot + (size_t)BT * K;
@@ -752,6 +832,7 @@ extern "C" int lpm_triangulation_cnn_attention_bwd(const float* x, const float* 
     A.inv_ns = A.inv_nt = 0.f;
     A.B = B; A.T = T; A.K = K;
     A.cnn_s = cnn_s; A.cnn_t = cnn_t; A.dso = dso; A.dto = dto; A.F = F;
+    A.it = A.dtg = A.dng = A.p = nullptr; A.s1g = nullptr;
     A.dpart = nullptr;
     A.dot = (float*)workspace;
     A.da_part = A.dot + (size_t)BT * K;
@@ -761,6 +842,82 @@ extern "C" int lpm_triangulation_cnn_attention_bwd(const float* x, const float* 
         constexpr int DD = decltype(d)::value;
         hipLaunchKernelGGL((tb_bwd_kernel<DD, 2, true>), grid_k, block, lds, s, A);
         hipLaunchKernelGGL((tb_bwd_kernel<DD, 3, true>), grid_c, block, lds, s, A);
+    });
+    if (const int rc = ta_reduce_partials(dx, A.da_part, B, T, D, K, 1, TP_SUM_CHUNK, dx, danchors, s, name)) return rc;
+    return check_launch(name);
+}
+
+// ---- triangulation_magnitude (TriangulationMagnitudeNsCnnIndirectAttentionModule, JuhanTestModelV3): the Grams with the temporal operand
+// normalised again, and the chain under the MAG policy -- tb_mag_s1, then tb_bwd's sweeps 2 and 3.  q, p [2, B T, K] are tv_norms'
+// (lpm_triangulation_magnitude_norms): the squared norms, then their clamped reciprocal roots ----
+extern "C" int lpm_triangulation_magnitude_gram(const float* x, const float* anchors, const float* q, const float* p, const float* aff, int B, int T,
+                                                int D, int K, float* gram_s, float* gram_t, void* workspace, size_t workspace_bytes,
+                                                lpm_stream_t stream) {
+    using namespace lpm;
+    const char* name = "lpm_triangulation_magnitude_gram";
+    LPM_REQUIRE(x && anchors && q && p && aff && gram_s && gram_t, LPM_ERR_BADARG, "%s: null pointer", name);
+    if (const int rc = tb_check(name, B, T, D, K)) return rc;
+    const size_t need = lpm_triangulation_bn_moments_workspace_bytes(1, B, T, D, K);
+    LPM_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), LPM_ERR_WORKSPACE, "%s: workspace too small", name);
+    const int S = tb_slices(B, T, K), NT = ta_tiles(T), T1 = T - 1;
+    const int64_t BTK = (int64_t)B * T * K;
+    float* part_s = S > 1 ? (float*)workspace : gram_s;
+    float* part_t = S > 1 ? part_s + (size_t)B * S * T * T : gram_t;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)(B * S * NT * NT)), block(64 * TA_WAVES);
+    tp_dispatch_d(D, [&](auto d) {
+        hipLaunchKernelGGL((tb_gram_kernel<decltype(d)::value, true>), grid, block, 0, s, x, anchors, q + BTK, p + BTK, aff, T, K, S, NT, part_s,
+                           part_t);
+    });
+    if (S > 1) {
+        if (const int rc = ta_sum_slices(part_s, B, (int64_t)T * T, S, gram_s, s, name)) return rc;
+        if (const int rc = ta_sum_slices(part_t, B, (int64_t)T1 * T1, S, gram_t, s, name)) return rc;
+    }
+    return check_launch(name);
+}
+
+extern "C" size_t lpm_triangulation_magnitude_workspace_bytes(int B, int T, int D, int K) {
+    if (B <= 0 || T <= 1 || D <= 0 || K <= 0) return 0;
+    return (2 * (size_t)B * T * K + (size_t)B * K * D) * sizeof(float);             // s1g, the dot products, danchors partials
+}
+
+extern "C" int lpm_triangulation_magnitude_bwd(const float* x, const float* anchors, const float* q, const float* p, const float* cnn_s,
+                                               const float* cnn_t, const float* dso, const float* dto, const float* dng, const float* dtg,
+                                               const float* m_s, const float* m_t, int B, int T, int D, int K, int F, float* dx, float* danchors,
+                                               void* workspace, size_t workspace_bytes, lpm_stream_t stream) {
+    using namespace lpm;
+    const char* name = "lpm_triangulation_magnitude_bwd";
+    LPM_REQUIRE(x && anchors && q && p && cnn_s && cnn_t && dso && dto && dng && dtg && dx && danchors, LPM_ERR_BADARG, "%s: null pointer", name);
+    LPM_REQUIRE(!m_s == !m_t, LPM_ERR_BADARG, "%s: M of both streams, or none", name);
+    if (const int rc = tb_check(name, B, T, D, K)) return rc;
+    LPM_REQUIRE(F >= 1 && (int64_t)B * T * K * F < (1ll << 31), LPM_ERR_UNSUPPORTED_SHAPE, "%s: need F >= 1 and B * T * K * F < 2^31 (F=%d)", name, F);
+    LPM_REQUIRE(workspace && workspace_bytes >= lpm_triangulation_magnitude_workspace_bytes(B, T, D, K), LPM_ERR_WORKSPACE,
+                "%s: workspace too small", name);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t BT = (int64_t)B * T;
+    const size_t lds = tb_bwd_lds(T);
+    if (const int rc = tp_reserve_lds<tb_mag_s1_kernel<1024>, tb_mag_s1_kernel<128>, tb_bwd_kernel<1024, 2, true, true>,
+                                      tb_bwd_kernel<1024, 3, true, true>, tb_bwd_kernel<128, 2, true, true>, tb_bwd_kernel<128, 3, true, true>>(
+            name, (int)tb_bwd_lds(TA_MAX_FRAMES)))
+        return rc;
+    TbBwdArgs A;
+    A.x = x; A.anchors = anchors; A.q = q; A.iq = q + BT * K; A.aff = nullptr; A.w_s = A.w_t = nullptr; A.m_s = m_s; A.m_t = m_t;
+    A.rawbar = A.corr = A.g_s = A.g_t = A.dgrad = nullptr;
+    A.inv_ns = A.inv_nt = 0.f;
+    A.B = B; A.T = T; A.K = K;
+    A.cnn_s = cnn_s; A.cnn_t = cnn_t; A.dso = dso; A.dto = dto; A.F = F;
+    A.p = p; A.it = p + BT * K; A.dtg = dtg; A.dng = dng;
+    A.dpart = nullptr;
+    A.s1g = (float*)workspace;
+    A.dot = A.s1g + (size_t)BT * K;
+    A.da_part = A.dot + (size_t)BT * K;
+    A.dx = dx;
+    const dim3 block(64 * TA_WAVES), grid_k((unsigned)(B * K)), grid_c((unsigned)(B * (D / TA_CH)));
+    tp_dispatch_d(D, [&](auto d) {
+        constexpr int DD = decltype(d)::value;
+        hipLaunchKernelGGL(tb_mag_s1_kernel<DD>, grid_k, block, lds, s, A);
+        hipLaunchKernelGGL((tb_bwd_kernel<DD, 2, true, true>), grid_k, block, lds, s, A);
+        hipLaunchKernelGGL((tb_bwd_kernel<DD, 3, true, true>), grid_c, block, lds, s, A);
     });
     if (const int rc = ta_reduce_partials(dx, A.da_part, B, T, D, K, 1, TP_SUM_CHUNK, dx, danchors, s, name)) return rc;
     return check_launch(name);

@@ -120,8 +120,8 @@ __global__ __launch_bounds__(64 * TA_WAVES) void tv_norms_kernel(const float* __
     }
 }
 
-// so[m,k,f], to[m,k,f] for 128 rows, one anchor and 32 filters (to = 0 on frame 0 of a clip)
-template <int D>
+// so[m,k,f], to[m,k,f] for 128 rows, one anchor and 32 filters (to = 0 on frame 0 of a clip); RELU: both rectified (triangulation_magnitude)
+template <int D, bool RELU = false>
 __global__ __launch_bounds__(64 * TA_WAVES) void tv_conv_kernel(const float* __restrict__ x, const float* __restrict__ anchors,
                                                                 const float* __restrict__ ws, const float* __restrict__ wt,
                                                                 const float* __restrict__ iq, const float* __restrict__ it, int64_t BT, int K, int F,
@@ -184,8 +184,8 @@ __global__ __launch_bounds__(64 * TA_WAVES) void tv_conv_kernel(const float* __r
     for (int r = 0; r < 16; ++r) {
         const int64_t R = R0 + 32 * wave + mfma32_row(r, lane);
         if (R < BT && f < F) {
-            so[(R * K + k) * F + f] = acc_s[r];
-            to[(R * K + k) * F + f] = acc_t[r];
+            so[(R * K + k) * F + f] = RELU ? fmaxf(acc_s[r], 0.f) : acc_s[r];
+            to[(R * K + k) * F + f] = RELU ? fmaxf(acc_t[r], 0.f) : acc_t[r];
         }
     }
 }
@@ -742,5 +742,167 @@ extern "C" int lpm_triangulation_cnn_attention_dweights(const float* x, const fl
         hipLaunchKernelGGL(tv_dw_kernel<decltype(d)::value>, dim3((unsigned)((int64_t)K * NF * (D / (32 * TA_WAVES)))), dim3(64 * TA_WAVES), 0,
                            (hipStream_t)stream, x, anchors, iq, ind, dso, dto, (int64_t)B * T, K, F, dcnn_s, dcnn_t);
     });
+    return check_launch(name);
+}
+
+// ---- the convolution side of triangulation_magnitude (TriangulationMagnitudeNsCnnIndirectAttentionModule :634-888, JuhanTestModelV3) ----
+// V5's two normalisations (tv_norms, tv_conv with both reciprocal norms, tv_dw through lpm_triangulation_cnn_attention_dweights with `ind` = the
+// temporal reciprocal norm) under V2's attention weights, both convolutions rectified before they are pooled.  The pools are over the
+// W = K F + K columns [relu(conv) | norm]:  pool = [ (1/T') sum_t w_t out_t | mean_t (out_t - mean_t out)^2 ], the norms sqrt(q), sqrt(p)
+// taken where they are read.  Backward: dout[t] = (w_t gm + 2 gv ((out[t] - mean) - c)) / T' on every column -- on a convolution column
+// times [out > 0], on a norm column times [squared norm > eps] into dng / dtg [B T, K] -- and dw[t] = <gm, out[t]> / T' over all W columns.
+namespace lpm {
+
+// a thread per (clip, column), blockIdx.y = stream: pool [B, 2 W]; stats [2, 2, B, W] = each stream's plain mean, then the mean of the
+// deviations from it (what the rounded mean is off by); sums over t two-level
+__global__ __launch_bounds__(256) void tm_pool_kernel(const float* __restrict__ so, const float* __restrict__ to, const float* __restrict__ q,
+                                                      const float* __restrict__ p, const float* __restrict__ w_s, const float* __restrict__ w_t,
+                                                      int B, int T, int K, int F, int NC, float* __restrict__ pool_s, float* __restrict__ pool_t,
+                                                      float* __restrict__ stats) {
+    const int64_t KF = (int64_t)K * F, W = KF + NC;         // NC = K, or 0 without the norm columns
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= B * W) return;
+    const int64_t b = i / W, j = i % W;
+    const int z = blockIdx.y, Tz = T - z;
+    const bool conv = j < KF;
+    const float* v = conv ? (z ? to : so) + b * T * KF + j : (z ? p : q) + b * T * K + (j - KF);
+    const int64_t stride = conv ? KF : K;
+    const float* w = z ? w_t : w_s;                          // null: the plain mean
+    if (w) w += b * Tz;
+    const float cnt = (float)Tz;
+    float tot = 0.f, acc = 0.f, wtot = 0.f, wacc = 0.f;
+    for (int t = z; t < T; ++t) {
+        const float val = conv ? v[t * stride] : sqrtf(v[t * stride]);
+        acc += val;
+        if (w) wacc = fmaf(w[t - z], val, wacc);
+        if (((t - z) & (TP_SUM_CHUNK - 1)) == TP_SUM_CHUNK - 1) {
+            tot += acc;
+            wtot += wacc;
+            acc = wacc = 0.f;
+        }
+    }
+    const float mean = (tot + acc) / cnt, wsum = wtot + wacc;
+    float dtot = 0.f, dacc = 0.f;
+    tot = acc = 0.f;
+    for (int t = z; t < T; ++t) {
+        const float dev = (conv ? v[t * stride] : sqrtf(v[t * stride])) - mean;
+        acc = fmaf(dev, dev, acc);
+        dacc += dev;
+        if (((t - z) & (TP_SUM_CHUNK - 1)) == TP_SUM_CHUNK - 1) {
+            tot += acc;
+            dtot += dacc;
+            acc = dacc = 0.f;
+        }
+    }
+    float* pool = (z ? pool_t : pool_s) + b * 2 * W;
+    pool[j] = w ? wsum / cnt : mean;
+    pool[W + j] = (tot + acc) / cnt;
+    float* st = stats + (int64_t)z * 2 * B * W;
+    st[b * W + j] = mean;
+    st[(B + b) * W + j] = (dtot + dacc) / cnt;
+}
+
+// a workgroup per (clip, frame), blockIdx.y = stream: the masked dout [B T, K F] (the temporal one zero on frame 0), the gated gradient of
+// the norm [B T, K] (always written: zero without the norm columns) and dw[b,t] = <gm[b], out_t> / T'
+__global__ __launch_bounds__(256) void tm_dout_kernel(const float* __restrict__ so, const float* __restrict__ to, const float* __restrict__ q,
+                                                      const float* __restrict__ p, const float* __restrict__ w_s, const float* __restrict__ w_t,
+                                                      const float* __restrict__ stats, const float* __restrict__ g_s, const float* __restrict__ g_t,
+                                                      int B, int T, int K, int F, int NC, float* __restrict__ dso, float* __restrict__ dto,
+                                                      float* __restrict__ dng, float* __restrict__ dtg, float* __restrict__ dw_s,
+                                                      float* __restrict__ dw_t) {
+    __shared__ float red[4];
+    const int64_t KF = (int64_t)K * F, W = KF + NC;
+    const int z = blockIdx.y, b = blockIdx.x / T, t = blockIdx.x % T, Tz = T - z;
+    const int64_t n = (int64_t)b * T + t;
+    float* dout = (z ? dto : dso) + n * KF;
+    float* dnorm = (z ? dtg : dng) + n * K;
+    if ((z && t == 0) || NC == 0)                          // (uniform over the workgroup)
+        for (int k = threadIdx.x; k < K; k += 256) dnorm[k] = 0.f;
+    if (z && t == 0) {
+        for (int64_t j = threadIdx.x; j < KF; j += 256) dout[j] = 0.f;
+        return;
+    }
+    const float* out = (z ? to : so) + n * KF;
+    const float* sq = (z ? p : q) + n * K;
+    const float* g = (z ? g_t : g_s) + (int64_t)b * 2 * W;
+    const float* st = stats + (int64_t)z * 2 * B * W;
+    const float *mean = st + (int64_t)b * W, *corr = st + (int64_t)(B + b) * W;
+    const float* w = z ? w_t : w_s;
+    const float wt = w ? w[(int64_t)b * Tz + t - z] : 1.f, cnt = (float)Tz;
+    float acc = 0.f;
+    for (int64_t j = threadIdx.x; j < W; j += 256) {
+        const bool conv = j < KF;
+        const float s = conv ? 0.f : sq[j - KF];
+        const float v = conv ? out[j] : sqrtf(s), gm = g[j];
+        const float d = (wt * gm + 2.f * g[W + j] * ((v - mean[j]) - corr[j])) / cnt;
+        if (conv) dout[j] = v > 0.f ? d : 0.f; else dnorm[j - KF] = s > kL2Eps ? d : 0.f;
+        acc = fmaf(gm, v, acc);
+    }
+    acc = wave_sum_dpp(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0 && w) {
+        const float d = ((red[0] + red[1]) + (red[2] + red[3])) / cnt;
+        if (z) dw_t[(int64_t)b * (T - 1) + t - 1] = d; else dw_s[n] = d;
+    }
+}
+
+}  // namespace lpm
+
+extern "C" int lpm_triangulation_magnitude_norms(const float* x, const float* anchors, int B, int T, int D, int K, float* q, float* p,
+                                                 lpm_stream_t stream) {
+    using namespace lpm;
+    const char* name = "lpm_triangulation_magnitude_norms";
+    LPM_REQUIRE(x && anchors && q && p, LPM_ERR_BADARG, "%s: null pointer", name);
+    if (const int rc = tv_check(name, B, T, D, K, 1)) return rc;
+    LPM_REQUIRE(((uintptr_t)x & 15) == 0, LPM_ERR_BADARG, "%s: x must be 16-byte aligned", name);
+    const int64_t BT = (int64_t)B * T;
+    const dim3 grid((unsigned)((BT * ((K + TV_KC - 1) / TV_KC) + TA_WAVES - 1) / TA_WAVES));
+    tp_dispatch_d(D, [&](auto d) {
+        hipLaunchKernelGGL(tv_norms_kernel<decltype(d)::value>, grid, dim3(64 * TA_WAVES), 0, (hipStream_t)stream, x, anchors, BT, T, K, q, p);
+    });
+    return check_launch(name);
+}
+
+extern "C" int lpm_triangulation_magnitude_conv(const float* x, const float* anchors, const float* cnn_s, const float* cnn_t, const float* q,
+                                                const float* p, int B, int T, int D, int K, int F, float* so, float* to, lpm_stream_t stream) {
+    using namespace lpm;
+    const char* name = "lpm_triangulation_magnitude_conv";
+    LPM_REQUIRE(x && anchors && cnn_s && cnn_t && q && p && so && to, LPM_ERR_BADARG, "%s: null pointer", name);
+    if (const int rc = tv_check(name, B, T, D, K, F)) return rc;
+    const int64_t BT = (int64_t)B * T, BTK = BT * K;
+    const int NR = tv_row_tiles(BT), NF = (F + 31) / 32;
+    tp_dispatch_d(D, [&](auto d) {
+        hipLaunchKernelGGL((tv_conv_kernel<decltype(d)::value, true>), dim3((unsigned)((int64_t)K * NF * NR)), dim3(64 * TA_WAVES), 0,
+                           (hipStream_t)stream, x, anchors, cnn_s, cnn_t, q + BTK, p + BTK, BT, K, F, NR, so, to);
+    });
+    return check_launch(name);
+}
+
+extern "C" int lpm_triangulation_magnitude_pool(const float* so, const float* to, const float* q, const float* p, const float* w_s,
+                                                const float* w_t, int B, int T, int K, int F, int add_norm, float* pool_s, float* pool_t,
+                                                float* stats, lpm_stream_t stream) {
+    using namespace lpm;
+    const char* name = "lpm_triangulation_magnitude_pool";
+    LPM_REQUIRE(so && to && q && p && pool_s && pool_t && stats && !w_s == !w_t, LPM_ERR_BADARG, "%s: null pointer", name);
+    if (const int rc = tv_check(name, B, T, 128, K, F)) return rc;
+    const int NC = add_norm ? K : 0;
+    const int64_t cols = (int64_t)B * ((int64_t)K * F + NC);
+    hipLaunchKernelGGL(tm_pool_kernel, dim3((unsigned)((cols + 255) / 256), 2), dim3(256), 0, (hipStream_t)stream, so, to, q, p, w_s, w_t, B, T, K, F,
+                       NC, pool_s, pool_t, stats);
+    return check_launch(name);
+}
+
+extern "C" int lpm_triangulation_magnitude_dout(const float* so, const float* to, const float* q, const float* p, const float* w_s,
+                                                const float* w_t, const float* stats, const float* g_s, const float* g_t, int B, int T, int K,
+                                                int F, int add_norm, float* dso, float* dto, float* dng, float* dtg, float* dw_s, float* dw_t,
+                                                lpm_stream_t stream) {
+    using namespace lpm;
+    const char* name = "lpm_triangulation_magnitude_dout";
+    LPM_REQUIRE(so && to && q && p && stats && g_s && g_t && dso && dto && dng && dtg && !w_s == !w_t && !w_s == !dw_s && !w_t == !dw_t,
+                LPM_ERR_BADARG, "%s: null pointer (the weights and dw of both streams, or none)", name);
+    if (const int rc = tv_check(name, B, T, 128, K, F)) return rc;
+    hipLaunchKernelGGL(tm_dout_kernel, dim3((unsigned)(B * T), 2), dim3(256), 0, (hipStream_t)stream, so, to, q, p, w_s, w_t, stats, g_s, g_t, B, T,
+                       K, F, add_norm ? K : 0, dso, dto, dng, dtg, dw_s, dw_t);
     return check_launch(name);
 }

@@ -142,6 +142,29 @@ FLAGS.define("triangulation_v2_fused", False, "build extension: on the GPU each 
              "tools/bench_triangulation_v2.py measured forward + backward of one stream at 37.3 ms fused against 11.6 ms at (B, T, D, K, F) = "
              "(16, 200, 1024, 32, 64) and 3.44 against 1.51 ms at (16, 200, 128, 8, 16) (with 148 against 2594 MiB and 19 against 125 MiB "
              "allocated), and the default is on only if the fused path is not slower at both (profiles/bench_triangulation_v2.json)")
+FLAGS.define("jtmv3_iteration", 200, "JuhanTestModelV3 (frame_level_models.py:272): sampled frames per clip")
+FLAGS.define("jtmv3_add_batch_norm", True, "JuhanTestModelV3 (:274): batch norm inside each stream's module")
+FLAGS.define("jtmv3_sample_random_frames", True, "JuhanTestModelV3 (:276): defined and read nowhere, as written")
+FLAGS.define("jtmv3_video_anchor_size", 32, "JuhanTestModelV3 (:278): anchors of the video stream")
+FLAGS.define("jtmv3_audio_anchor_size", 8, "JuhanTestModelV3 (:280): anchors of the audio stream")
+FLAGS.define("jtmv3_video_kernel_size", 64, "JuhanTestModelV3 (:282): filters per anchor of the video stream's two convolutions")
+FLAGS.define("jtmv3_audio_kernel_size", 16, "JuhanTestModelV3 (:284): filters per anchor of the audio stream's two convolutions")
+FLAGS.define("jtmv3_video_hidden", 2048, "JuhanTestModelV3 (:286): width of the video stream's hidden layer")
+FLAGS.define("jtmv3_video_output_dim", 2048, "JuhanTestModelV3 (:288): width of the video stream's fused output")
+FLAGS.define("jtmv3_audio_hidden", 256, "JuhanTestModelV3 (:290): width of the audio stream's hidden layer")
+FLAGS.define("jtmv3_audio_output_dim", 256, "JuhanTestModelV3 (:292): width of the audio stream's fused output")
+FLAGS.define("jtmv3_use_attention", True, "JuhanTestModelV3 (:294): the soft-attention weights on the pooled means")
+FLAGS.define("jtmv3_use_relu", False, "JuhanTestModelV3 (:296): relu behind the hidden and the fusion layer")
+FLAGS.define("jtmv3_video_level_model", "ClassLearningFourNnModel", "JuhanTestModelV3 (:298): the classifier, a class of video_level_models "
+             "taken by name")
+FLAGS.define("triangulation_v3_fused", False, "build extension: on the GPU each stream of JuhanTestModelV3 pools through "
+             "ops.triangulation_magnitude_moments (both norms, the Grams of the embedding and of its normalised rolled differences, the softmax "
+             "weights, the rectified per-anchor convolutions and the weighted mean and variance over the frames of [relu(conv) | norm], without "
+             "any [B, T, K*D] tensor); False: TriangulationMagnitudeNsCnnIndirectAttentionModule.pool materialises it (the CPU path; same "
+             "variables, same results).  Off: tools/bench_triangulation_v3.py measured forward + backward of one stream at 44.7 ms fused against "
+             "14.7 ms at (B, T, D, K, F) = (16, 200, 1024, 32, 64) and 4.08 against 1.79 ms at (16, 200, 128, 8, 16) (with 149 against 3048 MiB "
+             "and 19 against 125 MiB allocated), and the default is on only if the fused path is not slower at both "
+             "(profiles/bench_triangulation_v3.json)")
 FLAGS.define("batch_norm", True, "TriangulationRelationalModel (frame_level_models.py:1503): True iff add batch normalization")
 FLAGS.define("audio_triangulation_anchor_size_v1", 4, "TriangulationRelationalModel (:1505): anchors of the audio stream")
 FLAGS.define("video_triangulation_anchor_size_v1", 16, "TriangulationRelationalModel (:1507): anchors of the video stream")

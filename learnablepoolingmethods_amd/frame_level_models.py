@@ -1,7 +1,7 @@
 """NetVLAD prototypes behind the reference's model-registry API
 (reference: frame_level_models.py:2193-2513 NetVladV1 / NetVladV2, :2765-2877 NetVLAD / LightVLAD) and the triangulation-embedding
 family's RegularizedTriangulationModel (:1148-1307), SoftAttentionTriangulationModel (:965-1145), TriangulationCnnClusterModel
-(:757-939), JuhanTestModelV5 (:491-606), JuhanTestModelV1 (:59-154), JuhanTestModelV2 (:158-268) and the recurrent TriangulationRelationalModel (:1511-1630).
+(:757-939), JuhanTestModelV5 (:491-606), JuhanTestModelV1 (:59-154), JuhanTestModelV2 (:158-268), JuhanTestModelV3 (:302-378) and the recurrent TriangulationRelationalModel (:1511-1630).
 
 Same names, ``create_model`` signature, variable names and output contract as the reference; the hot
 ops (frame sampling + input_bn, soft-assignment GEMM, fused softmax/residual aggregation/normalise,
@@ -744,6 +744,57 @@ class JuhanTestModelV2(models.BaseModel):
         aggregated_model = getattr(video_level_models, "ClassLearningFourNnModel")
         return aggregated_model().create_model(model_input=activation, vocab_size=vocab_size, is_training=is_training,
                                                **unused_params)                                              # :262-268
+
+
+class JuhanTestModelV3(models.BaseModel):
+    """One TriangulationMagnitudeNsCnnIndirectAttentionModule per stream (JuhanTestModelV2's pooling with the rolled differences
+    normalised again, both convolutions rectified and the two norm columns appended: "magnitude preserving"), the two streams joined
+    WITHOUT a batch norm, and the classifier FLAGS.jtmv3_video_level_model names (frame_level_models.py:302-378).  No input batch norm.
+    As written: SURVEY App. C29, C32, C33, C39, C42-C44 (and C23).
+
+    On the GPU with FLAGS.triangulation_v3_fused each stream's pooling goes through ops.triangulation_magnitude_moments: no
+    [(B*T), K*D] tensor (419 MB at the video defaults B = 16, T = 200, K = 32, D = 1024) is written; otherwise the module's ``pool``
+    materialises them.  The variables and the results are the same either way.  ``frame_uniform`` [B, iterations] replaces the random draw
+    of SampleRandomFrames; ``video_anchor_size``, ``audio_anchor_size``, ``video_kernel_size``, ``audio_kernel_size``, ``video_hidden``,
+    ``audio_hidden``, ``video_output_dim`` and ``audio_output_dim`` override the flags (the reference reads the flags only)."""
+
+    def create_model(self, model_input, vocab_size, num_frames, iterations=None, add_batch_norm=None, sample_random_frames=None,
+                     hidden_size=None, is_training=True, frame_uniform=None, video_anchor_size=None, audio_anchor_size=None,
+                     video_kernel_size=None, audio_kernel_size=None, video_hidden=None, audio_hidden=None, video_output_dim=None,
+                     audio_output_dim=None, quantised_training=False, **unused_params):
+        iterations = iterations or FLAGS.jtmv3_iteration                                                      # :313
+        add_batch_norm = add_batch_norm or FLAGS.jtmv3_add_batch_norm                                         # :314 (C23)
+        video_anchor_size = int(video_anchor_size or FLAGS.jtmv3_video_anchor_size)                           # :315-322
+        audio_anchor_size = int(audio_anchor_size or FLAGS.jtmv3_audio_anchor_size)
+        video_hidden = int(video_hidden or FLAGS.jtmv3_video_hidden)
+        audio_hidden = int(audio_hidden or FLAGS.jtmv3_audio_hidden)
+        video_kernel_size = int(video_kernel_size or FLAGS.jtmv3_video_kernel_size)
+        audio_kernel_size = int(audio_kernel_size or FLAGS.jtmv3_audio_kernel_size)
+        video_output_dim = int(video_output_dim or FLAGS.jtmv3_video_output_dim)
+        audio_output_dim = int(audio_output_dim or FLAGS.jtmv3_audio_output_dim)
+        use_attention, use_relu = FLAGS.jtmv3_use_attention, FLAGS.jtmv3_use_relu                             # :323-324
+        aggregated_model = getattr(video_level_models, FLAGS.jtmv3_video_level_model)                         # :325, :372-373 (raises)
+        # sample_random_frames and hidden_size are accepted and read nowhere, as written
+        quantised, model_input, max_frames, feature_size = _random_frames(model_input, num_frames, iterations, frame_uniform)  # :327-333
+        if feature_size <= 1024:
+            raise ValueError("JuhanTestModelV3 slices a 1024-wide video and a 128-wide audio stream out of its input "
+                             f"(frame_level_models.py:363-368); got {feature_size} features")
+        streams = (("video", 1024, video_anchor_size, video_kernel_size, video_hidden, video_output_dim),
+                   ("audio", feature_size - 1024, audio_anchor_size, audio_kernel_size, audio_hidden, audio_output_dim))
+        features = _stream_features(quantised, model_input, num_frames, iterations, frame_uniform, False, is_training,
+                                    quantised_training)                                                       # (no input batch norm)
+        v3_modules = [video_pooling_modules.TriangulationMagnitudeNsCnnIndirectAttentionModule(
+            feature_size=D, max_frames=max_frames, anchor_size=K, self_attention=use_attention, hidden_layer_size=H, kernel_size=F,
+            output_dim=O, add_relu=use_relu, add_norm=True, batch_norm=add_batch_norm, is_training=is_training, scope_id=None)
+            for _, D, K, F, H, O in streams]                                                                  # :335-361
+        fused = bool(FLAGS.triangulation_v3_fused and model_input.is_cuda and max_frames >= 2)
+        acts = []
+        for (name, *_), x, module in zip(streams, features, v3_modules):
+            with vs.variable_scope(name + "_triangulation_embedding"):                                        # :363-369
+                acts.append(module.head(*module.fused_pool(x.contiguous())) if fused else module.forward(x))
+        activation = torch.cat(acts, 1)                                                                       # :371 (no batch norm behind it)
+        return aggregated_model().create_model(model_input=activation, vocab_size=vocab_size, is_training=is_training,
+                                               **unused_params)                                              # :374-378
 
 
 class TriangulationRelationalModel(models.BaseModel):

@@ -4775,6 +4775,117 @@ def triangulation_cnn_attention_moments(x, anchors, cnn_s, cnn_t, max_frames, se
 
 
 # ----------------------------------------------------------------------------------------------
+# rectified attention moments of the twice-normalised triangulation embedding: TriangulationMagnitudeNsCnnIndirectAttentionModule's pooling
+# (csrc/triangulation_moments.hip: the norms, the convolutions and their moments; csrc/triangulation_bn_moments.hip: the Grams, the chain)
+# ----------------------------------------------------------------------------------------------
+class _TriangulationMagnitudeMoments(torch.autograd.Function):
+    """The saved state is the inputs, the squared norms and their reciprocal roots q, p [2, B*T, K], the rectified convolutions so, to
+    [B*T, K*F] (their sign is the relu's mask), the per-clip means and their corrections stats [2, 2, B, W] and, with attention, the two
+    Grams and weight vectors; e and h are recomputed in the backward, whose workspaces (dso, dto [B*T, K*F] among them) live for that call
+    only."""
+
+    @staticmethod
+    def forward(ctx, x, anchors, cnn_s, cnn_t, T, attention, add_norm):
+        lib = _capi.load()
+        D, K = anchors.shape
+        F = cnn_s.shape[1]
+        B, J = x.shape[0] // T, K * D
+        W = K * F + (K if add_norm else 0)
+        dims = (B, T, D, K, F)
+        q, p = _empty((2, B * T, K), x), _empty((2, B * T, K), x)
+        with _timed("triangulation_magnitude_norms", dims):
+            lib.check(lib._lpm_triangulation_magnitude_norms(ptr(x), ptr(anchors), B, T, D, K, ptr(q), ptr(p), stream_ptr()),
+                      "lpm_triangulation_magnitude_norms")
+        gram_s = gram_t = w_s = w_t = None
+        if attention:
+            aff = _empty((8, J), x)                   # the Gram kernel's affine table: the identity (a product with 1 and a sum with 0 are exact)
+            aff.copy_(torch.tensor([1.0, 0.0, 0.0, 1.0] * 2, device=x.device).unsqueeze(1).expand(8, J))
+            gram_s, gram_t = _empty((B, T, T), x), _empty((B, T - 1, T - 1), x)
+            wsb = int(lib._lpm_triangulation_bn_moments_workspace_bytes(1, B, T, D, K))
+            ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+            with _timed("triangulation_magnitude_gram", dims):
+                lib.check(lib._lpm_triangulation_magnitude_gram(ptr(x), ptr(anchors), ptr(q), ptr(p), ptr(aff), B, T, D, K, ptr(gram_s), ptr(gram_t),
+                                                                ptr(ws) if wsb else None, wsb, stream_ptr()), "lpm_triangulation_magnitude_gram")
+            del aff, ws
+            with _timed("triangulation_magnitude_softmax", dims):
+                w_s, w_t = _attention_weights(gram_s), _attention_weights(gram_t)
+        so, to = _empty((B * T, K * F), x), _empty((B * T, K * F), x)
+        with _timed("triangulation_magnitude_conv", dims):
+            lib.check(lib._lpm_triangulation_magnitude_conv(ptr(x), ptr(anchors), ptr(cnn_s), ptr(cnn_t), ptr(q), ptr(p), B, T, D, K, F, ptr(so),
+                                                            ptr(to), stream_ptr()), "lpm_triangulation_magnitude_conv")
+        pool_s, pool_t = _empty((B, 2 * W), x), _empty((B, 2 * W), x)
+        stats = _empty((2, 2, B, W), x)
+        with _timed("triangulation_magnitude_pool", dims):
+            lib.check(lib._lpm_triangulation_magnitude_pool(ptr(so), ptr(to), ptr(q), ptr(p), ptr(w_s) if attention else None,
+                                                            ptr(w_t) if attention else None, B, T, K, F, int(add_norm), ptr(pool_s), ptr(pool_t),
+                                                            ptr(stats), stream_ptr()), "lpm_triangulation_magnitude_pool")
+        ctx.save_for_backward(x, anchors, cnn_s, cnn_t, q, p, so, to, stats, *((gram_s, gram_t, w_s, w_t) if attention else ()))
+        ctx.dims = (B, T, D, K, F, attention, add_norm)
+        return pool_s, pool_t
+
+    @staticmethod
+    def backward(ctx, g_s, g_t):
+        lib = _capi.load()
+        x, anchors, cnn_s, cnn_t, q, p, so, to, stats, *att = ctx.saved_tensors
+        B, T, D, K, F, attention, add_norm = ctx.dims
+        dims = (B, T, D, K, F)
+        g_s, g_t = g_s.contiguous(), g_t.contiguous()
+        dso, dto = torch.empty_like(so), torch.empty_like(to)
+        dng, dtg = _empty((B * T, K), x), _empty((B * T, K), x)
+        w_s = w_t = dw_s = dw_t = m_s = m_t = None
+        if attention:
+            gram_s, gram_t, w_s, w_t = att
+            dw_s, dw_t = _empty((B, T), x), _empty((B, T - 1), x)
+        opt = (lambda t: ptr(t)) if attention else (lambda t: None)
+        with _timed("triangulation_magnitude_dout", dims):
+            lib.check(lib._lpm_triangulation_magnitude_dout(ptr(so), ptr(to), ptr(q), ptr(p), opt(w_s), opt(w_t), ptr(stats), ptr(g_s), ptr(g_t), B,
+                                                            T, K, F, int(add_norm), ptr(dso), ptr(dto), ptr(dng), ptr(dtg), opt(dw_s), opt(dw_t),
+                                                            stream_ptr()), "lpm_triangulation_magnitude_dout")
+        if attention:
+            with _timed("triangulation_magnitude_softmax_bwd", dims):
+                m_s, m_t = _attention_weights_bwd(gram_s, w_s, dw_s), _attention_weights_bwd(gram_t, w_t, dw_t)
+        dx, danchors, dcnn_s, dcnn_t = torch.empty_like(x), torch.empty_like(anchors), torch.empty_like(cnn_s), torch.empty_like(cnn_t)
+        with _timed("triangulation_magnitude_dweights", dims):        # V2's entry: its `ind` is the temporal operand's scale, here 1 / tau
+            lib.check(lib._lpm_triangulation_cnn_attention_dweights(ptr(x), ptr(anchors), ptr(q[1]), ptr(p[1]), ptr(dso), ptr(dto), B, T, D, K, F,
+                                                                    ptr(dcnn_s), ptr(dcnn_t), stream_ptr()),
+                      "lpm_triangulation_cnn_attention_dweights")
+        wsb = int(lib._lpm_triangulation_magnitude_workspace_bytes(B, T, D, K))
+        ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+        with _timed("triangulation_magnitude_bwd", dims):
+            lib.check(lib._lpm_triangulation_magnitude_bwd(ptr(x), ptr(anchors), ptr(q), ptr(p), ptr(cnn_s), ptr(cnn_t), ptr(dso), ptr(dto), ptr(dng),
+                                                           ptr(dtg), opt(m_s), opt(m_t), B, T, D, K, F, ptr(dx), ptr(danchors), ptr(ws), wsb,
+                                                           stream_ptr()), "lpm_triangulation_magnitude_bwd")
+        return dx, danchors, dcnn_s, dcnn_t, None, None, None
+
+
+def triangulation_magnitude_moments(x, anchors, cnn_s, cnn_t, max_frames, self_attention=True, add_norm=True):
+    """One stream of TriangulationMagnitudeNsCnnIndirectAttentionModule's pooling (video_pooling_modules.py:634-888, JuhanTestModelV3): x
+    [B * max_frames, D] (a clip's rows contiguous), anchors [D, K] as they are (NOT normalised), ``cnn_s``, ``cnn_t`` [K, F, D] as the
+    variables are stored -> (spatial_pool, temporal_pool), each [B, 2 W] = [mean | variance] of [convolution (element k * F + f) | norm],
+    W = K*F + K (W = K*F without ``add_norm``):
+        n = |x - a_k|, e = l2_normalize(x - a_k);  g = e - roll(e, 1) over the FEATURE axis of the flattened [K*D] row, frame 0 dropped;
+        tau = |g_k|, h = l2_normalize(g_k);  so = relu(<cnn_s[k,f], e_k>), to = relu(<cnn_t[k,f], h_k>);  per clip G_s = E E^T, G_t = H H^T
+        over all K*D, w = softmax_t(sum_u relu(G[t,u]));  mean = (1/T') sum_t w_t out_t (the plain mean without ``self_attention``), var =
+        the mean of squared deviations from the unweighted mean.
+    Differentiable in all four tensors; where a squared norm does not exceed 1e-12 the gradient of that norm output is zero.  Nothing of
+    size B * T * K * D is written.  GPU only; D in TRIANGULATION_FEATURES, 2 <= max_frames <= 320, contiguous fp32 input; the same inputs
+    give the same bits."""
+    what = "triangulation_magnitude_moments"
+    T = _attention_args(what, x, anchors, max_frames)
+    D, K = anchors.shape
+    for name, cnn in (("cnn_s", cnn_s), ("cnn_t", cnn_t)):
+        if not torch.is_tensor(cnn) or cnn.dim() != 3 or cnn.shape[0] != K or cnn.shape[2] != D or cnn.shape[1] < 1:
+            raise LpmError(f"{what}: {name} must be [K, F, D] = [{K}, F, {D}] (got {tuple(cnn.shape) if torch.is_tensor(cnn) else type(cnn)})")
+        _f32(cnn, f"{what} {name}")
+        if cnn.device != x.device:
+            raise LpmError(f"{what}: {name} is on {cnn.device}, x on {x.device}")
+    if cnn_s.shape != cnn_t.shape:
+        raise LpmError(f"{what}: cnn_s {tuple(cnn_s.shape)} and cnn_t {tuple(cnn_t.shape)} must have one shape")
+    return _TriangulationMagnitudeMoments.apply(x, anchors.contiguous(), cnn_s.contiguous(), cnn_t.contiguous(), T, bool(self_attention),
+                                                bool(add_norm))
+
+
+# ----------------------------------------------------------------------------------------------
 # one LSTM layer: a kernel per time step each way (csrc/lstm.hip)
 # ----------------------------------------------------------------------------------------------
 def lstm_layer_ok(B, T, H) -> bool:

@@ -1,6 +1,7 @@
 """NetVladOrthoReg and NetVladAttenCluster (reference: video_pooling_modules.py:1499-1586, 1589-1663) and the triangulation
 embeddings (TriangulationEmbedding :376-428, WeightedTriangulationEmbedding :1395-1459, TriangulationTemporalEmbedding :1462-1497,
-TriangulationV5Module :142-373, TriangulationCnnIndirectAttentionModule :431-631, TriangulationNsCnnIndirectAttentionModule :1108-1342)."""
+TriangulationV5Module :142-373, TriangulationCnnIndirectAttentionModule :431-631, TriangulationNsCnnIndirectAttentionModule :1108-1342,
+TriangulationMagnitudeNsCnnIndirectAttentionModule :634-888)."""
 from __future__ import annotations
 
 import math
@@ -464,3 +465,51 @@ class TriangulationNsCnnIndirectAttentionModule(modules.BaseModule):
     def forward(self, inputs, **unused_params):
         """inputs [(B*max_frames), D] -> [B, output_dim]."""
         return self.head(*self.pool(inputs))
+
+
+class TriangulationMagnitudeNsCnnIndirectAttentionModule(TriangulationNsCnnIndirectAttentionModule):
+    """:634-888 (JuhanTestModelV3's module), "non-sharing CNN / magnitude preserving": TriangulationNsCnnIndirectAttentionModule with the
+    rolled difference normalised again per anchor (:732; C34 does not hold here), the attention Gram of the temporal stream taken of
+    those normalised rows (C39's resolution: over the frames of a clip), a relu on both convolutions' results before they are pooled
+    (:793-794) and, with ``add_norm``, the two tf.norm columns |x - a_k| and |g_k| appended to them (:799-801), so the weighted mean
+    (C32) and the unweighted reduce_var (C33) are of [relu(conv) | norm], K*F + K columns.  The variables and the head are the sibling's,
+    the two ``*_hidden`` matrices with 2 (K*F + K) rows.  ``pool`` MATERIALISES [(B*T), K*D] several times: the drop-in surface and the
+    CPU path; ``variables`` + ops.triangulation_magnitude_moments + ``head`` is the fused one (``fused_pool``)."""
+
+    def __init__(self, feature_size, max_frames, anchor_size, self_attention, hidden_layer_size, kernel_size, output_dim, add_relu,
+                 add_norm, batch_norm, is_training, scope_id=None):
+        super().__init__(feature_size, max_frames, anchor_size, self_attention, hidden_layer_size, kernel_size, output_dim, add_relu,
+                         batch_norm, is_training, scope_id)
+        self.add_norm = add_norm
+
+    def pool(self, inputs):
+        """inputs [(B*max_frames), D] -> (spatial_pool, temporal_pool), each [B, 2 (K*F + K)] (2 K*F without ``add_norm``; :684-814)."""
+        D, K, F, T = self.feature_size, self.anchor_size, self.kernel_size, self.max_frames
+        anchor_weights, spatial_cnn_weights, temporal_cnn_weights = self.variables(inputs.device)
+        spatial = inputs.unsqueeze(1) - anchor_weights.t().unsqueeze(0)                                # :692-701 -> [M, K, D]
+        spatial_norm = torch.linalg.vector_norm(spatial, dim=2)                                        # :702
+        spatial = layers.l2_normalize(spatial, 2).reshape(-1, K * D)                                   # :706-707
+        temporal = spatial - torch.roll(spatial, shifts=1, dims=1)                                     # :718-719: the feature axis (C29)
+        temporal = temporal.reshape(-1, T, K * D)[:, 1:].reshape(-1, K, D)                             # :720-725
+        temporal_norm = torch.linalg.vector_norm(temporal, dim=2)                                      # :726
+        temporal = layers.l2_normalize(temporal, 2).reshape(-1, K * D)                                 # :732
+        pools = []
+        for v, norm, cnn, Tz in ((spatial, spatial_norm, spatial_cnn_weights, T), (temporal, temporal_norm, temporal_cnn_weights, T - 1)):
+            out = v.reshape(-1, K, D).transpose(0, 1).matmul(cnn.transpose(1, 2)).transpose(0, 1).reshape(-1, Tz, K * F)   # :777-791
+            out = torch.relu(out)                                                                      # :793-794
+            if self.add_norm:
+                out = torch.cat([out, norm.reshape(-1, Tz, K)], 2)                                     # :799-801
+            if self.self_attention:
+                v = v.reshape(-1, Tz, K * D)                                                           # (C39: the frames of a clip)
+                weight = torch.softmax(torch.relu(v.matmul(v.transpose(1, 2))).sum(dim=2), dim=1)      # :741-756
+                mean = (out * weight.unsqueeze(2)).mean(dim=1)                                         # :804-805 (C32)
+            else:
+                mean = out.mean(dim=1)                                                                 # :807-808
+            pools.append(torch.cat([mean, module_utils.reduce_var(out, 1)], 1))                        # :810-814 (C33)
+        return pools[0], pools[1]
+
+    def fused_pool(self, inputs):
+        """``pool`` through ops.triangulation_magnitude_moments: the same variables in the same order."""
+        anchor_weights, spatial_cnn_weights, temporal_cnn_weights = self.variables(inputs.device)
+        return ops.triangulation_magnitude_moments(inputs, anchor_weights, spatial_cnn_weights, temporal_cnn_weights, self.max_frames,
+                                                   self_attention=bool(self.self_attention), add_norm=bool(self.add_norm))
