@@ -1311,6 +1311,29 @@ int lpm_triangulation_magnitude_bwd(const float* x, const float* anchors, const 
                                     lpm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The same embedding's per-frame features (video_pooling_modules.py:891-1040 TriangulationMagnitudeNsCnnNetVladModule up to its two
+ * NetVLADs, the pooling of JuhanTestModelV4), csrc/triangulation_moments.hip: one row [relu(conv) | norm | 0 ..] per frame instead of the
+ * pooled moments.  With q, p [2, B * T, K] of lpm_triangulation_magnitude_norms, W = K F + K and ld >= W the row stride:
+ *   _frames_fwd:   -> feat_s [B * T, ld], feat_t [B * (T-1), ld].  Column k F + f = relu(<cnn_s[k,f,:], e_k>) / relu(<cnn_t[k,f,:], h_k>): the
+ *                  kernel of lpm_triangulation_magnitude_conv under another output policy, so these columns carry the bits that entry
+ *                  writes to so / to for the same inputs.  Column K F + k = sqrt(q) / sqrt(p); columns W .. ld-1 = 0.  Row b (T-1) + (t-1) of
+ *                  feat_t is frame t >= 1 of clip b: frame 0 is dropped and the rows are compacted.  One launch.
+ *   _frames_dout:  dfeat_s, dfeat_t (the shapes of feat_s, feat_t) -> dso, dto [B * T, K * F] = dfeat [feat > 0] (the temporal rows expanded
+ *                  back to T per clip, frame 0 zero) and dng, dtg [B * T, K] = the norm columns' gradients times [squared norm > 1e-12] (dtg
+ *                  zero on frame 0): the operands of lpm_triangulation_cnn_attention_dweights (iq = q + B T K, ind = p + B T K) and of
+ *                  lpm_triangulation_magnitude_bwd with m_s = m_t = NULL.  One pass; 16-byte accesses of the convolution columns where ld
+ *                  and K F are multiples of 4 and the pointers 16-byte aligned.
+ * The saved state of a backward is feat_s, feat_t themselves (the sign of a convolution column is the relu's mask) and q, p.  Nothing of
+ * size B * T * K * D is written; no atomics.  Shapes as above and B * T * ld < 2^31; anything else LPM_ERR_UNSUPPORTED_SHAPE /
+ * LPM_ERR_BADARG before any launch. */
+int lpm_triangulation_magnitude_frames_fwd(const float* x, const float* anchors, const float* cnn_s, const float* cnn_t, const float* q,
+                                           const float* p, int B, int T, int D, int K, int F, int ld, float* feat_s, float* feat_t,
+                                           lpm_stream_t stream);
+int lpm_triangulation_magnitude_frames_dout(const float* feat_s, const float* feat_t, const float* q, const float* p, const float* dfeat_s,
+                                            const float* dfeat_t, int B, int T, int K, int F, int ld, float* dso, float* dto, float* dng,
+                                            float* dtg, lpm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The rows of the inference CSV as text (inference.py:88-96), csrc/csv_rows.hip and csrc/format_pairs.h.  index int32 [B, k] and value
  * fp32 [B, k] (the outputs of lpm_topk_rows; any int32 is accepted) -> text uint8 [B, stride] with stride = lpm_format_pairs_stride of k
  * = 25 k rounded up to 16 (a pair is at most 11 + 1 + 12 + 1 bytes), and length int32 [B]: row r is

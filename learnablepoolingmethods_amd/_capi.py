@@ -242,6 +242,8 @@ SIGNATURES = {
     "lpm_triangulation_magnitude_pool": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _f]),
     "lpm_triangulation_magnitude_dout": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f]),
     "lpm_triangulation_magnitude_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _s, _f]),
+    "lpm_triangulation_magnitude_frames_fwd": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _f, _f, _f]),
+    "lpm_triangulation_magnitude_frames_dout": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f]),
     "lpm_lstm_supported": (_i, [_i, _i, _i]),
     "lpm_lstm_layer_fwd": (_i, [_f, _f, _l, _f, _f, _i, _i, _i, _fl, _f, _f, _f, _f, _f]),
     "lpm_lstm_layer_bwd": (_i, [_f, _l, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _f]),

@@ -120,12 +120,24 @@ __global__ __launch_bounds__(64 * TA_WAVES) void tv_norms_kernel(const float* __
     }
 }
 
+// tv_conv's FRAMES output policy (triangulation_magnitude_frames): the squared norms q, p [B T, K] of tv_norms, the frames per clip and
+// the row stride of the two feature matrices; all unread under the other policies
+struct TvFrames {
+    const float *sq_s, *sq_t;
+    int T, ld;
+};
+
 // so[m,k,f], to[m,k,f] for 128 rows, one anchor and 32 filters (to = 0 on frame 0 of a clip); RELU: both rectified (triangulation_magnitude)
-template <int D, bool RELU = false>
+// FRAMES (with RELU; triangulation_magnitude_frames): so, to are the per-frame feature matrices [B T, ld] and [B (T-1), ld], the same
+// values at column k F + f of rows fr.ld floats apart, the temporal rows COMPACTED (row b (T-1) + t-1; frame 0 is not written).  The
+// workgroups of filter tile 0 also write their anchor's norm column K F + k = sqrt(squared norm), those of anchor 0 the zero columns
+// K F + K .. ld-1 as well.
+template <int D, bool RELU = false, bool FRAMES = false>
 __global__ __launch_bounds__(64 * TA_WAVES) void tv_conv_kernel(const float* __restrict__ x, const float* __restrict__ anchors,
                                                                 const float* __restrict__ ws, const float* __restrict__ wt,
                                                                 const float* __restrict__ iq, const float* __restrict__ it, int64_t BT, int K, int F,
-                                                                int NR, float* __restrict__ so, float* __restrict__ to) {
+                                                                int NR, float* __restrict__ so, float* __restrict__ to, const TvFrames fr) {
+    static_assert(RELU || !FRAMES, "the per-frame features are rectified");
     __shared__ float tE[TV_ROWS][TA_LD], tH[TV_ROWS][TA_LD], tWs[32][TA_LD], tWt[32][TA_LD];
     __shared__ float iqs[TV_ROWS], iqp[TV_ROWS], its[TV_ROWS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -141,6 +153,19 @@ __global__ __launch_bounds__(64 * TA_WAVES) void tv_conv_kernel(const float* __r
         iqs[threadIdx.x] = valid ? iq[R * K + k] : 0.f;
         iqp[threadIdx.x] = valid ? iq[R * K + km1] : 0.f;
         its[threadIdx.x] = valid ? it[R * K + k] : 0.f;
+        if (FRAMES && valid && ft == 0) {                  // (ft is uniform over the workgroup)
+            const int KF = K * F, W = KF + K;
+            const int64_t b = R / fr.T;
+            float* rs = so + R * fr.ld;
+            float* rt = R - b * fr.T >= 1 ? to + (R - b - 1) * fr.ld : nullptr;
+            rs[KF + k] = sqrtf(fr.sq_s[R * K + k]);
+            if (rt) rt[KF + k] = sqrtf(fr.sq_t[R * K + k]);
+            if (k == 0)
+                for (int j = W; j < fr.ld; ++j) {
+                    rs[j] = 0.f;
+                    if (rt) rt[j] = 0.f;
+                }
+        }
     }
     __syncthreads();
     const int c = threadIdx.x & 31, r0 = threadIdx.x >> 5;
@@ -184,8 +209,14 @@ __global__ __launch_bounds__(64 * TA_WAVES) void tv_conv_kernel(const float* __r
     for (int r = 0; r < 16; ++r) {
         const int64_t R = R0 + 32 * wave + mfma32_row(r, lane);
         if (R < BT && f < F) {
-            so[(R * K + k) * F + f] = RELU ? fmaxf(acc_s[r], 0.f) : acc_s[r];
-            to[(R * K + k) * F + f] = RELU ? fmaxf(acc_t[r], 0.f) : acc_t[r];
+            if (FRAMES) {
+                const int64_t b = R / fr.T;
+                so[R * fr.ld + k * F + f] = fmaxf(acc_s[r], 0.f);
+                if (R - b * fr.T >= 1) to[(R - b - 1) * fr.ld + k * F + f] = fmaxf(acc_t[r], 0.f);
+            } else {
+                so[(R * K + k) * F + f] = RELU ? fmaxf(acc_s[r], 0.f) : acc_s[r];
+                to[(R * K + k) * F + f] = RELU ? fmaxf(acc_t[r], 0.f) : acc_t[r];
+            }
         }
     }
 }
@@ -547,7 +578,8 @@ extern "C" int lpm_triangulation_moments_fwd(const float* x, const float* anchor
     tp_dispatch_d(D, [&](auto d) {
         constexpr int DD = decltype(d)::value;
         hipLaunchKernelGGL(tv_norms_kernel<DD>, grid_n, block, 0, s, x, anchors, BT, T, K, q, p);
-        hipLaunchKernelGGL(tv_conv_kernel<DD>, grid_c, block, 0, s, x, anchors, cnn_s, cnn_t, q + BT * K, p + BT * K, BT, K, F, NR, so, to);
+        hipLaunchKernelGGL(tv_conv_kernel<DD>, grid_c, block, 0, s, x, anchors, cnn_s, cnn_t, q + BT * K, p + BT * K, BT, K, F, NR, so, to,
+                           TvFrames{});
     });
     const int64_t cols = (int64_t)B * ((int64_t)K * F + K);
     hipLaunchKernelGGL(tv_moments_kernel, dim3((unsigned)((cols + 255) / 256), 2), dim3(256), 0, s, so, to, q, p, B, T, K, F, pool_s, pool_t, corr);
@@ -700,7 +732,7 @@ extern "C" int lpm_triangulation_cnn_attention_conv(const float* x, const float*
     hipLaunchKernelGGL(tc_ind_kernel, dim3((unsigned)((BTK + 255) / 256)), dim3(256), 0, s, BTK, T, K, ind);
     tp_dispatch_d(D, [&](auto d) {
         hipLaunchKernelGGL(tv_conv_kernel<decltype(d)::value>, dim3((unsigned)((int64_t)K * NF * NR)), dim3(64 * TA_WAVES), 0, s, x, anchors, cnn_s,
-                           cnn_t, iq, ind, BT, K, F, NR, so, to);
+                           cnn_t, iq, ind, BT, K, F, NR, so, to, TvFrames{});
     });
     return check_launch(name);
 }
@@ -874,7 +906,7 @@ extern "C" int lpm_triangulation_magnitude_conv(const float* x, const float* anc
     const int NR = tv_row_tiles(BT), NF = (F + 31) / 32;
     tp_dispatch_d(D, [&](auto d) {
         hipLaunchKernelGGL((tv_conv_kernel<decltype(d)::value, true>), dim3((unsigned)((int64_t)K * NF * NR)), dim3(64 * TA_WAVES), 0,
-                           (hipStream_t)stream, x, anchors, cnn_s, cnn_t, q + BTK, p + BTK, BT, K, F, NR, so, to);
+                           (hipStream_t)stream, x, anchors, cnn_s, cnn_t, q + BTK, p + BTK, BT, K, F, NR, so, to, TvFrames{});
     });
     return check_launch(name);
 }
@@ -904,5 +936,92 @@ extern "C" int lpm_triangulation_magnitude_dout(const float* so, const float* to
     if (const int rc = tv_check(name, B, T, 128, K, F)) return rc;
     hipLaunchKernelGGL(tm_dout_kernel, dim3((unsigned)(B * T), 2), dim3(256), 0, (hipStream_t)stream, so, to, q, p, w_s, w_t, stats, g_s, g_t, B, T,
                        K, F, add_norm ? K : 0, dso, dto, dng, dtg, dw_s, dw_t);
+    return check_launch(name);
+}
+
+// ---- the per-frame features of triangulation_magnitude (TriangulationMagnitudeNsCnnNetVladModule :891-1040, JuhanTestModelV4): the rows
+// [relu(conv) | norm | 0 ..] that the module hands to its two NetVLADs, one per frame (the temporal ones of the frames t >= 1, compacted).
+// Forward: tv_norms as it is, then tv_conv under the FRAMES policy.  Backward: tf_dout turns the two feature gradients into the operands
+// lpm_triangulation_cnn_attention_dweights and lpm_triangulation_magnitude_bwd (m_s = m_t = NULL) take. ----
+namespace lpm {
+
+// a workgroup per (clip, frame), blockIdx.y = stream: dout [B T, K F] = dfeat [feat > 0] (the temporal rows expanded back to T per clip,
+// frame 0 zero) and the norm columns' gradients [B T, K] times [squared norm > eps]; VEC: 16-byte accesses of the convolution columns
+template <bool VEC>
+__global__ __launch_bounds__(256) void tf_dout_kernel(const float* __restrict__ feat_s, const float* __restrict__ feat_t,
+                                                      const float* __restrict__ q, const float* __restrict__ p, const float* __restrict__ dfeat_s,
+                                                      const float* __restrict__ dfeat_t, int T, int K, int F, int ld, float* __restrict__ dso,
+                                                      float* __restrict__ dto, float* __restrict__ dng, float* __restrict__ dtg) {
+    const int KF = K * F;
+    const int z = blockIdx.y, b = blockIdx.x / T, t = blockIdx.x % T;
+    const int64_t n = (int64_t)b * T + t;
+    float* dout = (z ? dto : dso) + n * KF;
+    float* dnorm = (z ? dtg : dng) + n * K;
+    if (z && t == 0) {                                     // (uniform over the workgroup)
+        for (int j = threadIdx.x; j < KF; j += 256) dout[j] = 0.f;
+        for (int k = threadIdx.x; k < K; k += 256) dnorm[k] = 0.f;
+        return;
+    }
+    const int64_t m = z ? n - b - 1 : n;                   // the row of the (compacted) feature matrix
+    const float* feat = (z ? feat_t : feat_s) + m * ld;
+    const float* g = (z ? dfeat_t : dfeat_s) + m * ld;
+    const float* sq = (z ? p : q) + n * K;
+    if (VEC) {
+        const float4* f4 = reinterpret_cast<const float4*>(feat);
+        const float4* g4 = reinterpret_cast<const float4*>(g);
+        float4* d4 = reinterpret_cast<float4*>(dout);
+        for (int j = threadIdx.x; j < KF / 4; j += 256) {
+            const float4 v = f4[j], d = g4[j];
+            d4[j] = make_float4(v.x > 0.f ? d.x : 0.f, v.y > 0.f ? d.y : 0.f, v.z > 0.f ? d.z : 0.f, v.w > 0.f ? d.w : 0.f);
+        }
+    } else {
+        for (int j = threadIdx.x; j < KF; j += 256) dout[j] = feat[j] > 0.f ? g[j] : 0.f;
+    }
+    for (int k = threadIdx.x; k < K; k += 256) dnorm[k] = sq[k] > kL2Eps ? g[KF + k] : 0.f;
+}
+
+static int tf_check(const char* name, int B, int T, int D, int K, int F, int ld) {
+    if (const int rc = tv_check(name, B, T, D, K, F)) return rc;
+    const int64_t W = (int64_t)K * F + K;
+    LPM_REQUIRE(ld >= W && (int64_t)B * T * ld < (1ll << 31), LPM_ERR_UNSUPPORTED_SHAPE,
+                "%s: need K * F + K <= ld and B * T * ld < 2^31 (ld=%d, K * F + K = %lld)", name, ld, (long long)W);
+    return LPM_OK;
+}
+
+}  // namespace lpm
+
+extern "C" int lpm_triangulation_magnitude_frames_fwd(const float* x, const float* anchors, const float* cnn_s, const float* cnn_t, const float* q,
+                                                      const float* p, int B, int T, int D, int K, int F, int ld, float* feat_s, float* feat_t,
+                                                      lpm_stream_t stream) {
+    using namespace lpm;
+    const char* name = "lpm_triangulation_magnitude_frames_fwd";
+    LPM_REQUIRE(x && anchors && cnn_s && cnn_t && q && p && feat_s && feat_t, LPM_ERR_BADARG, "%s: null pointer", name);
+    if (const int rc = tf_check(name, B, T, D, K, F, ld)) return rc;
+    const int64_t BT = (int64_t)B * T, BTK = BT * K;
+    const int NR = tv_row_tiles(BT), NF = (F + 31) / 32;
+    const TvFrames fr{q, p, T, ld};
+    tp_dispatch_d(D, [&](auto d) {
+        hipLaunchKernelGGL((tv_conv_kernel<decltype(d)::value, true, true>), dim3((unsigned)((int64_t)K * NF * NR)), dim3(64 * TA_WAVES), 0,
+                           (hipStream_t)stream, x, anchors, cnn_s, cnn_t, q + BTK, p + BTK, BT, K, F, NR, feat_s, feat_t, fr);
+    });
+    return check_launch(name);
+}
+
+extern "C" int lpm_triangulation_magnitude_frames_dout(const float* feat_s, const float* feat_t, const float* q, const float* p,
+                                                       const float* dfeat_s, const float* dfeat_t, int B, int T, int K, int F, int ld, float* dso,
+                                                       float* dto, float* dng, float* dtg, lpm_stream_t stream) {
+    using namespace lpm;
+    const char* name = "lpm_triangulation_magnitude_frames_dout";
+    LPM_REQUIRE(feat_s && feat_t && q && p && dfeat_s && dfeat_t && dso && dto && dng && dtg, LPM_ERR_BADARG, "%s: null pointer", name);
+    if (const int rc = tf_check(name, B, T, 128, K, F, ld)) return rc;
+    const uintptr_t bits = (uintptr_t)feat_s | (uintptr_t)feat_t | (uintptr_t)dfeat_s | (uintptr_t)dfeat_t | (uintptr_t)dso | (uintptr_t)dto;
+    const bool vec = (bits & 15) == 0 && ld % 4 == 0 && ((int64_t)K * F) % 4 == 0;
+    const dim3 grid((unsigned)(B * T), 2), block(256);
+    if (vec)
+        hipLaunchKernelGGL(tf_dout_kernel<true>, grid, block, 0, (hipStream_t)stream, feat_s, feat_t, q, p, dfeat_s, dfeat_t, T, K, F, ld, dso, dto,
+                           dng, dtg);
+    else
+        hipLaunchKernelGGL(tf_dout_kernel<false>, grid, block, 0, (hipStream_t)stream, feat_s, feat_t, q, p, dfeat_s, dfeat_t, T, K, F, ld, dso,
+                           dto, dng, dtg);
     return check_launch(name);
 }

@@ -165,6 +165,31 @@ FLAGS.define("triangulation_v3_fused", False, "build extension: on the GPU each 
              "14.7 ms at (B, T, D, K, F) = (16, 200, 1024, 32, 64) and 4.08 against 1.79 ms at (16, 200, 128, 8, 16) (with 149 against 3048 MiB "
              "and 19 against 125 MiB allocated), and the default is on only if the fused path is not slower at both "
              "(profiles/bench_triangulation_v3.json)")
+FLAGS.define("jtmv4_iteration", 200, "JuhanTestModelV4 (frame_level_models.py:381): sampled frames per clip")
+FLAGS.define("jtmv4_add_batch_norm", True, "JuhanTestModelV4 (:383): batch norm inside each stream's module")
+FLAGS.define("jtmv4_sample_random_frames", True, "JuhanTestModelV4 (:385): defined and read nowhere, as written")
+FLAGS.define("jtmv4_video_anchor_size", 32, "JuhanTestModelV4 (:387): anchors of the video stream")
+FLAGS.define("jtmv4_audio_anchor_size", 8, "JuhanTestModelV4 (:389): anchors of the audio stream")
+FLAGS.define("jtmv4_video_kernel_size", 64, "JuhanTestModelV4 (:391): filters per anchor of the video stream's two convolutions")
+FLAGS.define("jtmv4_audio_kernel_size", 16, "JuhanTestModelV4 (:393): filters per anchor of the audio stream's two convolutions")
+FLAGS.define("jtmv4_video_hidden", 2048, "JuhanTestModelV4 (:395): output width of the video stream's two NetVLADs")
+FLAGS.define("jtmv4_video_output_dim", 2048, "JuhanTestModelV4 (:397): width of the video stream's fused output")
+FLAGS.define("jtmv4_audio_hidden", 256, "JuhanTestModelV4 (:399): output width of the audio stream's two NetVLADs")
+FLAGS.define("jtmv4_audio_output_dim", 256, "JuhanTestModelV4 (:401): width of the audio stream's fused output")
+FLAGS.define("jtmv4_use_attention", True, "JuhanTestModelV4 (:403): handed to the module as self_attention, which never reads it (App. C46)")
+FLAGS.define("jtmv4_use_relu", False, "JuhanTestModelV4 (:405): relu behind the NetVLADs' batch norms and the fusion layer")
+FLAGS.define("jtmv4_video_level_model", "ClassLearningFourNnModel", "JuhanTestModelV4 (:407): defined and read nowhere, as written: the "
+             "classifier is taken from jtmv3_video_level_model (:434, App. C47)")
+FLAGS.define("jtmv4_cluster_size", 256, "build extension: clusters of each of JuhanTestModelV4's four NetVLADs (the reference writes 256 into "
+             "the module, video_pooling_modules.py:1043)")
+FLAGS.define("triangulation_v4_fused", False, "build extension: on the GPU each stream of JuhanTestModelV4 takes its per-frame features from "
+             "ops.triangulation_magnitude_frames (both norms, the rectified per-anchor convolutions and the norm columns written as the rows "
+             "the two NetVLADs read, without any [B, T, K*D] tensor); False: TriangulationMagnitudeNsCnnNetVladModule.frames materialises "
+             "them (the CPU path; same variables, same results).  Off: tools/bench_triangulation_v4.py measured forward + backward of one stream's "
+             "features at 13.8 ms fused against 8.3 ms at (B, T, D, K, F) = (16, 200, 1024, 32, 64) and 1.55 against 0.89 ms at "
+             "(16, 200, 128, 8, 16) (with 192 against 2637 MiB and 18 against 132 MiB allocated; the whole module 20.1 against 14.3 ms and "
+             "3.18 against 2.54 ms), and the default is on only if the fused path is not slower at both "
+             "(profiles/bench_triangulation_v4.json)")
 FLAGS.define("batch_norm", True, "TriangulationRelationalModel (frame_level_models.py:1503): True iff add batch normalization")
 FLAGS.define("audio_triangulation_anchor_size_v1", 4, "TriangulationRelationalModel (:1505): anchors of the audio stream")
 FLAGS.define("video_triangulation_anchor_size_v1", 16, "TriangulationRelationalModel (:1507): anchors of the video stream")

@@ -1,7 +1,7 @@
 """NetVLAD prototypes behind the reference's model-registry API
 (reference: frame_level_models.py:2193-2513 NetVladV1 / NetVladV2, :2765-2877 NetVLAD / LightVLAD) and the triangulation-embedding
 family's RegularizedTriangulationModel (:1148-1307), SoftAttentionTriangulationModel (:965-1145), TriangulationCnnClusterModel
-(:757-939), JuhanTestModelV5 (:491-606), JuhanTestModelV1 (:59-154), JuhanTestModelV2 (:158-268), JuhanTestModelV3 (:302-378) and the recurrent TriangulationRelationalModel (:1511-1630).
+(:757-939), JuhanTestModelV5 (:491-606), JuhanTestModelV1 (:59-154), JuhanTestModelV2 (:158-268), JuhanTestModelV3 (:302-378), JuhanTestModelV4 (:411-487) and the recurrent TriangulationRelationalModel (:1511-1630).
 
 Same names, ``create_model`` signature, variable names and output contract as the reference; the hot
 ops (frame sampling + input_bn, soft-assignment GEMM, fused softmax/residual aggregation/normalise,
@@ -795,6 +795,61 @@ class JuhanTestModelV3(models.BaseModel):
         activation = torch.cat(acts, 1)                                                                       # :371 (no batch norm behind it)
         return aggregated_model().create_model(model_input=activation, vocab_size=vocab_size, is_training=is_training,
                                                **unused_params)                                              # :374-378
+
+
+class JuhanTestModelV4(models.BaseModel):
+    """One TriangulationMagnitudeNsCnnNetVladModule per stream (JuhanTestModelV3's front end -- the twice-normalised embedding, the
+    rectified per-anchor convolutions, the two norm columns -- handed per frame to a loupe_modules.NetVLAD per stream and a projection
+    onto ``*_hidden`` in place of V3's moments), the two streams joined WITHOUT a batch norm, and the classifier
+    FLAGS.jtmv3_video_level_model names: line :434 reads V3's flag, not jtmv4_video_level_model (frame_level_models.py:411-487).  No input
+    batch norm.  As written / resolved: SURVEY App. C29, C45-C47 (and C23).
+
+    On the GPU with FLAGS.triangulation_v4_fused each stream's per-frame features come from ops.triangulation_magnitude_frames: no
+    [(B*T), K*D] tensor (419 MB at the video defaults B = 16, T = 200, K = 32, D = 1024) is written; otherwise the module's ``frames``
+    materialises them.  The variables and the results are the same either way.  At the defaults the two video ``hidden1_weights`` are
+    [256 * 2080, 2048], 4.4 GB each in fp32; NetVladV1's factored / early update routes of its hidden1_weights are NOT extended to them.
+    ``frame_uniform`` [B, iterations] replaces the random draw of SampleRandomFrames; ``video_anchor_size``, ``audio_anchor_size``,
+    ``video_kernel_size``, ``audio_kernel_size``, ``video_hidden``, ``audio_hidden``, ``video_output_dim``, ``audio_output_dim`` and
+    ``cluster_size`` override the flags (the reference reads the flags only, and writes 256 clusters into the module)."""
+
+    def create_model(self, model_input, vocab_size, num_frames, iterations=None, add_batch_norm=None, sample_random_frames=None,
+                     hidden_size=None, is_training=True, frame_uniform=None, video_anchor_size=None, audio_anchor_size=None,
+                     video_kernel_size=None, audio_kernel_size=None, video_hidden=None, audio_hidden=None, video_output_dim=None,
+                     audio_output_dim=None, cluster_size=None, quantised_training=False, **unused_params):
+        iterations = iterations or FLAGS.jtmv4_iteration                                                      # :422
+        add_batch_norm = add_batch_norm or FLAGS.jtmv4_add_batch_norm                                         # :423 (C23)
+        video_anchor_size = int(video_anchor_size or FLAGS.jtmv4_video_anchor_size)                           # :424-431
+        audio_anchor_size = int(audio_anchor_size or FLAGS.jtmv4_audio_anchor_size)
+        video_hidden = int(video_hidden or FLAGS.jtmv4_video_hidden)
+        audio_hidden = int(audio_hidden or FLAGS.jtmv4_audio_hidden)
+        video_kernel_size = int(video_kernel_size or FLAGS.jtmv4_video_kernel_size)
+        audio_kernel_size = int(audio_kernel_size or FLAGS.jtmv4_audio_kernel_size)
+        video_output_dim = int(video_output_dim or FLAGS.jtmv4_video_output_dim)
+        audio_output_dim = int(audio_output_dim or FLAGS.jtmv4_audio_output_dim)
+        cluster_size = int(cluster_size or FLAGS.jtmv4_cluster_size)
+        use_attention, use_relu = FLAGS.jtmv4_use_attention, FLAGS.jtmv4_use_relu                             # :432-433
+        aggregated_model = getattr(video_level_models, FLAGS.jtmv3_video_level_model)                         # :434 (C47), :481-482 (raises)
+        # sample_random_frames and hidden_size are accepted and read nowhere, as written
+        quantised, model_input, max_frames, feature_size = _random_frames(model_input, num_frames, iterations, frame_uniform)  # :436-442
+        if feature_size <= 1024:
+            raise ValueError("JuhanTestModelV4 slices a 1024-wide video and a 128-wide audio stream out of its input "
+                             f"(frame_level_models.py:472-477); got {feature_size} features")
+        streams = (("video", 1024, video_anchor_size, video_kernel_size, video_hidden, video_output_dim),
+                   ("audio", feature_size - 1024, audio_anchor_size, audio_kernel_size, audio_hidden, audio_output_dim))
+        features = _stream_features(quantised, model_input, num_frames, iterations, frame_uniform, False, is_training,
+                                    quantised_training)                                                       # (no input batch norm)
+        v4_modules = [video_pooling_modules.TriangulationMagnitudeNsCnnNetVladModule(
+            feature_size=D, max_frames=max_frames, anchor_size=K, self_attention=use_attention, hidden_layer_size=H, kernel_size=F,
+            output_dim=O, add_relu=use_relu, add_norm=True, batch_norm=add_batch_norm, is_training=is_training, scope_id=None,
+            cluster_size=cluster_size) for _, D, K, F, H, O in streams]                                       # :444-470
+        fused = bool(FLAGS.triangulation_v4_fused and model_input.is_cuda and max_frames >= 2)
+        acts = []
+        for (name, *_), x, module in zip(streams, features, v4_modules):
+            with vs.variable_scope(name + "_triangulation_embedding"):                                        # :472-478
+                acts.append(module.head(*module.fused_frames(x.contiguous())) if fused else module.forward(x))
+        activation = torch.cat(acts, 1)                                                                       # :480 (no batch norm behind it)
+        return aggregated_model().create_model(model_input=activation, vocab_size=vocab_size, is_training=is_training,
+                                               **unused_params)                                              # :483-487
 
 
 class TriangulationRelationalModel(models.BaseModel):

@@ -2779,6 +2779,11 @@ def projection(x, W):
     return _Projection.apply(x, W)
 
 
+def projection_ok(M, K, N):
+    """The weight-streaming kernel of ``projection`` exists for x [M, K] . W [K, N] (lpm_proj_supported)."""
+    return bool(_capi.load()._lpm_proj_supported(int(M), int(K), int(N)))
+
+
 class _ProjectionParts(torch.autograd.Function):
     """y = [x1 * scale | x2] . W (tf.concat + tf.matmul, frame_level_models.py:2445 + :2319) with x1 the lazily normalised d-major
     descriptor of the video stream (vlad_aggregate(lazy=True): un-normalised sums + one scale per (clip, cluster)) and x2 the audio
@@ -4870,7 +4875,13 @@ def triangulation_magnitude_moments(x, anchors, cnn_s, cnn_t, max_frames, self_a
     Differentiable in all four tensors; where a squared norm does not exceed 1e-12 the gradient of that norm output is zero.  Nothing of
     size B * T * K * D is written.  GPU only; D in TRIANGULATION_FEATURES, 2 <= max_frames <= 320, contiguous fp32 input; the same inputs
     give the same bits."""
-    what = "triangulation_magnitude_moments"
+    T = _magnitude_args("triangulation_magnitude_moments", x, anchors, cnn_s, cnn_t, max_frames)
+    return _TriangulationMagnitudeMoments.apply(x, anchors.contiguous(), cnn_s.contiguous(), cnn_t.contiguous(), T, bool(self_attention),
+                                                bool(add_norm))
+
+
+def _magnitude_args(what, x, anchors, cnn_s, cnn_t, max_frames):
+    """The argument checks the two triangulation_magnitude ops share -> max_frames."""
     T = _attention_args(what, x, anchors, max_frames)
     D, K = anchors.shape
     for name, cnn in (("cnn_s", cnn_s), ("cnn_t", cnn_t)):
@@ -4881,8 +4892,84 @@ def triangulation_magnitude_moments(x, anchors, cnn_s, cnn_t, max_frames, self_a
             raise LpmError(f"{what}: {name} is on {cnn.device}, x on {x.device}")
     if cnn_s.shape != cnn_t.shape:
         raise LpmError(f"{what}: cnn_s {tuple(cnn_s.shape)} and cnn_t {tuple(cnn_t.shape)} must have one shape")
-    return _TriangulationMagnitudeMoments.apply(x, anchors.contiguous(), cnn_s.contiguous(), cnn_t.contiguous(), T, bool(self_attention),
-                                                bool(add_norm))
+    return T
+
+
+# ----------------------------------------------------------------------------------------------
+# the same embedding's per-frame features: TriangulationMagnitudeNsCnnNetVladModule up to its two NetVLADs (csrc/triangulation_moments.hip:
+# V3's norms, its convolution kernel under the FRAMES output policy, one dout pass; csrc/triangulation_bn_moments.hip: V3's chain)
+# ----------------------------------------------------------------------------------------------
+class _TriangulationMagnitudeFrames(torch.autograd.Function):
+    """The saved state is the inputs, the squared norms and their reciprocal roots q, p [2, B*T, K] and the two outputs themselves (the
+    sign of a convolution column is the relu's mask); e and h are recomputed in the backward, whose workspaces (dso, dto [B*T, K*F] among
+    them) live for that call only."""
+
+    @staticmethod
+    def forward(ctx, x, anchors, cnn_s, cnn_t, T, Wp):
+        lib = _capi.load()
+        D, K = anchors.shape
+        F = cnn_s.shape[1]
+        B = x.shape[0] // T
+        dims = (B, T, D, K, F)
+        q, p = _empty((2, B * T, K), x), _empty((2, B * T, K), x)
+        with _timed("triangulation_magnitude_norms", dims):
+            lib.check(lib._lpm_triangulation_magnitude_norms(ptr(x), ptr(anchors), B, T, D, K, ptr(q), ptr(p), stream_ptr()),
+                      "lpm_triangulation_magnitude_norms")
+        feat_s, feat_t = _empty((B * T, Wp), x), _empty((B * (T - 1), Wp), x)
+        with _timed("triangulation_magnitude_frames_fwd", dims):
+            lib.check(lib._lpm_triangulation_magnitude_frames_fwd(ptr(x), ptr(anchors), ptr(cnn_s), ptr(cnn_t), ptr(q), ptr(p), B, T, D, K, F, Wp,
+                                                                  ptr(feat_s), ptr(feat_t), stream_ptr()),
+                      "lpm_triangulation_magnitude_frames_fwd")
+        ctx.save_for_backward(x, anchors, cnn_s, cnn_t, q, p, feat_s, feat_t)
+        ctx.dims = (B, T, D, K, F, Wp)
+        return feat_s, feat_t
+
+    @staticmethod
+    def backward(ctx, g_s, g_t):
+        lib = _capi.load()
+        x, anchors, cnn_s, cnn_t, q, p, feat_s, feat_t = ctx.saved_tensors
+        B, T, D, K, F, Wp = ctx.dims
+        dims = (B, T, D, K, F)
+        g_s, g_t = g_s.contiguous(), g_t.contiguous()
+        dso, dto = _empty((B * T, K * F), x), _empty((B * T, K * F), x)
+        dng, dtg = _empty((B * T, K), x), _empty((B * T, K), x)
+        with _timed("triangulation_magnitude_frames_dout", dims):
+            lib.check(lib._lpm_triangulation_magnitude_frames_dout(ptr(feat_s), ptr(feat_t), ptr(q), ptr(p), ptr(g_s), ptr(g_t), B, T, K, F, Wp,
+                                                                   ptr(dso), ptr(dto), ptr(dng), ptr(dtg), stream_ptr()),
+                      "lpm_triangulation_magnitude_frames_dout")
+        dx, danchors, dcnn_s, dcnn_t = torch.empty_like(x), torch.empty_like(anchors), torch.empty_like(cnn_s), torch.empty_like(cnn_t)
+        with _timed("triangulation_magnitude_dweights", dims):        # V2's entry: its `ind` is the temporal operand's scale, here 1 / tau
+            lib.check(lib._lpm_triangulation_cnn_attention_dweights(ptr(x), ptr(anchors), ptr(q[1]), ptr(p[1]), ptr(dso), ptr(dto), B, T, D, K, F,
+                                                                    ptr(dcnn_s), ptr(dcnn_t), stream_ptr()),
+                      "lpm_triangulation_cnn_attention_dweights")
+        wsb = int(lib._lpm_triangulation_magnitude_workspace_bytes(B, T, D, K))
+        ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+        with _timed("triangulation_magnitude_bwd", dims):             # V3's chain without attention: no M V product
+            lib.check(lib._lpm_triangulation_magnitude_bwd(ptr(x), ptr(anchors), ptr(q), ptr(p), ptr(cnn_s), ptr(cnn_t), ptr(dso), ptr(dto), ptr(dng),
+                                                           ptr(dtg), None, None, B, T, D, K, F, ptr(dx), ptr(danchors), ptr(ws), wsb,
+                                                           stream_ptr()), "lpm_triangulation_magnitude_bwd")
+        return dx, danchors, dcnn_s, dcnn_t, None, None
+
+
+def triangulation_magnitude_frames(x, anchors, cnn_s, cnn_t, max_frames, pad_to=1):
+    """The per-frame features of TriangulationMagnitudeNsCnnNetVladModule (video_pooling_modules.py:891-1040, JuhanTestModelV4), the rows
+    its two NetVLADs read: x [B * max_frames, D] (a clip's rows contiguous), anchors [D, K] as they are (NOT normalised), ``cnn_s``,
+    ``cnn_t`` [K, F, D] as the variables are stored -> (feat_s [B * T, Wp], feat_t [B * (T-1), Wp]), W = K*F + K and Wp = W rounded up to a
+    multiple of ``pad_to``.  With e, g, h and the feature-axis roll of ``triangulation_magnitude_moments``:
+        column k*F + f = relu(<cnn_s[k,f], e_k>) / relu(<cnn_t[k,f], h_k>);  column K*F + k = |x - a_k| / |g_k|;  columns W .. Wp-1 = 0
+        (exact zeros: a NetVLAD over the padded rows with zero rows in its cluster matrices is the NetVLAD over the W columns)
+    Row b*(T-1) + (t-1) of feat_t is frame t >= 1 of clip b: frame 0 is dropped and the rows are compacted, max_samples = T-1 per clip.
+    Differentiable in all four tensors; where a squared norm does not exceed 1e-12 the gradient of that norm column is zero.  Nothing of
+    size B * T * K * D is written in either direction.  GPU only; D in TRIANGULATION_FEATURES, 2 <= max_frames <= 320, contiguous fp32
+    input; no atomics: the same inputs give the same bits."""
+    what = "triangulation_magnitude_frames"
+    T = _magnitude_args(what, x, anchors, cnn_s, cnn_t, max_frames)
+    pad_to = int(pad_to)
+    if pad_to < 1:
+        raise LpmError(f"{what}: pad_to must be >= 1 (got {pad_to})")
+    W = anchors.shape[1] * (cnn_s.shape[1] + 1)
+    Wp = (W + pad_to - 1) // pad_to * pad_to
+    return _TriangulationMagnitudeFrames.apply(x, anchors.contiguous(), cnn_s.contiguous(), cnn_t.contiguous(), T, Wp)
 
 
 # ----------------------------------------------------------------------------------------------

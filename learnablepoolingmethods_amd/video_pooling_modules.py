@@ -1,14 +1,14 @@
 """NetVladOrthoReg and NetVladAttenCluster (reference: video_pooling_modules.py:1499-1586, 1589-1663) and the triangulation
 embeddings (TriangulationEmbedding :376-428, WeightedTriangulationEmbedding :1395-1459, TriangulationTemporalEmbedding :1462-1497,
 TriangulationV5Module :142-373, TriangulationCnnIndirectAttentionModule :431-631, TriangulationNsCnnIndirectAttentionModule :1108-1342,
-TriangulationMagnitudeNsCnnIndirectAttentionModule :634-888)."""
+TriangulationMagnitudeNsCnnIndirectAttentionModule :634-888, TriangulationMagnitudeNsCnnNetVladModule :891-1105)."""
 from __future__ import annotations
 
 import math
 
 import torch
 
-from . import layers, module_utils, modules, ops, transformer_utils
+from . import layers, loupe_modules, module_utils, modules, ops, transformer_utils
 from . import variables as vs
 
 
@@ -482,8 +482,9 @@ class TriangulationMagnitudeNsCnnIndirectAttentionModule(TriangulationNsCnnIndir
                          batch_norm, is_training, scope_id)
         self.add_norm = add_norm
 
-    def pool(self, inputs):
-        """inputs [(B*max_frames), D] -> (spatial_pool, temporal_pool), each [B, 2 (K*F + K)] (2 K*F without ``add_norm``; :684-814)."""
+    def _features(self, inputs, add_norm):
+        """inputs [(B*max_frames), D] -> per stream (out [B, T', K*F + K] = [relu(conv) | norm] (K*F columns without ``add_norm``), the
+        normalised embedding [(B*T'), K*D]); T' = T and T - 1 (:684-801).  Shared with TriangulationMagnitudeNsCnnNetVladModule.frames."""
         D, K, F, T = self.feature_size, self.anchor_size, self.kernel_size, self.max_frames
         anchor_weights, spatial_cnn_weights, temporal_cnn_weights = self.variables(inputs.device)
         spatial = inputs.unsqueeze(1) - anchor_weights.t().unsqueeze(0)                                # :692-701 -> [M, K, D]
@@ -493,12 +494,20 @@ class TriangulationMagnitudeNsCnnIndirectAttentionModule(TriangulationNsCnnIndir
         temporal = temporal.reshape(-1, T, K * D)[:, 1:].reshape(-1, K, D)                             # :720-725
         temporal_norm = torch.linalg.vector_norm(temporal, dim=2)                                      # :726
         temporal = layers.l2_normalize(temporal, 2).reshape(-1, K * D)                                 # :732
-        pools = []
+        streams = []
         for v, norm, cnn, Tz in ((spatial, spatial_norm, spatial_cnn_weights, T), (temporal, temporal_norm, temporal_cnn_weights, T - 1)):
             out = v.reshape(-1, K, D).transpose(0, 1).matmul(cnn.transpose(1, 2)).transpose(0, 1).reshape(-1, Tz, K * F)   # :777-791
             out = torch.relu(out)                                                                      # :793-794
-            if self.add_norm:
+            if add_norm:
                 out = torch.cat([out, norm.reshape(-1, Tz, K)], 2)                                     # :799-801
+            streams.append((out, v))
+        return streams
+
+    def pool(self, inputs):
+        """inputs [(B*max_frames), D] -> (spatial_pool, temporal_pool), each [B, 2 (K*F + K)] (2 K*F without ``add_norm``; :684-814)."""
+        K, D, T = self.anchor_size, self.feature_size, self.max_frames
+        pools = []
+        for (out, v), Tz in zip(self._features(inputs, self.add_norm), (T, T - 1)):
             if self.self_attention:
                 v = v.reshape(-1, Tz, K * D)                                                           # (C39: the frames of a clip)
                 weight = torch.softmax(torch.relu(v.matmul(v.transpose(1, 2))).sum(dim=2), dim=1)      # :741-756
@@ -513,3 +522,67 @@ class TriangulationMagnitudeNsCnnIndirectAttentionModule(TriangulationNsCnnIndir
         anchor_weights, spatial_cnn_weights, temporal_cnn_weights = self.variables(inputs.device)
         return ops.triangulation_magnitude_moments(inputs, anchor_weights, spatial_cnn_weights, temporal_cnn_weights, self.max_frames,
                                                    self_attention=bool(self.self_attention), add_norm=bool(self.add_norm))
+
+
+class TriangulationMagnitudeNsCnnNetVladModule(TriangulationMagnitudeNsCnnIndirectAttentionModule):
+    """:891-1105 (JuhanTestModelV4's module): the sibling's front end -- the twice-normalised embedding, the rectified per-anchor
+    convolutions and the two norm columns -- handed PER FRAME to a ``loupe_modules.NetVLAD`` per stream (scopes ``spatial_vlad`` and
+    ``temporal_vlad``, max_samples T and T - 1, ``cluster_size`` clusters: 256 as written, :1043) in place of the moments and the hidden
+    layers; then the sibling's batch norms, optional relu and fusion layer.  As written ``self_attention`` and ``add_norm`` are taken and
+    never read: there is no Gram, and the norm columns are always appended.  ``frames`` MATERIALISES [(B*T), K*D] several
+    times: the drop-in surface and the CPU path; ``fused_frames`` (ops.triangulation_magnitude_frames) + ``head`` is the fused one."""
+
+    def __init__(self, feature_size, max_frames, anchor_size, self_attention, hidden_layer_size, kernel_size, output_dim, add_relu,
+                 add_norm, batch_norm, is_training, scope_id=None, cluster_size=256):
+        super().__init__(feature_size, max_frames, anchor_size, self_attention, hidden_layer_size, kernel_size, output_dim, add_relu,
+                         add_norm, batch_norm, is_training, scope_id)
+        self.cluster_size = int(cluster_size)
+
+    def frames(self, inputs):
+        """inputs [(B*max_frames), D] -> (spatial_output [(B*T), K*F + K], temporal_output [(B*(T-1)), K*F + K]) (:938-1039)."""
+        W = self.anchor_size * self.kernel_size + self.anchor_size
+        (out_s, _), (out_t, _) = self._features(inputs, True)
+        return out_s.reshape(-1, W), out_t.reshape(-1, W)
+
+    def fused_frames(self, inputs):
+        """``frames`` through ops.triangulation_magnitude_frames: the same variables in the same order.  The rows come zero-padded to the
+        width loupe_modules.NetVLAD hands to ops.netvlad (loupe_modules.padded_size), when it will."""
+        anchor_weights, spatial_cnn_weights, temporal_cnn_weights = self.variables(inputs.device)
+        W, T = self.anchor_size * self.kernel_size + self.anchor_size, self.max_frames
+        pad = all(loupe_modules.fused_ok(Tz, W, self.cluster_size) for Tz in (T, T - 1))
+        return ops.triangulation_magnitude_frames(inputs, anchor_weights, spatial_cnn_weights, temporal_cnn_weights, T,
+                                                  pad_to=loupe_modules.padded_size(W, self.cluster_size) if pad else 1)
+
+    def pool(self, inputs):
+        raise NotImplementedError("TriangulationMagnitudeNsCnnNetVladModule pools with NetVLAD: frames / fused_frames + head")
+
+    fused_pool = pool
+
+    def head(self, spatial_output, temporal_output):
+        """The two streams' per-frame rows -> [B, output_dim] (:1040-1105)."""
+        dev, T = spatial_output.device, self.max_frames
+        W = self.anchor_size * self.kernel_size + self.anchor_size
+
+        def bn(x, scope):
+            return layers.batch_norm(x, self.is_training, scope) if self.batch_norm else x
+
+        def act(x):
+            return torch.relu(x) if self.add_relu else x
+        spatial_vlad, temporal_vlad = (loupe_modules.NetVLAD(feature_size=W, max_samples=Tz, cluster_size=self.cluster_size,
+                                                             output_dim=self.hidden_layer_size, gating=False,
+                                                             add_batch_norm=self.batch_norm, is_training=self.is_training)
+                                       for Tz in (T, T - 1))                                                              # :1041-1055
+        with vs.variable_scope("spatial_vlad"):
+            spatial_agg = spatial_vlad.forward(spatial_output)                                                           # :1056-1057
+        with vs.variable_scope("temporal_vlad"):
+            temporal_agg = temporal_vlad.forward(temporal_output)                                                        # :1059-1060
+        spatial_agg = act(bn(spatial_agg, "spatial_activation_bn"))                                                      # :1062-1079
+        temporal_agg = act(bn(temporal_agg, "temporal_activation_bn"))
+        spatial_temporal_concat = torch.cat([spatial_agg, temporal_agg], 1)                                              # :1084
+        sp_weights = vs.get_variable("spa_temp_fusion", [spatial_temporal_concat.shape[1], self.output_dim],
+                                     vs.random_normal_initializer(1 / math.sqrt(self.output_dim)), device=dev)           # :1086-1091
+        return act(bn(spatial_temporal_concat.matmul(sp_weights), "activation_bn"))                                      # :1093-1102
+
+    def forward(self, inputs, **unused_params):
+        """inputs [(B*max_frames), D] -> [B, output_dim]."""
+        return self.head(*self.frames(inputs))
