@@ -656,6 +656,49 @@ static int tb_check(const char* name, int B, int T, int D, int K) {
     return LPM_OK;
 }
 
+// the body of the two Gram entries: the slices' partial Grams (or the Grams themselves with one slice), then their sums in slice order;
+// it [B T, K] is read under MAG only
+template <bool MAG>
+static int tb_gram_launch(const char* name, const float* x, const float* anchors, const float* iq, const float* it, const float* aff, int B, int T,
+                          int D, int K, float* gram_s, float* gram_t, void* workspace, size_t workspace_bytes, hipStream_t s) {
+    if (const int rc = tb_check(name, B, T, D, K)) return rc;
+    const size_t need = lpm_triangulation_bn_moments_workspace_bytes(1, B, T, D, K);
+    LPM_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), LPM_ERR_WORKSPACE, "%s: workspace too small", name);
+    const int S = tb_slices(B, T, K), NT = ta_tiles(T), T1 = T - 1;
+    float* part_s = S > 1 ? (float*)workspace : gram_s;
+    float* part_t = S > 1 ? part_s + (size_t)B * S * T * T : gram_t;
+    const dim3 grid((unsigned)(B * S * NT * NT)), block(64 * TA_WAVES);
+    tp_dispatch_d(D, [&](auto d) {
+        hipLaunchKernelGGL((tb_gram_kernel<decltype(d)::value, MAG>), grid, block, 0, s, x, anchors, iq, it, aff, T, K, S, NT, part_s, part_t);
+    });
+    if (S > 1) {
+        if (const int rc = ta_sum_slices(part_s, B, (int64_t)T * T, S, gram_s, s, name)) return rc;
+        if (const int rc = ta_sum_slices(part_t, B, (int64_t)T1 * T1, S, gram_t, s, name)) return rc;
+    }
+    return check_launch(name);
+}
+
+// What the three chains share.  A arrives value-initialised with the fields its policy reads and the entry's carving of the workspace
+// (dot, da_part among it); this fills in the operands every policy reads, runs the entry's own `sweep1(d, A, grid_k, block, lds)` -- the
+// sweeps in front of the other two differ in kind --, then sweeps 2 and 3 and the sum of the danchors partials.
+template <bool CONV, bool MAG, class Sweep1>
+static int tb_chain_launch(const char* name, TbBwdArgs A, const float* x, const float* anchors, const float* q, const float* m_s, const float* m_t,
+                           int B, int T, int D, int K, float* dx, float* danchors, hipStream_t s, Sweep1 sweep1) {
+    A.x = x; A.anchors = anchors; A.q = q; A.iq = q + (int64_t)B * T * K; A.m_s = m_s; A.m_t = m_t;
+    A.B = B; A.T = T; A.K = K;
+    A.dx = dx;
+    const size_t lds = tb_bwd_lds(T);
+    const dim3 block(64 * TA_WAVES), grid_k((unsigned)(B * K)), grid_c((unsigned)(B * (D / TA_CH)));
+    tp_dispatch_d(D, [&](auto d) {
+        constexpr int DD = decltype(d)::value;
+        sweep1(d, A, grid_k, block, lds);
+        hipLaunchKernelGGL((tb_bwd_kernel<DD, 2, CONV, MAG>), grid_k, block, lds, s, A);
+        hipLaunchKernelGGL((tb_bwd_kernel<DD, 3, CONV, MAG>), grid_c, block, lds, s, A);
+    });
+    if (const int rc = ta_reduce_partials(dx, A.da_part, B, T, D, K, 1, TP_SUM_CHUNK, dx, danchors, s, name)) return rc;
+    return check_launch(name);
+}
+
 }  // namespace lpm
 
 extern "C" size_t lpm_triangulation_bn_moments_workspace_bytes(int which, int B, int T, int D, int K) {
@@ -705,23 +748,7 @@ extern "C" int lpm_triangulation_bn_moments_gram(const float* x, const float* an
     using namespace lpm;
     const char* name = "lpm_triangulation_bn_moments_gram";
     LPM_REQUIRE(x && anchors && iq && aff && gram_s && gram_t, LPM_ERR_BADARG, "%s: null pointer", name);
-    if (const int rc = tb_check(name, B, T, D, K)) return rc;
-    const size_t need = lpm_triangulation_bn_moments_workspace_bytes(1, B, T, D, K);
-    LPM_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), LPM_ERR_WORKSPACE, "%s: workspace too small", name);
-    const int S = tb_slices(B, T, K), NT = ta_tiles(T), T1 = T - 1;
-    float* part_s = S > 1 ? (float*)workspace : gram_s;
-    float* part_t = S > 1 ? part_s + (size_t)B * S * T * T : gram_t;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)(B * S * NT * NT)), block(64 * TA_WAVES);
-    tp_dispatch_d(D, [&](auto d) {
-        hipLaunchKernelGGL(tb_gram_kernel<decltype(d)::value>, grid, block, 0, s, x, anchors, iq, (const float*)nullptr, aff, T, K, S, NT, part_s,
-                           part_t);
-    });
-    if (S > 1) {
-        if (const int rc = ta_sum_slices(part_s, B, (int64_t)T * T, S, gram_s, s, name)) return rc;
-        if (const int rc = ta_sum_slices(part_t, B, (int64_t)T1 * T1, S, gram_t, s, name)) return rc;
-    }
-    return check_launch(name);
+    return tb_gram_launch<false>(name, x, anchors, iq, nullptr, aff, B, T, D, K, gram_s, gram_t, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int lpm_triangulation_bn_moments_pool(const float* x, const float* anchors, const float* iq, const float* aff, const float* w_s,
@@ -769,36 +796,25 @@ extern "C" int lpm_triangulation_bn_moments_bwd(const float* x, const float* anc
     hipStream_t s = (hipStream_t)stream;
     const int64_t BT = (int64_t)B * T;
     const int J = K * D;
-    const size_t lds = tb_bwd_lds(T);
     if (const int rc = tp_reserve_lds<tb_bwd_kernel<1024, 1>, tb_bwd_kernel<1024, 2>, tb_bwd_kernel<1024, 3>, tb_bwd_kernel<128, 1>,
                                       tb_bwd_kernel<128, 2>, tb_bwd_kernel<128, 3>>(name, (int)tb_bwd_lds(TA_MAX_FRAMES)))
         return rc;
-    TbBwdArgs A;
-    A.x = x; A.anchors = anchors; A.q = q; A.iq = q + BT * K; A.aff = aff; A.w_s = w_s; A.w_t = w_t; A.m_s = m_s; A.m_t = m_t;
-    A.rawbar = rawbar; A.corr = corr; A.g_s = g_s; A.g_t = g_t; A.dgrad = dgrad;
+    TbBwdArgs A{};
+    A.aff = aff; A.w_s = w_s; A.w_t = w_t; A.rawbar = rawbar; A.corr = corr; A.g_s = g_s; A.g_t = g_t; A.dgrad = dgrad;
     A.inv_ns = training ? 1.f / (float)BT : 0.f;
     A.inv_nt = training ? 1.f / (float)(BT - B) : 0.f;
-    A.B = B; A.T = T; A.K = K;
-    A.cnn_s = A.cnn_t = A.dso = A.dto = nullptr; A.F = 0;
-    A.it = A.dtg = A.dng = A.p = nullptr; A.s1g = nullptr;
     A.dpart = (float*)workspace;
     A.dot = A.dpart + (size_t)4 * B * J;
     A.da_part = A.dot + (size_t)BT * K;
-    A.dx = dx;
-    const dim3 block(64 * TA_WAVES), grid_k((unsigned)(B * K)), grid_c((unsigned)(B * (D / TA_CH)));
-    tp_dispatch_d(D, [&](auto d) {
-        constexpr int DD = decltype(d)::value;
+    return tb_chain_launch<false, false>(name, A, x, anchors, q, m_s, m_t, B, T, D, K, dx, danchors, s,
+                                         [&](auto d, const TbBwdArgs& args, dim3 grid_k, dim3 block, size_t lds) {
         if (affine_grads) {
-            hipLaunchKernelGGL((tb_bwd_kernel<DD, 1>), grid_k, block, lds, s, A);
-            hipLaunchKernelGGL(tb_colsum_kernel, dim3((J + 255) / 256, 4), dim3(256), 0, s, A.dpart, B, J, (int64_t)J, 1.f, 1.f, 0, dgrad);
+            hipLaunchKernelGGL((tb_bwd_kernel<decltype(d)::value, 1>), grid_k, block, lds, s, args);
+            hipLaunchKernelGGL(tb_colsum_kernel, dim3((J + 255) / 256, 4), dim3(256), 0, s, args.dpart, B, J, (int64_t)J, 1.f, 1.f, 0, dgrad);
         } else {
             (void)hipMemsetAsync(dgrad, 0, (size_t)4 * J * sizeof(float), s);
         }
-        hipLaunchKernelGGL((tb_bwd_kernel<DD, 2>), grid_k, block, lds, s, A);
-        hipLaunchKernelGGL((tb_bwd_kernel<DD, 3>), grid_c, block, lds, s, A);
     });
-    if (const int rc = ta_reduce_partials(dx, A.da_part, B, T, D, K, 1, TP_SUM_CHUNK, dx, danchors, s, name)) return rc;
-    return check_launch(name);
 }
 
 // ---- the chain of triangulation_cnn_attention (TriangulationNsCnnIndirectAttentionModule, JuhanTestModelV2): tb_bwd's sweeps 2 and 3 under the
@@ -820,31 +836,15 @@ extern "C" int lpm_triangulation_cnn_attention_bwd(const float* x, const float* 
     LPM_REQUIRE(F >= 1 && (int64_t)B * T * K * F < (1ll << 31), LPM_ERR_UNSUPPORTED_SHAPE, "%s: need F >= 1 and B * T * K * F < 2^31 (F=%d)", name, F);
     LPM_REQUIRE(workspace && workspace_bytes >= lpm_triangulation_cnn_attention_workspace_bytes(B, T, D, K), LPM_ERR_WORKSPACE,
                 "%s: workspace too small", name);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t BT = (int64_t)B * T;
-    const size_t lds = tb_bwd_lds(T);
     if (const int rc = tp_reserve_lds<tb_bwd_kernel<1024, 2, true>, tb_bwd_kernel<1024, 3, true>, tb_bwd_kernel<128, 2, true>,
                                       tb_bwd_kernel<128, 3, true>>(name, (int)tb_bwd_lds(TA_MAX_FRAMES)))
         return rc;
-    TbBwdArgs A;
-    A.x = x; A.anchors = anchors; A.q = q; A.iq = q + BT * K; A.aff = nullptr; A.w_s = A.w_t = nullptr; A.m_s = m_s; A.m_t = m_t;
-    A.rawbar = A.corr = A.g_s = A.g_t = A.dgrad = nullptr;
-    A.inv_ns = A.inv_nt = 0.f;
-    A.B = B; A.T = T; A.K = K;
+    TbBwdArgs A{};
     A.cnn_s = cnn_s; A.cnn_t = cnn_t; A.dso = dso; A.dto = dto; A.F = F;
-    A.it = A.dtg = A.dng = A.p = nullptr; A.s1g = nullptr;
-    A.dpart = nullptr;
     A.dot = (float*)workspace;
-    A.da_part = A.dot + (size_t)BT * K;
-    A.dx = dx;
-    const dim3 block(64 * TA_WAVES), grid_k((unsigned)(B * K)), grid_c((unsigned)(B * (D / TA_CH)));
-    tp_dispatch_d(D, [&](auto d) {
-        constexpr int DD = decltype(d)::value;
-        hipLaunchKernelGGL((tb_bwd_kernel<DD, 2, true>), grid_k, block, lds, s, A);
-        hipLaunchKernelGGL((tb_bwd_kernel<DD, 3, true>), grid_c, block, lds, s, A);
-    });
-    if (const int rc = ta_reduce_partials(dx, A.da_part, B, T, D, K, 1, TP_SUM_CHUNK, dx, danchors, s, name)) return rc;
-    return check_launch(name);
+    A.da_part = A.dot + (size_t)B * T * K;
+    return tb_chain_launch<true, false>(name, A, x, anchors, q, m_s, m_t, B, T, D, K, dx, danchors, (hipStream_t)stream,
+                                        [](auto, const TbBwdArgs&, dim3, dim3, size_t) {});      // no batch norm: no sweep 1
 }
 
 // ---- triangulation_magnitude (TriangulationMagnitudeNsCnnIndirectAttentionModule, JuhanTestModelV3): the Grams with the temporal operand
@@ -856,24 +856,9 @@ extern "C" int lpm_triangulation_magnitude_gram(const float* x, const float* anc
     using namespace lpm;
     const char* name = "lpm_triangulation_magnitude_gram";
     LPM_REQUIRE(x && anchors && q && p && aff && gram_s && gram_t, LPM_ERR_BADARG, "%s: null pointer", name);
-    if (const int rc = tb_check(name, B, T, D, K)) return rc;
-    const size_t need = lpm_triangulation_bn_moments_workspace_bytes(1, B, T, D, K);
-    LPM_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), LPM_ERR_WORKSPACE, "%s: workspace too small", name);
-    const int S = tb_slices(B, T, K), NT = ta_tiles(T), T1 = T - 1;
-    const int64_t BTK = (int64_t)B * T * K;
-    float* part_s = S > 1 ? (float*)workspace : gram_s;
-    float* part_t = S > 1 ? part_s + (size_t)B * S * T * T : gram_t;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)(B * S * NT * NT)), block(64 * TA_WAVES);
-    tp_dispatch_d(D, [&](auto d) {
-        hipLaunchKernelGGL((tb_gram_kernel<decltype(d)::value, true>), grid, block, 0, s, x, anchors, q + BTK, p + BTK, aff, T, K, S, NT, part_s,
-                           part_t);
-    });
-    if (S > 1) {
-        if (const int rc = ta_sum_slices(part_s, B, (int64_t)T * T, S, gram_s, s, name)) return rc;
-        if (const int rc = ta_sum_slices(part_t, B, (int64_t)T1 * T1, S, gram_t, s, name)) return rc;
-    }
-    return check_launch(name);
+    const int64_t BTK = (int64_t)B * T * K;                // (tb_check comes first in the launcher: nothing is read through these before it)
+    return tb_gram_launch<true>(name, x, anchors, q + BTK, p + BTK, aff, B, T, D, K, gram_s, gram_t, workspace, workspace_bytes,
+                                (hipStream_t)stream);
 }
 
 extern "C" size_t lpm_triangulation_magnitude_workspace_bytes(int B, int T, int D, int K) {
@@ -895,30 +880,18 @@ extern "C" int lpm_triangulation_magnitude_bwd(const float* x, const float* anch
                 "%s: workspace too small", name);
     hipStream_t s = (hipStream_t)stream;
     const int64_t BT = (int64_t)B * T;
-    const size_t lds = tb_bwd_lds(T);
     if (const int rc = tp_reserve_lds<tb_mag_s1_kernel<1024>, tb_mag_s1_kernel<128>, tb_bwd_kernel<1024, 2, true, true>,
                                       tb_bwd_kernel<1024, 3, true, true>, tb_bwd_kernel<128, 2, true, true>, tb_bwd_kernel<128, 3, true, true>>(
             name, (int)tb_bwd_lds(TA_MAX_FRAMES)))
         return rc;
-    TbBwdArgs A;
-    A.x = x; A.anchors = anchors; A.q = q; A.iq = q + BT * K; A.aff = nullptr; A.w_s = A.w_t = nullptr; A.m_s = m_s; A.m_t = m_t;
-    A.rawbar = A.corr = A.g_s = A.g_t = A.dgrad = nullptr;
-    A.inv_ns = A.inv_nt = 0.f;
-    A.B = B; A.T = T; A.K = K;
+    TbBwdArgs A{};
     A.cnn_s = cnn_s; A.cnn_t = cnn_t; A.dso = dso; A.dto = dto; A.F = F;
     A.p = p; A.it = p + BT * K; A.dtg = dtg; A.dng = dng;
-    A.dpart = nullptr;
     A.s1g = (float*)workspace;
     A.dot = A.s1g + (size_t)BT * K;
     A.da_part = A.dot + (size_t)BT * K;
-    A.dx = dx;
-    const dim3 block(64 * TA_WAVES), grid_k((unsigned)(B * K)), grid_c((unsigned)(B * (D / TA_CH)));
-    tp_dispatch_d(D, [&](auto d) {
-        constexpr int DD = decltype(d)::value;
-        hipLaunchKernelGGL(tb_mag_s1_kernel<DD>, grid_k, block, lds, s, A);
-        hipLaunchKernelGGL((tb_bwd_kernel<DD, 2, true, true>), grid_k, block, lds, s, A);
-        hipLaunchKernelGGL((tb_bwd_kernel<DD, 3, true, true>), grid_c, block, lds, s, A);
+    return tb_chain_launch<true, true>(name, A, x, anchors, q, m_s, m_t, B, T, D, K, dx, danchors, s,
+                                       [&](auto d, const TbBwdArgs& args, dim3 grid_k, dim3 block, size_t lds) {
+        hipLaunchKernelGGL(tb_mag_s1_kernel<decltype(d)::value>, grid_k, block, lds, s, args);
     });
-    if (const int rc = ta_reduce_partials(dx, A.da_part, B, T, D, K, 1, TP_SUM_CHUNK, dx, danchors, s, name)) return rc;
-    return check_launch(name);
 }

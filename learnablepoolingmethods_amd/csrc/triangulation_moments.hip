@@ -14,7 +14,7 @@
 //
 // forward: tv_norms (one wave per frame row and 16 anchors: q, p by direct sums of squares) -> tv_conv (a workgroup owns an anchor, 32
 // filters and 128 frame rows ACROSS clips: per 32-column chunk of D the e and h tiles [128, 33] and the two weight tiles go to LDS, one
-// 32x32 product per wave and stream; the row tiles of one weight tile are neighbours in the grid) -> tv_moments (a thread per clip and
+// 32x32 product per wave and stream; the row tiles of one weight tile are neighbours in the grid) -> tm_pool (a thread per clip and
 // column: the mean, then the squared deviations from it, both two-level over t).
 //
 // backward, with (gm, gv) the upstream gradient of a pool and T' its frame count: dout[t] = (gm + 2 gv ((out[t] - mean) - c)) / T', where
@@ -221,46 +221,74 @@ __global__ __launch_bounds__(64 * TA_WAVES) void tv_conv_kernel(const float* __r
     }
 }
 
-// a thread per (clip, column of [conv | norm]): the mean over the frames, then the mean of the squared deviations from it and the mean of
-// the deviations themselves (corr [2, B, W]: the rounding error of the mean, which the backward takes out again); blockIdx.y = pool
-__global__ __launch_bounds__(256) void tv_moments_kernel(const float* __restrict__ so, const float* __restrict__ to, const float* __restrict__ q,
-                                                         const float* __restrict__ p, int B, int T, int K, int F, float* __restrict__ pool_s,
-                                                         float* __restrict__ pool_t, float* __restrict__ corr) {
-    const int64_t KF = (int64_t)K * F, W = KF + K;
+// one column of tm_pool, its values `stride` floats apart from frame z on (norm: squared norms, their roots taken as they are read): the
+// plain mean, then the deviations from it -- sum_t w_t val, the mean, the mean of the squared deviations and the mean of the deviations
+// themselves (what the rounded mean is off by); every sum over t two-level.  ROOTS: some lane of the wave walks a norm column.  The
+// walks are bound by their chain of loads and what hangs on it, so a wave of convolution columns alone takes the instantiation without
+// the root, and a mixed wave walks once with a select per lane, not once per kind.
+template <bool ROOTS>
+__device__ __forceinline__ void tm_pool_column(const float* __restrict__ v, int64_t stride, bool norm, const float* __restrict__ w, int z, int T,
+                                               float cnt, float& wsum, float& mean, float& var, float& corr) {
+    float tot = 0.f, acc = 0.f, wtot = 0.f, wacc = 0.f;
+    for (int t = z; t < T; ++t) {
+        const float val = (ROOTS && norm) ? sqrtf(v[t * stride]) : v[t * stride];
+        acc += val;
+        if (w) wacc = fmaf(w[t - z], val, wacc);
+        if (((t - z) & (TP_SUM_CHUNK - 1)) == TP_SUM_CHUNK - 1) {
+            tot += acc;
+            wtot += wacc;
+            acc = wacc = 0.f;
+        }
+    }
+    mean = (tot + acc) / cnt;
+    wsum = wtot + wacc;
+    float dtot = 0.f, dacc = 0.f;
+    tot = acc = 0.f;
+    for (int t = z; t < T; ++t) {
+        const float dev = ((ROOTS && norm) ? sqrtf(v[t * stride]) : v[t * stride]) - mean;
+        acc = fmaf(dev, dev, acc);
+        dacc += dev;
+        if (((t - z) & (TP_SUM_CHUNK - 1)) == TP_SUM_CHUNK - 1) {
+            tot += acc;
+            dtot += dacc;
+            acc = dacc = 0.f;
+        }
+    }
+    var = (tot + acc) / cnt;
+    corr = (dtot + dacc) / cnt;
+}
+
+// The moments of all three pooled ops.  A thread per (clip, column of [conv | norm]), blockIdx.y = stream: pool [B, 2 W] = [(1/T') sum_t w_t out_t
+// (the plain mean where the weights are null) | the mean of the squared deviations from the plain mean]; mean_out (nullable: without
+// weights it is the pool's own first half) and corr_out, element z zstride + b W + j = the stream's plain mean and the rounding error
+// of that mean, which the backward takes out again.  W = K F + NC with NC = K norm columns sqrt(q), sqrt(p), or NC = 0 without them (q, p
+// are then unread and may be null).
+__global__ __launch_bounds__(256) void tm_pool_kernel(const float* __restrict__ so, const float* __restrict__ to, const float* __restrict__ q,
+                                                      const float* __restrict__ p, const float* __restrict__ w_s, const float* __restrict__ w_t,
+                                                      int B, int T, int K, int F, int NC, float* __restrict__ pool_s, float* __restrict__ pool_t,
+                                                      float* __restrict__ mean_out, float* __restrict__ corr_out, int64_t zstride) {
+    const int64_t KF = (int64_t)K * F, W = KF + NC;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= B * W) return;
     const int64_t b = i / W, j = i % W;
-    const bool temporal = blockIdx.y == 1, conv = j < KF;
-    const int lo = temporal ? 1 : 0;
-    const float* v = conv ? (temporal ? to : so) + b * T * KF + j : (temporal ? p : q) + b * T * K + (j - KF);
-    const int64_t stride = conv ? KF : K;
-    const float cnt = (float)(T - lo);
-    float tot = 0.f, part = 0.f;
-    for (int t = lo; t < T; ++t) {
-        const float val = conv ? v[t * stride] : sqrtf(v[t * stride]);
-        part += val;
-        if (((t - lo) & (TP_SUM_CHUNK - 1)) == TP_SUM_CHUNK - 1) {
-            tot += part;
-            part = 0.f;
-        }
-    }
-    const float mean = (tot + part) / cnt;
-    tot = part = 0.f;
-    float dtot = 0.f, dpart = 0.f;                         // the deviations' own sum: what the rounded mean is off by, times the count
-    for (int t = lo; t < T; ++t) {
-        const float dev = (conv ? v[t * stride] : sqrtf(v[t * stride])) - mean;
-        part = fmaf(dev, dev, part);
-        dpart += dev;
-        if (((t - lo) & (TP_SUM_CHUNK - 1)) == TP_SUM_CHUNK - 1) {
-            tot += part;
-            dtot += dpart;
-            part = dpart = 0.f;
-        }
-    }
-    float* pool = (temporal ? pool_t : pool_s) + b * 2 * W;
-    pool[j] = mean;
-    pool[W + j] = (tot + part) / cnt;
-    corr[((int64_t)blockIdx.y * B + b) * W + j] = (dtot + dpart) / cnt;
+    const int z = blockIdx.y, Tz = T - z;
+    const bool norm = j >= KF;
+    const float* v = norm ? (z ? p : q) + b * T * K + (j - KF) : (z ? to : so) + b * T * KF + j;
+    const int64_t stride = norm ? K : KF;
+    const float* w = z ? w_t : w_s;                          // null: the plain mean
+    if (w) w += b * Tz;
+    const float cnt = (float)Tz;
+    float wsum, mean, var, corr;
+    if (__ballot(norm) != 0)                               // (uniform over the wave)
+        tm_pool_column<true>(v, stride, norm, w, z, T, cnt, wsum, mean, var, corr);
+    else
+        tm_pool_column<false>(v, stride, false, w, z, T, cnt, wsum, mean, var, corr);
+    float* pool = (z ? pool_t : pool_s) + b * 2 * W;
+    pool[j] = w ? wsum / cnt : mean;
+    pool[W + j] = var;
+    const int64_t o = z * zstride + b * W + j;
+    if (mean_out) mean_out[o] = mean;
+    corr_out[o] = corr;
 }
 
 // one wave per (row, anchor): dso, dto [B T, K F]; sa = sum_f dso so + ([p > eps] ? dtau tau : (h . gh)); s1g = (h . gh) [p > eps];
@@ -552,6 +580,18 @@ static int tv_check(const char* name, int B, int T, int D, int K, int F) {
     return LPM_OK;
 }
 
+// tv_conv's launch: a workgroup per (anchor, 32 filters, 128 rows); iq, it [B T, K] scale the spatial and the temporal operand
+template <bool RELU, bool FRAMES>
+static void tv_conv_launch(const float* x, const float* anchors, const float* cnn_s, const float* cnn_t, const float* iq, const float* it, int B,
+                           int T, int D, int K, int F, float* so, float* to, const TvFrames fr, hipStream_t s) {
+    const int64_t BT = (int64_t)B * T;
+    const int NR = tv_row_tiles(BT), NF = (F + 31) / 32;
+    tp_dispatch_d(D, [&](auto d) {
+        hipLaunchKernelGGL((tv_conv_kernel<decltype(d)::value, RELU, FRAMES>), dim3((unsigned)((int64_t)K * NF * NR)), dim3(64 * TA_WAVES), 0, s, x,
+                           anchors, cnn_s, cnn_t, iq, it, BT, K, F, NR, so, to, fr);
+    });
+}
+
 }  // namespace lpm
 
 extern "C" size_t lpm_triangulation_moments_workspace_bytes(int B, int T, int D, int K, int F) {
@@ -572,17 +612,15 @@ extern "C" int lpm_triangulation_moments_fwd(const float* x, const float* anchor
     LPM_REQUIRE(((uintptr_t)x & 15) == 0, LPM_ERR_BADARG, "%s: x must be 16-byte aligned", name);
     hipStream_t s = (hipStream_t)stream;
     const int64_t BT = (int64_t)B * T;
-    const int NR = tv_row_tiles(BT), NF = (F + 31) / 32;
-    const dim3 block(64 * TA_WAVES);
-    const dim3 grid_n((unsigned)((BT * ((K + TV_KC - 1) / TV_KC) + TA_WAVES - 1) / TA_WAVES)), grid_c((unsigned)((int64_t)K * NF * NR));
+    const dim3 grid_n((unsigned)((BT * ((K + TV_KC - 1) / TV_KC) + TA_WAVES - 1) / TA_WAVES));
     tp_dispatch_d(D, [&](auto d) {
-        constexpr int DD = decltype(d)::value;
-        hipLaunchKernelGGL(tv_norms_kernel<DD>, grid_n, block, 0, s, x, anchors, BT, T, K, q, p);
-        hipLaunchKernelGGL(tv_conv_kernel<DD>, grid_c, block, 0, s, x, anchors, cnn_s, cnn_t, q + BT * K, p + BT * K, BT, K, F, NR, so, to,
-                           TvFrames{});
+        hipLaunchKernelGGL(tv_norms_kernel<decltype(d)::value>, grid_n, dim3(64 * TA_WAVES), 0, s, x, anchors, BT, T, K, q, p);
     });
-    const int64_t cols = (int64_t)B * ((int64_t)K * F + K);
-    hipLaunchKernelGGL(tv_moments_kernel, dim3((unsigned)((cols + 255) / 256), 2), dim3(256), 0, s, so, to, q, p, B, T, K, F, pool_s, pool_t, corr);
+    tv_conv_launch<false, false>(x, anchors, cnn_s, cnn_t, q + BT * K, p + BT * K, B, T, D, K, F, so, to, TvFrames{}, s);
+    // no weights: the plain mean is the pool's first half, and only corr [2, B, W] is kept beside it
+    const int64_t W = (int64_t)K * F + K, cols = B * W;
+    hipLaunchKernelGGL(tm_pool_kernel, dim3((unsigned)((cols + 255) / 256), 2), dim3(256), 0, s, so, to, q, p, (const float*)nullptr,
+                       (const float*)nullptr, B, T, K, F, K, pool_s, pool_t, (float*)nullptr, corr, B * W);
     return check_launch(name);
 }
 
@@ -631,7 +669,7 @@ extern "C" int lpm_triangulation_moments_bwd(const float* x, const float* anchor
 // The temporal operand is g itself, NOT normalised again: tv_conv and tv_dw run as they are with `it` = ind [B T, K], 1 on the frames
 // t >= 1 and 0 on frame 0 of a clip (a product with 1 is exact), so the walks above exist once.  The pools take the softmax weights of
 // the caller's Grams:  pool = [ (1/T') sum_t w_t out_t  |  mean_t (out_t - mean_t out)^2 ]  (the plain mean without weights), and the
-// backward's  dout[t] = (w_t gm + 2 gv ((out[t] - mean) - c)) / T',  dw[t] = <gm, out[t]> / T'.
+// backward's  dout[t] = (w_t gm + 2 gv ((out[t] - mean) - c)) / T',  dw[t] = <gm, out[t]> / T':  tm_pool without norm columns and tm_dout<false>.
 namespace lpm {
 
 __global__ __launch_bounds__(256) void tc_ind_kernel(int64_t BTK, int T, int K, float* __restrict__ ind) {
@@ -639,74 +677,48 @@ __global__ __launch_bounds__(256) void tc_ind_kernel(int64_t BTK, int T, int K, 
     if (m < BTK) ind[m] = (m / K) % T ? 1.f : 0.f;
 }
 
-// a thread per (clip, column), blockIdx.y = stream: pool [B, 2 K F]; stats [2, 2, B, K F] = each stream's plain mean, then the mean of the
-// deviations from it (what the rounded mean is off by); sums over t two-level
-__global__ __launch_bounds__(256) void tc_pool_kernel(const float* __restrict__ so, const float* __restrict__ to, const float* __restrict__ w_s,
-                                                      const float* __restrict__ w_t, int B, int T, int64_t KF, float* __restrict__ pool_s,
-                                                      float* __restrict__ pool_t, float* __restrict__ stats) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= B * KF) return;
-    const int64_t b = i / KF, j = i % KF;
-    const int z = blockIdx.y, Tz = T - z;
-    const float* v = (z ? to : so) + b * T * KF + j;
-    const float* w = z ? w_t : w_s;                          // null: the plain mean
-    if (w) w += b * Tz;
-    const float cnt = (float)Tz;
-    float tot = 0.f, acc = 0.f, wtot = 0.f, wacc = 0.f;
-    for (int t = z; t < T; ++t) {
-        const float val = v[t * KF];
-        acc += val;
-        if (w) wacc = fmaf(w[t - z], val, wacc);
-        if (((t - z) & (TP_SUM_CHUNK - 1)) == TP_SUM_CHUNK - 1) {
-            tot += acc;
-            wtot += wacc;
-            acc = wacc = 0.f;
-        }
-    }
-    const float mean = (tot + acc) / cnt, wsum = wtot + wacc;
-    float dtot = 0.f, dacc = 0.f;
-    tot = acc = 0.f;
-    for (int t = z; t < T; ++t) {
-        const float dev = v[t * KF] - mean;
-        acc = fmaf(dev, dev, acc);
-        dacc += dev;
-        if (((t - z) & (TP_SUM_CHUNK - 1)) == TP_SUM_CHUNK - 1) {
-            tot += acc;
-            dtot += dacc;
-            acc = dacc = 0.f;
-        }
-    }
-    float* pool = (z ? pool_t : pool_s) + b * 2 * KF;
-    pool[j] = w ? wsum / cnt : mean;
-    pool[KF + j] = (tot + acc) / cnt;
-    float* st = stats + (int64_t)z * 2 * B * KF;
-    st[b * KF + j] = mean;
-    st[(B + b) * KF + j] = (dtot + dacc) / cnt;
-}
-
 // a workgroup per (clip, frame), blockIdx.y = stream: dout [B T, K F] (the temporal one zero on frame 0) and dw[b,t] = <gm[b], out_t> / T'
-__global__ __launch_bounds__(256) void tc_dout_kernel(const float* __restrict__ so, const float* __restrict__ to, const float* __restrict__ w_s,
-                                                      const float* __restrict__ w_t, const float* __restrict__ stats, const float* __restrict__ g_s,
-                                                      const float* __restrict__ g_t, int B, int T, int64_t KF, float* __restrict__ dso,
-                                                      float* __restrict__ dto, float* __restrict__ dw_s, float* __restrict__ dw_t) {
+// over all W = K F + NC columns (tm_pool's).  RELU (triangulation_magnitude): dout times [out > 0], and the gradient of the norm columns times
+// [squared norm > eps] into dng / dtg [B T, K] (always written: zero without the norm columns).  Without RELU (triangulation_cnn_attention)
+// there are no norm columns, NC = 0: q, p, dng and dtg are not touched and may be null.
+template <bool RELU>
+__global__ __launch_bounds__(256) void tm_dout_kernel(const float* __restrict__ so, const float* __restrict__ to, const float* __restrict__ q,
+                                                      const float* __restrict__ p, const float* __restrict__ w_s, const float* __restrict__ w_t,
+                                                      const float* __restrict__ stats, const float* __restrict__ g_s, const float* __restrict__ g_t,
+                                                      int B, int T, int K, int F, int NC, float* __restrict__ dso, float* __restrict__ dto,
+                                                      float* __restrict__ dng, float* __restrict__ dtg, float* __restrict__ dw_s,
+                                                      float* __restrict__ dw_t) {
     __shared__ float red[4];
+    const int64_t KF = (int64_t)K * F, W = KF + NC;
     const int z = blockIdx.y, b = blockIdx.x / T, t = blockIdx.x % T, Tz = T - z;
     const int64_t n = (int64_t)b * T + t;
     float* dout = (z ? dto : dso) + n * KF;
-    if (z && t == 0) {                                     // (uniform over the workgroup)
+    float* dnorm = RELU ? (z ? dtg : dng) + n * K : nullptr;
+    if (RELU && ((z && t == 0) || NC == 0))                // (uniform over the workgroup)
+        for (int k = threadIdx.x; k < K; k += 256) dnorm[k] = 0.f;
+    if (z && t == 0) {
         for (int64_t j = threadIdx.x; j < KF; j += 256) dout[j] = 0.f;
         return;
     }
     const float* out = (z ? to : so) + n * KF;
-    const float* g = (z ? g_t : g_s) + (int64_t)b * 2 * KF;
-    const float* st = stats + (int64_t)z * 2 * B * KF;
-    const float *mean = st + (int64_t)b * KF, *corr = st + (int64_t)(B + b) * KF;
+    const float* sq = RELU ? (z ? p : q) + n * K : nullptr;
+    const float* g = (z ? g_t : g_s) + (int64_t)b * 2 * W;
+    const float* st = stats + (int64_t)z * 2 * B * W;
+    const float *mean = st + (int64_t)b * W, *corr = st + (int64_t)(B + b) * W;
     const float* w = z ? w_t : w_s;
     const float wt = w ? w[(int64_t)b * Tz + t - z] : 1.f, cnt = (float)Tz;
     float acc = 0.f;
-    for (int64_t j = threadIdx.x; j < KF; j += 256) {
+    int64_t j = threadIdx.x;
+    for (; j < KF; j += 256) {                              // the convolution columns ...
         const float v = out[j], gm = g[j];
-        dout[j] = (wt * gm + 2.f * g[KF + j] * ((v - mean[j]) - corr[j])) / cnt;
+        const float d = (wt * gm + 2.f * g[W + j] * ((v - mean[j]) - corr[j])) / cnt;
+        dout[j] = (!RELU || v > 0.f) ? d : 0.f;
+        acc = fmaf(gm, v, acc);
+    }
+    for (; RELU && j < W; j += 256) {                       // ... then the norm columns, each thread going on in its own stride
+        const float s = sq[j - KF], v = sqrtf(s), gm = g[j];
+        const float d = (wt * gm + 2.f * g[W + j] * ((v - mean[j]) - corr[j])) / cnt;
+        dnorm[j - KF] = s > kL2Eps ? d : 0.f;
         acc = fmaf(gm, v, acc);
     }
     acc = wave_sum_dpp(acc);
@@ -727,13 +739,9 @@ extern "C" int lpm_triangulation_cnn_attention_conv(const float* x, const float*
     LPM_REQUIRE(x && anchors && cnn_s && cnn_t && iq && ind && so && to, LPM_ERR_BADARG, "%s: null pointer", name);
     if (const int rc = tv_check(name, B, T, D, K, F)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int64_t BT = (int64_t)B * T, BTK = BT * K;
-    const int NR = tv_row_tiles(BT), NF = (F + 31) / 32;
+    const int64_t BTK = (int64_t)B * T * K;
     hipLaunchKernelGGL(tc_ind_kernel, dim3((unsigned)((BTK + 255) / 256)), dim3(256), 0, s, BTK, T, K, ind);
-    tp_dispatch_d(D, [&](auto d) {
-        hipLaunchKernelGGL(tv_conv_kernel<decltype(d)::value>, dim3((unsigned)((int64_t)K * NF * NR)), dim3(64 * TA_WAVES), 0, s, x, anchors, cnn_s,
-                           cnn_t, iq, ind, BT, K, F, NR, so, to, TvFrames{});
-    });
+    tv_conv_launch<false, false>(x, anchors, cnn_s, cnn_t, iq, ind, B, T, D, K, F, so, to, TvFrames{}, s);
     return check_launch(name);
 }
 
@@ -743,9 +751,9 @@ extern "C" int lpm_triangulation_cnn_attention_pool(const float* so, const float
     const char* name = "lpm_triangulation_cnn_attention_pool";
     LPM_REQUIRE(so && to && pool_s && pool_t && stats && !w_s == !w_t, LPM_ERR_BADARG, "%s: null pointer", name);
     if (const int rc = tv_check(name, B, T, 128, K, F)) return rc;
-    const int64_t KF = (int64_t)K * F, cols = B * KF;
-    hipLaunchKernelGGL(tc_pool_kernel, dim3((unsigned)((cols + 255) / 256), 2), dim3(256), 0, (hipStream_t)stream, so, to, w_s, w_t, B, T, KF, pool_s,
-                       pool_t, stats);
+    const int64_t cols = (int64_t)B * K * F;                // stats [2, 2, B, K F]: each stream's mean, then its corr
+    hipLaunchKernelGGL(tm_pool_kernel, dim3((unsigned)((cols + 255) / 256), 2), dim3(256), 0, (hipStream_t)stream, so, to, (const float*)nullptr,
+                       (const float*)nullptr, w_s, w_t, B, T, K, F, 0, pool_s, pool_t, stats, stats + cols, 2 * cols);
     return check_launch(name);
 }
 
@@ -757,8 +765,8 @@ extern "C" int lpm_triangulation_cnn_attention_dout(const float* so, const float
     LPM_REQUIRE(so && to && stats && g_s && g_t && dso && dto && !w_s == !w_t && !w_s == !dw_s && !w_t == !dw_t, LPM_ERR_BADARG,
                 "%s: null pointer (the weights and dw of both streams, or none)", name);
     if (const int rc = tv_check(name, B, T, 128, K, F)) return rc;
-    hipLaunchKernelGGL(tc_dout_kernel, dim3((unsigned)(B * T), 2), dim3(256), 0, (hipStream_t)stream, so, to, w_s, w_t, stats, g_s, g_t, B, T,
-                       (int64_t)K * F, dso, dto, dw_s, dw_t);
+    hipLaunchKernelGGL(tm_dout_kernel<false>, dim3((unsigned)(B * T), 2), dim3(256), 0, (hipStream_t)stream, so, to, (const float*)nullptr,
+                       (const float*)nullptr, w_s, w_t, stats, g_s, g_t, B, T, K, F, 0, dso, dto, (float*)nullptr, (float*)nullptr, dw_s, dw_t);
     return check_launch(name);
 }
 
@@ -782,105 +790,8 @@ extern "C" int lpm_triangulation_cnn_attention_dweights(const float* x, const fl
 // temporal reciprocal norm) under V2's attention weights, both convolutions rectified before they are pooled.  The pools are over the
 // W = K F + K columns [relu(conv) | norm]:  pool = [ (1/T') sum_t w_t out_t | mean_t (out_t - mean_t out)^2 ], the norms sqrt(q), sqrt(p)
 // taken where they are read.  Backward: dout[t] = (w_t gm + 2 gv ((out[t] - mean) - c)) / T' on every column -- on a convolution column
-// times [out > 0], on a norm column times [squared norm > eps] into dng / dtg [B T, K] -- and dw[t] = <gm, out[t]> / T' over all W columns.
-namespace lpm {
-
-// a thread per (clip, column), blockIdx.y = stream: pool [B, 2 W]; stats [2, 2, B, W] = each stream's plain mean, then the mean of the
-// deviations from it (what the rounded mean is off by); sums over t two-level
-__global__ __launch_bounds__(256) void tm_pool_kernel(const float* __restrict__ so, const float* __restrict__ to, const float* __restrict__ q,
-                                                      const float* __restrict__ p, const float* __restrict__ w_s, const float* __restrict__ w_t,
-                                                      int B, int T, int K, int F, int NC, float* __restrict__ pool_s, float* __restrict__ pool_t,
-                                                      float* __restrict__ stats) {
-    const int64_t KF = (int64_t)K * F, W = KF + NC;         // NC = K, or 0 without the norm columns
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= B * W) return;
-    const int64_t b = i / W, j = i % W;
-    const int z = blockIdx.y, Tz = T - z;
-    const bool conv = j < KF;
-    const float* v = conv ? (z ? to : so) + b * T * KF + j : (z ? p : q) + b * T * K + (j - KF);
-    const int64_t stride = conv ? KF : K;
-    const float* w = z ? w_t : w_s;                          // null: the plain mean
-    if (w) w += b * Tz;
-    const float cnt = (float)Tz;
-    float tot = 0.f, acc = 0.f, wtot = 0.f, wacc = 0.f;
-    for (int t = z; t < T; ++t) {
-        const float val = conv ? v[t * stride] : sqrtf(v[t * stride]);
-        acc += val;
-        if (w) wacc = fmaf(w[t - z], val, wacc);
-        if (((t - z) & (TP_SUM_CHUNK - 1)) == TP_SUM_CHUNK - 1) {
-            tot += acc;
-            wtot += wacc;
-            acc = wacc = 0.f;
-        }
-    }
-    const float mean = (tot + acc) / cnt, wsum = wtot + wacc;
-    float dtot = 0.f, dacc = 0.f;
-    tot = acc = 0.f;
-    for (int t = z; t < T; ++t) {
-        const float dev = (conv ? v[t * stride] : sqrtf(v[t * stride])) - mean;
-        acc = fmaf(dev, dev, acc);
-        dacc += dev;
-        if (((t - z) & (TP_SUM_CHUNK - 1)) == TP_SUM_CHUNK - 1) {
-            tot += acc;
-            dtot += dacc;
-            acc = dacc = 0.f;
-        }
-    }
-    float* pool = (z ? pool_t : pool_s) + b * 2 * W;
-    pool[j] = w ? wsum / cnt : mean;
-    pool[W + j] = (tot + acc) / cnt;
-    float* st = stats + (int64_t)z * 2 * B * W;
-    st[b * W + j] = mean;
-    st[(B + b) * W + j] = (dtot + dacc) / cnt;
-}
-
-// a workgroup per (clip, frame), blockIdx.y = stream: the masked dout [B T, K F] (the temporal one zero on frame 0), the gated gradient of
-// the norm [B T, K] (always written: zero without the norm columns) and dw[b,t] = <gm[b], out_t> / T'
-__global__ __launch_bounds__(256) void tm_dout_kernel(const float* __restrict__ so, const float* __restrict__ to, const float* __restrict__ q,
-                                                      const float* __restrict__ p, const float* __restrict__ w_s, const float* __restrict__ w_t,
-                                                      const float* __restrict__ stats, const float* __restrict__ g_s, const float* __restrict__ g_t,
-                                                      int B, int T, int K, int F, int NC, float* __restrict__ dso, float* __restrict__ dto,
-                                                      float* __restrict__ dng, float* __restrict__ dtg, float* __restrict__ dw_s,
-                                                      float* __restrict__ dw_t) {
-    __shared__ float red[4];
-    const int64_t KF = (int64_t)K * F, W = KF + NC;
-    const int z = blockIdx.y, b = blockIdx.x / T, t = blockIdx.x % T, Tz = T - z;
-    const int64_t n = (int64_t)b * T + t;
-    float* dout = (z ? dto : dso) + n * KF;
-    float* dnorm = (z ? dtg : dng) + n * K;
-    if ((z && t == 0) || NC == 0)                          // (uniform over the workgroup)
-        for (int k = threadIdx.x; k < K; k += 256) dnorm[k] = 0.f;
-    if (z && t == 0) {
-        for (int64_t j = threadIdx.x; j < KF; j += 256) dout[j] = 0.f;
-        return;
-    }
-    const float* out = (z ? to : so) + n * KF;
-    const float* sq = (z ? p : q) + n * K;
-    const float* g = (z ? g_t : g_s) + (int64_t)b * 2 * W;
-    const float* st = stats + (int64_t)z * 2 * B * W;
-    const float *mean = st + (int64_t)b * W, *corr = st + (int64_t)(B + b) * W;
-    const float* w = z ? w_t : w_s;
-    const float wt = w ? w[(int64_t)b * Tz + t - z] : 1.f, cnt = (float)Tz;
-    float acc = 0.f;
-    for (int64_t j = threadIdx.x; j < W; j += 256) {
-        const bool conv = j < KF;
-        const float s = conv ? 0.f : sq[j - KF];
-        const float v = conv ? out[j] : sqrtf(s), gm = g[j];
-        const float d = (wt * gm + 2.f * g[W + j] * ((v - mean[j]) - corr[j])) / cnt;
-        if (conv) dout[j] = v > 0.f ? d : 0.f; else dnorm[j - KF] = s > kL2Eps ? d : 0.f;
-        acc = fmaf(gm, v, acc);
-    }
-    acc = wave_sum_dpp(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0 && w) {
-        const float d = ((red[0] + red[1]) + (red[2] + red[3])) / cnt;
-        if (z) dw_t[(int64_t)b * (T - 1) + t - 1] = d; else dw_s[n] = d;
-    }
-}
-
-}  // namespace lpm
-
+// times [out > 0], on a norm column times [squared norm > eps] into dng / dtg [B T, K] -- and dw[t] = <gm, out[t]> / T' over all W columns:
+// tm_pool and tm_dout<true>, above.
 extern "C" int lpm_triangulation_magnitude_norms(const float* x, const float* anchors, int B, int T, int D, int K, float* q, float* p,
                                                  lpm_stream_t stream) {
     using namespace lpm;
@@ -902,12 +813,8 @@ extern "C" int lpm_triangulation_magnitude_conv(const float* x, const float* anc
     const char* name = "lpm_triangulation_magnitude_conv";
     LPM_REQUIRE(x && anchors && cnn_s && cnn_t && q && p && so && to, LPM_ERR_BADARG, "%s: null pointer", name);
     if (const int rc = tv_check(name, B, T, D, K, F)) return rc;
-    const int64_t BT = (int64_t)B * T, BTK = BT * K;
-    const int NR = tv_row_tiles(BT), NF = (F + 31) / 32;
-    tp_dispatch_d(D, [&](auto d) {
-        hipLaunchKernelGGL((tv_conv_kernel<decltype(d)::value, true>), dim3((unsigned)((int64_t)K * NF * NR)), dim3(64 * TA_WAVES), 0,
-                           (hipStream_t)stream, x, anchors, cnn_s, cnn_t, q + BTK, p + BTK, BT, K, F, NR, so, to, TvFrames{});
-    });
+    const int64_t BTK = (int64_t)B * T * K;
+    tv_conv_launch<true, false>(x, anchors, cnn_s, cnn_t, q + BTK, p + BTK, B, T, D, K, F, so, to, TvFrames{}, (hipStream_t)stream);
     return check_launch(name);
 }
 
@@ -919,9 +826,9 @@ extern "C" int lpm_triangulation_magnitude_pool(const float* so, const float* to
     LPM_REQUIRE(so && to && q && p && pool_s && pool_t && stats && !w_s == !w_t, LPM_ERR_BADARG, "%s: null pointer", name);
     if (const int rc = tv_check(name, B, T, 128, K, F)) return rc;
     const int NC = add_norm ? K : 0;
-    const int64_t cols = (int64_t)B * ((int64_t)K * F + NC);
+    const int64_t cols = (int64_t)B * ((int64_t)K * F + NC);   // stats [2, 2, B, W]: each stream's mean, then its corr
     hipLaunchKernelGGL(tm_pool_kernel, dim3((unsigned)((cols + 255) / 256), 2), dim3(256), 0, (hipStream_t)stream, so, to, q, p, w_s, w_t, B, T, K, F,
-                       NC, pool_s, pool_t, stats);
+                       NC, pool_s, pool_t, stats, stats + cols, 2 * cols);
     return check_launch(name);
 }
 
@@ -934,7 +841,7 @@ extern "C" int lpm_triangulation_magnitude_dout(const float* so, const float* to
     LPM_REQUIRE(so && to && q && p && stats && g_s && g_t && dso && dto && dng && dtg && !w_s == !w_t && !w_s == !dw_s && !w_t == !dw_t,
                 LPM_ERR_BADARG, "%s: null pointer (the weights and dw of both streams, or none)", name);
     if (const int rc = tv_check(name, B, T, 128, K, F)) return rc;
-    hipLaunchKernelGGL(tm_dout_kernel, dim3((unsigned)(B * T), 2), dim3(256), 0, (hipStream_t)stream, so, to, q, p, w_s, w_t, stats, g_s, g_t, B, T,
+    hipLaunchKernelGGL(tm_dout_kernel<true>, dim3((unsigned)(B * T), 2), dim3(256), 0, (hipStream_t)stream, so, to, q, p, w_s, w_t, stats, g_s, g_t, B, T,
                        K, F, add_norm ? K : 0, dso, dto, dng, dtg, dw_s, dw_t);
     return check_launch(name);
 }
@@ -997,13 +904,8 @@ extern "C" int lpm_triangulation_magnitude_frames_fwd(const float* x, const floa
     const char* name = "lpm_triangulation_magnitude_frames_fwd";
     LPM_REQUIRE(x && anchors && cnn_s && cnn_t && q && p && feat_s && feat_t, LPM_ERR_BADARG, "%s: null pointer", name);
     if (const int rc = tf_check(name, B, T, D, K, F, ld)) return rc;
-    const int64_t BT = (int64_t)B * T, BTK = BT * K;
-    const int NR = tv_row_tiles(BT), NF = (F + 31) / 32;
-    const TvFrames fr{q, p, T, ld};
-    tp_dispatch_d(D, [&](auto d) {
-        hipLaunchKernelGGL((tv_conv_kernel<decltype(d)::value, true, true>), dim3((unsigned)((int64_t)K * NF * NR)), dim3(64 * TA_WAVES), 0,
-                           (hipStream_t)stream, x, anchors, cnn_s, cnn_t, q + BTK, p + BTK, BT, K, F, NR, feat_s, feat_t, fr);
-    });
+    const int64_t BTK = (int64_t)B * T * K;
+    tv_conv_launch<true, true>(x, anchors, cnn_s, cnn_t, q + BTK, p + BTK, B, T, D, K, F, feat_s, feat_t, TvFrames{q, p, T, ld}, (hipStream_t)stream);
     return check_launch(name);
 }
 

@@ -4207,6 +4207,12 @@ def clip_update_step(spec, param, grad, slots, offsets, ntensors, clip_norm, lr,
 TRIANGULATION_FEATURES = (128, 1024)      # the two feature sizes the reference hard-codes (frame_level_models.py:1173-1193)
 
 
+def _workspace(nbytes, like):
+    """An entry's scratch buffer, alive for that call only -> (fp32 tensor of at least ``nbytes`` bytes on ``like``'s device, nbytes)."""
+    nbytes = int(nbytes)
+    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=like.device), nbytes
+
+
 class _TriangulationPool(torch.autograd.Function):
     """lpm_triangulation_pool_fwd / _bwd: the saved state is the inputs and one int32 [B, K*D] arg-max tensor; e, u and f are
     recomputed in the backward, whose workspace lives for that call only."""
@@ -4232,8 +4238,7 @@ class _TriangulationPool(torch.autograd.Function):
         B, T, D, K, scale = ctx.dims
         grads = [g.contiguous() for g in (g_max_d, g_mean_d, g_max_t, g_mean_t)]
         dx, danchors = torch.empty_like(x), torch.empty_like(anchors)
-        wsb = int(lib._lpm_triangulation_pool_workspace_bytes(B, T, D, K))
-        ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+        ws, wsb = _workspace(lib._lpm_triangulation_pool_workspace_bytes(B, T, D, K), x)
         with _timed("triangulation_pool_bwd", (B, T, D, K)):
             lib.check(lib._lpm_triangulation_pool_bwd(ptr(x), ptr(anchors), ptr(argmax), *(ptr(g) for g in grads), B, T, D, K, scale, ptr(dx),
                                                       ptr(danchors), ptr(ws), wsb, stream_ptr()), "lpm_triangulation_pool_bwd")
@@ -4247,22 +4252,8 @@ def triangulation_pool(x, anchors, max_frames, scale=1.0):
     1 .. max_frames - 1, of  f = l2_normalize(e[t] - e[t-1])  -- WeightedTriangulationEmbedding (scale = 1 / sqrt(K)) or
     TriangulationEmbedding (scale = 1, anchors normalised by the caller) + TriangulationTemporalEmbedding + MaxMeanPoolingModule
     without any [B, T, K * D] tensor.  GPU only; D in TRIANGULATION_FEATURES, max_frames >= 2, contiguous fp32 input."""
-    what = "triangulation_pool"
-    if not (torch.is_tensor(x) and torch.is_tensor(anchors)) or x.dim() != 2 or anchors.dim() != 2:
-        raise LpmError(f"{what}: expected x [B * max_frames, D] and anchors [D, K]")
-    _f32(x, what + " x"), _f32(anchors, what + " anchors")
-    if not (x.is_cuda and anchors.is_cuda and x.device == anchors.device):
-        raise LpmError(f"{what}: needs tensors on one MI355X (cuda/hip device); got {x.device} / {anchors.device}.  There is no CPU "
-                       "fallback: video_pooling_modules' TriangulationEmbedding classes are the host path")
-    if not x.is_contiguous():
-        raise LpmError(f"{what}: x must be contiguous (a column slice of a wider matrix is not: copy the stream's block first)")
-    T = int(max_frames)
-    D, K = anchors.shape
-    if D not in TRIANGULATION_FEATURES or x.shape[1] != D or K < 1:
-        raise LpmError(f"{what}: need a feature size in {TRIANGULATION_FEATURES} shared by x and anchors (x {tuple(x.shape)}, anchors {tuple(anchors.shape)})")
-    if T < 2 or x.shape[0] == 0 or x.shape[0] % T:
-        raise LpmError(f"{what}: need max_frames >= 2 dividing the {x.shape[0]} rows of x (max_frames = {T}): the temporal embedding is a "
-                       "frame-to-frame difference")
+    T = _attention_args("triangulation_pool", x, anchors, max_frames, frame_limit=False,
+                        host_path="video_pooling_modules' TriangulationEmbedding classes are")
     return _TriangulationPool.apply(x, anchors.contiguous(), T, float(scale))
 
 
@@ -4272,8 +4263,7 @@ def triangulation_pool(x, anchors, max_frames, scale=1.0):
 def _attention_gram(lib, x, anchors, B, T, D, K, scale):
     """lpm_triangulation_attention_gram -> (G_d [B, T, T], G_t [B, T-1, T-1])."""
     gram_d, gram_t = _empty((B, T, T), x), _empty((B, T - 1, T - 1), x)
-    wsb = int(lib._lpm_triangulation_attention_workspace_bytes(0, B, T, D, K))
-    ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+    ws, wsb = _workspace(lib._lpm_triangulation_attention_workspace_bytes(0, B, T, D, K), x)
     with _timed("triangulation_attention_gram", (B, T, D, K)):
         lib.check(lib._lpm_triangulation_attention_gram(ptr(x), ptr(anchors), B, T, D, K, scale, ptr(gram_d), ptr(gram_t),
                                                         ptr(ws) if wsb else None, wsb, stream_ptr()), "lpm_triangulation_attention_gram")
@@ -4290,6 +4280,35 @@ def _attention_weights_bwd(gram, w, dw):
     dl = w * (dw - (w * dw).sum(dim=1, keepdim=True))
     dG = dl.unsqueeze(2) * (gram > 0).to(dl.dtype)
     return (dG + dG.transpose(1, 2)).contiguous()
+
+
+def _attention_m(op, dims, gram_s, gram_t, w_s, w_t, dw_s, dw_t):
+    """_attention_weights_bwd of both streams under the op's ``<op>_softmax_bwd`` label -> (M_s, M_t)."""
+    with _timed(op + "_softmax_bwd", dims):
+        return _attention_weights_bwd(gram_s, w_s, dw_s), _attention_weights_bwd(gram_t, w_t, dw_t)
+
+
+def _identity_affine(J, like):
+    """The Gram kernel's affine table [8, J] = (scale, mean, shift, 1 / std) per stream as the identity: a product with 1 and a sum
+    with 0 are exact."""
+    return torch.tensor([1.0, 0.0, 0.0, 1.0] * 2, device=like.device).unsqueeze(1).expand(8, J).contiguous()
+
+
+def _gram_weights(lib, op, dims, gram, name, x, anchors, *operands, aff=None):
+    """One of the two Gram entries of csrc/triangulation_bn_moments.hip (``gram``, ``name``; ``operands``: its norms), then
+    _attention_weights of both Grams, under the op's ``<op>_gram`` and ``<op>_softmax`` labels -> (gram_s, gram_t, w_s, w_t).  aff: the
+    affine table, the identity if None; it and the workspace are dropped before the softmax allocates."""
+    B, T, D, K = dims[:4]
+    if aff is None:
+        aff = _identity_affine(K * D, x)
+    gram_s, gram_t = _empty((B, T, T), x), _empty((B, T - 1, T - 1), x)
+    ws, wsb = _workspace(lib._lpm_triangulation_bn_moments_workspace_bytes(1, B, T, D, K), x)
+    with _timed(op + "_gram", dims):
+        lib.check(gram(ptr(x), ptr(anchors), *(ptr(o) for o in operands), ptr(aff), B, T, D, K, ptr(gram_s), ptr(gram_t),
+                       ptr(ws) if wsb else None, wsb, stream_ptr()), name)
+    del aff, ws
+    with _timed(op + "_softmax", dims):
+        return gram_s, gram_t, _attention_weights(gram_s), _attention_weights(gram_t)
 
 
 class _TriangulationAttentionPool(torch.autograd.Function):
@@ -4323,16 +4342,13 @@ class _TriangulationAttentionPool(torch.autograd.Function):
         dims = (B, T, D, K)
         grads = [g.contiguous() for g in (g_mean_d, g_max_d, g_mean_t, g_max_t)]
         dw_d, dw_t = _empty((B, T), x), _empty((B, T - 1), x)
-        wsb = int(lib._lpm_triangulation_attention_workspace_bytes(1, B, T, D, K))
-        ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+        ws, wsb = _workspace(lib._lpm_triangulation_attention_workspace_bytes(1, B, T, D, K), x)
         with _timed("triangulation_attention_dw", dims):
             lib.check(lib._lpm_triangulation_attention_dw(ptr(x), ptr(anchors), ptr(grads[0]), ptr(grads[2]), B, T, D, K, scale, ptr(dw_d),
                                                           ptr(dw_t), ptr(ws), wsb, stream_ptr()), "lpm_triangulation_attention_dw")
-        with _timed("triangulation_attention_softmax_bwd", dims):
-            m_d, m_t = _attention_weights_bwd(gram_d, w_d, dw_d), _attention_weights_bwd(gram_t, w_t, dw_t)
+        m_d, m_t = _attention_m("triangulation_attention", dims, gram_d, gram_t, w_d, w_t, dw_d, dw_t)
         dx, danchors = torch.empty_like(x), torch.empty_like(anchors)
-        wsb = int(lib._lpm_triangulation_attention_workspace_bytes(2, B, T, D, K))
-        ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+        ws, wsb = _workspace(lib._lpm_triangulation_attention_workspace_bytes(2, B, T, D, K), x)
         with _timed("triangulation_attention_bwd", dims):
             lib.check(lib._lpm_triangulation_attention_bwd(ptr(x), ptr(anchors), ptr(argmax), ptr(w_d), ptr(w_t), ptr(m_d), ptr(m_t),
                                                            *(ptr(g) for g in grads), B, T, D, K, scale, ptr(dx), ptr(danchors), ptr(ws), wsb,
@@ -4340,24 +4356,42 @@ class _TriangulationAttentionPool(torch.autograd.Function):
         return dx, danchors, None, None
 
 
-def _attention_args(what, x, anchors, max_frames):
+def _attention_args(what, x, anchors, max_frames, frame_limit=True,
+                    host_path="aggregation_modules.IndirectClusterMaxMeanPoolModule over video_pooling_modules' embeddings is"):
+    """The checks every triangulation op makes of its stream -> max_frames.  frame_limit: the op's backward keeps a [max_frames, 32]
+    tile on chip (every op but ``triangulation_pool``); host_path: what the refusal of a CPU tensor points to."""
     if not (torch.is_tensor(x) and torch.is_tensor(anchors)) or x.dim() != 2 or anchors.dim() != 2:
         raise LpmError(f"{what}: expected x [B * max_frames, D] and anchors [D, K]")
     _f32(x, what + " x"), _f32(anchors, what + " anchors")
     if not (x.is_cuda and anchors.is_cuda and x.device == anchors.device):
         raise LpmError(f"{what}: needs tensors on one MI355X (cuda/hip device); got {x.device} / {anchors.device}.  There is no CPU "
-                       "fallback: aggregation_modules.IndirectClusterMaxMeanPoolModule over video_pooling_modules' embeddings is the host path")
+                       f"fallback: {host_path} the host path")
     if not x.is_contiguous():
         raise LpmError(f"{what}: x must be contiguous (a column slice of a wider matrix is not: copy the stream's block first)")
     T = int(max_frames)
     D, K = anchors.shape
     if D not in TRIANGULATION_FEATURES or x.shape[1] != D or K < 1:
         raise LpmError(f"{what}: need a feature size in {TRIANGULATION_FEATURES} shared by x and anchors (x {tuple(x.shape)}, anchors {tuple(anchors.shape)})")
-    most = int(_capi.load()._lpm_triangulation_attention_max_frames())
-    if T < 2 or T > most or x.shape[0] == 0 or x.shape[0] % T:
-        raise LpmError(f"{what}: need 2 <= max_frames <= {most} dividing the {x.shape[0]} rows of x (max_frames = {T}): the temporal embedding "
-                       "is a frame-to-frame difference, and the backward keeps a [max_frames, 32] tile of each embedding on chip")
+    most = int(_capi.load()._lpm_triangulation_attention_max_frames()) if frame_limit else None
+    if T < 2 or (frame_limit and T > most) or x.shape[0] == 0 or x.shape[0] % T:
+        need, why = ((f"2 <= max_frames <= {most}", ", and the backward keeps a [max_frames, 32] tile of each embedding on chip") if frame_limit
+                     else ("max_frames >= 2", ""))
+        raise LpmError(f"{what}: need {need} dividing the {x.shape[0]} rows of x (max_frames = {T}): the temporal embedding is a "
+                       f"frame-to-frame difference{why}")
     return T
+
+
+def _cnn_args(what, x, K, D, named_cnns, same_shape):
+    """The checks of an op's two per-anchor convolution weights [K, F, D], in the order given; same_shape: one F for both."""
+    for name, cnn in named_cnns:
+        if not torch.is_tensor(cnn) or cnn.dim() != 3 or cnn.shape[0] != K or cnn.shape[2] != D or cnn.shape[1] < 1:
+            raise LpmError(f"{what}: {name} must be [K, F, D] = [{K}, F, {D}] (got {tuple(cnn.shape) if torch.is_tensor(cnn) else type(cnn)})")
+        _f32(cnn, f"{what} {name}")
+        if cnn.device != x.device:
+            raise LpmError(f"{what}: {name} is on {cnn.device}, x on {x.device}")
+    (name_a, cnn_a), (name_b, cnn_b) = named_cnns
+    if same_shape and cnn_a.shape != cnn_b.shape:
+        raise LpmError(f"{what}: {name_a} {tuple(cnn_a.shape)} and {name_b} {tuple(cnn_b.shape)} must have one shape")
 
 
 def triangulation_attention_pool(x, anchors, max_frames, scale=1.0):
@@ -4386,8 +4420,7 @@ def triangulation_attention_gram(x, anchors, max_frames, scale=1.0):
 def _mean_gram(lib, x, anchors, B, T, D, K, scale):
     """lpm_triangulation_mean_gram -> G_d [B, T, T]."""
     gram_d = _empty((B, T, T), x)
-    wsb = int(lib._lpm_triangulation_mean_workspace_bytes(0, B, T, D, K))
-    ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+    ws, wsb = _workspace(lib._lpm_triangulation_mean_workspace_bytes(0, B, T, D, K), x)
     with _timed("triangulation_mean_gram", (B, T, D, K)):
         lib.check(lib._lpm_triangulation_mean_gram(ptr(x), ptr(anchors), B, T, D, K, scale, ptr(gram_d), ptr(ws) if wsb else None, wsb,
                                                    stream_ptr()), "lpm_triangulation_mean_gram")
@@ -4423,16 +4456,14 @@ class _TriangulationMeanPool(torch.autograd.Function):
         dims = (B, T, D, K)
         g_d, g_t = g_d.contiguous(), g_t.contiguous()
         dw_d = _empty((B, T), x)
-        wsb = int(lib._lpm_triangulation_mean_workspace_bytes(1, B, T, D, K))
-        ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+        ws, wsb = _workspace(lib._lpm_triangulation_mean_workspace_bytes(1, B, T, D, K), x)
         with _timed("triangulation_mean_dw", dims):
             lib.check(lib._lpm_triangulation_mean_dw(ptr(x), ptr(anchors), ptr(g_d), B, T, D, K, scale, ptr(dw_d), ptr(ws), wsb, stream_ptr()),
                       "lpm_triangulation_mean_dw")
         with _timed("triangulation_mean_softmax_bwd", dims):
             m_d = _attention_weights_bwd(gram_d, w_d, dw_d)
         dx, danchors = torch.empty_like(x), torch.empty_like(anchors)
-        wsb = int(lib._lpm_triangulation_mean_workspace_bytes(2, B, T, D, K))
-        ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+        ws, wsb = _workspace(lib._lpm_triangulation_mean_workspace_bytes(2, B, T, D, K), x)
         with _timed("triangulation_mean_bwd", dims):
             lib.check(lib._lpm_triangulation_mean_bwd(ptr(x), ptr(anchors), ptr(w_d), ptr(m_d), ptr(g_d), ptr(g_t), B, T, D, K, scale, ptr(dx),
                                                       ptr(danchors), ptr(ws), wsb, stream_ptr()), "lpm_triangulation_mean_bwd")
@@ -4466,12 +4497,7 @@ def triangulation_cnn_pool(x, anchors, cnn_d, cnn_t, max_frames, scale=1.0):
     what = "triangulation_cnn_pool"
     T = _attention_args(what, x, anchors, max_frames)
     D, K = anchors.shape
-    for name, cnn in (("cnn_d", cnn_d), ("cnn_t", cnn_t)):
-        if not torch.is_tensor(cnn) or cnn.dim() != 3 or cnn.shape[0] != K or cnn.shape[2] != D or cnn.shape[1] < 1:
-            raise LpmError(f"{what}: {name} must be [K, F, D] = [{K}, F, {D}] (got {tuple(cnn.shape) if torch.is_tensor(cnn) else type(cnn)})")
-        _f32(cnn, f"{what} {name}")
-        if cnn.device != x.device:
-            raise LpmError(f"{what}: {name} is on {cnn.device}, x on {x.device}")
+    _cnn_args(what, x, K, D, (("cnn_d", cnn_d), ("cnn_t", cnn_t)), same_shape=False)
     m_d, m_t = _TriangulationMeanPool.apply(x, anchors.contiguous(), T, float(scale))
     B = m_d.shape[0]
     with _timed("triangulation_cnn_projection", (B, T, D, K)):
@@ -4512,8 +4538,7 @@ class _TriangulationCnnMoments(torch.autograd.Function):
         B, T, D, K, F = ctx.dims
         g_s, g_t = g_s.contiguous(), g_t.contiguous()
         dx, danchors, dcnn_s, dcnn_t = torch.empty_like(x), torch.empty_like(anchors), torch.empty_like(cnn_s), torch.empty_like(cnn_t)
-        wsb = int(lib._lpm_triangulation_moments_workspace_bytes(B, T, D, K, F))
-        ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+        ws, wsb = _workspace(lib._lpm_triangulation_moments_workspace_bytes(B, T, D, K, F), x)
         with _timed("triangulation_moments_bwd", (B, T, D, K, F)):
             lib.check(lib._lpm_triangulation_moments_bwd(ptr(x), ptr(anchors), ptr(cnn_s), ptr(cnn_t), ptr(q), ptr(p), ptr(so), ptr(to),
                                                          ptr(pool_s), ptr(pool_t), ptr(corr), ptr(g_s), ptr(g_t), B, T, D, K, F, ptr(dx), ptr(danchors),
@@ -4534,14 +4559,7 @@ def triangulation_cnn_moments(x, anchors, cnn_s, cnn_t, max_frames):
     what = "triangulation_cnn_moments"
     T = _attention_args(what, x, anchors, max_frames)
     D, K = anchors.shape
-    for name, cnn in (("cnn_s", cnn_s), ("cnn_t", cnn_t)):
-        if not torch.is_tensor(cnn) or cnn.dim() != 3 or cnn.shape[0] != K or cnn.shape[2] != D or cnn.shape[1] < 1:
-            raise LpmError(f"{what}: {name} must be [K, F, D] = [{K}, F, {D}] (got {tuple(cnn.shape) if torch.is_tensor(cnn) else type(cnn)})")
-        _f32(cnn, f"{what} {name}")
-        if cnn.device != x.device:
-            raise LpmError(f"{what}: {name} is on {cnn.device}, x on {x.device}")
-    if cnn_s.shape != cnn_t.shape:
-        raise LpmError(f"{what}: cnn_s {tuple(cnn_s.shape)} and cnn_t {tuple(cnn_t.shape)} must have one shape")
+    _cnn_args(what, x, K, D, (("cnn_s", cnn_s), ("cnn_t", cnn_t)), same_shape=True)
     return _TriangulationCnnMoments.apply(x, anchors.contiguous(), cnn_s.contiguous(), cnn_t.contiguous(), T)
 
 
@@ -4564,37 +4582,30 @@ class _TriangulationBnMoments(torch.autograd.Function):
         dims = (B, T, D, K)
         q = _empty((2, B * T, K), x)
         bstats = _empty((4, J), x) if batch_norm else None
-        wsb = int(lib._lpm_triangulation_bn_moments_workspace_bytes(0, B, T, D, K)) if batch_norm else 0
-        ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+        ws, wsb = _workspace(lib._lpm_triangulation_bn_moments_workspace_bytes(0, B, T, D, K) if batch_norm else 0, x)
         with _timed("triangulation_bn_moments_stats", dims):
             lib.check(lib._lpm_triangulation_bn_moments_stats(ptr(x), ptr(anchors), B, T, D, K, int(batch_norm), ptr(q),
                                                               ptr(bstats) if batch_norm else None, ptr(ws) if wsb else None, wsb, stream_ptr()),
                       "lpm_triangulation_bn_moments_stats")
-        aff = _empty((8, J), x)
+        del ws
         if batch_norm:
+            aff = _empty((8, J), x)
             use = bstats if stats is None else torch.stack([s.detach() for s in stats])
             for z, (gamma, beta) in enumerate(((gamma_s, beta_s), (gamma_t, beta_t))):
                 istd = torch.rsqrt(use[2 * z + 1] + TRIANGULATION_BN_EPS)
                 aff[4 * z], aff[4 * z + 1], aff[4 * z + 2], aff[4 * z + 3] = gamma.detach() * istd, use[2 * z], beta.detach(), istd
         else:
-            aff.copy_(torch.tensor([1.0, 0.0, 0.0, 1.0] * 2, device=x.device).unsqueeze(1).expand(8, J))
+            aff = _identity_affine(J, x)
         iq = q[1]
         gram_s = gram_t = w_s = w_t = None
         if attention:
-            gram_s, gram_t = _empty((B, T, T), x), _empty((B, T - 1, T - 1), x)
-            wsb = int(lib._lpm_triangulation_bn_moments_workspace_bytes(1, B, T, D, K))
-            ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
-            with _timed("triangulation_bn_moments_gram", dims):
-                lib.check(lib._lpm_triangulation_bn_moments_gram(ptr(x), ptr(anchors), ptr(iq), ptr(aff), B, T, D, K, ptr(gram_s), ptr(gram_t),
-                                                                 ptr(ws) if wsb else None, wsb, stream_ptr()), "lpm_triangulation_bn_moments_gram")
-            with _timed("triangulation_bn_moments_softmax", dims):
-                w_s, w_t = _attention_weights(gram_s), _attention_weights(gram_t)
+            gram_s, gram_t, w_s, w_t = _gram_weights(lib, "triangulation_bn_moments", dims, lib._lpm_triangulation_bn_moments_gram,
+                                                     "lpm_triangulation_bn_moments_gram", x, anchors, iq, aff=aff)
         pool_s, pool_t = _empty((B, 2 * J), x), _empty((B, 2 * J), x)
         rawbar, corr = _empty((2, B, J), x), _empty((2, B, J), x)
         with _timed("triangulation_bn_moments_pool", dims):
-            lib.check(lib._lpm_triangulation_bn_moments_pool(ptr(x), ptr(anchors), ptr(iq), ptr(aff), ptr(w_s) if attention else None,
-                                                             ptr(w_t) if attention else None, B, T, D, K, ptr(pool_s), ptr(pool_t), ptr(rawbar),
-                                                             ptr(corr), stream_ptr()), "lpm_triangulation_bn_moments_pool")
+            lib.check(lib._lpm_triangulation_bn_moments_pool(ptr(x), ptr(anchors), ptr(iq), ptr(aff), ptr(w_s), ptr(w_t), B, T, D, K, ptr(pool_s),
+                                                             ptr(pool_t), ptr(rawbar), ptr(corr), stream_ptr()), "lpm_triangulation_bn_moments_pool")
         ctx.save_for_backward(x, anchors, q, aff, rawbar, corr, *((gram_s, gram_t, w_s, w_t) if attention else ()))
         ctx.dims = (B, T, D, K, attention, batch_norm, batch_norm and stats is None)
         if batch_norm:
@@ -4617,14 +4628,11 @@ class _TriangulationBnMoments(torch.autograd.Function):
             with _timed("triangulation_bn_moments_dw", dims):
                 lib.check(lib._lpm_triangulation_bn_moments_dw(ptr(x), ptr(anchors), ptr(q[1]), ptr(aff), ptr(g_s), ptr(g_t), B, T, D, K, ptr(dw_s),
                                                                ptr(dw_t), stream_ptr()), "lpm_triangulation_bn_moments_dw")
-            with _timed("triangulation_bn_moments_softmax_bwd", dims):
-                m_s, m_t = _attention_weights_bwd(gram_s, w_s, dw_s), _attention_weights_bwd(gram_t, w_t, dw_t)
+            m_s, m_t = _attention_m("triangulation_bn_moments", dims, gram_s, gram_t, w_s, w_t, dw_s, dw_t)
         dx, danchors, dgrad = torch.empty_like(x), torch.empty_like(anchors), _empty((4, J), x)
-        wsb = int(lib._lpm_triangulation_bn_moments_workspace_bytes(2, B, T, D, K))
-        ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
-        opt = (lambda t: ptr(t)) if attention else (lambda t: None)
-        with _timed("triangulation_bn_moments_bwd", dims):
-            lib.check(lib._lpm_triangulation_bn_moments_bwd(ptr(x), ptr(anchors), ptr(q), ptr(aff), opt(w_s), opt(w_t), opt(m_s), opt(m_t), ptr(rawbar),
+        ws, wsb = _workspace(lib._lpm_triangulation_bn_moments_workspace_bytes(2, B, T, D, K), x)
+        with _timed("triangulation_bn_moments_bwd", dims):      # (w and M are None without attention: NULL)
+            lib.check(lib._lpm_triangulation_bn_moments_bwd(ptr(x), ptr(anchors), ptr(q), ptr(aff), ptr(w_s), ptr(w_t), ptr(m_s), ptr(m_t), ptr(rawbar),
                                                             ptr(corr), ptr(g_s), ptr(g_t), B, T, D, K, int(batch_norm), int(training), ptr(dx),
                                                             ptr(danchors), ptr(dgrad), ptr(ws), wsb, stream_ptr()), "lpm_triangulation_bn_moments_bwd")
         if not batch_norm:
@@ -4685,7 +4693,7 @@ class _TriangulationCnnAttentionMoments(torch.autograd.Function):
         lib = _capi.load()
         D, K = anchors.shape
         F = cnn_s.shape[1]
-        B, J = x.shape[0] // T, K * D
+        B = x.shape[0] // T
         dims = (B, T, D, K, F)
         q = _empty((2, B * T, K), x)
         with _timed("triangulation_cnn_attention_norms", dims):
@@ -4694,17 +4702,8 @@ class _TriangulationCnnAttentionMoments(torch.autograd.Function):
         iq = q[1]
         gram_s = gram_t = w_s = w_t = None
         if attention:
-            aff = _empty((8, J), x)                   # the Gram kernel's affine table: the identity (a product with 1 and a sum with 0 are exact)
-            aff.copy_(torch.tensor([1.0, 0.0, 0.0, 1.0] * 2, device=x.device).unsqueeze(1).expand(8, J))
-            gram_s, gram_t = _empty((B, T, T), x), _empty((B, T - 1, T - 1), x)
-            wsb = int(lib._lpm_triangulation_bn_moments_workspace_bytes(1, B, T, D, K))
-            ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
-            with _timed("triangulation_cnn_attention_gram", dims):
-                lib.check(lib._lpm_triangulation_bn_moments_gram(ptr(x), ptr(anchors), ptr(iq), ptr(aff), B, T, D, K, ptr(gram_s), ptr(gram_t),
-                                                                 ptr(ws) if wsb else None, wsb, stream_ptr()), "lpm_triangulation_bn_moments_gram")
-            del aff, ws
-            with _timed("triangulation_cnn_attention_softmax", dims):
-                w_s, w_t = _attention_weights(gram_s), _attention_weights(gram_t)
+            gram_s, gram_t, w_s, w_t = _gram_weights(lib, "triangulation_cnn_attention", dims, lib._lpm_triangulation_bn_moments_gram,
+                                                     "lpm_triangulation_bn_moments_gram", x, anchors, iq)
         ind = _empty((B * T, K), x)
         so, to = _empty((B * T, K * F), x), _empty((B * T, K * F), x)
         with _timed("triangulation_cnn_attention_conv", dims):
@@ -4713,9 +4712,8 @@ class _TriangulationCnnAttentionMoments(torch.autograd.Function):
         pool_s, pool_t = _empty((B, 2 * K * F), x), _empty((B, 2 * K * F), x)
         stats = _empty((2, 2, B, K * F), x)
         with _timed("triangulation_cnn_attention_pool", dims):
-            lib.check(lib._lpm_triangulation_cnn_attention_pool(ptr(so), ptr(to), ptr(w_s) if attention else None,
-                                                                ptr(w_t) if attention else None, B, T, K, F, ptr(pool_s), ptr(pool_t), ptr(stats),
-                                                                stream_ptr()), "lpm_triangulation_cnn_attention_pool")
+            lib.check(lib._lpm_triangulation_cnn_attention_pool(ptr(so), ptr(to), ptr(w_s), ptr(w_t), B, T, K, F, ptr(pool_s), ptr(pool_t),
+                                                                ptr(stats), stream_ptr()), "lpm_triangulation_cnn_attention_pool")
         ctx.save_for_backward(x, anchors, cnn_s, cnn_t, q, ind, so, to, stats, *((gram_s, gram_t, w_s, w_t) if attention else ()))
         ctx.dims = (B, T, D, K, F, attention)
         return pool_s, pool_t
@@ -4732,24 +4730,21 @@ class _TriangulationCnnAttentionMoments(torch.autograd.Function):
         if attention:
             gram_s, gram_t, w_s, w_t = att
             dw_s, dw_t = _empty((B, T), x), _empty((B, T - 1), x)
-        opt = (lambda t: ptr(t)) if attention else (lambda t: None)
-        with _timed("triangulation_cnn_attention_dout", dims):
-            lib.check(lib._lpm_triangulation_cnn_attention_dout(ptr(so), ptr(to), opt(w_s), opt(w_t), ptr(stats), ptr(g_s), ptr(g_t), B, T, K, F,
-                                                                ptr(dso), ptr(dto), opt(dw_s), opt(dw_t), stream_ptr()),
+        with _timed("triangulation_cnn_attention_dout", dims):  # (w, dw and M are None without attention: NULL)
+            lib.check(lib._lpm_triangulation_cnn_attention_dout(ptr(so), ptr(to), ptr(w_s), ptr(w_t), ptr(stats), ptr(g_s), ptr(g_t), B, T, K, F,
+                                                                ptr(dso), ptr(dto), ptr(dw_s), ptr(dw_t), stream_ptr()),
                       "lpm_triangulation_cnn_attention_dout")
         if attention:
-            with _timed("triangulation_cnn_attention_softmax_bwd", dims):
-                m_s, m_t = _attention_weights_bwd(gram_s, w_s, dw_s), _attention_weights_bwd(gram_t, w_t, dw_t)
+            m_s, m_t = _attention_m("triangulation_cnn_attention", dims, gram_s, gram_t, w_s, w_t, dw_s, dw_t)
         dx, danchors, dcnn_s, dcnn_t = torch.empty_like(x), torch.empty_like(anchors), torch.empty_like(cnn_s), torch.empty_like(cnn_t)
         with _timed("triangulation_cnn_attention_dweights", dims):
             lib.check(lib._lpm_triangulation_cnn_attention_dweights(ptr(x), ptr(anchors), ptr(q[1]), ptr(ind), ptr(dso), ptr(dto), B, T, D, K, F,
                                                                     ptr(dcnn_s), ptr(dcnn_t), stream_ptr()),
                       "lpm_triangulation_cnn_attention_dweights")
-        wsb = int(lib._lpm_triangulation_cnn_attention_workspace_bytes(B, T, D, K))
-        ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+        ws, wsb = _workspace(lib._lpm_triangulation_cnn_attention_workspace_bytes(B, T, D, K), x)
         with _timed("triangulation_cnn_attention_bwd", dims):
-            lib.check(lib._lpm_triangulation_cnn_attention_bwd(ptr(x), ptr(anchors), ptr(q), ptr(cnn_s), ptr(cnn_t), ptr(dso), ptr(dto), opt(m_s),
-                                                               opt(m_t), B, T, D, K, F, ptr(dx), ptr(danchors), ptr(ws), wsb, stream_ptr()),
+            lib.check(lib._lpm_triangulation_cnn_attention_bwd(ptr(x), ptr(anchors), ptr(q), ptr(cnn_s), ptr(cnn_t), ptr(dso), ptr(dto), ptr(m_s),
+                                                               ptr(m_t), B, T, D, K, F, ptr(dx), ptr(danchors), ptr(ws), wsb, stream_ptr()),
                       "lpm_triangulation_cnn_attention_bwd")
         return dx, danchors, dcnn_s, dcnn_t, None, None
 
@@ -4768,14 +4763,7 @@ def triangulation_cnn_attention_moments(x, anchors, cnn_s, cnn_t, max_frames, se
     what = "triangulation_cnn_attention_moments"
     T = _attention_args(what, x, anchors, max_frames)
     D, K = anchors.shape
-    for name, cnn in (("cnn_s", cnn_s), ("cnn_t", cnn_t)):
-        if not torch.is_tensor(cnn) or cnn.dim() != 3 or cnn.shape[0] != K or cnn.shape[2] != D or cnn.shape[1] < 1:
-            raise LpmError(f"{what}: {name} must be [K, F, D] = [{K}, F, {D}] (got {tuple(cnn.shape) if torch.is_tensor(cnn) else type(cnn)})")
-        _f32(cnn, f"{what} {name}")
-        if cnn.device != x.device:
-            raise LpmError(f"{what}: {name} is on {cnn.device}, x on {x.device}")
-    if cnn_s.shape != cnn_t.shape:
-        raise LpmError(f"{what}: cnn_s {tuple(cnn_s.shape)} and cnn_t {tuple(cnn_t.shape)} must have one shape")
+    _cnn_args(what, x, K, D, (("cnn_s", cnn_s), ("cnn_t", cnn_t)), same_shape=True)
     return _TriangulationCnnAttentionMoments.apply(x, anchors.contiguous(), cnn_s.contiguous(), cnn_t.contiguous(), T, bool(self_attention))
 
 
@@ -4794,7 +4782,7 @@ class _TriangulationMagnitudeMoments(torch.autograd.Function):
         lib = _capi.load()
         D, K = anchors.shape
         F = cnn_s.shape[1]
-        B, J = x.shape[0] // T, K * D
+        B = x.shape[0] // T
         W = K * F + (K if add_norm else 0)
         dims = (B, T, D, K, F)
         q, p = _empty((2, B * T, K), x), _empty((2, B * T, K), x)
@@ -4803,17 +4791,8 @@ class _TriangulationMagnitudeMoments(torch.autograd.Function):
                       "lpm_triangulation_magnitude_norms")
         gram_s = gram_t = w_s = w_t = None
         if attention:
-            aff = _empty((8, J), x)                   # the Gram kernel's affine table: the identity (a product with 1 and a sum with 0 are exact)
-            aff.copy_(torch.tensor([1.0, 0.0, 0.0, 1.0] * 2, device=x.device).unsqueeze(1).expand(8, J))
-            gram_s, gram_t = _empty((B, T, T), x), _empty((B, T - 1, T - 1), x)
-            wsb = int(lib._lpm_triangulation_bn_moments_workspace_bytes(1, B, T, D, K))
-            ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
-            with _timed("triangulation_magnitude_gram", dims):
-                lib.check(lib._lpm_triangulation_magnitude_gram(ptr(x), ptr(anchors), ptr(q), ptr(p), ptr(aff), B, T, D, K, ptr(gram_s), ptr(gram_t),
-                                                                ptr(ws) if wsb else None, wsb, stream_ptr()), "lpm_triangulation_magnitude_gram")
-            del aff, ws
-            with _timed("triangulation_magnitude_softmax", dims):
-                w_s, w_t = _attention_weights(gram_s), _attention_weights(gram_t)
+            gram_s, gram_t, w_s, w_t = _gram_weights(lib, "triangulation_magnitude", dims, lib._lpm_triangulation_magnitude_gram,
+                                                     "lpm_triangulation_magnitude_gram", x, anchors, q, p)
         so, to = _empty((B * T, K * F), x), _empty((B * T, K * F), x)
         with _timed("triangulation_magnitude_conv", dims):
             lib.check(lib._lpm_triangulation_magnitude_conv(ptr(x), ptr(anchors), ptr(cnn_s), ptr(cnn_t), ptr(q), ptr(p), B, T, D, K, F, ptr(so),
@@ -4821,9 +4800,8 @@ class _TriangulationMagnitudeMoments(torch.autograd.Function):
         pool_s, pool_t = _empty((B, 2 * W), x), _empty((B, 2 * W), x)
         stats = _empty((2, 2, B, W), x)
         with _timed("triangulation_magnitude_pool", dims):
-            lib.check(lib._lpm_triangulation_magnitude_pool(ptr(so), ptr(to), ptr(q), ptr(p), ptr(w_s) if attention else None,
-                                                            ptr(w_t) if attention else None, B, T, K, F, int(add_norm), ptr(pool_s), ptr(pool_t),
-                                                            ptr(stats), stream_ptr()), "lpm_triangulation_magnitude_pool")
+            lib.check(lib._lpm_triangulation_magnitude_pool(ptr(so), ptr(to), ptr(q), ptr(p), ptr(w_s), ptr(w_t), B, T, K, F, int(add_norm),
+                                                            ptr(pool_s), ptr(pool_t), ptr(stats), stream_ptr()), "lpm_triangulation_magnitude_pool")
         ctx.save_for_backward(x, anchors, cnn_s, cnn_t, q, p, so, to, stats, *((gram_s, gram_t, w_s, w_t) if attention else ()))
         ctx.dims = (B, T, D, K, F, attention, add_norm)
         return pool_s, pool_t
@@ -4841,24 +4819,21 @@ class _TriangulationMagnitudeMoments(torch.autograd.Function):
         if attention:
             gram_s, gram_t, w_s, w_t = att
             dw_s, dw_t = _empty((B, T), x), _empty((B, T - 1), x)
-        opt = (lambda t: ptr(t)) if attention else (lambda t: None)
-        with _timed("triangulation_magnitude_dout", dims):
-            lib.check(lib._lpm_triangulation_magnitude_dout(ptr(so), ptr(to), ptr(q), ptr(p), opt(w_s), opt(w_t), ptr(stats), ptr(g_s), ptr(g_t), B,
-                                                            T, K, F, int(add_norm), ptr(dso), ptr(dto), ptr(dng), ptr(dtg), opt(dw_s), opt(dw_t),
+        with _timed("triangulation_magnitude_dout", dims):      # (w, dw and M are None without attention: NULL)
+            lib.check(lib._lpm_triangulation_magnitude_dout(ptr(so), ptr(to), ptr(q), ptr(p), ptr(w_s), ptr(w_t), ptr(stats), ptr(g_s), ptr(g_t), B,
+                                                            T, K, F, int(add_norm), ptr(dso), ptr(dto), ptr(dng), ptr(dtg), ptr(dw_s), ptr(dw_t),
                                                             stream_ptr()), "lpm_triangulation_magnitude_dout")
         if attention:
-            with _timed("triangulation_magnitude_softmax_bwd", dims):
-                m_s, m_t = _attention_weights_bwd(gram_s, w_s, dw_s), _attention_weights_bwd(gram_t, w_t, dw_t)
+            m_s, m_t = _attention_m("triangulation_magnitude", dims, gram_s, gram_t, w_s, w_t, dw_s, dw_t)
         dx, danchors, dcnn_s, dcnn_t = torch.empty_like(x), torch.empty_like(anchors), torch.empty_like(cnn_s), torch.empty_like(cnn_t)
         with _timed("triangulation_magnitude_dweights", dims):        # V2's entry: its `ind` is the temporal operand's scale, here 1 / tau
             lib.check(lib._lpm_triangulation_cnn_attention_dweights(ptr(x), ptr(anchors), ptr(q[1]), ptr(p[1]), ptr(dso), ptr(dto), B, T, D, K, F,
                                                                     ptr(dcnn_s), ptr(dcnn_t), stream_ptr()),
                       "lpm_triangulation_cnn_attention_dweights")
-        wsb = int(lib._lpm_triangulation_magnitude_workspace_bytes(B, T, D, K))
-        ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+        ws, wsb = _workspace(lib._lpm_triangulation_magnitude_workspace_bytes(B, T, D, K), x)
         with _timed("triangulation_magnitude_bwd", dims):
             lib.check(lib._lpm_triangulation_magnitude_bwd(ptr(x), ptr(anchors), ptr(q), ptr(p), ptr(cnn_s), ptr(cnn_t), ptr(dso), ptr(dto), ptr(dng),
-                                                           ptr(dtg), opt(m_s), opt(m_t), B, T, D, K, F, ptr(dx), ptr(danchors), ptr(ws), wsb,
+                                                           ptr(dtg), ptr(m_s), ptr(m_t), B, T, D, K, F, ptr(dx), ptr(danchors), ptr(ws), wsb,
                                                            stream_ptr()), "lpm_triangulation_magnitude_bwd")
         return dx, danchors, dcnn_s, dcnn_t, None, None, None
 
@@ -4884,14 +4859,7 @@ def _magnitude_args(what, x, anchors, cnn_s, cnn_t, max_frames):
     """The argument checks the two triangulation_magnitude ops share -> max_frames."""
     T = _attention_args(what, x, anchors, max_frames)
     D, K = anchors.shape
-    for name, cnn in (("cnn_s", cnn_s), ("cnn_t", cnn_t)):
-        if not torch.is_tensor(cnn) or cnn.dim() != 3 or cnn.shape[0] != K or cnn.shape[2] != D or cnn.shape[1] < 1:
-            raise LpmError(f"{what}: {name} must be [K, F, D] = [{K}, F, {D}] (got {tuple(cnn.shape) if torch.is_tensor(cnn) else type(cnn)})")
-        _f32(cnn, f"{what} {name}")
-        if cnn.device != x.device:
-            raise LpmError(f"{what}: {name} is on {cnn.device}, x on {x.device}")
-    if cnn_s.shape != cnn_t.shape:
-        raise LpmError(f"{what}: cnn_s {tuple(cnn_s.shape)} and cnn_t {tuple(cnn_t.shape)} must have one shape")
+    _cnn_args(what, x, K, D, (("cnn_s", cnn_s), ("cnn_t", cnn_t)), same_shape=True)
     return T
 
 
@@ -4942,8 +4910,7 @@ class _TriangulationMagnitudeFrames(torch.autograd.Function):
             lib.check(lib._lpm_triangulation_cnn_attention_dweights(ptr(x), ptr(anchors), ptr(q[1]), ptr(p[1]), ptr(dso), ptr(dto), B, T, D, K, F,
                                                                     ptr(dcnn_s), ptr(dcnn_t), stream_ptr()),
                       "lpm_triangulation_cnn_attention_dweights")
-        wsb = int(lib._lpm_triangulation_magnitude_workspace_bytes(B, T, D, K))
-        ws = torch.empty((wsb + 3) // 4, dtype=torch.float32, device=x.device)
+        ws, wsb = _workspace(lib._lpm_triangulation_magnitude_workspace_bytes(B, T, D, K), x)
         with _timed("triangulation_magnitude_bwd", dims):             # V3's chain without attention: no M V product
             lib.check(lib._lpm_triangulation_magnitude_bwd(ptr(x), ptr(anchors), ptr(q), ptr(p), ptr(cnn_s), ptr(cnn_t), ptr(dso), ptr(dto), ptr(dng),
                                                            ptr(dtg), None, None, B, T, D, K, F, ptr(dx), ptr(danchors), ptr(ws), wsb,
