@@ -1373,6 +1373,44 @@ int lpm_lstm_layer_fwd(const float* xw, const float* wh, int64_t ldw, const floa
 int lpm_lstm_layer_bwd(const float* wh, int64_t ldw, const int32_t* lengths, const float* cs, const float* gates, const float* g_out,
                        float* dhp, float* dc, float* dz, int B, int T, int H, lpm_stream_t stream);
 
+/* ---- csrc/triangulation_onefc.hip: the one-FC attention-cluster pooling of TriangulationV6Module (JuhanTestModelV6) ----
+ * x [B * T, D] (a clip's rows contiguous), anchors_t [K, D] (the [D, K] variable TRANSPOSED), J = K * D, feature j = k * D + d, C clusters:
+ *     e = l2_normalize(x - a_k),  s = l2_normalize(e over all J),  v = g s + h (batch norm folded per feature),
+ *     p = softmax_t((1 / sqrt(J)) s . (g W)),  S = sum_t p s,  z = alpha (g S + h) + shift,  y = l2_normalize(z over J) / sqrt(C)
+ * Softmax over the frames and its backward are [B, T, C] work of the caller, the statistics' finish and the parameter gradients' last
+ * step [J] and [J, C] work.  Nothing of size B * T * K * D is written; no floating-point atomics (the same inputs give the same bits);
+ * all products are fp32 fmaf on the VALU.
+ *   _norms:   -> norms [B * T * (3 K + 2)]: iq [B T, K], the gates [q > 1e-12], |e_k|^2, then r [B T] and the second norm's gate
+ *   _stats:   -> sums [3, J]: sum_n s, sum_n (s - mu0)^2, sum_n (s - mu0) with mu0 = sums[0] * (1.f / (B T)); workspace which = 0
+ *   _project: out [B, T, C] = scale * sum_j s[b,t,j] colscale_j w(b,j,c); mode 0: w [J, C], mode 1: w [B, C, J]; colscale [J] or NULL;
+ *             workspace which = 1 (may be 0 bytes)
+ *   _pool:    p [B, T, C] -> out [B, C, J] = sum_t p s; sum_out [C, J] (or NULL): out added over the clips b = 0, 1, ...
+ *   _finish:  S [B, C, J], g, h [J], alpha, shift [1] (device) -> y [B, C * J], nrm2 [B * C] = |z|^2
+ *   _dz:      dy [B, C * J] -> dA [B, C, J] = alpha dz, scal [B * C, 2] = (sum_j dz A, sum_j dz), dhg [2, J] = (sum dA, sum dA S) over
+ *             the B * C rows; workspace which = 2
+ *   _bwd:     dl [B, T, C], w [J, C], mu, c1, c2 [J] (all three NULL: no gradient through the statistics; else ds += c1 + c2 (s - mu))
+ *             -> dx [B * T, D], danchors [D, K] (NOT transposed); workspace which = 3
+ * D in {128, 1024}, 1 <= T <= lpm_triangulation_attention_max_frames(), 1 <= C <= lpm_triangulation_onefc_max_clusters(), K >= 1; x and
+ * anchors_t 16-byte aligned; anything else LPM_ERR_UNSUPPORTED_SHAPE / LPM_ERR_BADARG before any launch. */
+int lpm_triangulation_onefc_max_clusters(void);
+size_t lpm_triangulation_onefc_workspace_bytes(int which, int B, int T, int D, int K, int C);
+int lpm_triangulation_onefc_norms(const float* x, const float* anchors_t, int B, int T, int D, int K, float* norms, lpm_stream_t stream);
+int lpm_triangulation_onefc_stats(const float* x, const float* anchors_t, const float* norms, int B, int T, int D, int K, float* sums,
+                                  void* workspace, size_t workspace_bytes, lpm_stream_t stream);
+int lpm_triangulation_onefc_project(const float* x, const float* anchors_t, const float* norms, const float* w, const float* colscale, int mode,
+                                    float scale, int B, int T, int D, int K, int C, float* out, void* workspace, size_t workspace_bytes,
+                                    lpm_stream_t stream);
+int lpm_triangulation_onefc_pool(const float* x, const float* anchors_t, const float* norms, const float* p, int B, int T, int D, int K, int C,
+                                 float* out, float* sum_out, lpm_stream_t stream);
+int lpm_triangulation_onefc_finish(const float* S, const float* g, const float* h, const float* alpha, const float* shift, int B, int C, int J,
+                                   float* y, float* nrm2, lpm_stream_t stream);
+int lpm_triangulation_onefc_dz(const float* S, const float* g, const float* h, const float* alpha, const float* shift, const float* nrm2,
+                               const float* dy, int B, int C, int J, float* dA, float* scal, float* dhg, void* workspace,
+                               size_t workspace_bytes, lpm_stream_t stream);
+int lpm_triangulation_onefc_bwd(const float* x, const float* anchors_t, const float* norms, const float* p, const float* dl, const float* dA,
+                                const float* w, const float* g, const float* mu, const float* c1, const float* c2, int B, int T, int D, int K,
+                                int C, float* dx, float* danchors, void* workspace, size_t workspace_bytes, lpm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -245,6 +245,15 @@ SIGNATURES = {
     "lpm_triangulation_magnitude_frames_fwd": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _f, _f, _f]),
     "lpm_triangulation_magnitude_frames_dout": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f]),
     "lpm_lstm_supported": (_i, [_i, _i, _i]),
+    "lpm_triangulation_onefc_max_clusters": (_i, []),
+    "lpm_triangulation_onefc_workspace_bytes": (_s, [_i, _i, _i, _i, _i, _i]),
+    "lpm_triangulation_onefc_norms": (_i, [_f, _f, _i, _i, _i, _i, _f, _f]),
+    "lpm_triangulation_onefc_stats": (_i, [_f, _f, _f, _i, _i, _i, _i, _f, _f, _s, _f]),
+    "lpm_triangulation_onefc_project": (_i, [_f, _f, _f, _f, _f, _i, _fl, _i, _i, _i, _i, _i, _f, _f, _s, _f]),
+    "lpm_triangulation_onefc_pool": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f]),
+    "lpm_triangulation_onefc_finish": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _f, _f, _f]),
+    "lpm_triangulation_onefc_dz": (_i, [_f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _f, _f, _f, _f, _s, _f]),
+    "lpm_triangulation_onefc_bwd": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _s, _f]),
     "lpm_lstm_layer_fwd": (_i, [_f, _f, _l, _f, _f, _i, _i, _i, _fl, _f, _f, _f, _f, _f]),
     "lpm_lstm_layer_bwd": (_i, [_f, _l, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _f]),
     "lpm_format_pairs_stride": (_i, [_i]),

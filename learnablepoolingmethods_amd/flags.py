@@ -190,6 +190,28 @@ FLAGS.define("triangulation_v4_fused", False, "build extension: on the GPU each 
              "(16, 200, 128, 8, 16) (with 192 against 2637 MiB and 18 against 132 MiB allocated; the whole module 20.1 against 14.3 ms and "
              "3.18 against 2.54 ms), and the default is on only if the fused path is not slower at both "
              "(profiles/bench_triangulation_v4.json)")
+FLAGS.define("jtmv6_iteration", 30, "JuhanTestModelV6 (frame_level_models.py:610): sampled frames per clip")
+FLAGS.define("jtmv6_add_batch_norm", True, "JuhanTestModelV6 (:612): batch norm on the streams and inside each stream's module")
+FLAGS.define("jtmv6_sample_random_frames", True, "JuhanTestModelV6 (:614): read nowhere, as written: the frames are always sampled at random")
+FLAGS.define("jtmv6_video_anchor_size", 256, "JuhanTestModelV6 (:616): anchors of the video stream")
+FLAGS.define("jtmv6_audio_anchor_size", 32, "JuhanTestModelV6 (:618): anchors of the audio stream")
+FLAGS.define("jtmv6_video_kernel_size", 512, "JuhanTestModelV6 (:620): handed to the video module, read nowhere, as written")
+FLAGS.define("jtmv6_audio_kernel_size", 64, "JuhanTestModelV6 (:622): handed to the audio module, read nowhere, as written")
+FLAGS.define("jtmv6_video_hidden", 2048, "JuhanTestModelV6 (:624): handed to the video module, read nowhere, as written")
+FLAGS.define("jtmv6_video_output_dim", 4096, "JuhanTestModelV6 (:626): width of the video stream's output")
+FLAGS.define("jtmv6_audio_hidden", 256, "JuhanTestModelV6 (:628): handed to the audio module, read nowhere, as written")
+FLAGS.define("jtmv6_audio_output_dim", 512, "JuhanTestModelV6 (:630): width of the audio stream's output")
+FLAGS.define("jtmv6_video_cluster_size", 64, "JuhanTestModelV6 (:632): attention clusters of the video stream.  With the defaults the video "
+             "stream's hidden_weight is [64 * 256 * 1024, 4096], 275 GB: the model refuses it before any variable is created")
+FLAGS.define("jtmv6_audio_cluster_size", 8, "JuhanTestModelV6 (:634): attention clusters of the audio stream")
+FLAGS.define("triangulation_v6_fused", True, "build extension: on the GPU each stream of JuhanTestModelV6 pools through "
+             "ops.triangulation_onefc_pool (csrc/triangulation_onefc.hip: both normalisations, the folded batch norm, the logits, the "
+             "cluster sums and the shifted row norms straight from the frames, without any [B*T, K*D] tensor); False: "
+             "TriangulationV6Module.pool materialises them (the CPU path; same variables, same results).  On: tools/bench_triangulation_v6.py "
+             "measured forward + backward of one stream's pooling at 0.82 ms fused against 0.91 ms at (B, T, D, K, C) = (16, 30, 128, 32, 8), "
+             "0.88 against 1.02 ms at (16, 30, 1024, 16, 8) and 1.47 against 2.99 ms at (80, 30, 1024, 16, 8) (with 11 against 201 MiB, 41 "
+             "against 194 MiB and 202 against 971 MiB allocated), and the default is on only if the fused path is not slower at all three "
+             "(profiles/bench_triangulation_v6.json, DESIGN.md section 34)")
 FLAGS.define("batch_norm", True, "TriangulationRelationalModel (frame_level_models.py:1503): True iff add batch normalization")
 FLAGS.define("audio_triangulation_anchor_size_v1", 4, "TriangulationRelationalModel (:1505): anchors of the audio stream")
 FLAGS.define("video_triangulation_anchor_size_v1", 16, "TriangulationRelationalModel (:1507): anchors of the video stream")

@@ -1,7 +1,7 @@
 """NetVLAD prototypes behind the reference's model-registry API
 (reference: frame_level_models.py:2193-2513 NetVladV1 / NetVladV2, :2765-2877 NetVLAD / LightVLAD) and the triangulation-embedding
 family's RegularizedTriangulationModel (:1148-1307), SoftAttentionTriangulationModel (:965-1145), TriangulationCnnClusterModel
-(:757-939), JuhanTestModelV5 (:491-606), JuhanTestModelV1 (:59-154), JuhanTestModelV2 (:158-268), JuhanTestModelV3 (:302-378), JuhanTestModelV4 (:411-487) and the recurrent TriangulationRelationalModel (:1511-1630).
+(:757-939), JuhanTestModelV5 (:491-606), JuhanTestModelV1 (:59-154), JuhanTestModelV2 (:158-268), JuhanTestModelV3 (:302-378), JuhanTestModelV4 (:411-487), JuhanTestModelV6 (:638-733) and the recurrent TriangulationRelationalModel (:1511-1630).
 
 Same names, ``create_model`` signature, variable names and output contract as the reference; the hot
 ops (frame sampling + input_bn, soft-assignment GEMM, fused softmax/residual aggregation/normalise,
@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import contextlib
 import math
+import os
 
 import torch
 
@@ -641,6 +642,92 @@ class JuhanTestModelV5(models.BaseModel):
         aggregated_model = getattr(video_level_models, "FourLayerBatchNeuralModel")
         return aggregated_model().create_model(model_input=activation, vocab_size=vocab_size, is_training=is_training,
                                                **unused_params)                                              # :600-606
+
+
+def weight_fits(nbytes: int, limit: int) -> bool:
+    """Whether a weight of ``nbytes`` bytes can be held at all by a device with ``limit`` bytes of memory."""
+    return int(nbytes) <= int(limit)
+
+
+def device_memory_bytes(device) -> int:
+    """The total memory of the device a model is built on: the GPU's, or the host's for the CPU."""
+    device = torch.device(device)
+    if device.type == "cuda":
+        return int(torch.cuda.get_device_properties(device).total_memory)
+    return int(os.sysconf("SC_PHYS_PAGES")) * int(os.sysconf("SC_PAGE_SIZE"))
+
+
+def check_v6_hidden_weight(stream, feature_size, anchor_size, cluster_size, output_dim, limit, is_training=False):
+    """JuhanTestModelV6's size check, before any variable of ``stream`` is created: hidden_weight [C * K * D, O] in fp32 against ``limit``
+    bytes -- in training together with its gradient, which every step holds beside it (an MI355X reports 309 GB: the 275 GB of the video
+    defaults alone would pass, and no step could run).  -> the weight's size in bytes; ValueError naming the stream, the size and the three
+    flags that reduce it."""
+    nbytes = 4 * int(feature_size) * int(anchor_size) * int(cluster_size) * int(output_dim)
+    if not weight_fits(nbytes * (2 if is_training else 1), limit):
+        raise ValueError(
+            f"JuhanTestModelV6: the {stream} stream's hidden_weight [{cluster_size} * {anchor_size} * {feature_size}, {output_dim}] takes "
+            f"{nbytes / 1e9:.1f} GB ({nbytes} bytes) in fp32{' and as much again for its gradient' if is_training else ''}, more than the device's "
+            f"{limit / 1e9:.1f} GB: reduce "
+            f"jtmv6_{stream}_anchor_size ({anchor_size}), jtmv6_{stream}_cluster_size ({cluster_size}) or jtmv6_{stream}_output_dim "
+            f"({output_dim}), or pass the keyword overrides of the same names")
+    return nbytes
+
+
+class JuhanTestModelV6(models.BaseModel):
+    """Batch norm of both streams, one TriangulationV6Module per stream (the twice-normalised triangulation embedding, a batch norm over
+    all K*D features, OneFcAttention's C attention-weighted sums over the frames, shifted and normalised, one matrix to the stream's
+    output, batch norm and relu) and the four-layer batch-norm classifier (frame_level_models.py:638-733).  As written: SURVEY App.
+    C48-C50 (and C23).
+
+    Each stream's hidden_weight is [C * K * D, O]; at the flags' defaults the video stream's takes 275 GB, so its size is checked against
+    the device's memory before any of the stream's variables is created (``memory_limit`` replaces the device's).  On the GPU with
+    FLAGS.triangulation_v6_fused each stream's pooling goes through ops.triangulation_onefc_pool: no [(B*T), K*D] tensor is written;
+    otherwise TriangulationV6Module.pool materialises five.  The variables and the results are the same either way.  ``frame_uniform``
+    [B, iterations] replaces the random draw of SampleRandomFrames; ``video_anchor_size``, ``audio_anchor_size``,
+    ``video_cluster_size``, ``audio_cluster_size``, ``video_output_dim`` and ``audio_output_dim`` override the flags (the reference reads
+    the flags only)."""
+
+    def create_model(self, model_input, vocab_size, num_frames, iterations=None, add_batch_norm=None, sample_random_frames=None,
+                     hidden_size=None, is_training=True, frame_uniform=None, video_anchor_size=None, audio_anchor_size=None,
+                     video_cluster_size=None, audio_cluster_size=None, video_output_dim=None, audio_output_dim=None,
+                     quantised_training=False, memory_limit=None, **unused_params):
+        iterations = iterations or FLAGS.jtmv6_iteration                                                      # :649
+        add_batch_norm = add_batch_norm or FLAGS.jtmv6_add_batch_norm                                         # :650 (C23)
+        video_anchor_size = int(video_anchor_size or FLAGS.jtmv6_video_anchor_size)                           # :651-660
+        audio_anchor_size = int(audio_anchor_size or FLAGS.jtmv6_audio_anchor_size)
+        video_cluster_size = int(video_cluster_size or FLAGS.jtmv6_video_cluster_size)
+        audio_cluster_size = int(audio_cluster_size or FLAGS.jtmv6_audio_cluster_size)
+        video_output_dim = int(video_output_dim or FLAGS.jtmv6_video_output_dim)
+        audio_output_dim = int(audio_output_dim or FLAGS.jtmv6_audio_output_dim)
+        # the kernel sizes and the hidden sizes go to the modules and are read nowhere; sample_random_frames and hidden_size are accepted
+        # and read nowhere, as written (C48)
+        quantised, model_input, max_frames, feature_size = _random_frames(model_input, num_frames, iterations, frame_uniform)  # :662-663
+        if feature_size <= 1024:
+            raise ValueError("JuhanTestModelV6 slices a 1024-wide video and a 128-wide audio stream out of its input "
+                             f"(frame_level_models.py:671-672); got {feature_size} features")
+        dev = model_input.device
+        streams = (("video", 1024, video_anchor_size, FLAGS.jtmv6_video_kernel_size, FLAGS.jtmv6_video_hidden, video_cluster_size,
+                    video_output_dim),
+                   ("audio", feature_size - 1024, audio_anchor_size, FLAGS.jtmv6_audio_kernel_size, FLAGS.jtmv6_audio_hidden,
+                    audio_cluster_size, audio_output_dim))
+        limit = device_memory_bytes(dev) if memory_limit is None else int(memory_limit)
+        for name, D, K, _, _, C, O in streams:                                                                # (before any variable)
+            check_v6_hidden_weight(name, D, K, C, O, limit, is_training)
+        features = _stream_features(quantised, model_input, num_frames, iterations, frame_uniform, add_batch_norm, is_training,
+                                    quantised_training)                                                       # :671-687
+        v6_modules = [video_pooling_modules.TriangulationV6Module(
+            feature_size=D, max_frames=max_frames, anchor_size=K, kernel_size=F, self_attention=False, cluster_size=C, hidden_layer_size=H,
+            output_dim=O, add_relu=True, batch_norm=add_batch_norm, is_training=is_training, scope_id=None)
+            for _, D, K, F, H, C, O in streams]                                                               # :689-715
+        fused = bool(FLAGS.triangulation_v6_fused and dev.type == "cuda")
+        acts = []
+        for (name, *_), x, module in zip(streams, features, v6_modules):
+            with vs.variable_scope(name + "_triangulation_embedding"):                                        # :717-723
+                acts.append(module.head(module.fused_pool(x.contiguous())) if fused else module.forward(x))
+        activation = torch.cat(acts, 1)                                                                       # :725
+        aggregated_model = getattr(video_level_models, "FourLayerBatchNeuralModel")
+        return aggregated_model().create_model(model_input=activation, vocab_size=vocab_size, is_training=is_training,
+                                               **unused_params)                                              # :727-733
 
 
 class JuhanTestModelV1(models.BaseModel):

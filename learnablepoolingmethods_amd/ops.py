@@ -7,6 +7,7 @@ PyTorch only supplies device memory, streams and the autograd tape.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import weakref
 from typing import NamedTuple, Optional
@@ -4937,6 +4938,174 @@ def triangulation_magnitude_frames(x, anchors, cnn_s, cnn_t, max_frames, pad_to=
     W = anchors.shape[1] * (cnn_s.shape[1] + 1)
     Wp = (W + pad_to - 1) // pad_to * pad_to
     return _TriangulationMagnitudeFrames.apply(x, anchors.contiguous(), cnn_s.contiguous(), cnn_t.contiguous(), T, Wp)
+
+
+# ----------------------------------------------------------------------------------------------
+# one-FC attention-cluster pooling of the triangulation embedding: TriangulationV6Module's pooling (csrc/triangulation_onefc.hip)
+# ----------------------------------------------------------------------------------------------
+class _TriangulationOneFcPool(torch.autograd.Function):
+    """The saved state is the inputs, the norms [B*T*(3K+2)], the folded affine vectors [J], p [B, T, C], S [B, C, J] and |z|^2 [B*C];
+    s is recomputed wherever it is needed, and every workspace lives for its call only."""
+
+    @staticmethod
+    def forward(ctx, x, anchors, gamma, beta, w, alpha, shift, T, batch_norm, stats):
+        lib = _capi.load()
+        D, K = anchors.shape
+        B, J, C = x.shape[0] // T, K * D, w.shape[1]
+        N = B * T
+        dims = (B, T, D, K, C)
+        at = anchors.t().contiguous()
+        norms = _empty((N * (3 * K + 2),), x)
+        with _timed("triangulation_onefc_norms", dims):
+            lib.check(lib._lpm_triangulation_onefc_norms(ptr(x), ptr(at), B, T, D, K, ptr(norms), stream_ptr()), "lpm_triangulation_onefc_norms")
+        bstats = mu = istd = None
+        if batch_norm:
+            sums = _empty((3, J), x)
+            ws, wsb = _workspace(lib._lpm_triangulation_onefc_workspace_bytes(0, B, T, D, K, C), x)
+            with _timed("triangulation_onefc_stats", dims):
+                lib.check(lib._lpm_triangulation_onefc_stats(ptr(x), ptr(at), ptr(norms), B, T, D, K, ptr(sums), ptr(ws), wsb, stream_ptr()),
+                          "lpm_triangulation_onefc_stats")
+            del ws
+            inv_n = 1.0 / N
+            off = sums[2] * inv_n                       # what the rounded mean sums[0] * inv_n is off by
+            bstats = torch.stack([sums[0] * inv_n + off, torch.clamp(sums[1] * inv_n - off * off, min=0.0)])
+            mu, var = (bstats[0], bstats[1]) if stats is None else (stats[0].detach(), stats[1].detach())
+            istd = torch.rsqrt(var + TRIANGULATION_BN_EPS)
+            g = gamma.detach() * istd
+            h = beta.detach() - g * mu
+        else:
+            g, h = torch.ones(J, dtype=x.dtype, device=x.device), torch.zeros(J, dtype=x.dtype, device=x.device)
+        logits = _empty((B, T, C), x)
+        ws, wsb = _workspace(lib._lpm_triangulation_onefc_workspace_bytes(1, B, T, D, K, C), x)
+        with _timed("triangulation_onefc_logits", dims):
+            lib.check(lib._lpm_triangulation_onefc_project(ptr(x), ptr(at), ptr(norms), ptr(w), ptr(g) if batch_norm else None, 0,
+                                                           1.0 / math.sqrt(J), B, T, D, K, C, ptr(logits), ptr(ws) if wsb else None, wsb,
+                                                           stream_ptr()), "lpm_triangulation_onefc_project")
+        del ws
+        p = torch.softmax(logits, dim=1)
+        S, y, nrm2 = _empty((B, C, J), x), _empty((B, C * J), x), _empty((B * C,), x)
+        with _timed("triangulation_onefc_pool", dims):
+            lib.check(lib._lpm_triangulation_onefc_pool(ptr(x), ptr(at), ptr(norms), ptr(p), B, T, D, K, C, ptr(S), None, stream_ptr()),
+                      "lpm_triangulation_onefc_pool")
+            lib.check(lib._lpm_triangulation_onefc_finish(ptr(S), ptr(g), ptr(h), ptr(alpha), ptr(shift), B, C, J, ptr(y), ptr(nrm2),
+                                                          stream_ptr()), "lpm_triangulation_onefc_finish")
+        saved = (x, at, norms, w, alpha, shift, g, h, p, S, nrm2) + ((mu, istd, gamma) if batch_norm else ())
+        ctx.save_for_backward(*saved)
+        ctx.dims = (B, T, D, K, C, batch_norm, batch_norm and stats is None)
+        if batch_norm:
+            ctx.mark_non_differentiable(bstats)
+        return y, bstats
+
+    @staticmethod
+    def backward(ctx, dy, _g_stats):
+        lib = _capi.load()
+        x, at, norms, w, alpha, shift, g, h, p, S, nrm2, *bn = ctx.saved_tensors
+        B, T, D, K, C, batch_norm, training = ctx.dims
+        dims, J, N = (B, T, D, K, C), K * D, B * T
+        isj = 1.0 / math.sqrt(J)
+        dy = dy.contiguous()
+        dA, scal, dhg = _empty((B, C, J), x), _empty((B * C, 2), x), _empty((2, J), x)
+        ws, wsb = _workspace(lib._lpm_triangulation_onefc_workspace_bytes(2, B, T, D, K, C), x)
+        with _timed("triangulation_onefc_dz", dims):
+            lib.check(lib._lpm_triangulation_onefc_dz(ptr(S), ptr(g), ptr(h), ptr(alpha), ptr(shift), ptr(nrm2), ptr(dy), B, C, J, ptr(dA),
+                                                      ptr(scal), ptr(dhg), ptr(ws), wsb, stream_ptr()), "lpm_triangulation_onefc_dz")
+        del ws
+        dalpha, dshift = scal[:, 0].sum().reshape(1), scal[:, 1].sum().reshape(1)
+        dp = _empty((B, T, C), x)
+        ws, wsb = _workspace(lib._lpm_triangulation_onefc_workspace_bytes(1, B, T, D, K, C), x)
+        with _timed("triangulation_onefc_dp", dims):
+            lib.check(lib._lpm_triangulation_onefc_project(ptr(x), ptr(at), ptr(norms), ptr(dA), ptr(g), 1, 1.0, B, T, D, K, C, ptr(dp),
+                                                           ptr(ws) if wsb else None, wsb, stream_ptr()), "lpm_triangulation_onefc_project")
+        del ws
+        # dl = p (dp - sum_t p dp), taken about dp of the clip's heaviest frame (sum_t p = 1): where one weight rounds to 1 - eps the
+        # plain form leaves dp_top - fl(sum) as rounding noise of the size of dp, 40 x the fp32 restatement's error in dW when saturated
+        dd = dp - dp.gather(1, p.argmax(dim=1, keepdim=True))
+        dl = (p * (dd - (p * dd).sum(dim=1, keepdim=True))).contiguous()
+        r_part, r_sum = _empty((B, C, J), x), _empty((C, J), x)
+        with _timed("triangulation_onefc_dweight", dims):
+            lib.check(lib._lpm_triangulation_onefc_pool(ptr(x), ptr(at), ptr(norms), ptr(dl), B, T, D, K, C, ptr(r_part), ptr(r_sum),
+                                                        stream_ptr()), "lpm_triangulation_onefc_pool")
+        del r_part
+        r_jc = r_sum.t()
+        dw = (g[:, None] * r_jc * isj).contiguous()
+        dg = dhg[1] + (w * r_jc).sum(dim=1) * isj
+        dh = dhg[0]
+        dgamma = dbeta = mu = c1 = c2 = None
+        if batch_norm:
+            mu, istd, gamma = bn
+            dbeta, dgamma = dh, (dg - mu * dh) * istd
+            if training:                                # through the batch's own statistics: dmu / N and 2 dvar / N
+                c1 = (-g * dh / N).contiguous()
+                c2 = (-(dg - mu * dh) * gamma * istd * istd * istd / N).contiguous()
+                mu = mu.contiguous()
+        through = c1 is not None
+        dx, danchors = torch.empty_like(x), _empty((D, K), x)
+        ws, wsb = _workspace(lib._lpm_triangulation_onefc_workspace_bytes(3, B, T, D, K, C), x)
+        with _timed("triangulation_onefc_bwd", dims):
+            lib.check(lib._lpm_triangulation_onefc_bwd(ptr(x), ptr(at), ptr(norms), ptr(p), ptr(dl), ptr(dA), ptr(w), ptr(g),
+                                                       ptr(mu) if through else None, ptr(c1) if through else None,
+                                                       ptr(c2) if through else None, B, T, D, K, C, ptr(dx), ptr(danchors), ptr(ws), wsb,
+                                                       stream_ptr()), "lpm_triangulation_onefc_bwd")
+        return dx, danchors, dgamma, dbeta, dw, dalpha, dshift, None, None, None
+
+
+def triangulation_onefc_pool(x, anchors, gamma, beta, attention_weight, alpha, shift, max_frames, batch_norm=True, stats=None):
+    """TriangulationV6Module's pooling of one stream (video_pooling_modules.py:94-119 with attention_modules.OneFcAttention;
+    csrc/triangulation_onefc.hip): x [B * max_frames, D] (a clip's rows contiguous), anchors [D, K] as they are, J = K * D, feature
+    j = k * D + d, ``attention_weight`` [J, C], ``alpha`` and ``shift`` [1]:
+        e = l2_normalize(x - a_k);  s = l2_normalize(e flattened over all J);  v = batch_norm(s) over the B * max_frames rows (gamma, beta [J]);
+        p = softmax over the frames of (1 / sqrt(J)) v W;  A[b,c,:] = sum_t p[b,t,c] v[b,t,:];
+        y[b,c,:] = l2_normalize(alpha A + shift over J) / sqrt(C)
+    -> (pooled [B, C * J] cluster-major, batch_stats): batch_stats = (mean, var), each [J], the batch's own statistics with the BIASED
+    variance, not differentiable (they feed the moving averages; None without ``batch_norm``).  ``stats`` = (mean, var): normalise with
+    these constants instead (inference mode).  Without ``batch_norm`` gamma and beta may be None.  Differentiable in x, anchors, gamma,
+    beta, attention_weight, alpha and shift; in training mode the gradient runs through the batch statistics.  Batch norm is affine per
+    feature, so nothing of size B * T * K * D is written in either direction.  GPU only; D in TRIANGULATION_FEATURES,
+    1 <= max_frames <= 320, 1 <= C <= 64, contiguous fp32 input; no atomics: the same inputs give the same bits."""
+    what = "triangulation_onefc_pool"
+    w = attention_weight
+    if not (torch.is_tensor(x) and torch.is_tensor(anchors)) or x.dim() != 2 or anchors.dim() != 2:
+        raise LpmError(f"{what}: expected x [B * max_frames, D] and anchors [D, K]")
+    _f32(x, what + " x"), _f32(anchors, what + " anchors")
+    if not (x.is_cuda and anchors.is_cuda and x.device == anchors.device):
+        raise LpmError(f"{what}: needs tensors on one MI355X (cuda/hip device); got {x.device} / {anchors.device}.  There is no CPU "
+                       f"fallback: video_pooling_modules.TriangulationV6Module.pool is the host path")
+    if not x.is_contiguous():
+        raise LpmError(f"{what}: x must be contiguous (a column slice of a wider matrix is not: copy the stream's block first)")
+    T = int(max_frames)
+    D, K = anchors.shape
+    J = K * D
+    if D not in TRIANGULATION_FEATURES or x.shape[1] != D or K < 1:
+        raise LpmError(f"{what}: need a feature size in {TRIANGULATION_FEATURES} shared by x and anchors (x {tuple(x.shape)}, anchors {tuple(anchors.shape)})")
+    lib = _capi.load()
+    most, most_c = int(lib._lpm_triangulation_attention_max_frames()), int(lib._lpm_triangulation_onefc_max_clusters())
+    if T < 1 or T > most or x.shape[0] == 0 or x.shape[0] % T:
+        raise LpmError(f"{what}: need 1 <= max_frames <= {most} dividing the {x.shape[0]} rows of x (max_frames = {T})")
+    if not torch.is_tensor(w) or w.dim() != 2 or w.shape[0] != J or not 1 <= w.shape[1] <= most_c:
+        raise LpmError(f"{what}: attention_weight must be [K * D, C] = [{J}, C] with 1 <= C <= {most_c} "
+                       f"(got {tuple(w.shape) if torch.is_tensor(w) else type(w)})")
+    named = [("attention_weight", w, tuple(w.shape)), ("alpha", alpha, (1,)), ("shift", shift, (1,))]
+    if batch_norm:
+        if stats is not None and len(stats) != 2:
+            raise LpmError(f"{what}: stats must be (mean, var)")
+        named += [("gamma", gamma, (J,)), ("beta", beta, (J,))]
+        named += [] if stats is None else [("stats[0]", stats[0], (J,)), ("stats[1]", stats[1], (J,))]
+    elif stats is not None:
+        raise LpmError(f"{what}: stats given without batch_norm")
+    for name, v, shape in named:
+        if not torch.is_tensor(v) or tuple(v.shape) != shape:
+            raise LpmError(f"{what}: {name} must be {list(shape)} (got {tuple(v.shape) if torch.is_tensor(v) else type(v)})")
+        _f32(v, f"{what} {name}")
+        if v.device != x.device:
+            raise LpmError(f"{what}: {name} is on {v.device}, x on {x.device}")
+    if batch_norm:
+        gamma, beta = gamma.contiguous(), beta.contiguous()
+        stats = None if stats is None else tuple(s.contiguous() for s in stats)
+    else:
+        gamma = beta = None
+    y, bstats = _TriangulationOneFcPool.apply(x, anchors.contiguous(), gamma, beta, w.contiguous(), alpha.contiguous(), shift.contiguous(), T,
+                                              bool(batch_norm), stats)
+    return y, (tuple(bstats.unbind(0)) if batch_norm else None)
 
 
 # ----------------------------------------------------------------------------------------------

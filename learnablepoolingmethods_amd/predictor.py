@@ -27,7 +27,7 @@ FUSED_Q8_MODELS = ("NetVladV1", "NetVladV2")
 GATHER_Q8_MODELS = ("RegularizedTriangulationModel", "SoftAttentionTriangulationModel", "TriangulationCnnClusterModel", "JuhanTestModelV5",
                     "JuhanTestModelV1")
 # likewise, added after the five above (whose tuple the frame-gather tests pin by value)
-GATHER_Q8_LATER_MODELS = ("JuhanTestModelV2", "JuhanTestModelV3", "JuhanTestModelV4")
+GATHER_Q8_LATER_MODELS = ("JuhanTestModelV2", "JuhanTestModelV3", "JuhanTestModelV4", "JuhanTestModelV6")
 
 
 def takes_quantised_frames(model, frames) -> bool:

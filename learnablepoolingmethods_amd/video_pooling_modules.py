@@ -1,7 +1,8 @@
 """NetVladOrthoReg and NetVladAttenCluster (reference: video_pooling_modules.py:1499-1586, 1589-1663) and the triangulation
 embeddings (TriangulationEmbedding :376-428, WeightedTriangulationEmbedding :1395-1459, TriangulationTemporalEmbedding :1462-1497,
 TriangulationV5Module :142-373, TriangulationCnnIndirectAttentionModule :431-631, TriangulationNsCnnIndirectAttentionModule :1108-1342,
-TriangulationMagnitudeNsCnnIndirectAttentionModule :634-888, TriangulationMagnitudeNsCnnNetVladModule :891-1105)."""
+TriangulationMagnitudeNsCnnIndirectAttentionModule :634-888, TriangulationMagnitudeNsCnnNetVladModule :891-1105,
+TriangulationV6Module :39-138)."""
 from __future__ import annotations
 
 import math
@@ -586,3 +587,95 @@ class TriangulationMagnitudeNsCnnNetVladModule(TriangulationMagnitudeNsCnnIndire
     def forward(self, inputs, **unused_params):
         """inputs [(B*max_frames), D] -> [B, output_dim]."""
         return self.head(*self.frames(inputs))
+
+
+class TriangulationV6Module(modules.BaseModule):
+    """:39-138 (JuhanTestModelV6's module): the triangulation embedding of every frame against the anchors AS THEY ARE (xavier, not
+    normalised), normalised once more over the whole flattened [K*D] row (:106: e / sqrt(K) unless a norm was clamped), a batch norm over
+    all K*D features (``spatial_bn``), then attention_modules.OneFcAttention(K*D, max_frames, cluster_size, do_shift=True): a softmax
+    over the FRAMES of (1 / sqrt(K*D)) v W, the C weighted sums of the frames, ``alpha`` * . + ``beta``, an l2 normalisation of each
+    cluster's row and 1 / sqrt(C); then one matrix ``hidden_weight`` [C*K*D, output_dim], batch norm (``spatial_pool2_bn``) and relu.
+    ``self_attention``, ``hidden_layer_size``, ``kernel_size`` and ``add_relu`` are stored and read nowhere, as written.
+    ``pool`` MATERIALISES [(B*T), K*D] five times: the drop-in surface, the CPU path and the unfused GPU path; it creates OneFcAttention's
+    three variables itself under the reference's names (attention_modules.OneFcAttention's K2 route is GPU-only, limited in width, and
+    gives nan at alpha == 0: C49).  ``fused_pool`` is ops.triangulation_onefc_pool with the same variables in the same order."""
+
+    def __init__(self, feature_size, max_frames, anchor_size, self_attention, hidden_layer_size, kernel_size, output_dim, cluster_size,
+                 add_relu, batch_norm, is_training, scope_id=None):
+        self.feature_size = feature_size
+        self.max_frames = max_frames
+        self.anchor_size = int(anchor_size)
+        self.self_attention = self_attention
+        self.hidden_layer_size = hidden_layer_size
+        self.kernel_size = kernel_size
+        self.output_dim = int(output_dim)
+        self.add_relu = add_relu
+        self.cluster_size = int(cluster_size)
+        self.batch_norm = batch_norm
+        self.is_training = is_training
+        self.scope_id = scope_id
+
+    def variables(self, device):
+        """anchor_weights [D, K] without a forward (:86-91)."""
+        sid = "" if self.scope_id is None else str(self.scope_id)
+        anchor_weights = vs.get_variable("anchor_weights" + sid, [self.feature_size, self.anchor_size], vs.glorot_uniform_initializer(),
+                                         device=device)
+        vs.summary("anchor_weights" + sid, anchor_weights)
+        return anchor_weights
+
+    def attention_variables(self, device):
+        """OneFcAttention's (one_fc_attention_weight [K*D, C], alpha [1] = 1, beta [1] = 0.01), in its order (attention_modules.py:30-54)."""
+        J = self.feature_size * self.anchor_size
+        weight = vs.get_variable("one_fc_attention_weight", [J, self.cluster_size], vs.glorot_uniform_initializer(), device=device)
+        alpha = vs.get_variable("alpha", [1], lambda shape, d, gen: torch.full(shape, 1.0, device=d), device=device)
+        beta = vs.get_variable("beta", [1], lambda shape, d, gen: torch.full(shape, 0.01, device=d), device=device)
+        return weight, alpha, beta
+
+    def pool(self, inputs):
+        """inputs [(B*max_frames), D] -> [B, C * K*D] cluster-major (:86-119)."""
+        D, K, C, T = self.feature_size, self.anchor_size, self.cluster_size, self.max_frames
+        J = K * D
+        anchor_weights = self.variables(inputs.device)
+        spatial = inputs.unsqueeze(1) - anchor_weights.t().unsqueeze(0)                                # :94-101 -> [M, K, D]
+        spatial = layers.l2_normalize(spatial, 2).reshape(-1, J)                                       # :104-105
+        spatial = layers.l2_normalize(spatial, 1)                                                      # :106
+        if self.batch_norm:
+            spatial = layers.batch_norm(spatial, self.is_training, "spatial_bn")                       # :108-114
+        weight, alpha, beta = self.attention_variables(inputs.device)
+        attention = spatial.matmul(weight).reshape(-1, T, C) * (1 / math.sqrt(J))                      # attention_modules.py:34-36
+        attention = torch.softmax(attention, dim=1)                                                    # :37: over the frames
+        activation = attention.transpose(1, 2).matmul(spatial.reshape(-1, T, J)).reshape(-1, J)        # :39-44
+        activation = layers.l2_normalize(alpha * activation + beta, 1) * (1 / math.sqrt(C))            # :56-59
+        return activation.reshape(-1, C * J)                                                           # :61
+
+    def fused_pool(self, inputs):
+        """``pool`` through ops.triangulation_onefc_pool: the same variables in the same order, the moving averages updated from the op's
+        batch statistics by layers.batch_norm's rank-2 rule (the unbiased estimate into the moving variance)."""
+        T, J = self.max_frames, self.feature_size * self.anchor_size
+        anchor_weights = self.variables(inputs.device)
+        gamma = beta_bn = stats = mm = mv = None
+        if self.batch_norm:
+            gamma, beta_bn, mm, mv = layers.bn_variables("spatial_bn", J, inputs.device)
+            stats = None if self.is_training else (mm, mv)
+        weight, alpha, beta = self.attention_variables(inputs.device)
+        pooled, batch_stats = ops.triangulation_onefc_pool(inputs, anchor_weights, gamma, beta_bn, weight, alpha, beta, T,
+                                                           batch_norm=bool(self.batch_norm), stats=stats)
+        if self.batch_norm and self.is_training:
+            n = inputs.shape[0]
+            with torch.no_grad():
+                mm.mul_(layers.BN_DECAY).add_(batch_stats[0], alpha=1 - layers.BN_DECAY)
+                mv.mul_(layers.BN_DECAY).add_(batch_stats[1] * (n / max(n - 1, 1)), alpha=1 - layers.BN_DECAY)
+        return pooled
+
+    def head(self, pooled):
+        """[B, C * K*D] -> [B, output_dim] (:121-136)."""
+        hidden_weight = vs.get_variable("hidden_weight", [pooled.shape[1], self.output_dim], vs.glorot_uniform_initializer(),
+                                        device=pooled.device)
+        spatial_activation = pooled.matmul(hidden_weight)
+        if self.batch_norm:
+            spatial_activation = layers.batch_norm(spatial_activation, self.is_training, "spatial_pool2_bn")
+        return torch.relu(spatial_activation)
+
+    def forward(self, inputs, **unused_params):
+        """inputs [(B*max_frames), D] -> [B, output_dim]."""
+        return self.head(self.pool(inputs))
