@@ -103,26 +103,36 @@ int lpm_dequantize_l2_normalize(const unsigned char* q, const int32_t* num_frame
  * a2 + a3: SampleUniformFrames + input_bn
  *   replaces model_utils.py:101-122 (gather_nd) + frame_level_models.py:2265-2271 (slim.batch_norm).
  * raw [B, max_frames, F]; num_frames [B] int32; S sampled frames per clip; rows = B*S.
- * Training: lpm_frame_stats writes per-block column partials (sum, sum of squares) of the gathered
- * rows into `partial` (lpm_frame_stats_workspace_bytes); lpm_bn_fold turns them into the folded
- * affine and updates the moving statistics; lpm_frame_apply writes y = gather(raw)*scale + shift.
+ * Training: lpm_frame_stats (and its _q8 / _idx / _idx_q8 forms) writes per-block column partials of the gathered
+ * rows into `partial`, lpm_frame_stats_partial_bytes(B, S, F) bytes: the raw (sum, sum of squares) [nblk, 2, F] as
+ * lpm_bn_fold reads them, then the same two sums of the values less a per-column pivot [nblk, 2, F], then the
+ * pivots [F]; lpm_frame_bn_fold (below, beside lpm_bn_fold) turns them into the folded affine and updates the
+ * moving statistics; lpm_frame_apply writes y = (gather(raw) - centre)*scale + shift.
+ * centre (every lpm_frame_apply* form's last parameter; NULL: zeros): one value per column, taken off the frames first.
+ * lpm_frame_bn_fold leaves the column's fp32 mean there where it takes the shifted sums (4 mean^2 > var), with shift = beta - (mean - centre)*scale, and 0
+ * elsewhere: the frames less their mean are exact, so shift stays of beta's size -- v*scale + (beta - mean*scale) carries half
+ * an ulp of mean*scale, eps32 (mean/std) of the result -- and where centre is 0 every bit is that of the two-vector form.
+ * partial_bytes is the size of `partial`: each of the four forms refuses (LPM_ERR_WORKSPACE) a buffer smaller than
+ * lpm_frame_stats_partial_bytes -- NOT lpm_frame_stats_workspace_bytes, which sized `partial` before the shifted sums and is
+ * now the workspace of the lpm_frame_bn_bwd* forms only.
  * ------------------------------------------------------------------------------------------- */
 size_t lpm_frame_stats_workspace_bytes(int B, int S, int F);
+size_t lpm_frame_stats_partial_bytes(int B, int S, int F);
 int lpm_frame_stats(const float* raw, const int32_t* num_frames, int B, int max_frames, int F, int S,
-                    float* partial, lpm_stream_t stream);
+                    float* partial, size_t partial_bytes, lpm_stream_t stream);
 int lpm_frame_apply(const float* raw, const int32_t* num_frames, int B, int max_frames, int F, int S,
-                    const float* scale, const float* shift, float* y, lpm_stream_t stream);
+                    const float* scale, const float* shift, float* y, lpm_stream_t stream, const float* centre);
 /* lpm_frame_apply that also emits the split-bf16 tile copies K2 reads (see lpm_split_frames): columns [0,Dv) -> xt_video,
  * [Dv, Dv+Da) -> xt_audio (either may be NULL); Dv + Da == F. */
 int lpm_frame_apply_tiles(const float* raw, const int32_t* num_frames, int B, int max_frames, int F, int S,
                           const float* scale, const float* shift, float* y, void* xt_video, int Dv, void* xt_audio, int Da,
-                          lpm_stream_t stream);
+                          lpm_stream_t stream, const float* centre);
 /* ... with the two column blocks as TWO contiguous matrices, y_video [B*S, Dv] and y_audio [B*S, Da] (round 6: NetVladV2, whose frame
  * encoders and aggregations want whole rows -- a column slice of one [B*S, F] matrix cost a contiguous copy per stream, a second
  * lpm_split_frames per stream and a concatenation of the two gradients), and lpm_frame_bn_bwd taking the gradient the same way. */
 int lpm_frame_apply_tiles_split(const float* raw, const int32_t* num_frames, int B, int max_frames, int F, int S, const float* scale,
                                 const float* shift, float* y_video, float* y_audio, void* xt_video, int Dv, void* xt_audio, int Da,
-                                lpm_stream_t stream);
+                                lpm_stream_t stream, const float* centre);
 int lpm_frame_bn_bwd_split(const float* dy_video, int64_t ldv, const float* dy_audio, int64_t lda, int Dv, const float* raw,
                            const int32_t* num_frames, int B, int max_frames, int F, int S, const float* mean, const float* var, float eps,
                            float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, lpm_stream_t stream);
@@ -130,8 +140,8 @@ int lpm_frame_bn_bwd_split(const float* dy_video, int64_t ldv, const float* dy_a
  * NULL), so that no pass over the fp32 matrix is needed between a3 and K1. */
 int lpm_frame_apply_tiles2(const float* raw, const int32_t* num_frames, int B, int max_frames, int F, int S,
                            const float* scale, const float* shift, float* y, void* xt_video, void* xr_video, int Dv,
-                           void* xt_audio, void* xr_audio, int Da, lpm_stream_t stream);
-int lpm_frame_stats_nblk(int B, int S);   /* rows of `partial` lpm_frame_stats writes (for lpm_bn_fold) */
+                           void* xt_audio, void* xr_audio, int Da, lpm_stream_t stream, const float* centre);
+int lpm_frame_stats_nblk(int B, int S);   /* row blocks of `partial` lpm_frame_stats writes (for lpm_frame_bn_fold) */
 /* Eval mode from the reader's quantised frames: the apply forms above with the dequantisation and the per-frame L2 normalisation of
  * lpm_dequantize_l2_normalize folded in, for the S SAMPLED frames only.  lpm_frame_inv_norm_q8 writes inv_norm [B*S] fp32, the inverse
  * L2 norm of the dequantised frame behind every sampled row (0: a frame at or past num_frames, zero after the reader's padding; F <= 2048);
@@ -142,26 +152,26 @@ int lpm_frame_inv_norm_q8(const unsigned char* q, const int32_t* num_frames, int
                           float max_quantized_value, float min_quantized_value, float* inv_norm, lpm_stream_t stream);
 int lpm_frame_apply_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
                        const int32_t* num_frames, int B, int max_frames, int F, int S, const float* scale, const float* shift, float* y,
-                       lpm_stream_t stream);
+                       lpm_stream_t stream, const float* centre);
 int lpm_frame_apply_tiles_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
                              const int32_t* num_frames, int B, int max_frames, int F, int S, const float* scale, const float* shift, float* y,
-                             void* xt_video, int Dv, void* xt_audio, int Da, lpm_stream_t stream);
+                             void* xt_video, int Dv, void* xt_audio, int Da, lpm_stream_t stream, const float* centre);
 int lpm_frame_apply_tiles_split_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
                                    const int32_t* num_frames, int B, int max_frames, int F, int S, const float* scale, const float* shift,
-                                   float* y_video, float* y_audio, void* xt_video, int Dv, void* xt_audio, int Da, lpm_stream_t stream);
+                                   float* y_video, float* y_audio, void* xt_video, int Dv, void* xt_audio, int Da, lpm_stream_t stream, const float* centre);
 int lpm_frame_apply_tiles2_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
                               const int32_t* num_frames, int B, int max_frames, int F, int S, const float* scale, const float* shift, float* y,
-                              void* xt_video, void* xr_video, int Dv, void* xt_audio, void* xr_audio, int Da, lpm_stream_t stream);
+                              void* xt_video, void* xr_video, int Dv, void* xt_audio, void* xr_audio, int Da, lpm_stream_t stream, const float* centre);
 int lpm_frame_apply_tiles_bf16_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
                                   const int32_t* num_frames, int B, int max_frames, int F, int S, const float* scale, const float* shift,
                                   float* y, void* xt_video, void* xr_video, int Dv, void* xt_audio, void* xr_audio, int Da,
-                                  lpm_stream_t stream);
+                                  lpm_stream_t stream, const float* centre);
 /* Training mode from the reader's quantised frames: lpm_frame_stats, lpm_frame_bn_bwd and lpm_frame_bn_bwd_split reading q and inv_norm
  * (lpm_frame_inv_norm_q8) in place of `raw`.  Every frame value is formed as the *_q8 apply forms form it, and every column sums the
  * rows of its 32-row block in the fp32 forms' order, so `partial`, dgamma and dbeta are bit for bit those of the fp32 forms on
  * lpm_dequantize_l2_normalize's output.  The gradients and the workspace must be 16-byte aligned, row strides and Dv multiples of 4. */
 int lpm_frame_stats_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
-                       const int32_t* num_frames, int B, int max_frames, int F, int S, float* partial, lpm_stream_t stream);
+                       const int32_t* num_frames, int B, int max_frames, int F, int S, float* partial, size_t partial_bytes, lpm_stream_t stream);
 int lpm_frame_bn_bwd_q8(const float* dy, int64_t lddy, const unsigned char* q, const float* inv_norm, float max_quantized_value,
                         float min_quantized_value, const int32_t* num_frames, int B, int max_frames, int F, int S, const float* mean,
                         const float* var, float eps, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
@@ -179,15 +189,15 @@ int lpm_frame_bn_bwd_split_q8(const float* dy_video, int64_t ldv, const float* d
  * inv_norm in place of `raw` and writes exactly the bytes its fp32 form writes from lpm_dequantize_l2_normalize's frames. */
 int lpm_frame_inv_norm_q8_idx(const unsigned char* q, const int32_t* num_frames, const int32_t* frame_index, int B, int max_frames, int F,
                               int S, float max_quantized_value, float min_quantized_value, float* inv_norm, lpm_stream_t stream);
-int lpm_frame_stats_idx(const float* raw, const int32_t* frame_index, int B, int max_frames, int F, int S, float* partial,
+int lpm_frame_stats_idx(const float* raw, const int32_t* frame_index, int B, int max_frames, int F, int S, float* partial, size_t partial_bytes,
                         lpm_stream_t stream);
 int lpm_frame_stats_idx_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
-                           const int32_t* frame_index, int B, int max_frames, int F, int S, float* partial, lpm_stream_t stream);
+                           const int32_t* frame_index, int B, int max_frames, int F, int S, float* partial, size_t partial_bytes, lpm_stream_t stream);
 int lpm_frame_apply_split_idx(const float* raw, const int32_t* frame_index, int B, int max_frames, int F, int S, const float* scale,
-                              const float* shift, float* y_video, float* y_audio, int Dv, lpm_stream_t stream);
+                              const float* shift, float* y_video, float* y_audio, int Dv, lpm_stream_t stream, const float* centre);
 int lpm_frame_apply_split_idx_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
                                  const int32_t* frame_index, int B, int max_frames, int F, int S, const float* scale, const float* shift,
-                                 float* y_video, float* y_audio, int Dv, lpm_stream_t stream);
+                                 float* y_video, float* y_audio, int Dv, lpm_stream_t stream, const float* centre);
 int lpm_frame_bn_bwd_split_idx(const float* dy_video, int64_t ldv, const float* dy_audio, int64_t lda, int Dv, const float* raw,
                                const int32_t* frame_index, int B, int max_frames, int F, int S, const float* mean, const float* var,
                                float eps, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, lpm_stream_t stream);
@@ -197,7 +207,7 @@ int lpm_frame_bn_bwd_split_idx_q8(const float* dy_video, int64_t ldv, const floa
                                   float* dbeta, void* workspace, size_t workspace_bytes, lpm_stream_t stream);
 /* backward of input_bn's affine parameters only (the frames are data, never a trainable tensor, so no
  * gradient w.r.t. raw is produced): dgamma = sum dy*xhat, dbeta = sum dy over the gathered rows.
- * dy [B*S, F] with row stride lddy; mean/var = the batch statistics lpm_bn_fold returned.
+ * dy [B*S, F] with row stride lddy; mean/var = the batch statistics lpm_frame_bn_fold returned.
  * workspace: lpm_frame_stats_workspace_bytes(B,S,F). */
 int lpm_frame_bn_bwd(const float* dy, int64_t lddy, const float* raw, const int32_t* num_frames, int B,
                      int max_frames, int F, int S, const float* mean, const float* var, float eps, float* dgamma,
@@ -213,6 +223,14 @@ int lpm_frame_bn_bwd(const float* dy, int64_t lddy, const float* raw, const int3
 int lpm_bn_fold(const float* partial, int nblk, int C, int64_t rows, const float* gamma, const float* beta,
                 float eps, float decay, float* mean, float* var, float* scale, float* shift,
                 float* moving_mean, float* moving_var, lpm_stream_t stream);
+/* The same fold of the lpm_frame_stats* forms' `partial` (lpm_frame_stats_partial_bytes).  var = sumsq/rows - mean^2 from raw fp32
+ * sums loses eps32 (mean/std)^2 of the variance; this fold also forms mean = pivot + s'/rows, var = q'/rows - (s'/rows)^2 from the
+ * shifted sums (s', q'), which is accurate at any offset, and lets it decide: where 4 x that mean^2 <= that var the raw sums are taken --
+ * every result is then bit for bit lpm_bn_fold's -- and elsewhere the shifted ones.  centre [C] (may be NULL: then shift is
+ * beta - mean*scale throughout): see the lpm_frame_apply forms. */
+int lpm_frame_bn_fold(const float* partial, int nblk, int C, int64_t rows, const float* gamma, const float* beta,
+                      float eps, float decay, float* mean, float* var, float* scale, float* shift,
+                      float* moving_mean, float* moving_var, lpm_stream_t stream, float* centre);
 
 /* ---------------------------------------------------------------------------------------------
  * K1: soft-assignment GEMM  logits[M,K] = x[M,D] (row stride ldx) . w[D,K]
@@ -445,7 +463,7 @@ size_t lpm_frame_tiles_bf16_bytes(int B, int S, int D);
 int lpm_frame_steps_bf16(int T);
 int lpm_frame_apply_tiles_bf16(const float* raw, const int32_t* num_frames, int B, int max_frames, int F, int S,
                                const float* scale, const float* shift, float* y, void* xt_video, void* xr_video, int Dv,
-                               void* xt_audio, void* xr_audio, int Da, lpm_stream_t stream);
+                               void* xt_audio, void* xr_audio, int Da, lpm_stream_t stream, const float* centre);
 int lpm_split_weight_tiles_bf16(const float* w, int R, int N, int transposed, void* wt, lpm_stream_t stream);
 int lpm_split_frames_bf16(const float* x, int64_t ldx, int B, int T, int D, void* xt, lpm_stream_t stream);
 int lpm_assign_gemm_tiles_fwd_bf16(const void* xr, const void* wt, int B, int T, int D, int K, void* logits_bf16, float* partial,

@@ -43,30 +43,32 @@ SIGNATURES = {
     "lpm_l2_normalize_rows": (_i, [_f, _l, _i, _f, _f]),
     "lpm_dequantize_l2_normalize": (_i, [_f, _f, _i, _i, _i, _fl, _fl, _f, _f]),
     "lpm_frame_stats_workspace_bytes": (_s, [_i, _i, _i]),
-    "lpm_frame_stats": (_i, [_f, _f, _i, _i, _i, _i, _f, _f]),
-    "lpm_frame_apply": (_i, [_f, _f, _i, _i, _i, _i, _f, _f, _f, _f]),
-    "lpm_frame_apply_tiles": (_i, [_f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _i, _f, _i, _f]),
-    "lpm_frame_apply_tiles_split": (_i, [_f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _i, _f]),
+    "lpm_frame_stats_partial_bytes": (_s, [_i, _i, _i]),
+    "lpm_frame_stats": (_i, [_f, _f, _i, _i, _i, _i, _f, _s, _f]),
+    "lpm_frame_apply": (_i, [_f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f]),
+    "lpm_frame_apply_tiles": (_i, [_f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _i, _f, _i, _f, _f]),
+    "lpm_frame_apply_tiles_split": (_i, [_f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _i, _f, _f]),
     "lpm_frame_stats_nblk": (_i, [_i, _i]),
     "lpm_frame_bn_bwd": (_i, [_f, _l, _f, _f, _i, _i, _i, _i, _f, _f, _fl, _f, _f, _f, _s, _f]),
     "lpm_frame_bn_bwd_split": (_i, [_f, _l, _f, _l, _i, _f, _f, _i, _i, _i, _i, _f, _f, _fl, _f, _f, _f, _s, _f]),
-    "lpm_frame_stats_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f]),
+    "lpm_frame_stats_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _s, _f]),
     "lpm_frame_bn_bwd_q8": (_i, [_f, _l, _f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _fl, _f, _f, _f, _s, _f]),
     "lpm_frame_bn_bwd_split_q8": (_i, [_f, _l, _f, _l, _i, _f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _fl, _f, _f, _f, _s, _f]),
     "lpm_frame_inv_norm_q8": (_i, [_f, _f, _i, _i, _i, _i, _fl, _fl, _f, _f]),
     "lpm_frame_inv_norm_q8_idx": (_i, [_f, _f, _f, _i, _i, _i, _i, _fl, _fl, _f, _f]),
-    "lpm_frame_stats_idx": (_i, [_f, _f, _i, _i, _i, _i, _f, _f]),
-    "lpm_frame_stats_idx_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f]),
-    "lpm_frame_apply_split_idx": (_i, [_f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _i, _f]),
-    "lpm_frame_apply_split_idx_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _f, _f, _i, _f]),
+    "lpm_frame_stats_idx": (_i, [_f, _f, _i, _i, _i, _i, _f, _s, _f]),
+    "lpm_frame_stats_idx_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _s, _f]),
+    "lpm_frame_apply_split_idx": (_i, [_f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _i, _f, _f]),
+    "lpm_frame_apply_split_idx_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _f, _f, _i, _f, _f]),
     "lpm_frame_bn_bwd_split_idx": (_i, [_f, _l, _f, _l, _i, _f, _f, _i, _i, _i, _i, _f, _f, _fl, _f, _f, _f, _s, _f]),
     "lpm_frame_bn_bwd_split_idx_q8": (_i, [_f, _l, _f, _l, _i, _f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _fl, _f, _f, _f, _s, _f]),
-    "lpm_frame_apply_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _f, _f]),
-    "lpm_frame_apply_tiles_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _f, _f, _i, _f, _i, _f]),
-    "lpm_frame_apply_tiles_split_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _i, _f]),
-    "lpm_frame_apply_tiles2_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _f, _i, _f]),
-    "lpm_frame_apply_tiles_bf16_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _f, _i, _f]),
+    "lpm_frame_apply_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f]),
+    "lpm_frame_apply_tiles_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _f, _f, _i, _f, _i, _f, _f]),
+    "lpm_frame_apply_tiles_split_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _i, _f, _f]),
+    "lpm_frame_apply_tiles2_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _f, _i, _f, _f]),
+    "lpm_frame_apply_tiles_bf16_q8": (_i, [_f, _f, _fl, _fl, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _f, _i, _f, _f]),
     "lpm_bn_fold": (_i, [_f, _i, _i, _l, _f, _f, _fl, _fl, _f, _f, _f, _f, _f, _f, _f]),
+    "lpm_frame_bn_fold": (_i, [_f, _i, _i, _l, _f, _f, _fl, _fl, _f, _f, _f, _f, _f, _f, _f, _f]),
     "lpm_assign_gemm_nblk": (_i, [_i]),
     "lpm_assign_gemm_fwd": (_i, [_f, _l, _f, _i, _i, _i, _i, _f, _f, _f]),
     "lpm_row_tiles_bytes": (_s, [_i, _i, _i]),
@@ -107,8 +109,8 @@ SIGNATURES = {
     "lpm_proj_dx_w16": (_i, [_f, _f, _i, _l, _i, _f, _l, _f]),
     "lpm_frame_tiles_bf16_bytes": (_s, [_i, _i, _i]),
     "lpm_frame_steps_bf16": (_i, [_i]),
-    "lpm_frame_apply_tiles2": (_i, [_f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _f, _i, _f]),
-    "lpm_frame_apply_tiles_bf16": (_i, [_f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _f, _i, _f]),
+    "lpm_frame_apply_tiles2": (_i, [_f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _f, _i, _f, _f]),
+    "lpm_frame_apply_tiles_bf16": (_i, [_f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _f, _i, _f, _f]),
     "lpm_split_weight_tiles_bf16": (_i, [_f, _i, _i, _i, _f, _f]),
     "lpm_split_frames_bf16": (_i, [_f, _l, _i, _i, _i, _f, _f]),
     "lpm_assign_gemm_tiles_fwd_bf16": (_i, [_f, _f, _i, _i, _i, _i, _f, _f, _f]),

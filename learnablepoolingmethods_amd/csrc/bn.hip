@@ -13,7 +13,8 @@ namespace lpm {
 // K = pivot[c], the mean of the matrix's first BN_PIVOT_ROWS rows; from them the same fold loses eps32 (1 + ((mean - K)/std)^2), under
 // 3 eps32 at any offset -- and more than the raw sums where the mean is small against the spread.  Both forms are evaluated; the shifted one decides: where mean^2 <= var the raw sums
 // are taken (there the results are bit for bit what they were before the shifted sums existed), elsewhere the shifted ones (as ln_moments,
-// layer_norm.hip).  shifted == NULL (lpm_bn_fold: K1's epilogue, frame_prep.hip, the attention's logit statistics): the raw sums alone.
+// layer_norm.hip).  lpm_frame_bn_fold (frame_prep.hip's frame_stats_kernel) passes its own shifted sums, the pivot the mean of eight gathered
+// rows spread over the batch.  shifted == NULL (lpm_bn_fold: K1's epilogue, the attention's logit statistics): the raw sums alone.
 template <int CW>
 __global__ __launch_bounds__(1024) void bn_fold_kernel(const float* __restrict__ partial, int nblk, int C,
                                                        double inv_rows, double unbias,
@@ -21,7 +22,14 @@ __global__ __launch_bounds__(1024) void bn_fold_kernel(const float* __restrict__
                                                        const float* __restrict__ beta, float eps, float decay,
                                                        float* mean, float* var, float* scale, float* shift,
                                                        float* moving_mean, float* moving_var,
-                                                       const float* __restrict__ shifted, const float* __restrict__ pivot) {
+                                                       const float* __restrict__ shifted, const float* __restrict__ pivot,
+                                                       float* __restrict__ centre, double take) {
+    // take: the shifted sums are taken where take mean^2 > var.  1 for lpm_bn_rows_* (as ever).  4 for lpm_frame_bn_fold: a clip of one
+    // frame fills its S sampled rows with ONE row, and hundreds of equal addends round the same way every time -- measured with half the
+    // batch such a row, the raw sums stood at 1.02 of the bound of tests/test_gpu_frame_prep_bounds.py in columns at |mean|/std = 0.92 .. 0.96
+    // and at 0.8 at 0.82; the shifted sums (the pivot rows see the repeated row too) lose a third of that there.
+    // centre != NULL (lpm_frame_bn_fold): where the shifted sums are taken, the column's fp32 mean goes there and shift becomes
+    // beta - (mean - centre) scale, for the apply pass y = (x - centre) scale + shift (frame_apply_kernel); elsewhere 0 and the shift as ever
     double s, q, ss = 0.0, sq = 0.0;
     int c;
     partial_colsums<CW>(partial, nblk, 2 * (int64_t)C, C, C, s, q, c);
@@ -33,13 +41,15 @@ __global__ __launch_bounds__(1024) void bn_fold_kernel(const float* __restrict__
         double mu = s * inv_rows;
         double vr = q * inv_rows - mu * mu;
         if (vr < 0.0) vr = 0.0;
+        bool taken = false;
         if (shifted) {
             const double dm = ss * inv_rows, mu_s = (double)pivot[c] + dm;
             double vr_s = sq * inv_rows - dm * dm;
             if (vr_s < 0.0) vr_s = 0.0;
-            if (mu_s * mu_s > vr_s) {
+            if (take * (mu_s * mu_s) > vr_s) {
                 mu = mu_s;
                 vr = vr_s;
+                taken = true;
             }
         }
         const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
@@ -47,7 +57,13 @@ __global__ __launch_bounds__(1024) void bn_fold_kernel(const float* __restrict__
         if (mean) mean[c] = (float)mu;
         if (var) var[c] = (float)vr;
         scale[c] = sc;
-        shift[c] = b - (float)mu * sc;
+        if (centre && taken) {
+            centre[c] = (float)mu;
+            shift[c] = (float)((double)b - (mu - (double)(float)mu) * (double)sc);
+        } else {
+            if (centre) centre[c] = 0.f;
+            shift[c] = b - (float)mu * sc;
+        }
         if (moving_mean) {
             moving_mean[c] = moving_mean[c] * decay + (float)mu * (1.f - decay);
             moving_var[c] = moving_var[c] * decay + (float)(vr * unbias) * (1.f - decay);
@@ -501,7 +517,7 @@ static int bn_rows_fwd_impl(const float* x, const float* pre_bias, int pre_relu,
     hipLaunchKernelGGL(bn_rows_stats_kernel, dim3(nblk, bn_col_chunks(C)), dim3(256), 0, s, x, M, C, partial, pre_bias, pre_relu, shifted, pivot);
     const double unbias = (biased_moving_variance || M <= 1) ? 1.0 : (double)M / (double)(M - 1);
     hipLaunchKernelGGL(bn_fold_kernel<16>, dim3((C + 15) / 16), dim3(1024), 0, s, partial, nblk, C, 1.0 / (double)M, unbias, gamma, beta, eps,
-                       decay, mean, var, scale, shift, moving_mean, moving_var, (const float*)shifted, (const float*)pivot);
+                       decay, mean, var, scale, shift, moving_mean, moving_var, (const float*)shifted, (const float*)pivot, (float*)nullptr, 1.0);
     const int64_t total4 = (int64_t)M * C / 4;
     const int64_t want = (total4 + 255) / 256;
     hipLaunchKernelGGL(bn_rows_apply_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, s, x, scale, shift, total4, C / 4, y, pre_bias,
@@ -640,24 +656,42 @@ extern "C" int lpm_bn_small_bwd(const float* dy, const float* x, int M, int C, c
     return check_launch("lpm_bn_small_bwd");
 }
 
-extern "C" int lpm_bn_fold(const float* partial, int nblk, int C, int64_t rows, const float* gamma, const float* beta,
-                           float eps, float decay, float* mean, float* var, float* scale, float* shift,
-                           float* moving_mean, float* moving_var, lpm_stream_t stream) {
+// shifted / pivot: NULL (lpm_bn_fold), or the second partial array and the pivots (lpm_frame_bn_fold)
+static int bn_fold_launch(const float* partial, int nblk, int C, int64_t rows, const float* gamma, const float* beta, float eps, float decay,
+                          float* mean, float* var, float* scale, float* shift, float* moving_mean, float* moving_var, const float* shifted,
+                          const float* pivot, float* centre, double take, lpm_stream_t stream, const char* name) {
     using namespace lpm;
-    LPM_REQUIRE(partial && scale && shift, LPM_ERR_BADARG, "lpm_bn_fold: null pointer");
-    LPM_REQUIRE(nblk > 0 && C > 0 && rows > 0, LPM_ERR_BADARG, "lpm_bn_fold: bad sizes");
-    LPM_REQUIRE((moving_mean == nullptr) == (moving_var == nullptr), LPM_ERR_BADARG,
-                "lpm_bn_fold: moving_mean and moving_var must be given together");
+    LPM_REQUIRE(partial && scale && shift, LPM_ERR_BADARG, "%s: null pointer", name);
+    LPM_REQUIRE(nblk > 0 && C > 0 && rows > 0, LPM_ERR_BADARG, "%s: bad sizes", name);
+    LPM_REQUIRE((moving_mean == nullptr) == (moving_var == nullptr), LPM_ERR_BADARG, "%s: moving_mean and moving_var must be given together",
+                name);
     const double unbias = rows > 1 ? (double)rows / (double)(rows - 1) : 1.0;
     if (partial_colsums_cw(nblk) == 4)
         hipLaunchKernelGGL(bn_fold_kernel<4>, dim3((C + 3) / 4), dim3(1024), 0, (hipStream_t)stream, partial, nblk, C,
-                           1.0 / (double)rows, unbias, gamma, beta, eps, decay, mean, var, scale, shift, moving_mean, moving_var, (const float*)nullptr,
-                           (const float*)nullptr);
+                           1.0 / (double)rows, unbias, gamma, beta, eps, decay, mean, var, scale, shift, moving_mean, moving_var, shifted, pivot, centre, take);
     else
         hipLaunchKernelGGL(bn_fold_kernel<16>, dim3((C + 15) / 16), dim3(1024), 0, (hipStream_t)stream, partial, nblk, C,
-                           1.0 / (double)rows, unbias, gamma, beta, eps, decay, mean, var, scale, shift, moving_mean, moving_var, (const float*)nullptr,
-                           (const float*)nullptr);
-    return check_launch("lpm_bn_fold");
+                           1.0 / (double)rows, unbias, gamma, beta, eps, decay, mean, var, scale, shift, moving_mean, moving_var, shifted, pivot, centre, take);
+    return check_launch(name);
+}
+
+extern "C" int lpm_bn_fold(const float* partial, int nblk, int C, int64_t rows, const float* gamma, const float* beta,
+                           float eps, float decay, float* mean, float* var, float* scale, float* shift,
+                           float* moving_mean, float* moving_var, lpm_stream_t stream) {
+    return bn_fold_launch(partial, nblk, C, rows, gamma, beta, eps, decay, mean, var, scale, shift, moving_mean, moving_var, nullptr, nullptr,
+                          nullptr, 1.0, stream, "lpm_bn_fold");
+}
+
+// The fold of the lpm_frame_stats* forms' `partial` (lpm_frame_stats_partial_bytes: raw partials [nblk][2][C], shifted partials
+// [nblk][2][C], pivots [C]): lpm_bn_fold's arithmetic and results wherever 4 mean^2 <= var, the shifted sums' moments elsewhere
+// (bn_fold_kernel's ``take`` says why 4).
+extern "C" int lpm_frame_bn_fold(const float* partial, int nblk, int C, int64_t rows, const float* gamma, const float* beta,
+                                 float eps, float decay, float* mean, float* var, float* scale, float* shift,
+                                 float* moving_mean, float* moving_var, lpm_stream_t stream, float* centre) {
+    const float* shifted = partial ? partial + (size_t)(nblk > 0 ? nblk : 0) * 2 * (size_t)(C > 0 ? C : 0) : nullptr;
+    const float* pivot = partial ? shifted + (size_t)(nblk > 0 ? nblk : 0) * 2 * (size_t)(C > 0 ? C : 0) : nullptr;
+    return bn_fold_launch(partial, nblk, C, rows, gamma, beta, eps, decay, mean, var, scale, shift, moving_mean, moving_var, shifted, pivot,
+                          centre, 4.0, stream, "lpm_frame_bn_fold");
 }
 
 extern "C" size_t lpm_bn_bwd_workspace_bytes(int M, int K) {

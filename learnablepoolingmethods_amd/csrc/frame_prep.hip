@@ -3,7 +3,7 @@
 //   y[b*S+j, :] = raw[b, idx[b,j], :] * scale + shift                 model_utils.py:119-122 +
 //                                                                      frame_level_models.py:2265-2271
 // The gathered [B,S,F] tensor is never materialised un-normalised: one pass reduces the column
-// statistics of the gathered rows (per-block partials -> lpm_bn_fold), a second pass gathers again
+// statistics of the gathered rows (per-block partials -> lpm_frame_bn_fold), a second pass gathers again
 // and writes the normalised rows that K1 and K2 consume.  Both are pure HBM streams (float4,
 // row-contiguous 4.6 KB reads).
 // Eval mode from the reader's quantised frames (the *_q8 entry points): the apply kernels read the uint8 frames of the sampled
@@ -114,14 +114,29 @@ __device__ __forceinline__ void storew_f32(float* __restrict__ p, const float (&
     }
 }
 
+// Column statistics of the gathered rows: per 32-row block the raw sums (s, q) = (sum v, sum v^2) -> partial [nblk][2][F], and beside them,
+// in the same pass, the sums of (v - K) and (v - K)^2 -> shifted [nblk][2][F], pivot [F] (then bn_fold_kernel, bn.hip, which says why: the
+// raw fold var = q/n - mean^2 loses eps32 (mean/std)^2 of the variance -- measured at mean/std = 30: batch_var 100 .. 360 times the bound of
+// tests/test_gpu_frame_prep_bounds.py, a quantised feature at 200 +- 3 levels 6 .. 15 times).  The raw sums keep their operations, their
+// order and their layout; the fold takes them wherever 4 mean^2 <= var, bit for bit as before the shifted sums existed.
+// K = the column's mean over FP_PIVOT_ROWS gathered rows spread evenly over ALL B S rows, row (u rows) / p for u < p = min(rows, 8), summed
+// in that order: every workgroup forms it itself (eight rows, in L2 after the first workgroup) and gets the same bits -- no pass, no launch,
+// nothing exchanged.  Spread over the batch, not the first eight rows: those are rows of ONE clip whenever S >= 8, and frames of one clip
+// lie close together (emulated on the CPU, tests/test_frame_prep_ref_host.py: the first eight rows leave batch_var at up to 1.9 of its
+// bound, row 0 alone at up to 3.1, the spread rows at 0.32).
+constexpr int FP_PIVOT_ROWS = 8;
 template <typename Src, typename Idx>
 __global__ __launch_bounds__(256) void frame_stats_kernel(Src raw, Idx ix, int B, int max_frames, int F, int S,
-                                                          float* __restrict__ partial) {
+                                                          float* __restrict__ partial, float* __restrict__ shifted,
+                                                          float* __restrict__ pivot) {
     constexpr int W = Src::W;
     const int r0 = blockIdx.x * FP_ROWS;
     const int rows = B * S;
     const int r1 = min(rows, r0 + FP_ROWS);
+    const int pr = min(rows, FP_PIVOT_ROWS);
     __shared__ int64_t base[FP_ROWS];
+    __shared__ int64_t pbase[FP_PIVOT_ROWS];
+    __shared__ int prow[FP_PIVOT_ROWS];
     if (threadIdx.x < FP_ROWS) {
         const int r = r0 + threadIdx.x;
         if (r < rows) {
@@ -129,12 +144,28 @@ __global__ __launch_bounds__(256) void frame_stats_kernel(Src raw, Idx ix, int B
             const int idx = max(0, min(ix(b, j, r), max_frames - 1));
             base[threadIdx.x] = ((int64_t)b * max_frames + idx) * F;
         }
+    } else if (threadIdx.x >= 64 && threadIdx.x < 64 + pr) {        // (the second wave)
+        const int u = threadIdx.x - 64;
+        const int r = (int)(((int64_t)u * rows) / pr);              // < rows
+        const int b = r / S, j = r % S;
+        const int idx = max(0, min(ix(b, j, r), max_frames - 1));
+        pbase[u] = ((int64_t)b * max_frames + idx) * F;
+        prow[u] = r;
     }
     __syncthreads();
+    const float inv_pr = 1.f / (float)pr;
     for (int c = threadIdx.x * W; c < F; c += 256 * W) {
-        float s[W], q[W];
+        float s[W], q[W], ss[W], sq[W], K[W];
 #pragma unroll
-        for (int k = 0; k < W; ++k) s[k] = q[k] = 0.f;
+        for (int k = 0; k < W; ++k) s[k] = q[k] = ss[k] = sq[k] = K[k] = 0.f;
+        for (int u = 0; u < pr; ++u) {
+            float v[W];
+            raw.loadw(pbase[u] + c, prow[u], v);
+#pragma unroll
+            for (int k = 0; k < W; ++k) K[k] += v[k];
+        }
+#pragma unroll
+        for (int k = 0; k < W; ++k) K[k] *= inv_pr;
         for (int r = 0; r < r1 - r0; ++r) {
             float v[W];
             raw.loadw(base[r] + c, r0 + r, v);
@@ -142,11 +173,18 @@ __global__ __launch_bounds__(256) void frame_stats_kernel(Src raw, Idx ix, int B
             for (int k = 0; k < W; ++k) {
                 s[k] += v[k];
                 q[k] = fmaf(v[k], v[k], q[k]);
+                const float d = v[k] - K[k];
+                ss[k] += d;
+                sq[k] = fmaf(d, d, sq[k]);
             }
         }
         float* p = partial + (int64_t)blockIdx.x * 2 * F;
         storew_f32<W>(p + c, s);
         storew_f32<W>(p + F + c, q);
+        float* ps = shifted + (int64_t)blockIdx.x * 2 * F;
+        storew_f32<W>(ps + c, ss);
+        storew_f32<W>(ps + F + c, sq);
+        if (blockIdx.x == 0) storew_f32<W>(pivot + c, K);
     }
 }
 
@@ -155,7 +193,11 @@ template <typename Src, typename Idx>
 __global__ __launch_bounds__(256) void frame_apply_kernel(Src raw, Idx ix, int B, int max_frames, int F, int S,
                                                           const float* __restrict__ scale,
                                                           const float* __restrict__ shift, float* __restrict__ y,
-                                                          float* __restrict__ y2, int Dv) {
+                                                          float* __restrict__ y2, int Dv, const float* __restrict__ centre) {
+    // centre != null: y = (v - centre) * scale + shift.  lpm_frame_bn_fold leaves centre = the column's fp32 mean where it took the shifted
+    // sums (4 mean^2 > var), eval mode (ops.frame_eval_affine) where moving_mean^2 > moving_var, and both 0 elsewhere
+    // (there v - 0 is v: the bits of the two-vector form): with v - mean formed first, exactly, shift stays of the size of beta and its
+    // rounding with it -- v * scale + (beta - mean * scale) carries half an ulp of mean * scale, eps32 (mean/std) of the result.
     const int F4 = F / 4;
     const int64_t total = (int64_t)B * S * F4;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
@@ -166,6 +208,10 @@ __global__ __launch_bounds__(256) void frame_apply_kernel(Src raw, Idx ix, int B
         if (scale) {
             const float4 sc = *reinterpret_cast<const float4*>(scale + c);
             const float4 sh = *reinterpret_cast<const float4*>(shift + c);
+            if (centre) {
+                const float4 ce = *reinterpret_cast<const float4*>(centre + c);
+                v.x -= ce.x; v.y -= ce.y; v.z -= ce.z; v.w -= ce.w;
+            }
             v.x = fmaf(v.x, sc.x, sh.x); v.y = fmaf(v.y, sc.y, sh.y);
             v.z = fmaf(v.z, sc.z, sh.z); v.w = fmaf(v.w, sc.w, sh.w);
         }
@@ -190,7 +236,8 @@ __global__ __launch_bounds__(256) void frame_apply_tiles_kernel(Src raw, const i
                                                                 const float* __restrict__ scale,
                                                                 const float* __restrict__ shift, float* __restrict__ y,
                                                                 uint4* __restrict__ xtv, int Dv,
-                                                                uint4* __restrict__ xta, int Da, float* __restrict__ y2) {
+                                                                uint4* __restrict__ xta, int Da, float* __restrict__ y2,
+                                                                const float* __restrict__ centre) {
     // y2 != null: the two column blocks leave as TWO contiguous matrices, y [B S, Dv] and y2 [B S, Da] (NetVladV2: each stream's encoder
     // and aggregation want whole rows -- no strided slices, no contiguous copies of them)
     const int F4 = F / 4, NS = (S + 15) / 16;
@@ -200,10 +247,11 @@ __global__ __launch_bounds__(256) void frame_apply_tiles_kernel(Src raw, const i
         const int64_t r = w / F4;
         const int kh = (int)(r & 1), st = (int)((r >> 1) % NS), b = (int)((r >> 1) / NS);
         const int c = 4 * c4;
-        float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = make_float4(0.f, 0.f, 0.f, 0.f), ce = sh;
         if (scale) {
             sc = *reinterpret_cast<const float4*>(scale + c);
             sh = *reinterpret_cast<const float4*>(shift + c);
+            if (centre) ce = *reinterpret_cast<const float4*>(centre + c);       // (frame_apply_kernel says what it is)
         }
         const int nf = num_frames[b];
         float v[4][8];
@@ -215,8 +263,8 @@ __global__ __launch_bounds__(256) void frame_apply_tiles_kernel(Src raw, const i
                 int idx = sample_index(j, step, nf);
                 idx = max(0, min(idx, max_frames - 1));
                 f = raw.load4(((int64_t)b * max_frames + idx) * F + c, (int64_t)b * S + j);
-                f.x = fmaf(f.x, sc.x, sh.x); f.y = fmaf(f.y, sc.y, sh.y);
-                f.z = fmaf(f.z, sc.z, sh.z); f.w = fmaf(f.w, sc.w, sh.w);
+                f.x = fmaf(f.x - ce.x, sc.x, sh.x); f.y = fmaf(f.y - ce.y, sc.y, sh.y);
+                f.z = fmaf(f.z - ce.z, sc.z, sh.z); f.w = fmaf(f.w - ce.w, sc.w, sh.w);
                 const int64_t row = (int64_t)b * S + j;
                 if (!y2) *reinterpret_cast<float4*>(y + row * F + c) = f;
                 else if (c < Dv) *reinterpret_cast<float4*>(y + row * Dv + c) = f;
@@ -244,12 +292,21 @@ __global__ __launch_bounds__(256) void frame_apply_tiles_kernel(Src raw, const i
     }
 }
 
-// column partials of (sum dy, sum dy * x) over the gathered rows, for dgamma/dbeta of input_bn
+// the centre the two backward kernels take off a column's frames: both form it from the same (mean, var), so they agree with each other.
+// It is chosen independently of the forward's centre (the fold's 4 mean^2 > var, eval mode's moving_mean^2 > moving_var) and need not
+// agree with it: dgamma = rstd (sum dy (x - c0) - (mean - c0) sum dy) is the same number for ANY c0, and only its rounding depends on it.
+__device__ __forceinline__ float fbb_centre(float mean, float var) { return mean * mean > var ? mean : 0.f; }
+
+// column partials of (sum dy, sum dy * (x - c0)) over the gathered rows, for dgamma/dbeta of input_bn
 template <typename Src, typename Idx>
 __global__ __launch_bounds__(256) void frame_bn_bwd_partial_kernel(const float* __restrict__ dy, int64_t lddy, Src raw, Idx ix, int B,
                                                                    int max_frames, int F, int S,
                                                                    float* __restrict__ partial, const float* __restrict__ dy2,
-                                                                   int64_t lddy2, int Dv) {
+                                                                   int64_t lddy2, int Dv, const float* __restrict__ mean,
+                                                                   const float* __restrict__ var) {
+    // The second sum is sum dy (x - c0) with c0 = fbb_centre(mean, var): the column's fp32 mean where mean^2 > var, 0 elsewhere (there
+    // x - 0 is x and every bit is what it was).  sum dy x from fp32 products loses eps32 (mean/std) of dgamma = rstd (sum dy x - mean sum dy):
+    // measured in eval mode at mean/std = 30, dgamma 6 .. 11 times the bound of tests/test_gpu_frame_prep_bounds.py.
     // dy2 != null: the gradient arrives as two matrices, columns [0, Dv) in dy and [Dv, F) in dy2 (lpm_frame_apply_tiles_split's outputs)
     constexpr int W = Src::W;       // W = 4: Dv, both row strides and both pointers are multiples of four floats (checked by the host)
     const int r0 = blockIdx.x * FP_ROWS;
@@ -266,9 +323,12 @@ __global__ __launch_bounds__(256) void frame_bn_bwd_partial_kernel(const float* 
     }
     __syncthreads();
     for (int c = threadIdx.x * W; c < F; c += 256 * W) {
-        float s[W], q[W];
+        float s[W], q[W], c0[W];
 #pragma unroll
-        for (int k = 0; k < W; ++k) s[k] = q[k] = 0.f;
+        for (int k = 0; k < W; ++k) {
+            s[k] = q[k] = 0.f;
+            c0[k] = fbb_centre(mean[c + k], var[c + k]);
+        }
         for (int r = 0; r < r1 - r0; ++r) {
             float g[W], x[W];
             loadw_f32<W>((dy2 && c >= Dv) ? dy2 + (int64_t)(r0 + r) * lddy2 + (c - Dv) : dy + (int64_t)(r0 + r) * lddy + c, g);
@@ -276,7 +336,7 @@ __global__ __launch_bounds__(256) void frame_bn_bwd_partial_kernel(const float* 
 #pragma unroll
             for (int k = 0; k < W; ++k) {
                 s[k] += g[k];
-                q[k] = fmaf(g[k], x[k], q[k]);
+                q[k] = fmaf(g[k], x[k] - c0[k], q[k]);
             }
         }
         float* p = partial + (int64_t)blockIdx.x * 2 * F;
@@ -293,10 +353,10 @@ __global__ __launch_bounds__(1024) void frame_bn_bwd_reduce_kernel(const float* 
     int c;
     partial_colsums16(partial, nblk, 2 * (int64_t)F, F, F, s, q, c);
     if (threadIdx.x < 16 && c < F) {
-        // sum dy * xhat = rstd * (sum dy*x - mean * sum dy)
+        // sum dy * xhat = rstd * (sum dy*(x - c0) - (mean - c0) * sum dy)
         const double rstd = 1.0 / sqrt((double)var[c] + (double)eps);
         dbeta[c] = (float)s;
-        dgamma[c] = (float)(rstd * (q - (double)mean[c] * s));
+        dgamma[c] = (float)(rstd * (q - ((double)mean[c] - (double)fbb_centre(mean[c], var[c])) * s));
     }
 }
 
@@ -389,7 +449,8 @@ __global__ __launch_bounds__(256) void frame_apply_tiles_bf16_kernel(Src raw, co
                                                                      int B, int max_frames, int F, int S, float step,
                                                                      const float* __restrict__ scale, const float* __restrict__ shift,
                                                                      float* __restrict__ y, uint4* __restrict__ xtv, uint4* __restrict__ xrv,
-                                                                     int Dv, uint4* __restrict__ xta, uint4* __restrict__ xra, int Da) {
+                                                                     int Dv, uint4* __restrict__ xta, uint4* __restrict__ xra, int Da,
+                                                                     const float* __restrict__ centre) {
     const int F8 = F / 8, NSP = 4 * ((S + 63) / 64), MT = NSP / 2;
     const int64_t total = (int64_t)B * NSP * 2 * F8;
     for (int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x; w < total; w += (int64_t)gridDim.x * 256) {
@@ -397,11 +458,12 @@ __global__ __launch_bounds__(256) void frame_apply_tiles_bf16_kernel(Src raw, co
         const int64_t r = w / F8;
         const int kh = (int)(r & 1), st = (int)((r >> 1) % NSP), b = (int)((r >> 1) / NSP);
         const int c = 8 * c8;
-        float sc[8], sh[8];
+        float sc[8], sh[8], ce[8];
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             sc[q] = scale ? scale[c + q] : 1.f;
             sh[q] = scale ? shift[c + q] : 0.f;
+            ce[q] = (scale && centre) ? centre[c + q] : 0.f;                   // (frame_apply_kernel says what it is)
         }
         const int nf = num_frames[b];
         float v[8][8];                    // [frame e][column q]
@@ -415,8 +477,10 @@ __global__ __launch_bounds__(256) void frame_apply_tiles_bf16_kernel(Src raw, co
                 const int64_t src = ((int64_t)b * max_frames + idx) * F + c, row = (int64_t)b * S + j;
                 f0 = raw.load4(src, row);
                 f1 = raw.load4(src + 4, row);
-                f0.x = fmaf(f0.x, sc[0], sh[0]); f0.y = fmaf(f0.y, sc[1], sh[1]); f0.z = fmaf(f0.z, sc[2], sh[2]); f0.w = fmaf(f0.w, sc[3], sh[3]);
-                f1.x = fmaf(f1.x, sc[4], sh[4]); f1.y = fmaf(f1.y, sc[5], sh[5]); f1.z = fmaf(f1.z, sc[6], sh[6]); f1.w = fmaf(f1.w, sc[7], sh[7]);
+                f0.x = fmaf(f0.x - ce[0], sc[0], sh[0]); f0.y = fmaf(f0.y - ce[1], sc[1], sh[1]);
+                f0.z = fmaf(f0.z - ce[2], sc[2], sh[2]); f0.w = fmaf(f0.w - ce[3], sc[3], sh[3]);
+                f1.x = fmaf(f1.x - ce[4], sc[4], sh[4]); f1.y = fmaf(f1.y - ce[5], sc[5], sh[5]);
+                f1.z = fmaf(f1.z - ce[6], sc[6], sh[6]); f1.w = fmaf(f1.w - ce[7], sc[7], sh[7]);
                 if (y) {
                     float* dst = y + ((int64_t)b * S + j) * F + c;
                     *reinterpret_cast<float4*>(dst) = f0;
@@ -470,6 +534,11 @@ extern "C" size_t lpm_frame_stats_workspace_bytes(int B, int S, int F) {
     return (size_t)fp_nblk(B, S) * 2 * F * sizeof(float);
 }
 extern "C" int lpm_frame_stats_nblk(int B, int S) { return fp_nblk(B, S); }
+// `partial` of the lpm_frame_stats* forms: the raw partials [nblk][2][F], the shifted partials [nblk][2][F], the pivots [F] -- what
+// lpm_frame_bn_fold reads (lpm_bn_fold reads the first array alone)
+extern "C" size_t lpm_frame_stats_partial_bytes(int B, int S, int F) {
+    return ((size_t)fp_nblk(B, S) * 4 * F + (size_t)F) * sizeof(float);
+}
 
 // index: num_frames (the uniform forms) or frame_index (the *_idx forms)
 #define LPM_FRAME_CHECK_(name, index)                                                                               \
@@ -492,6 +561,11 @@ extern "C" int lpm_frame_stats_nblk(int B, int S) { return fp_nblk(B, S); }
 #define LPM_FRAME_Q8_CHECK(name) LPM_FRAME_Q8_CHECK_(name, num_frames)
 #define LPM_FRAME_Q8_IDX_CHECK(name) LPM_FRAME_Q8_CHECK_(name, frame_index)
 
+// centre (the apply forms' last parameter, may be NULL): one value per column, taken off the frames before scale and shift
+#define LPM_FRAME_CENTRE_CHECK(name)                                                                                          \
+    LPM_REQUIRE(centre == nullptr || (scale != nullptr && ((uintptr_t)centre & 15) == 0), LPM_ERR_BADARG,                      \
+                "%s: centre needs scale and shift, and 16-byte alignment", name)
+
 namespace {
 
 using lpm::FrameSrc;
@@ -508,16 +582,17 @@ FrameSrc<unsigned char> q8_src(const unsigned char* q, const float* inv_norm, fl
 // y2 == NULL: one [B S, F] matrix y; else y [B S, Dv] and y2 [B S, F - Dv] (the *_split_idx forms)
 template <typename Src, typename Idx>
 int launch_frame_apply(Src raw, Idx ix, int B, int max_frames, int F, int S, const float* scale, const float* shift, float* y, float* y2,
-                       int Dv, hipStream_t stream, const char* name) {
+                       int Dv, hipStream_t stream, const char* name, const float* centre) {
     using namespace lpm;
     LPM_REQUIRE(y && ((scale == nullptr) == (shift == nullptr)), LPM_ERR_BADARG, "%s: bad pointers", name);
+    LPM_FRAME_CENTRE_CHECK(name);
     if (y2 != nullptr)
         LPM_REQUIRE(Dv > 0 && Dv < F && Dv % 4 == 0 && (((uintptr_t)y | (uintptr_t)y2 | (uintptr_t)scale | (uintptr_t)shift) & 15) == 0,
                     LPM_ERR_UNSUPPORTED_SHAPE, "%s: need 0 < Dv < F, Dv %% 4 == 0, 16-byte aligned buffers (F=%d Dv=%d)", name, F, Dv);
     const int64_t total = (int64_t)B * S * (F / 4);
     const int64_t want = (total + 255) / 256;
     hipLaunchKernelGGL((frame_apply_kernel<Src, Idx>), dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, stream, raw, ix, B,
-                       max_frames, F, S, scale, shift, y, y2, Dv);
+                       max_frames, F, S, scale, shift, y, y2, Dv, centre);
     return check_launch(name);
 }
 
@@ -525,8 +600,9 @@ int launch_frame_apply(Src raw, Idx ix, int B, int max_frames, int F, int S, con
 template <typename Src>
 int launch_frame_apply_tiles(Src raw, const int32_t* num_frames, int B, int max_frames, int F, int S, const float* scale,
                              const float* shift, float* y, float* y2, void* xt_video, int Dv, void* xt_audio, int Da, hipStream_t stream,
-                             const char* name) {
+                             const char* name, const float* centre) {
     using namespace lpm;
+    LPM_FRAME_CENTRE_CHECK(name);
     if (y2 == nullptr) {
         LPM_REQUIRE(y && ((scale == nullptr) == (shift == nullptr)), LPM_ERR_BADARG, "%s: bad pointers", name);
         LPM_REQUIRE(Dv > 0 && Da >= 0 && Dv + Da == F && Dv % 32 == 0 && Da % 32 == 0, LPM_ERR_UNSUPPORTED_SHAPE,
@@ -541,7 +617,7 @@ int launch_frame_apply_tiles(Src raw, const int32_t* num_frames, int B, int max_
     const int64_t total = (int64_t)B * ((S + 15) / 16) * 2 * (F / 4);
     const int64_t want = (total + 255) / 256;
     hipLaunchKernelGGL(frame_apply_tiles_kernel<Src>, dim3((unsigned)(want < 8192 ? want : 8192)), dim3(256), 0, stream, raw, num_frames,
-                       B, max_frames, F, S, step, scale, shift, y, (uint4*)xt_video, Dv, (uint4*)xt_audio, Da, y2);
+                       B, max_frames, F, S, step, scale, shift, y, (uint4*)xt_video, Dv, (uint4*)xt_audio, Da, y2, centre);
     return check_launch(name);
 }
 
@@ -549,8 +625,9 @@ int launch_frame_apply_tiles(Src raw, const int32_t* num_frames, int B, int max_
 template <int PL, typename Src>
 int launch_frame_apply_tiles_bf16(Src raw, const int32_t* num_frames, int B, int max_frames, int F, int S, const float* scale,
                                   const float* shift, float* y, void* xt_video, void* xr_video, int Dv, void* xt_audio, void* xr_audio,
-                                  int Da, hipStream_t stream, const char* name) {
+                                  int Da, hipStream_t stream, const char* name, const float* centre) {
     using namespace lpm;
+    LPM_FRAME_CENTRE_CHECK(name);
     if (PL == 1)
         LPM_REQUIRE(xt_video && xr_video && ((scale == nullptr) == (shift == nullptr)) && ((xt_audio == nullptr) == (xr_audio == nullptr)),
                     LPM_ERR_BADARG, "%s: bad pointers", name);
@@ -564,16 +641,21 @@ int launch_frame_apply_tiles_bf16(Src raw, const int32_t* num_frames, int B, int
     const int64_t want = (total + 255) / 256;
     hipLaunchKernelGGL((frame_apply_tiles_bf16_kernel<PL, Src>), dim3((unsigned)(want < 16384 ? want : 16384)), dim3(256), 0, stream, raw,
                        num_frames, B, max_frames, F, S, step, scale, shift, y, (uint4*)xt_video, (uint4*)xr_video, Dv, (uint4*)xt_audio,
-                       (uint4*)xr_audio, Da);
+                       (uint4*)xr_audio, Da, centre);
     return check_launch(name);
 }
 
 template <typename Src, typename Idx>
-int launch_frame_stats(Src raw, Idx ix, int B, int max_frames, int F, int S, float* partial, hipStream_t stream, const char* name) {
+int launch_frame_stats(Src raw, Idx ix, int B, int max_frames, int F, int S, float* partial, size_t partial_bytes, hipStream_t stream,
+                       const char* name) {
     using namespace lpm;
     LPM_REQUIRE(partial, LPM_ERR_BADARG, "%s: null workspace", name);
+    LPM_REQUIRE(partial_bytes >= lpm_frame_stats_partial_bytes(B, S, F), LPM_ERR_WORKSPACE,
+                "%s: partial too small (the raw partials, the shifted partials and the pivots: lpm_frame_stats_partial_bytes)", name);
     LPM_REQUIRE(Src::W == 1 || ((uintptr_t)partial & 15) == 0, LPM_ERR_UNSUPPORTED_SHAPE, "%s: need a 16-byte aligned workspace", name);
-    hipLaunchKernelGGL((frame_stats_kernel<Src, Idx>), dim3(fp_nblk(B, S)), dim3(256), 0, stream, raw, ix, B, max_frames, F, S, partial);
+    const size_t raw_floats = (size_t)fp_nblk(B, S) * 2 * F;       // `partial` holds lpm_frame_stats_partial_bytes(B, S, F)
+    hipLaunchKernelGGL((frame_stats_kernel<Src, Idx>), dim3(fp_nblk(B, S)), dim3(256), 0, stream, raw, ix, B, max_frames, F, S, partial,
+                       partial + raw_floats, partial + 2 * raw_floats);
     return check_launch(name);
 }
 
@@ -595,7 +677,7 @@ int launch_frame_bn_bwd(const float* dy, int64_t lddy, const float* dy2, int64_t
                     LPM_ERR_UNSUPPORTED_SHAPE, "%s: need 16-byte aligned gradients and workspace, row strides and Dv multiples of 4", name);
     const int nblk = fp_nblk(B, S);
     hipLaunchKernelGGL((frame_bn_bwd_partial_kernel<Src, Idx>), dim3(nblk), dim3(256), 0, stream, dy, lddy, raw, ix, B, max_frames, F, S,
-                       (float*)workspace, dy2, lddy2, dy2 ? Dv : F);
+                       (float*)workspace, dy2, lddy2, dy2 ? Dv : F, mean, var);
     hipLaunchKernelGGL(frame_bn_bwd_reduce_kernel, dim3((F + 15) / 16), dim3(1024), 0, stream, (const float*)workspace, nblk, F, mean, var,
                        eps, dgamma, dbeta);
     return check_launch(name);
@@ -604,33 +686,33 @@ int launch_frame_bn_bwd(const float* dy, int64_t lddy, const float* dy2, int64_t
 }  // namespace
 
 extern "C" int lpm_frame_stats(const float* raw, const int32_t* num_frames, int B, int max_frames, int F, int S,
-                               float* partial, lpm_stream_t stream) {
+                               float* partial, size_t partial_bytes, lpm_stream_t stream) {
     LPM_FRAME_CHECK("lpm_frame_stats");
-    return launch_frame_stats(FrameSrc<float>{raw}, uniform_idx(num_frames, S), B, max_frames, F, S, partial, (hipStream_t)stream, "lpm_frame_stats");
+    return launch_frame_stats(FrameSrc<float>{raw}, uniform_idx(num_frames, S), B, max_frames, F, S, partial, partial_bytes, (hipStream_t)stream, "lpm_frame_stats");
 }
 
 extern "C" int lpm_frame_apply(const float* raw, const int32_t* num_frames, int B, int max_frames, int F, int S,
-                               const float* scale, const float* shift, float* y, lpm_stream_t stream) {
+                               const float* scale, const float* shift, float* y, lpm_stream_t stream, const float* centre) {
     LPM_FRAME_CHECK("lpm_frame_apply");
     return launch_frame_apply(FrameSrc<float>{raw}, uniform_idx(num_frames, S), B, max_frames, F, S, scale, shift, y, nullptr, F,
-                              (hipStream_t)stream, "lpm_frame_apply");
+                              (hipStream_t)stream, "lpm_frame_apply", centre);
 }
 
 extern "C" int lpm_frame_apply_tiles(const float* raw, const int32_t* num_frames, int B, int max_frames, int F, int S,
                                      const float* scale, const float* shift, float* y, void* xt_video, int Dv,
-                                     void* xt_audio, int Da, lpm_stream_t stream) {
+                                     void* xt_audio, int Da, lpm_stream_t stream, const float* centre) {
     LPM_FRAME_CHECK("lpm_frame_apply_tiles");
     return launch_frame_apply_tiles(FrameSrc<float>{raw}, num_frames, B, max_frames, F, S, scale, shift, y, nullptr, xt_video, Dv, xt_audio,
-                                    Da, (hipStream_t)stream, "lpm_frame_apply_tiles");
+                                    Da, (hipStream_t)stream, "lpm_frame_apply_tiles", centre);
 }
 // ... with the two column blocks as two contiguous matrices y_video [B S, Dv] and y_audio [B S, Da] (round 6: NetVladV2)
 extern "C" int lpm_frame_apply_tiles_split(const float* raw, const int32_t* num_frames, int B, int max_frames, int F, int S,
                                            const float* scale, const float* shift, float* y_video, float* y_audio, void* xt_video, int Dv,
-                                           void* xt_audio, int Da, lpm_stream_t stream) {
+                                           void* xt_audio, int Da, lpm_stream_t stream, const float* centre) {
     LPM_FRAME_CHECK("lpm_frame_apply_tiles_split");
     LPM_REQUIRE(y_video && y_audio, LPM_ERR_BADARG, "lpm_frame_apply_tiles_split: bad pointers");
     return launch_frame_apply_tiles(FrameSrc<float>{raw}, num_frames, B, max_frames, F, S, scale, shift, y_video, y_audio, xt_video, Dv,
-                                    xt_audio, Da, (hipStream_t)stream, "lpm_frame_apply_tiles_split");
+                                    xt_audio, Da, (hipStream_t)stream, "lpm_frame_apply_tiles_split", centre);
 }
 
 // bf16 storage: see frame_apply_tiles_bf16_kernel.  y may be NULL (then the fp32 frames are not written at all); the tile buffers
@@ -638,20 +720,20 @@ extern "C" int lpm_frame_apply_tiles_split(const float* raw, const int32_t* num_
 extern "C" size_t lpm_frame_tiles_bf16_bytes(int B, int S, int D) { return (size_t)B * 4 * ((S + 63) / 64) * (D / 32) * 1024; }
 extern "C" int lpm_frame_apply_tiles_bf16(const float* raw, const int32_t* num_frames, int B, int max_frames, int F, int S,
                                           const float* scale, const float* shift, float* y, void* xt_video, void* xr_video, int Dv,
-                                          void* xt_audio, void* xr_audio, int Da, lpm_stream_t stream) {
+                                          void* xt_audio, void* xr_audio, int Da, lpm_stream_t stream, const float* centre) {
     LPM_FRAME_CHECK("lpm_frame_apply_tiles_bf16");
     return launch_frame_apply_tiles_bf16<1>(FrameSrc<float>{raw}, num_frames, B, max_frames, F, S, scale, shift, y, xt_video, xr_video, Dv,
-                                            xt_audio, xr_audio, Da, (hipStream_t)stream, "lpm_frame_apply_tiles_bf16");
+                                            xt_audio, xr_audio, Da, (hipStream_t)stream, "lpm_frame_apply_tiles_bf16", centre);
 }
 
 // fp32 storage: a2 + a3 -> y (fp32 [B*S, F]) AND the split-bf16 frame tiles (lpm_xt_bytes each: K2's operand) AND row tiles
 // (lpm_row_tiles_bytes each: K1's operand; NULL: not wanted) of both streams in one pass over the sampled frames.
 extern "C" int lpm_frame_apply_tiles2(const float* raw, const int32_t* num_frames, int B, int max_frames, int F, int S,
                                       const float* scale, const float* shift, float* y, void* xt_video, void* xr_video, int Dv,
-                                      void* xt_audio, void* xr_audio, int Da, lpm_stream_t stream) {
+                                      void* xt_audio, void* xr_audio, int Da, lpm_stream_t stream, const float* centre) {
     LPM_FRAME_CHECK("lpm_frame_apply_tiles2");
     return launch_frame_apply_tiles_bf16<2>(FrameSrc<float>{raw}, num_frames, B, max_frames, F, S, scale, shift, y, xt_video, xr_video, Dv,
-                                            xt_audio, xr_audio, Da, (hipStream_t)stream, "lpm_frame_apply_tiles2");
+                                            xt_audio, xr_audio, Da, (hipStream_t)stream, "lpm_frame_apply_tiles2", centre);
 }
 
 // ---- eval mode from the reader's quantised frames -----------------------------------------------------------------------------
@@ -678,49 +760,49 @@ extern "C" int lpm_frame_inv_norm_q8(const unsigned char* q, const int32_t* num_
 
 extern "C" int lpm_frame_apply_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
                                   const int32_t* num_frames, int B, int max_frames, int F, int S, const float* scale, const float* shift,
-                                  float* y, lpm_stream_t stream) {
+                                  float* y, lpm_stream_t stream, const float* centre) {
     LPM_FRAME_Q8_CHECK("lpm_frame_apply_q8");
     return launch_frame_apply(q8_src(q, inv_norm, max_quantized_value, min_quantized_value), uniform_idx(num_frames, S), B, max_frames, F, S,
-                              scale, shift, y, nullptr, F, (hipStream_t)stream, "lpm_frame_apply_q8");
+                              scale, shift, y, nullptr, F, (hipStream_t)stream, "lpm_frame_apply_q8", centre);
 }
 
 extern "C" int lpm_frame_apply_tiles_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value,
                                         float min_quantized_value, const int32_t* num_frames, int B, int max_frames, int F, int S,
                                         const float* scale, const float* shift, float* y, void* xt_video, int Dv, void* xt_audio, int Da,
-                                        lpm_stream_t stream) {
+                                        lpm_stream_t stream, const float* centre) {
     LPM_FRAME_Q8_CHECK("lpm_frame_apply_tiles_q8");
     return launch_frame_apply_tiles(q8_src(q, inv_norm, max_quantized_value, min_quantized_value), num_frames, B, max_frames, F, S, scale,
-                                    shift, y, nullptr, xt_video, Dv, xt_audio, Da, (hipStream_t)stream, "lpm_frame_apply_tiles_q8");
+                                    shift, y, nullptr, xt_video, Dv, xt_audio, Da, (hipStream_t)stream, "lpm_frame_apply_tiles_q8", centre);
 }
 
 extern "C" int lpm_frame_apply_tiles_split_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value,
                                               float min_quantized_value, const int32_t* num_frames, int B, int max_frames, int F, int S,
                                               const float* scale, const float* shift, float* y_video, float* y_audio, void* xt_video,
-                                              int Dv, void* xt_audio, int Da, lpm_stream_t stream) {
+                                              int Dv, void* xt_audio, int Da, lpm_stream_t stream, const float* centre) {
     LPM_FRAME_Q8_CHECK("lpm_frame_apply_tiles_split_q8");
     LPM_REQUIRE(y_video && y_audio, LPM_ERR_BADARG, "lpm_frame_apply_tiles_split_q8: bad pointers");
     return launch_frame_apply_tiles(q8_src(q, inv_norm, max_quantized_value, min_quantized_value), num_frames, B, max_frames, F, S, scale,
-                                    shift, y_video, y_audio, xt_video, Dv, xt_audio, Da, (hipStream_t)stream, "lpm_frame_apply_tiles_split_q8");
+                                    shift, y_video, y_audio, xt_video, Dv, xt_audio, Da, (hipStream_t)stream, "lpm_frame_apply_tiles_split_q8", centre);
 }
 
 extern "C" int lpm_frame_apply_tiles_bf16_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value,
                                              float min_quantized_value, const int32_t* num_frames, int B, int max_frames, int F, int S,
                                              const float* scale, const float* shift, float* y, void* xt_video, void* xr_video, int Dv,
-                                             void* xt_audio, void* xr_audio, int Da, lpm_stream_t stream) {
+                                             void* xt_audio, void* xr_audio, int Da, lpm_stream_t stream, const float* centre) {
     LPM_FRAME_Q8_CHECK("lpm_frame_apply_tiles_bf16_q8");
     return launch_frame_apply_tiles_bf16<1>(q8_src(q, inv_norm, max_quantized_value, min_quantized_value), num_frames, B, max_frames, F, S,
                                             scale, shift, y, xt_video, xr_video, Dv, xt_audio, xr_audio, Da, (hipStream_t)stream,
-                                            "lpm_frame_apply_tiles_bf16_q8");
+                                            "lpm_frame_apply_tiles_bf16_q8", centre);
 }
 
 extern "C" int lpm_frame_apply_tiles2_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value,
                                          float min_quantized_value, const int32_t* num_frames, int B, int max_frames, int F, int S,
                                          const float* scale, const float* shift, float* y, void* xt_video, void* xr_video, int Dv,
-                                         void* xt_audio, void* xr_audio, int Da, lpm_stream_t stream) {
+                                         void* xt_audio, void* xr_audio, int Da, lpm_stream_t stream, const float* centre) {
     LPM_FRAME_Q8_CHECK("lpm_frame_apply_tiles2_q8");
     return launch_frame_apply_tiles_bf16<2>(q8_src(q, inv_norm, max_quantized_value, min_quantized_value), num_frames, B, max_frames, F, S,
                                             scale, shift, y, xt_video, xr_video, Dv, xt_audio, xr_audio, Da, (hipStream_t)stream,
-                                            "lpm_frame_apply_tiles2_q8");
+                                            "lpm_frame_apply_tiles2_q8", centre);
 }
 
 extern "C" int lpm_frame_bn_bwd(const float* dy, int64_t lddy, const float* raw, const int32_t* num_frames, int B,
@@ -744,10 +826,10 @@ extern "C" int lpm_frame_bn_bwd_split(const float* dy_video, int64_t ldv, const 
 // ---- training mode from the reader's quantised frames: the batch statistics and the dgamma / dbeta partials, bit for bit those of the
 // fp32 forms on lpm_dequantize_l2_normalize's frames (inv_norm from lpm_frame_inv_norm_q8; gradients and workspace 16-byte aligned) ----
 extern "C" int lpm_frame_stats_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
-                                  const int32_t* num_frames, int B, int max_frames, int F, int S, float* partial, lpm_stream_t stream) {
+                                  const int32_t* num_frames, int B, int max_frames, int F, int S, float* partial, size_t partial_bytes, lpm_stream_t stream) {
     LPM_FRAME_Q8_CHECK("lpm_frame_stats_q8");
     return launch_frame_stats(q8_src(q, inv_norm, max_quantized_value, min_quantized_value), uniform_idx(num_frames, S), B, max_frames, F, S,
-                              partial, (hipStream_t)stream, "lpm_frame_stats_q8");
+                              partial, partial_bytes, (hipStream_t)stream, "lpm_frame_stats_q8");
 }
 
 extern "C" int lpm_frame_bn_bwd_q8(const float* dy, int64_t lddy, const unsigned char* q, const float* inv_norm, float max_quantized_value,
@@ -784,34 +866,34 @@ extern "C" int lpm_frame_inv_norm_q8_idx(const unsigned char* q, const int32_t* 
                                     inv_norm, (hipStream_t)stream, "lpm_frame_inv_norm_q8_idx");
 }
 
-extern "C" int lpm_frame_stats_idx(const float* raw, const int32_t* frame_index, int B, int max_frames, int F, int S, float* partial,
+extern "C" int lpm_frame_stats_idx(const float* raw, const int32_t* frame_index, int B, int max_frames, int F, int S, float* partial, size_t partial_bytes,
                                    lpm_stream_t stream) {
     LPM_FRAME_IDX_CHECK("lpm_frame_stats_idx");
-    return launch_frame_stats(FrameSrc<float>{raw}, TableIdx{frame_index}, B, max_frames, F, S, partial, (hipStream_t)stream,
+    return launch_frame_stats(FrameSrc<float>{raw}, TableIdx{frame_index}, B, max_frames, F, S, partial, partial_bytes, (hipStream_t)stream,
                               "lpm_frame_stats_idx");
 }
 extern "C" int lpm_frame_stats_idx_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value, float min_quantized_value,
-                                      const int32_t* frame_index, int B, int max_frames, int F, int S, float* partial, lpm_stream_t stream) {
+                                      const int32_t* frame_index, int B, int max_frames, int F, int S, float* partial, size_t partial_bytes, lpm_stream_t stream) {
     LPM_FRAME_Q8_IDX_CHECK("lpm_frame_stats_idx_q8");
     return launch_frame_stats(q8_src(q, inv_norm, max_quantized_value, min_quantized_value), TableIdx{frame_index}, B, max_frames, F, S,
-                              partial, (hipStream_t)stream, "lpm_frame_stats_idx_q8");
+                              partial, partial_bytes, (hipStream_t)stream, "lpm_frame_stats_idx_q8");
 }
 
 extern "C" int lpm_frame_apply_split_idx(const float* raw, const int32_t* frame_index, int B, int max_frames, int F, int S, const float* scale,
-                                         const float* shift, float* y_video, float* y_audio, int Dv, lpm_stream_t stream) {
+                                         const float* shift, float* y_video, float* y_audio, int Dv, lpm_stream_t stream, const float* centre) {
     LPM_FRAME_IDX_CHECK("lpm_frame_apply_split_idx");
     LPM_REQUIRE(y_video && y_audio, LPM_ERR_BADARG, "lpm_frame_apply_split_idx: bad pointers");
     return launch_frame_apply(FrameSrc<float>{raw}, TableIdx{frame_index}, B, max_frames, F, S, scale, shift, y_video, y_audio, Dv,
-                              (hipStream_t)stream, "lpm_frame_apply_split_idx");
+                              (hipStream_t)stream, "lpm_frame_apply_split_idx", centre);
 }
 extern "C" int lpm_frame_apply_split_idx_q8(const unsigned char* q, const float* inv_norm, float max_quantized_value,
                                             float min_quantized_value, const int32_t* frame_index, int B, int max_frames, int F, int S,
                                             const float* scale, const float* shift, float* y_video, float* y_audio, int Dv,
-                                            lpm_stream_t stream) {
+                                            lpm_stream_t stream, const float* centre) {
     LPM_FRAME_Q8_IDX_CHECK("lpm_frame_apply_split_idx_q8");
     LPM_REQUIRE(y_video && y_audio, LPM_ERR_BADARG, "lpm_frame_apply_split_idx_q8: bad pointers");
     return launch_frame_apply(q8_src(q, inv_norm, max_quantized_value, min_quantized_value), TableIdx{frame_index}, B, max_frames, F, S, scale,
-                              shift, y_video, y_audio, Dv, (hipStream_t)stream, "lpm_frame_apply_split_idx_q8");
+                              shift, y_video, y_audio, Dv, (hipStream_t)stream, "lpm_frame_apply_split_idx_q8", centre);
 }
 
 extern "C" int lpm_frame_bn_bwd_split_idx(const float* dy_video, int64_t ldv, const float* dy_audio, int64_t lda, int Dv, const float* raw,

@@ -161,6 +161,22 @@ def bn_fold(partial, nblk, C, rows, gamma, beta, moving_mean=None, moving_var=No
     return mean, var, scale, shift
 
 
+def _frame_partial(lib, B, S, F, like):
+    """-> (nblk, partial): the buffer the lpm_frame_stats* forms fill -- raw partials, shifted partials and pivots (lpm_frame_stats_partial_bytes)."""
+    return lib._lpm_frame_stats_nblk(B, S), _empty((lib._lpm_frame_stats_partial_bytes(B, S, F) // 4,), like)
+
+
+def frame_bn_fold(partial, nblk, C, rows, gamma, beta, moving_mean=None, moving_var=None, eps=BN_EPS, decay=BN_DECAY):
+    """bn_fold for the frame-prep statistics: the shifted sums beside the raw ones decide which pair gives the moments (lpm_frame_bn_fold).
+    -> (mean, var, scale, shift, centre) for the apply pass y = (x - centre) * scale + shift: centre is the fp32 mean where the fold took the
+    shifted sums (4 mean^2 > var), else 0."""
+    lib = _capi.load()
+    mean, var, scale, shift, centre = (_empty((C,), partial) for _ in range(5))
+    lib.check(lib._lpm_frame_bn_fold(ptr(partial), nblk, C, rows, ptr(gamma), ptr(beta), eps, decay, ptr(mean), ptr(var),
+                                     ptr(scale), ptr(shift), ptr(moving_mean), ptr(moving_var), stream_ptr(), ptr(centre)), "lpm_frame_bn_fold")
+    return mean, var, scale, shift, centre
+
+
 class _BNSmall(torch.autograd.Function):
     """Training-mode slim.batch_norm of a small [M, C] matrix fused with what follows it (lpm_bn_small_fwd / _bwd): act 0 nothing,
     1 relu6, 2 the context gate  mul * sigmoid(bn(x))."""
@@ -207,6 +223,16 @@ def folded_eval_affine(gamma, beta, moving_mean, moving_var, eps=BN_EPS):
     """Inference-mode batch norm is a constant affine (tiny [C] tensors: plain torch)."""
     scale = gamma * torch.rsqrt(moving_var + eps)
     return scale, beta - moving_mean * scale
+
+
+def frame_eval_affine(gamma, beta, moving_mean, moving_var, eps=BN_EPS):
+    """folded_eval_affine for the frame-prep apply forms -> (scale, shift, centre), y = (x - centre) * scale + shift: where
+    moving_mean^2 > moving_var the mean is taken off the frames first (centre = moving_mean, shift = beta) -- x * scale +
+    (beta - mean * scale) carries half an ulp of mean * scale -- and elsewhere centre = 0 and the pair is folded_eval_affine's."""
+    scale, shift = folded_eval_affine(gamma, beta, moving_mean, moving_var, eps)
+    off = moving_mean * moving_mean > moving_var
+    return (scale.contiguous(), torch.where(off, beta, shift).contiguous(),
+            torch.where(off, moving_mean, torch.zeros_like(moving_mean)).contiguous())
 
 
 def l2_normalize_rows(x):
@@ -277,12 +303,12 @@ def _frame_stats_call(lib, raw, inv, *args):
         lib.check(lib._lpm_frame_stats_q8(ptr(raw), ptr(inv), QUANT_MAX, QUANT_MIN, *args), "lpm_frame_stats_q8")
 
 
-def _frame_apply_call(lib, name, raw, inv, *args):
-    """lpm_<name>(raw, *args), or its quantised form lpm_<name>_q8(q, inv_norm, range, *args) when inv is given."""
+def _frame_apply_call(lib, name, raw, inv, *args, centre=None):
+    """lpm_<name>(raw, *args, centre), or its quantised form lpm_<name>_q8(q, inv_norm, range, *args, centre) when inv is given."""
     if inv is None:
-        lib.check(getattr(lib, "_lpm_" + name)(ptr(raw), *args), "lpm_" + name)
+        lib.check(getattr(lib, "_lpm_" + name)(ptr(raw), *args, ptr(centre)), "lpm_" + name)
     else:
-        lib.check(getattr(lib, "_lpm_" + name + "_q8")(ptr(raw), ptr(inv), QUANT_MAX, QUANT_MIN, *args), "lpm_" + name + "_q8")
+        lib.check(getattr(lib, "_lpm_" + name + "_q8")(ptr(raw), ptr(inv), QUANT_MAX, QUANT_MIN, *args, ptr(centre)), "lpm_" + name + "_q8")
 
 
 class _FrameSampleBN(torch.autograd.Function):
@@ -297,15 +323,13 @@ class _FrameSampleBN(torch.autograd.Function):
         mean = var = None
         if use_bn:
             if is_training:
-                nblk = lib._lpm_frame_stats_nblk(B, S)
-                partial = _empty((nblk, 2, F), raw)
-                _frame_stats_call(lib, raw, inv, ptr(nf), B, MF, F, S, ptr(partial), stream_ptr())
-                mean, var, scale, shift = bn_fold(partial, nblk, F, B * S, gamma, beta, moving_mean, moving_var)
+                nblk, partial = _frame_partial(lib, B, S, F, raw)
+                _frame_stats_call(lib, raw, inv, ptr(nf), B, MF, F, S, ptr(partial), partial.numel() * 4, stream_ptr())
+                mean, var, scale, shift, centre = frame_bn_fold(partial, nblk, F, B * S, gamma, beta, moving_mean, moving_var)
             else:
-                scale, shift = folded_eval_affine(gamma, beta, moving_mean, moving_var)
-                scale, shift = scale.contiguous(), shift.contiguous()
+                scale, shift, centre = frame_eval_affine(gamma, beta, moving_mean, moving_var)
         else:
-            scale = shift = None
+            scale = shift = centre = None
         tiles = VLAD_PRECISION == "bf16x3" and F in (1024, 1152)
         if storage == "bf16":
             # bf16 storage: the frames leave as plain bf16 operand tiles for K1 (row tiles) and K2 (frame tiles) in one pass; the
@@ -317,7 +341,7 @@ class _FrameSampleBN(torch.autograd.Function):
             xtv, xrv = nb(Dv), nb(Dv)
             xta, xra = (nb(Da), nb(Da)) if Da else (None, None)
             _frame_apply_call(lib, "frame_apply_tiles_bf16", raw, inv, ptr(nf), B, MF, F, S, ptr(scale), ptr(shift),
-                              ptr(y) if materialize else None, ptr(xtv), ptr(xrv), Dv, ptr(xta), ptr(xra), Da, stream_ptr())
+                              ptr(y) if materialize else None, ptr(xtv), ptr(xrv), Dv, ptr(xta), ptr(xra), Da, stream_ptr(), centre=centre)
             _XT_CACHE.clear()
             _XT_CACHE.update(base=weakref.ref(y), F=F, Dv=Dv, S=S, B=B, video=xtv, audio=xta, video_rows=xrv, audio_rows=xra,
                              storage="bf16", unmaterialised=None if materialize else y.untyped_storage().data_ptr())
@@ -331,14 +355,14 @@ class _FrameSampleBN(torch.autograd.Function):
                 xrv = torch.empty(lib._lpm_row_tiles_bytes(B, S, Dv) // 4, dtype=torch.int32, device=raw.device)
                 xra = torch.empty(lib._lpm_row_tiles_bytes(B, S, Da) // 4, dtype=torch.int32, device=raw.device) if Da else None
                 _frame_apply_call(lib, "frame_apply_tiles2", raw, inv, ptr(nf), B, MF, F, S, ptr(scale), ptr(shift), ptr(y), ptr(xtv),
-                                  ptr(xrv), Dv, ptr(xta), ptr(xra), Da, stream_ptr())
+                                  ptr(xrv), Dv, ptr(xta), ptr(xra), Da, stream_ptr(), centre=centre)
             else:
                 _frame_apply_call(lib, "frame_apply_tiles", raw, inv, ptr(nf), B, MF, F, S, ptr(scale), ptr(shift), ptr(y), ptr(xtv), Dv,
-                                  ptr(xta), Da, stream_ptr())
+                                  ptr(xta), Da, stream_ptr(), centre=centre)
             _XT_CACHE.clear()
             _XT_CACHE.update(base=weakref.ref(y), F=F, Dv=Dv, S=S, B=B, video=xtv, audio=xta, video_rows=xrv, audio_rows=xra)
         else:
-            _frame_apply_call(lib, "frame_apply", raw, inv, ptr(nf), B, MF, F, S, ptr(scale), ptr(shift), ptr(y), stream_ptr())
+            _frame_apply_call(lib, "frame_apply", raw, inv, ptr(nf), B, MF, F, S, ptr(scale), ptr(shift), ptr(y), stream_ptr(), centre=centre)
         ctx.use_bn, ctx.is_training, ctx.S = use_bn, is_training, S
         ctx.q8 = inv is not None
         if use_bn and ctx.q8:
@@ -891,19 +915,17 @@ class _FrameSampleBNSplit(torch.autograd.Function):
         B, MF, F = raw.shape
         Da = F - Dv
         if is_training:
-            nblk = lib._lpm_frame_stats_nblk(B, S)
-            partial = _empty((nblk, 2, F), raw)
-            _frame_stats_call(lib, raw, inv, ptr(nf), B, MF, F, S, ptr(partial), stream_ptr())
-            mean, var, scale, shift = bn_fold(partial, nblk, F, B * S, gamma, beta, moving_mean, moving_var)
+            nblk, partial = _frame_partial(lib, B, S, F, raw)
+            _frame_stats_call(lib, raw, inv, ptr(nf), B, MF, F, S, ptr(partial), partial.numel() * 4, stream_ptr())
+            mean, var, scale, shift, centre = frame_bn_fold(partial, nblk, F, B * S, gamma, beta, moving_mean, moving_var)
         else:
-            scale, shift = folded_eval_affine(gamma, beta, moving_mean, moving_var)
-            scale, shift = scale.contiguous(), shift.contiguous()
+            scale, shift, centre = frame_eval_affine(gamma, beta, moving_mean, moving_var)
             mean, var = moving_mean.detach().clone(), moving_var.detach().clone()
         yv, ya = _empty((B * S, Dv), raw), _empty((B * S, Da), raw)
         xtv = torch.empty(lib._lpm_xt_bytes(B, S, Dv) // 4, dtype=torch.int32, device=raw.device)
         xta = torch.empty(lib._lpm_xt_bytes(B, S, Da) // 4, dtype=torch.int32, device=raw.device)
         _frame_apply_call(lib, "frame_apply_tiles_split", raw, inv, ptr(nf), B, MF, F, S, ptr(scale), ptr(shift), ptr(yv), ptr(ya), ptr(xtv),
-                          Dv, ptr(xta), Da, stream_ptr())
+                          Dv, ptr(xta), Da, stream_ptr(), centre=centre)
         _XT_CACHE.clear()
         _XT_CACHE.update(split=True, F=F, Dv=Dv, S=S, B=B, video=xtv, audio=xta, video_t=yv, audio_t=ya,
                          video_ver=yv._version, audio_ver=ya._version)
@@ -957,7 +979,7 @@ def frame_sample_bn_split(raw, num_frames, S, gamma, beta, moving_mean, moving_v
 
 
 def _idx_call(lib, name, raw, inv, *args):
-    """lpm_<name>_idx(raw, *args), or lpm_<name>_idx_q8(q, inv_norm, range, *args) when inv is given."""
+    """lpm_<name>_idx(raw, *args), or lpm_<name>_idx_q8(q, inv_norm, range, *args) when inv is given (the apply form: centre last in args)."""
     if inv is None:
         lib.check(getattr(lib, f"_lpm_{name}_idx")(ptr(raw), *args), f"lpm_{name}_idx")
     else:
@@ -982,18 +1004,16 @@ class _FrameGatherBNSplit(torch.autograd.Function):
             lib.check(lib._lpm_frame_inv_norm_q8_idx(ptr(raw), ptr(nf), ptr(idx), B, MF, F, S, QUANT_MAX, QUANT_MIN, ptr(inv), stream_ptr()),
                       "lpm_frame_inv_norm_q8_idx")
         use_bn = gamma is not None
-        mean = var = scale = shift = None
+        mean = var = scale = shift = centre = None
         if use_bn and is_training:
-            nblk = lib._lpm_frame_stats_nblk(B, S)
-            partial = _empty((nblk, 2, F), raw)
-            _idx_call(lib, "frame_stats", raw, inv, ptr(idx), B, MF, F, S, ptr(partial), stream_ptr())
-            mean, var, scale, shift = bn_fold(partial, nblk, F, B * S, gamma, beta, moving_mean, moving_var)
+            nblk, partial = _frame_partial(lib, B, S, F, raw)
+            _idx_call(lib, "frame_stats", raw, inv, ptr(idx), B, MF, F, S, ptr(partial), partial.numel() * 4, stream_ptr())
+            mean, var, scale, shift, centre = frame_bn_fold(partial, nblk, F, B * S, gamma, beta, moving_mean, moving_var)
         elif use_bn:
-            scale, shift = folded_eval_affine(gamma, beta, moving_mean, moving_var)
-            scale, shift = scale.contiguous(), shift.contiguous()
+            scale, shift, centre = frame_eval_affine(gamma, beta, moving_mean, moving_var)
             mean, var = moving_mean.detach().clone(), moving_var.detach().clone()
         yv, ya = _empty((B * S, Dv), raw), _empty((B * S, F - Dv), raw)
-        _idx_call(lib, "frame_apply_split", raw, inv, ptr(idx), B, MF, F, S, ptr(scale), ptr(shift), ptr(yv), ptr(ya), Dv, stream_ptr())
+        _idx_call(lib, "frame_apply_split", raw, inv, ptr(idx), B, MF, F, S, ptr(scale), ptr(shift), ptr(yv), ptr(ya), Dv, stream_ptr(), ptr(centre))
         ctx.S, ctx.Dv, ctx.q8, ctx.is_training, ctx.use_bn = S, Dv, inv is not None, is_training, use_bn
         if use_bn and ctx.q8:
             if is_training:       # the uint8 frames, the table and the inverse norms stand in for the fp32 frames
@@ -1112,7 +1132,7 @@ def _k1_selfcheck(lib, planes, dev):
                 nb = lambda d: torch.empty(lib._lpm_frame_tiles_bf16_bytes(B, T, d) // 4, dtype=torch.int32, device=dev)
                 xtv, xr, xta, xra = nb(D), nb(D), nb(128), nb(128)
                 lib.check(lib._lpm_frame_apply_tiles_bf16(ptr(raw), ptr(nfr), B, T, D + 128, T, ptr(one), ptr(zero), None, ptr(xtv), ptr(xr), D,
-                                                          ptr(xta), ptr(xra), 128, st), "lpm_frame_apply_tiles_bf16")
+                                                          ptr(xta), ptr(xra), 128, st, None), "lpm_frame_apply_tiles_bf16")
                 wt = torch.empty(lib._lpm_weight_tiles_bytes(D, K) // 8, dtype=torch.int32, device=dev)
                 lib.check(lib._lpm_split_weight_tiles_bf16(ptr(W), D, K, 0, ptr(wt), st), "lpm_split_weight_tiles_bf16")
                 run = lambda lg, pt: lib.check(lib._lpm_assign_gemm_tiles_fwd_bf16(ptr(xr), ptr(wt), B, T, D, K, ptr(lg), ptr(pt), st),

@@ -45,6 +45,44 @@ def test_ctypes_table_matches_header():
         assert len(params) == len(args), f"{name}: header has {len(params)} parameters, ctypes table {len(args)}"
 
 
+def test_frame_stats_partial_holds_the_raw_sums_the_shifted_sums_and_the_pivots():
+    """lpm_frame_stats* fill, and lpm_frame_bn_fold reads, raw partials [nblk][2][F], shifted partials [nblk][2][F] and pivots [F];
+    lpm_frame_bn_fold has lpm_bn_fold's parameters and `centre`; every lpm_frame_apply* form ends in (stream, centre)."""
+    from learnablepoolingmethods_amd import _capi
+    ret, args = _capi.SIGNATURES["lpm_bn_fold"]
+    assert _capi.SIGNATURES["lpm_frame_bn_fold"] == (ret, args + [ctypes.c_void_p])              # ... and `centre` behind them
+    header = open(HEADER).read()
+    for name, (_, a) in _capi.SIGNATURES.items():
+        if name.startswith("lpm_frame_apply"):
+            assert a[-2:] == [ctypes.c_void_p, ctypes.c_void_p], name
+            assert re.search(r"\b" + name + r"\s*\([^;]*lpm_stream_t stream, const float\* centre\);", header), name
+    lib = _capi.load()
+    for B, S, F in ((1, 3, 128), (2, 16, 1024), (5, 7, 128), (3, 33, 1152), (128, 300, 1152)):
+        nblk = lib._lpm_frame_stats_nblk(B, S)
+        assert nblk == (B * S + 31) // 32
+        assert lib._lpm_frame_stats_workspace_bytes(B, S, F) == nblk * 2 * F * 4          # (the backward's workspace: unchanged)
+        assert lib._lpm_frame_stats_partial_bytes(B, S, F) == (nblk * 4 * F + F) * 4
+
+
+def test_frame_stats_refuse_a_partial_of_the_old_size():
+    """The four lpm_frame_stats* forms take the size of `partial` and refuse, before any launch, a buffer of
+    lpm_frame_stats_workspace_bytes -- what `partial` held before the shifted sums.  (The pointers are never dereferenced: the check fails.)"""
+    from learnablepoolingmethods_amd import _capi
+    lib = _capi.load()
+    B, MF, F, S = 2, 40, 128, 7
+    p = ctypes.c_void_p(4096)
+    old, new = lib._lpm_frame_stats_workspace_bytes(B, S, F), lib._lpm_frame_stats_partial_bytes(B, S, F)
+    assert new > 2 * old
+    calls = {"lpm_frame_stats": lambda n: lib._lpm_frame_stats(p, p, B, MF, F, S, p, n, None),
+             "lpm_frame_stats_idx": lambda n: lib._lpm_frame_stats_idx(p, p, B, MF, F, S, p, n, None),
+             "lpm_frame_stats_q8": lambda n: lib._lpm_frame_stats_q8(p, p, 2.0, -2.0, p, B, MF, F, S, p, n, None),
+             "lpm_frame_stats_idx_q8": lambda n: lib._lpm_frame_stats_idx_q8(p, p, 2.0, -2.0, p, B, MF, F, S, p, n, None)}
+    for name, call in calls.items():
+        assert _capi.SIGNATURES[name][1][-2] is ctypes.c_size_t, name
+        for n in (old, new - 1):
+            assert call(n) != 0 and name in lib.last_error() and "partial too small" in lib.last_error(), (name, n, lib.last_error())
+
+
 def test_version_and_error_string():
     from learnablepoolingmethods_amd import _capi
     lib = _capi.load()

@@ -5,6 +5,9 @@ Parts: y per clip (max over clips of max |error| / max |fp64 value| in the clip;
 10^(6 b / (B - 1) - 3)), dgamma, dbeta and, in training mode from zero moving statistics, 0.001 x the batch mean and 0.001 x the unbiased batch
 variance (precisely (1 - fp32(0.999)) x: tests/_netvlad_ref.ONE_MINUS_DECAY).  Ragged num_frames, one clip with a single frame.  That the
 gather moves the right rows bit for bit stays with tests/test_gpu_frame_gather.py and tests/test_gpu_kernels.test_frame_sample_bn.
+This file runs ONE regime (|mean| / std about 1, fp32 frames, two ops); the offset, spread, clip-offset and quantised regimes, the uint8
+forms and the other apply forms are held by tests/test_gpu_frame_prep_bounds.py, which is also where the raw-sum variance of these kernels
+(var = q / n - mean^2) was measured and replaced.
 
 Measured on the MI355X, worst error / bound over the parts:
 MEASURED-BEGIN
