@@ -1429,6 +1429,31 @@ int lpm_triangulation_onefc_bwd(const float* x, const float* anchors_t, const fl
                                 const float* w, const float* g, const float* mu, const float* c1, const float* c2, int B, int T, int D, int K,
                                 int C, float* dx, float* danchors, void* workspace, size_t workspace_bytes, lpm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The glue between the three GEMMs of the class filter behind MoeModel2 / JuhanMoeModel (video_level_models.py:518-539, :600-620):
+ * tf.layers.dense's bias and activation, tf.layers.batch_normalization over the batch, tf.nn.dropout, the residual add.  One launch
+ * each way, for a [B, C] fp32 contiguous, 1 <= B <= 1024, any C >= 1 (no alignment beyond fp32's is assumed):
+ *   pre = a (+ bias [C]) (+ residual [B, C]);  u = act(pre), act LPM_CLASS_FILTER_RELU | _LEAKY_RELU (pre > 0 ? pre : alpha pre) | _SIGMOID
+ *   v   = gamma (u - mean) rstd + beta   when gamma, beta, moving_mean, moving_variance are given (all four NULL: v = u):
+ *         is_training: mean and the BIASED variance of the batch per column, taken in two passes; rstd = 1 / sqrt(var + eps); mean and
+ *         rstd [C] are written, and moving_x = decay moving_x + (1 - decay) (mean | biased var) IN PLACE in the same launch;
+ *         otherwise mean = moving_mean, rstd = 1 / sqrt(moving_variance + eps) (written when mean and rstd are given)
+ *   y   = keep ? v / keep_prob : 0       keep [B, C], ONE BYTE per element (nonzero = kept), training only; NULL: y = v
+ * Backward (u recomputed from a, bias, residual): dv = keep ? dy / keep_prob : 0; dbeta = sum_b dv; dgamma = sum_b dv xhat;
+ *   du = gamma rstd (dv - dbeta / B - xhat dgamma / B) in training, gamma rstd dv in eval, dv without batch norm; dpre = du act'(pre),
+ *   the gradient of a and of the residual alike; dbias = sum_b dpre (bias and dbias both or neither).  mean / rstd: what the forward wrote.
+ * All sums are added in a fixed order (no atomics): the same inputs give the same bits.  Every argument is checked before any launch.
+ * ------------------------------------------------------------------------------------------- */
+enum { LPM_CLASS_FILTER_RELU = 1, LPM_CLASS_FILTER_LEAKY_RELU = 2, LPM_CLASS_FILTER_SIGMOID = 3 };
+int lpm_class_filter_fwd(const float* a, const float* bias, const float* residual, int B, int C, int act, float alpha,
+                         const float* gamma, const float* beta, float* moving_mean, float* moving_variance, int is_training,
+                         float eps, double decay, const uint8_t* keep, float keep_prob, float* y, float* mean, float* rstd,
+                         lpm_stream_t stream);
+int lpm_class_filter_bwd(const float* dy, const float* a, const float* bias, const float* residual, int B, int C, int act,
+                         float alpha, const float* gamma, const float* mean, const float* rstd, int is_training,
+                         const uint8_t* keep, float keep_prob, float* dpre, float* dbias, float* dgamma, float* dbeta,
+                         lpm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -285,7 +285,12 @@ SIGNATURES = {
     "lpm_mha_bn_dk_correct_image": (_i, [_f, _f, _l, _i, _i, _i, _i, _fl, _f, _f, _f, _f, _f, _f, _f]),
     "lpm_bn_rows_act_image_fwd_fmt": (_i, [_f, _f, _i, _i, _i, _f, _f, _fl, _fl, _i, _f, _f, _f, _f, _f, _f, _s, _f, _f]),
     "lpm_bn_act_bwd_image_fmt": (_i, [_f, _f, _f, _i, _f, _f, _f, _fl, _i, _i, _f, _f, _f, _f, _f, _s, _f, _f]),
+    "lpm_class_filter_fwd": (_i, [_f, _f, _f, _i, _i, _i, _fl, _f, _f, _f, _f, _i, _fl, C.c_double, _f, _fl, _f, _f, _f, _f]),
+    "lpm_class_filter_bwd": (_i, [_f, _f, _f, _f, _i, _i, _i, _fl, _f, _f, _f, _i, _f, _fl, _f, _f, _f, _f, _f]),
 }
+LPM_CLASS_FILTER_RELU = 1        # activations of lpm_class_filter_fwd / _bwd
+LPM_CLASS_FILTER_LEAKY_RELU = 2
+LPM_CLASS_FILTER_SIGMOID = 3
 LPM_LABEL_LOSS_HINGE = 1         # kinds of lpm_label_loss_fwd / _bwd
 LPM_LABEL_LOSS_SOFTMAX = 2
 LPM_ERR_WORKSPACE = -3

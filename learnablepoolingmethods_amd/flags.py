@@ -222,6 +222,14 @@ FLAGS.define("lstm_fused", True, "build extension: on the GPU every layer of rnn
              "same results).  On: tools/bench_lstm.py measured forward + backward of one layer at 0.93 ms fused against 10.6 ms per step at "
              "(B, T, In, H) = (16, 30, 512, 512) and 82.3 against 175.3 ms at (16, 30, 16384, 16384), and the default is on only if the "
              "fused route is not slower at both shapes (profiles/bench_lstm.json, DESIGN.md section 27)")
+FLAGS.define("class_filter_fused", True, "build extension: on the GPU the three glue stages of the class filter behind MoeModel2 / "
+             "JuhanMoeModel (bias, relu / leaky_relu / sigmoid, tf.layers.batch_normalization over the batch, the dropout mask, the "
+             "residual add) are ONE ops.class_filter launch each way per stage (csrc/class_filter.hip) between the three library GEMMs; "
+             "False: the torch formulation (the CPU path; same variables, same results).  On: tools/bench_class_filter.py measured forward "
+             "+ backward of the three stages together at 0.29 ms fused against 0.63 ms at (B, V) = (128, 3862) and 0.49 against 0.94 ms at "
+             "(1024, 3862) -- the bias + sigmoid stage alone is SLOWER fused, 0.055 against 0.038 ms and 0.065 against 0.050 ms -- and one "
+             "Trainer.step of MoeModel2 / JuhanMoeModel at 2.17 / 2.29 ms against 2.47 / 2.57 ms and 6.19 / 6.28 against 6.62 / 6.71 ms; the "
+             "default is on only if the fused route is faster at both shapes (profiles/bench_class_filter.json, DESIGN.md section 36)")
 FLAGS.define("wtm_projection_l1", 1e-5, "layers.l1_l2_regularizer(1e-5) on dis_projection_2 / temp_projection_2 (frame_level_models.py:1272,1287): "
              "tf.contrib's first positional argument is scale_l1")
 FLAGS.define("wtm_projection_l2", 1.0, "... and its scale_l2 keeps the default 1.0: the penalty is l1 * sum |w| + l2 * sum(w^2) / 2 (SURVEY App. B)")

@@ -67,6 +67,48 @@ def batch_norm(x: torch.Tensor, is_training: bool, scope: str, pre_bias: torch.T
     return (x - mean) * torch.rsqrt(var + BN_EPS) * gamma + beta
 
 
+TF_LAYERS_BN_EPS = 1e-3
+TF_LAYERS_BN_MOMENTUM = 0.99
+
+
+def tf_layers_bn_variables(channels: int, device, name: str = None):
+    """tf.layers.batch_normalization's variables in its creation order: gamma (ones), beta (zeros), moving_mean (zeros),
+    moving_variance (ones), the last two not trainable.  name None: ``batch_normalization``, ``batch_normalization_1``, ... in the order
+    of the calls under the enclosing variable scope (VariableStore.unique_layer_name: tf.layers' automatic layer names)."""
+    with vs.variable_scope(name or vs.default_store().unique_layer_name("batch_normalization")):
+        gamma = vs.get_variable("gamma", [channels], vs.ones_initializer(), device=device)
+        beta = vs.get_variable("beta", [channels], vs.zeros_initializer(), device=device)
+        mm = vs.get_variable("moving_mean", [channels], vs.zeros_initializer(), trainable=False, device=device)
+        mv = vs.get_variable("moving_variance", [channels], vs.ones_initializer(), trainable=False, device=device)
+    return gamma, beta, mm, mv
+
+
+def tf_layers_bn_apply(x: torch.Tensor, training: bool, gamma, beta, mm, mv, momentum: float = TF_LAYERS_BN_MOMENTUM,
+                       epsilon: float = TF_LAYERS_BN_EPS) -> torch.Tensor:
+    """tf.layers.batch_normalization on given variables, the last axis the channel.  Training: the batch mean and the biased batch
+    variance normalise, and the moving statistics move by (1 - momentum) towards them -- towards the BIASED variance, except at rank 4,
+    where TF1 takes its fused kernel, which hands the unbiased one to the moving average."""
+    if training:
+        red = tuple(range(x.dim() - 1))
+        n = x.numel() // x.shape[-1]
+        mean = x.mean(dim=red)
+        var = ((x - mean) ** 2).mean(dim=red)
+        with torch.no_grad():
+            uv = var * (n / max(n - 1, 1)) if x.dim() == 4 else var
+            mm.mul_(momentum).add_(mean.detach(), alpha=1 - momentum)
+            mv.mul_(momentum).add_(uv.detach(), alpha=1 - momentum)
+    else:
+        mean, var = mm, mv
+    return (x - mean) * torch.rsqrt(var + epsilon) * gamma + beta
+
+
+def tf_layers_batch_normalization(x: torch.Tensor, training: bool, name: str = None, momentum: float = TF_LAYERS_BN_MOMENTUM,
+                                  epsilon: float = TF_LAYERS_BN_EPS) -> torch.Tensor:
+    """tf.layers.batch_normalization(x, training=...) with TF1's defaults (momentum 0.99, epsilon 1e-3, centre and scale) as host torch
+    code -- NOT slim.batch_norm (``batch_norm`` above: decay 0.999, other variable order, the unbiased variance at rank 2)."""
+    return tf_layers_bn_apply(x, training, *tf_layers_bn_variables(x.shape[-1], x.device, name), momentum=momentum, epsilon=epsilon)
+
+
 def layer_norm_variables(scope: str, features: int, device):
     """tf.contrib.layers.layer_norm's variables in its creation order: beta (zeros), gamma (ones) -> (gamma, beta)."""
     with vs.variable_scope(scope):

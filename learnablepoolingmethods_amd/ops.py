@@ -3993,6 +3993,110 @@ def label_loss(predictions, labels, kind, b=1.0):
     return _LabelLoss.apply(predictions, labels, LABEL_LOSS_KINDS[kind], float(b))
 
 
+CLASS_FILTER_ACTS = {"relu": _capi.LPM_CLASS_FILTER_RELU, "leaky_relu": _capi.LPM_CLASS_FILTER_LEAKY_RELU,
+                     "sigmoid": _capi.LPM_CLASS_FILTER_SIGMOID}
+CLASS_FILTER_MAX_ROWS = 1024
+TF_LAYERS_BN_EPS = 1e-3          # tf.layers.batch_normalization's defaults (layers.tf_layers_batch_normalization)
+TF_LAYERS_BN_MOMENTUM = 0.99
+
+
+class _ClassFilter(torch.autograd.Function):
+    """(a, bias, residual, gamma, beta) -> y: one stage of the class filter in one launch each way (csrc/class_filter.hip).  The backward
+    recomputes act(a + bias + residual) from the saved inputs; the moving statistics are updated in place by the training forward."""
+
+    @staticmethod
+    def forward(ctx, a, bias, residual, gamma, beta, moving_mean, moving_var, act, alpha, is_training, keep, keep_prob, decay, eps):
+        lib = _capi.load()
+        B, C = a.shape
+        y = torch.empty_like(a)
+        has_bn = gamma is not None
+        mean, rstd = (_empty((C,), a), _empty((C,), a)) if has_bn else (None, None)
+        lib.check(lib._lpm_class_filter_fwd(ptr(a), ptr(bias), ptr(residual), B, C, act, alpha, ptr(gamma), ptr(beta), ptr(moving_mean),
+                                            ptr(moving_var), int(is_training), eps, decay, ptr(keep), keep_prob, ptr(y), ptr(mean), ptr(rstd),
+                                            stream_ptr()), "lpm_class_filter_fwd")
+        ctx.args = (act, alpha, is_training, keep_prob, B, C)
+        ctx.save_for_backward(a, bias, residual, gamma, mean, rstd, keep)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        lib = _capi.load()
+        act, alpha, is_training, keep_prob, B, C = ctx.args
+        a, bias, residual, gamma, mean, rstd, keep = ctx.saved_tensors
+        dy = _f32(dy, "class_filter: dy").contiguous()
+        dpre = torch.empty_like(a)
+        dbias = _empty((C,), a) if bias is not None else None
+        dgamma, dbeta = (_empty((C,), a), _empty((C,), a)) if gamma is not None else (None, None)
+        lib.check(lib._lpm_class_filter_bwd(ptr(dy), ptr(a), ptr(bias), ptr(residual), B, C, act, alpha, ptr(gamma), ptr(mean), ptr(rstd),
+                                            int(is_training), ptr(keep), keep_prob, ptr(dpre), ptr(dbias), ptr(dgamma), ptr(dbeta),
+                                            stream_ptr()), "lpm_class_filter_bwd")
+        return (dpre, dbias, dpre if residual is not None else None, dgamma, dbeta, None, None, None, None, None, None, None, None, None)
+
+
+def _class_filter_problem(a, bias, residual, act, bn, is_training, keep, keep_prob, decay):
+    """Why ops.class_filter would refuse these arguments, or None.  Nothing is launched."""
+    if not isinstance(a, torch.Tensor) or a.dim() != 2 or a.numel() == 0:
+        return "a must be a non-empty [B, C] tensor"
+    B, C = a.shape
+    tensors = {"a": a, "bias": bias, "residual": residual, "keep": keep}
+    if bn is not None:
+        if len(bn) != 4:
+            return "bn must be (gamma, beta, moving_mean, moving_variance)"
+        tensors.update(zip(("gamma", "beta", "moving_mean", "moving_variance"), bn))
+    for n, t in tensors.items():
+        if t is None and n in ("bias", "residual", "keep"):
+            continue
+        if not isinstance(t, torch.Tensor):
+            return f"{n} must be a tensor"
+        if not t.is_cuda:
+            return f"{n} is a CPU tensor (the op needs tensors on an MI355X; layers / video_level_models carry the torch formulation)"
+        if t.device != a.device:
+            return f"{n} is on {t.device}, a on {a.device}"
+        if not t.is_contiguous():
+            return f"{n} must be contiguous"
+        if n == "keep":
+            if t.dtype != torch.uint8:
+                return f"keep must be uint8 (one byte per element, non-zero = kept), got {t.dtype}"
+        elif t.dtype != torch.float32:
+            return f"{n}: expected float32, got {t.dtype}"
+        want = (B, C) if n in ("a", "residual", "keep") else (C,)
+        if tuple(t.shape) != want:
+            return f"{n} must be {list(want)} for a {[B, C]}, got {list(t.shape)}"
+    if B > CLASS_FILTER_MAX_ROWS:
+        return f"B = {B} rows: a workgroup walks at most {CLASS_FILTER_MAX_ROWS}"
+    if not isinstance(act, str) or act not in CLASS_FILTER_ACTS:
+        return f"unknown act {act!r}; the activations are {sorted(CLASS_FILTER_ACTS)}"
+    if keep is not None and not is_training:
+        return "a keep mask is applied in training only"
+    if keep is not None and not 0.0 < keep_prob <= 1.0:
+        return f"keep_prob must be in (0, 1], got {keep_prob}"
+    if not 0.0 <= decay <= 1.0:
+        return f"decay must be in [0, 1], got {decay}"
+    return None
+
+
+def class_filter_ok(a, bias=None, residual=None, act="relu", bn=None, is_training=True, keep=None, keep_prob=1.0, decay=TF_LAYERS_BN_MOMENTUM):
+    """Whether ops.class_filter takes these arguments (fp32 contiguous [B, C] on the GPU, B <= 1024, a uint8 keep mask, ...)."""
+    return _class_filter_problem(a, bias, residual, act, bn, is_training, keep, keep_prob, decay) is None
+
+
+def class_filter(a, bias=None, residual=None, act="relu", bn=None, is_training=True, keep=None, keep_prob=1.0, decay=TF_LAYERS_BN_MOMENTUM,
+                 alpha=0.2, eps=TF_LAYERS_BN_EPS):
+    """One stage of the class filter of MoeModel2 / JuhanMoeModel (video_level_models.py:518-539, :600-620) behind its GEMM, on the GPU:
+    y = dropout(BN(act(a + bias + residual))) with act "relu" | "leaky_relu" (alpha) | "sigmoid"; bn None or (gamma, beta, moving_mean,
+    moving_variance) of a tf.layers.batch_normalization -- in training the batch mean and the biased batch variance, and both moving
+    statistics updated in place with ``decay``; in eval the moving statistics; keep: a uint8 keep mask [B, C] (training only), kept units
+    scaled by 1 / keep_prob.  Differentiable (once) in a, bias, residual, gamma and beta; the same inputs give the same bits both ways.
+    Everything is checked before any launch."""
+    why = _class_filter_problem(a, bias, residual, act, bn, is_training, keep, keep_prob, decay)
+    if why is not None:
+        raise LpmError("class_filter: " + why)
+    gamma, beta, mm, mv = bn if bn is not None else (None, None, None, None)
+    return _ClassFilter.apply(a, bias, residual, gamma, beta, mm, mv, CLASS_FILTER_ACTS[act], float(alpha), bool(is_training), keep,
+                              float(keep_prob), float(decay), float(eps))
+
+
 class ComputeCopy:
     """The bf16 compute copy of a weight beside its fp32 master (SURVEY section 7 hard part 2: "keep master fp32 + bf16 compute copy";
     BASELINE configs[4]).  The owner (train.Trainer) attaches it to the variable as ``W._lpm_w16``; FactoredGradient.clip_adam keeps it

@@ -34,6 +34,8 @@ class VariableStore:
         # trainer parks the wait for a parameter all-gather here (train.ShardedVariableUpdate), so that the collective rides under
         # the part of the next forward that does not read the variable
         self.pending: Dict[str, Callable] = {}
+        # tf.layers' automatic layer names: uses of a base name per enclosing scope (unique_layer_name)
+        self._layer_uses: Dict[str, int] = {}
 
     # -- scopes ---------------------------------------------------------------------------------
     @contextlib.contextmanager
@@ -42,7 +44,19 @@ class VariableStore:
         try:
             yield
         finally:
+            closed = "/".join(self._scope) + "/"
             self._scope.pop()
+            for key in [k for k in self._layer_uses if k.startswith(closed)]:      # (TF closes the sub-scopes' counts with the scope)
+                del self._layer_uses[key]
+
+    def unique_layer_name(self, base: str) -> str:
+        """``base``, ``base_1``, ``base_2``, ... in the order of the calls under the enclosing scope: the names tf.layers gives to layers
+        created without one.  The count starts again whenever the enclosing scope is left, so that every forward under
+        ``variable_scope("tower")`` meets the same names (TF1: variable_scope's default_name under a re-entered scope)."""
+        key = self.full_name(base)
+        n = self._layer_uses.get(key, 0)
+        self._layer_uses[key] = n + 1
+        return base if n == 0 else f"{base}_{n}"
 
     def full_name(self, name: str) -> str:
         return "/".join(self._scope + [name])

@@ -1,6 +1,6 @@
-"""MoeModel (reference: video_level_models.py:48-158), FourLayerBatchNeuralModel (:625-684), ClassLearningThreeNnModel (:687-714) and
-ClassLearningFourNnModel (:717-749) --
-host-side PyTorch per the north-star."""
+"""MoeModel (reference: video_level_models.py:48-158), MoeModel2 (:441-541), JuhanMoeModel (:544-622), FourLayerBatchNeuralModel
+(:625-684), ClassLearningThreeNnModel (:687-714) and ClassLearningFourNnModel (:717-749) --
+host-side PyTorch per the north-star; the glue of the class filter behind MoeModel2 / JuhanMoeModel is ops.class_filter on the GPU."""
 from __future__ import annotations
 
 import math
@@ -78,6 +78,131 @@ class MoeModel(models.BaseModel):
             gates = layers.batch_norm(gates, is_training, "gating_prob_bn")                                # :149-154
             probabilities = probabilities * torch.sigmoid(gates)                                           # :156-158
         return {"predictions": probabilities}                                                             # :158
+
+
+CLASS_FILTER_KEEP_PROB = 0.8       # tf.nn.dropout(., 0.8): the second argument is the KEEP probability (:526, :598, :607)
+CLASS_FILTER_NUM_MIXTURES = 3      # num_mixtures = 3, whatever the argument says (:469, :570)
+
+
+def _mixture_of_experts(model_input, vocab_size, num_mixtures, l2_penalty, low_rank_gating=-1):
+    """The MoE mixture MoeModel2 and JuhanMoeModel start with (video_level_models.py:475-516, :572-596): bias-free gates (optionally
+    through a low_rank_gating bottleneck), experts with a bias, every weight under slim.l2_regularizer(l2_penalty) -> probabilities
+    [B, vocab_size].  On the GPU the softmax / sigmoid / sum tail is ops.moe_cross_entropy without labels."""
+    H = model_input.shape[1]
+    dev = model_input.device
+    store = vs.default_store()
+    if low_rank_gating == -1:
+        with vs.variable_scope("gates"):
+            wg = vs.get_variable("weights", [H, vocab_size * (num_mixtures + 1)], vs.glorot_uniform_initializer(), device=dev)
+        store.add_l2_regularizer(wg, l2_penalty)
+        gate_activations = _linear(model_input, wg)
+    else:
+        with vs.variable_scope("gates1"):
+            wg1 = vs.get_variable("weights", [H, low_rank_gating], vs.glorot_uniform_initializer(), device=dev)
+        with vs.variable_scope("gates2"):
+            wg2 = vs.get_variable("weights", [low_rank_gating, vocab_size * (num_mixtures + 1)], vs.glorot_uniform_initializer(), device=dev)
+        store.add_l2_regularizer(wg1, l2_penalty)
+        store.add_l2_regularizer(wg2, l2_penalty)
+        gate_activations = model_input.matmul(wg1).matmul(wg2)
+    with vs.variable_scope("experts"):
+        we = vs.get_variable("weights", [H, vocab_size * num_mixtures], vs.glorot_uniform_initializer(), device=dev)
+        be = vs.get_variable("biases", [vocab_size * num_mixtures], vs.zeros_initializer(), device=dev)
+    store.add_l2_regularizer(we, l2_penalty)
+    expert_activations = _linear(model_input, we, be)
+    if model_input.is_cuda and model_input.dtype == torch.float32:
+        from . import ops
+        return ops.moe_cross_entropy(gate_activations, expert_activations, None, num_mixtures)[0]
+    gating_distribution = torch.softmax(gate_activations.reshape(-1, num_mixtures + 1), dim=-1)
+    expert_distribution = torch.sigmoid(expert_activations.reshape(-1, num_mixtures))
+    return (gating_distribution[:, :num_mixtures] * expert_distribution).sum(dim=1).reshape(-1, vocab_size)
+
+
+def _keep_mask(masks, key, shape, device):
+    """The KEEP mask [B, C] (uint8, 1 = kept) of one tf.nn.dropout: the one handed in under ``key``, or a draw of ops.dropout_keep_mask
+    (allocated as a multiple of 16 elements, the size its kernel takes, and cut to [B, C])."""
+    keep = masks.get(key)
+    if keep is not None:
+        if tuple(keep.shape) != tuple(shape):
+            raise ValueError(f"dropout_masks[{key!r}] must be {list(shape)}, got {list(keep.shape)}")
+        return keep.to(device=device).ne(0).to(torch.uint8).contiguous()
+    from . import ops
+    n = shape[0] * shape[1]
+    return ops.dropout_keep_mask(((n + 15) // 16 * 16,), CLASS_FILTER_KEEP_PROB, device)[:n].view(*shape)
+
+
+def _filter_stage(a, bias, residual, act, batch_norm, is_training, keep):
+    """One stage of the class filter behind its GEMM ``a``: dropout(BN(act(a + bias + residual))), act "relu" | "leaky_relu" (alpha 0.2,
+    tf.nn.leaky_relu's default) | "sigmoid", BN a tf.layers.batch_normalization with the next automatic name.  FLAGS.class_filter_fused
+    on the GPU: one ops.class_filter launch each way; otherwise the torch formulation (the CPU path; same variables, same results)."""
+    from . import layers
+    bn = layers.tf_layers_bn_variables(a.shape[1], a.device) if batch_norm else None
+    keep = keep if is_training else None
+    if FLAGS.class_filter_fused and a.is_cuda:
+        from . import ops
+        if ops.class_filter_ok(a, bias, residual, act, bn, is_training, keep, CLASS_FILTER_KEEP_PROB):
+            return ops.class_filter(a, bias, residual, act=act, bn=bn, is_training=is_training, keep=keep,
+                                    keep_prob=CLASS_FILTER_KEEP_PROB, decay=layers.TF_LAYERS_BN_MOMENTUM, alpha=0.2)
+    return _filter_stage_torch(a, bias, residual, act, bn, is_training, keep)
+
+
+def _filter_stage_torch(a, bias, residual, act, bn, is_training, keep):
+    """_filter_stage's torch formulation on given batch-norm variables (gamma, beta, moving_mean, moving_variance) or None."""
+    from . import layers
+    pre = a if bias is None else a + bias
+    if residual is not None:
+        pre = pre + residual
+    u = {"relu": torch.relu, "leaky_relu": lambda t: torch.nn.functional.leaky_relu(t, 0.2), "sigmoid": torch.sigmoid}[act](pre)
+    if bn is not None:
+        u = layers.tf_layers_bn_apply(u, is_training, *bn)
+    if keep is not None:
+        u = u * keep.to(u.dtype) / CLASS_FILTER_KEEP_PROB
+    return u
+
+
+def _class_filter(probabilities, vocab_size, is_training, act, masks):
+    """The class filter over the vocabulary (video_level_models.py:518-539, :600-620): v-filter1 (V -> 2V, bias, act, batch norm, dropout
+    in training), v-filter2 (2V -> V, no bias), p + filter2 -> act -> batch norm, v-final_output (V -> V, bias, sigmoid).  The variables
+    carry tf.layers' names: v-filter1/{kernel,bias}, batch_normalization/..., v-filter2/kernel, batch_normalization_1/...,
+    v-final_output/{kernel,bias}."""
+    from . import layers
+    dev = probabilities.device
+    B = probabilities.shape[0]
+    w1, b1 = layers.dense_variables("v-filter1", vocab_size, vocab_size * 2, True, dev)
+    keep1 = _keep_mask(masks, "filter1", (B, vocab_size * 2), dev) if is_training else None
+    filter1 = _filter_stage(_linear(probabilities, w1), b1, None, act, True, is_training, keep1)              # :518-526 / :600-607
+    w2, _ = layers.dense_variables("v-filter2", vocab_size * 2, vocab_size, False, dev)
+    p = _filter_stage(_linear(filter1, w2), None, probabilities, act, True, is_training, None)                # :528-536 / :609-617
+    w3, b3 = layers.dense_variables("v-final_output", vocab_size, vocab_size, True, dev)
+    return _filter_stage(_linear(p, w3), b3, None, "sigmoid", False, is_training, None)                       # :538-539 / :619-620
+
+
+class MoeModel2(models.BaseModel):
+    """The MoE mixture with three experts, then the class filter with relu (video_level_models.py:441-541).  num_mixtures is 3 whatever
+    the argument says (:469), the penalty is FLAGS.moe_l2 (:471; the argument is ignored), moe_low_rank_gating is honoured as in MoeModel,
+    moe_prob_gating and moe_prob_gating_input are read and used nowhere (:472-473).  ``dropout_masks`` {"filter1"}: the KEEP mask
+    [B, 2 vocab_size] (non-zero = kept) in place of the random draw.  ``labels`` / ``fused_cross_entropy`` (the trainer's) are ignored:
+    the loss is taken of the filter's output."""
+
+    def create_model(self, model_input, vocab_size, is_training=True, num_mixtures=None, l2_penalty=1e-8, dropout_masks=None,
+                     labels=None, fused_cross_entropy=False, **unused_params):
+        probabilities = _mixture_of_experts(model_input, vocab_size, CLASS_FILTER_NUM_MIXTURES, FLAGS.moe_l2, FLAGS.moe_low_rank_gating)
+        return {"predictions": _class_filter(probabilities, vocab_size, is_training, "relu", dropout_masks or {})}
+
+
+class JuhanMoeModel(models.BaseModel):
+    """The MoE mixture with three experts, dropout of the probabilities in training (keep 0.8; the residual takes the dropped tensor),
+    then the class filter with leaky_relu (alpha 0.2) (video_level_models.py:544-622).  Reads no flag: the penalty is the ``l2_penalty``
+    argument.  ``dropout_masks`` {"probabilities": [B, vocab_size], "filter1": [B, 2 vocab_size]}: KEEP masks in place of the random
+    draws.  ``labels`` / ``fused_cross_entropy`` are ignored."""
+
+    def create_model(self, model_input, vocab_size, is_training=True, num_mixtures=None, l2_penalty=1e-8, dropout_masks=None,
+                     labels=None, fused_cross_entropy=False, **unused_params):
+        masks = dropout_masks or {}
+        probabilities = _mixture_of_experts(model_input, vocab_size, CLASS_FILTER_NUM_MIXTURES, l2_penalty)
+        if is_training:                                                                                      # :597-598
+            keep = _keep_mask(masks, "probabilities", tuple(probabilities.shape), probabilities.device)
+            probabilities = probabilities * keep.to(probabilities.dtype) / CLASS_FILTER_KEEP_PROB
+        return {"predictions": _class_filter(probabilities, vocab_size, is_training, "leaky_relu", masks)}
 
 
 class FourLayerBatchNeuralModel(models.BaseModel):
