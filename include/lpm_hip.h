@@ -1454,6 +1454,31 @@ int lpm_class_filter_bwd(const float* dy, const float* a, const float* bias, con
                          const uint8_t* keep, float keep_prob, float* dpre, float* dbias, float* dgamma, float* dbeta,
                          lpm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The row-wise glue over [B, C] class scores behind FishMoeModel3 (video_level_models.py:431-436) and the class-gating modules
+ * (attention_modules.py:157-273): tf.layers.dense's bias, the clipped gate, the residual add, then a layer norm or a softmax along the
+ * row.  One launch forward; the backward is one row-owned launch plus, with a bias or a layer norm, one column-owned launch for the sums
+ * over the batch.  a [B, C] fp32 contiguous, 1 <= B <= 1024, 1 <= C <= 16384 (no alignment beyond fp32's is assumed):
+ *   t   = a (+ bias [C]);  pre = phi(t) (+ residual [B, C]), phi LPM_CLASS_ROWS_IDENTITY | _RELU6 min(max(t, 0), 6) | _NEG_RELU6 -relu6(-t)
+ *   y   = pre                                   norm LPM_CLASS_ROWS_NONE
+ *       = softmax of pre over the row           norm LPM_CLASS_ROWS_SOFTMAX (the row maximum taken out)
+ *       = gamma (pre - mean) rstd + beta        norm LPM_CLASS_ROWS_LAYER_NORM: gamma, beta [C] (NULL with the other norms); the mean and the
+ *         BIASED variance over the row, taken in two passes; rstd = 1 / sqrt(var + eps); stats [B, 2] = (mean, rstd) is written
+ * Backward (t and xhat recomputed from a, bias, residual and stats; the softmax reads y): dpre = dy | y (dy - sum_j y_j dy_j) |
+ *   rstd (g - mean_j g - xhat mean_j (g xhat)) with g = dy gamma;  da = dpre phi'(t), phi' = [0 < t < 6] | [-6 < t < 0];  dresidual
+ *   (optional; needs a residual) = dpre -- with the identity da is dpre already;  dbias = sum_b da (bias and dbias both or neither);
+ *   dgamma = sum_b dy xhat, dbeta = sum_b dy (layer norm: gamma, stats, dgamma, dbeta all four).
+ * All sums are added in fp64 and in a fixed order (no atomics): the same inputs give the same bits.  Every argument is checked before
+ * any launch.
+ * ------------------------------------------------------------------------------------------- */
+enum { LPM_CLASS_ROWS_IDENTITY = 1, LPM_CLASS_ROWS_RELU6 = 2, LPM_CLASS_ROWS_NEG_RELU6 = 3 };
+enum { LPM_CLASS_ROWS_NONE = 1, LPM_CLASS_ROWS_SOFTMAX = 2, LPM_CLASS_ROWS_LAYER_NORM = 3 };
+int lpm_class_rows_fwd(const float* a, const float* bias, const float* residual, int B, int C, int phi, int norm, const float* gamma,
+                       const float* beta, float eps, float* y, float* stats, lpm_stream_t stream);
+int lpm_class_rows_bwd(const float* dy, const float* a, const float* bias, const float* residual, const float* y, int B, int C, int phi,
+                       int norm, const float* gamma, const float* stats, float* da, float* dresidual, float* dbias, float* dgamma,
+                       float* dbeta, lpm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -287,7 +287,15 @@ SIGNATURES = {
     "lpm_bn_act_bwd_image_fmt": (_i, [_f, _f, _f, _i, _f, _f, _f, _fl, _i, _i, _f, _f, _f, _f, _f, _s, _f, _f]),
     "lpm_class_filter_fwd": (_i, [_f, _f, _f, _i, _i, _i, _fl, _f, _f, _f, _f, _i, _fl, C.c_double, _f, _fl, _f, _f, _f, _f]),
     "lpm_class_filter_bwd": (_i, [_f, _f, _f, _f, _i, _i, _i, _fl, _f, _f, _f, _i, _f, _fl, _f, _f, _f, _f, _f]),
+    "lpm_class_rows_fwd": (_i, [_f, _f, _f, _i, _i, _i, _i, _f, _f, _fl, _f, _f, _f]),
+    "lpm_class_rows_bwd": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f]),
 }
+LPM_CLASS_ROWS_IDENTITY = 1      # phi of lpm_class_rows_fwd / _bwd
+LPM_CLASS_ROWS_RELU6 = 2
+LPM_CLASS_ROWS_NEG_RELU6 = 3
+LPM_CLASS_ROWS_NONE = 1          # ... and their norm
+LPM_CLASS_ROWS_SOFTMAX = 2
+LPM_CLASS_ROWS_LAYER_NORM = 3
 LPM_CLASS_FILTER_RELU = 1        # activations of lpm_class_filter_fwd / _bwd
 LPM_CLASS_FILTER_LEAKY_RELU = 2
 LPM_CLASS_FILTER_SIGMOID = 3

@@ -1,5 +1,5 @@
-"""Attention-cluster pooling and the per-head transformer block of the reference's attention_modules.py:22-161
-(SURVEY.md 8(f) rank 4), on the hot path's kernels:
+"""Attention-cluster pooling, the per-head transformer block (attention_modules.py:22-161) and the five
+class-gating modules over [B, vocab_size] class scores (:157-362) of the reference's attention_modules.py, on the hot path's kernels:
 
 * ``OneFcAttention``: the weighted frame sums are K2's aggregation (similarities given, no softmax over clusters) and their
   backward is K3.  Because the attention is a softmax over the FRAMES of a clip, every cluster's weights sum to one, so the
@@ -10,6 +10,10 @@
 * ``MultiHeadAttention``: every head owns its relu(dense) q / k / v; the per-head cores run as ONE K4 launch over the
   concatenated heads when the head width is one K4 covers (8 or 16), as library batched GEMMs otherwise.
 * ``TransformerEncoderBlock``: dense / conv1d(kernel_size=1) layers through ``layers.dense`` (split-bf16 library GEMMs).
+* ``PGateModule`` / ``PnGateModule`` / ``NpGateModule``: every clipped gate behind its [V, V] product is one ``layers.class_rows``
+  (ops.class_rows on the GPU: relu6 or -relu6(-t), the residual add and the closing softmax over the row in one launch).
+* ``CorNNGateModule``: three slim.fully_connected of width V, bias + relu / relu / sigmoid as ops.class_filter stages on the GPU.
+* ``ContextGateV1``: x * sigmoid(BN(x W)), host torch like MoeModel's probability gating.
 
 Variable names are the ones TF1 assigns by default (``dense``, ``dense_1``, ``conv1d``, ``LayerNorm_1`` ...) for the first
 block built under a variable scope; build further blocks under their own ``variable_scope``."""
@@ -19,7 +23,7 @@ import math
 
 import torch
 
-from . import layers, modules, ops
+from . import FLAGS, layers, modules, ops
 from . import variables as vs
 
 
@@ -125,3 +129,103 @@ class TransformerEncoderBlock(modules.BaseModule):
         output = _conv1d_k1(output, self.num_units, "conv1d_1")                                      # :152
         output = layers.layer_norm(output, "LayerNorm_1")                                            # :155 (rank 3: frames x units)
         return output.reshape(-1, self.feature_size)                                                 # :156
+
+
+def _gate_variable(name, vocab_size, device):
+    """A [V, V] gate of the P / N gate modules: random_normal(stddev = 1 / sqrt(V)) (:176-183)."""
+    return vs.get_variable(name, [vocab_size, vocab_size], vs.random_normal_initializer(1 / math.sqrt(vocab_size)), device=device)
+
+
+class _ClassGateModule(modules.BaseModule):
+    """The constructor the class-gating modules share (:158-168, :201-211, :244-254)."""
+
+    def __init__(self, vocab_size, is_training, scope_id=None):
+        self.vocab_size = int(vocab_size)
+        self.scope_id = scope_id
+        self.is_training = is_training
+
+
+class PnGateModule(_ClassGateModule):
+    """attention_modules.py:157-197: vocabularies -> P gate -> N gate -> softmax."""
+
+    def forward(self, inputs, **unused_params):
+        """inputs [B, vocab_size] -> [B, vocab_size]."""
+        p_gating_weights = _gate_variable("p_pn_gate", self.vocab_size, inputs.device)                       # :176-179
+        n_gating_weights = _gate_variable("n_pn_gate", self.vocab_size, inputs.device)                       # :180-183
+        p_gate = layers.class_rows(inputs.matmul(p_gating_weights), residual=inputs, phi="relu6")            # :186-188
+        return layers.class_rows(p_gate.matmul(n_gating_weights), residual=p_gate, phi="neg_relu6", norm="softmax")   # :191-196
+
+
+class NpGateModule(_ClassGateModule):
+    """attention_modules.py:200-240: vocabularies -> N gate -> P gate -> softmax.  The P gate's variable is created first, as written."""
+
+    def forward(self, inputs, **unused_params):
+        """inputs [B, vocab_size] -> [B, vocab_size]."""
+        p_gating_weights = _gate_variable("p_np_gate", self.vocab_size, inputs.device)                       # :219-222
+        n_gating_weights = _gate_variable("n_np_gate", self.vocab_size, inputs.device)                       # :223-226
+        n_gate = layers.class_rows(inputs.matmul(n_gating_weights), residual=inputs, phi="neg_relu6")        # :229-232
+        return layers.class_rows(n_gate.matmul(p_gating_weights), residual=n_gate, phi="relu6", norm="softmax")   # :235-238
+
+
+class PGateModule(_ClassGateModule):
+    """attention_modules.py:243-273: vocabularies -> P gate -> softmax."""
+
+    def forward(self, inputs, **unused_params):
+        """inputs [B, vocab_size] -> [B, vocab_size]."""
+        p_gating_weights = _gate_variable("p_p_gate", self.vocab_size, inputs.device)                        # :262-265
+        return layers.class_rows(inputs.matmul(p_gating_weights), residual=inputs, phi="relu6", norm="softmax")   # :268-271
+
+
+def _scope_suffix(scope_id):
+    return "" if scope_id is None else str(scope_id)
+
+
+class CorNNGateModule(modules.BaseModule):
+    """attention_modules.py:276-316: three slim.fully_connected of width vocab_size -- relu, relu, sigmoid -- under
+    vocab_gate{1,2,3}_v1{scope_id}/{weights,biases}.  ``batch_norm`` is accepted and read nowhere, as written."""
+
+    def __init__(self, vocab_size, is_training, batch_norm=True, scope_id=None):
+        self.vocab_size = int(vocab_size)
+        self.is_training = is_training
+        self.batch_norm = batch_norm
+        self.scope_id = scope_id
+
+    def _fully_connected(self, x, scope, act):
+        """slim.fully_connected(x, vocab_size, activation_fn=act): xavier weights, zero biases.  FLAGS.class_filter_fused on the GPU: the
+        bias and the activation are one ops.class_filter stage (no batch norm) behind the product."""
+        with vs.variable_scope(scope):
+            w = vs.get_variable("weights", [x.shape[1], self.vocab_size], vs.glorot_uniform_initializer(), device=x.device)
+            b = vs.get_variable("biases", [self.vocab_size], vs.zeros_initializer(), device=x.device)
+        a = x.matmul(w)
+        if FLAGS.class_filter_fused and a.is_cuda and ops.class_filter_ok(a, b, None, act, None, bool(self.is_training)):
+            return ops.class_filter(a, b, act=act, is_training=bool(self.is_training))
+        return (torch.relu if act == "relu" else torch.sigmoid)(a + b)
+
+    def forward(self, inputs, **unused_params):
+        """inputs [B, vocab_size] -> [B, vocab_size]."""
+        s = _scope_suffix(self.scope_id)
+        fc1_out = self._fully_connected(inputs, "vocab_gate1_v1" + s, "relu")                                # :295-300
+        fc2_out = self._fully_connected(fc1_out, "vocab_gate2_v1" + s, "relu")                               # :302-307
+        return self._fully_connected(fc2_out, "vocab_gate3_v1" + s, "sigmoid")                               # :309-316
+
+
+class ContextGateV1(modules.BaseModule):
+    """attention_modules.py:319-362 (WILLOW's context gating): x * sigmoid(BN(x W)), W ``vocab_gate_v1{scope_id}`` [V, V] created without
+    an initializer (tf.get_variable's default: glorot uniform), BN slim.batch_norm under ``vocab_gate_bn_v1{scope_id}`` when
+    ``batch_norm``; there is no bias otherwise.  Host torch."""
+
+    def __init__(self, vocab_size, is_training, batch_norm=True, scope_id=None):
+        self.vocab_size = int(vocab_size)
+        self.is_training = is_training
+        self.batch_norm = batch_norm
+        self.scope_id = scope_id
+
+    def forward(self, inputs, **unused_params):
+        """inputs [B, vocab_size] -> [B, vocab_size]."""
+        s = _scope_suffix(self.scope_id)
+        gating_weights = vs.get_variable("vocab_gate_v1" + s, [self.vocab_size, self.vocab_size], vs.glorot_uniform_initializer(),
+                                         device=inputs.device)                                               # :342-343
+        gates = inputs.matmul(gating_weights)                                                                # :346
+        if self.batch_norm:
+            gates = layers.batch_norm(gates, self.is_training, "vocab_gate_bn_v1" + s)                       # :348-354
+        return inputs * torch.sigmoid(gates)                                                                 # :356-362

@@ -230,6 +230,12 @@ FLAGS.define("class_filter_fused", True, "build extension: on the GPU the three 
              "(1024, 3862) -- the bias + sigmoid stage alone is SLOWER fused, 0.055 against 0.038 ms and 0.065 against 0.050 ms -- and one "
              "Trainer.step of MoeModel2 / JuhanMoeModel at 2.17 / 2.29 ms against 2.47 / 2.57 ms and 6.19 / 6.28 against 6.62 / 6.71 ms; the "
              "default is on only if the fused route is faster at both shapes (profiles/bench_class_filter.json, DESIGN.md section 36)")
+FLAGS.define("class_rows_fused", False, "build extension: on the GPU the row-wise glue over [B, V] class scores -- FishMoeModel3's "
+             "bias + residual + LayerNorm and bias + softmax, the clipped gates (relu6, -relu6(-t)) + residual (+ softmax) of "
+             "attention_modules' PGateModule / PnGateModule / NpGateModule -- is ONE ops.class_rows launch forward and one or two "
+             "backward per stage (csrc/class_rows.hip) behind its library GEMM; False: the torch formulation (the CPU path; same "
+             "variables, same results).  Off: tools/bench_class_rows.py measured forward + backward of FishMoeModel3's two row stages together at 0.165 ms fused against 0.225 ms at (B, V) = (1024, 3862) but 0.196 against 0.181 ms at (128, 3862), where both routes are bound by the host and an autograd node written in Python costs more than torch's own; the PN gate's two stages 0.099 against 0.113 ms and 0.100 against 0.100 ms; one Trainer.step of FishMoeModel3 5.90 against 5.96 ms and 2.13 against 2.12 ms; the default is on only if the fused route is faster at both shapes "
+             "(profiles/bench_class_rows.json, DESIGN.md section 37)")
 FLAGS.define("wtm_projection_l1", 1e-5, "layers.l1_l2_regularizer(1e-5) on dis_projection_2 / temp_projection_2 (frame_level_models.py:1272,1287): "
              "tf.contrib's first positional argument is scale_l1")
 FLAGS.define("wtm_projection_l2", 1.0, "... and its scale_l2 keeps the default 1.0: the penalty is l1 * sum |w| + l2 * sum(w^2) / 2 (SURVEY App. B)")

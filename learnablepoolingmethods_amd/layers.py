@@ -143,6 +143,35 @@ def layer_norm(x: torch.Tensor, scope: str = "LayerNorm", residual: torch.Tensor
     return y * gamma + beta
 
 
+def class_rows_torch(a, bias=None, residual=None, phi="identity", norm="none", ln=None, eps=LN_EPS):
+    """ops.class_rows' torch formulation: norm(phi(a + bias) + residual) along the rows of [B, C] class scores."""
+    t = a if bias is None else a + bias
+    if phi == "relu6":
+        t = F.relu6(t)                                               # tf.nn.relu6
+    elif phi == "neg_relu6":
+        t = -F.relu6(-t)                                             # -1 * relu6(-1 * t)
+    elif phi != "identity":
+        raise ValueError(f"class_rows: unknown phi {phi!r}")
+    pre = t if residual is None else t + residual
+    if norm == "none":
+        return pre
+    if norm == "softmax":
+        return torch.softmax(pre, dim=1)
+    if norm != "layer_norm":
+        raise ValueError(f"class_rows: unknown norm {norm!r}")
+    gamma, beta = ln
+    return F.layer_norm(pre, (pre.shape[1],), None, None, eps) * gamma + beta
+
+
+def class_rows(a, bias=None, residual=None, phi="identity", norm="none", ln=None):
+    """The row-wise glue over class scores behind a GEMM ``a`` [B, C]: norm(phi(a + bias) + residual), phi "identity" | "relu6" |
+    "neg_relu6", norm "none" | "softmax" | "layer_norm" with ln = (gamma, beta) (TF1's layer_norm: eps 1e-12).  FLAGS.class_rows_fused on
+    the GPU: one ops.class_rows launch forward; otherwise the torch formulation (the CPU path; same results)."""
+    if FLAGS.class_rows_fused and a.is_cuda and ops.class_rows_ok(a, bias, residual, phi, norm, ln, LN_EPS):
+        return ops.class_rows(a, bias, residual, phi=phi, norm=norm, ln=ln, eps=LN_EPS)
+    return class_rows_torch(a, bias, residual, phi, norm, ln, LN_EPS)
+
+
 def use_split_gemm(x: torch.Tensor, rows: int, units: int) -> bool:
     """Dense layers big enough to pay for the operand split run as split-bf16 library GEMMs (ops._DenseX3)."""
     return (FLAGS.dense_precision == "bf16x3" and x.is_cuda and rows >= 1024 and x.shape[-1] % 8 == 0 and units % 8 == 0)

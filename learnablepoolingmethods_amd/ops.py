@@ -4097,6 +4097,107 @@ def class_filter(a, bias=None, residual=None, act="relu", bn=None, is_training=T
                               float(keep_prob), float(decay), float(eps))
 
 
+CLASS_ROWS_PHIS = {"identity": _capi.LPM_CLASS_ROWS_IDENTITY, "relu6": _capi.LPM_CLASS_ROWS_RELU6,
+                   "neg_relu6": _capi.LPM_CLASS_ROWS_NEG_RELU6}
+CLASS_ROWS_NORMS = {"none": _capi.LPM_CLASS_ROWS_NONE, "softmax": _capi.LPM_CLASS_ROWS_SOFTMAX,
+                    "layer_norm": _capi.LPM_CLASS_ROWS_LAYER_NORM}
+CLASS_ROWS_MAX_COLS = 16384
+
+
+class _ClassRows(torch.autograd.Function):
+    """(a, bias, residual, gamma, beta) -> y: the row-wise glue in one launch forward, one or two backward (csrc/class_rows.hip).  The
+    backward recomputes t = a + bias and xhat from the saved inputs and stats [B, 2]; the softmax's reads the output y."""
+
+    @staticmethod
+    def forward(ctx, a, bias, residual, gamma, beta, phi, norm, eps):
+        lib = _capi.load()
+        B, C = a.shape
+        y = torch.empty_like(a)
+        stats = _empty((B, 2), a) if gamma is not None else None
+        lib.check(lib._lpm_class_rows_fwd(ptr(a), ptr(bias), ptr(residual), B, C, phi, norm, ptr(gamma), ptr(beta), eps, ptr(y), ptr(stats),
+                                          stream_ptr()), "lpm_class_rows_fwd")
+        ctx.args = (phi, norm, B, C)
+        ctx.save_for_backward(a, bias, residual, gamma, stats, y if norm == _capi.LPM_CLASS_ROWS_SOFTMAX else None)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        lib = _capi.load()
+        phi, norm, B, C = ctx.args
+        a, bias, residual, gamma, stats, y = ctx.saved_tensors
+        dy = _f32(dy, "class_rows: dy").contiguous()
+        da = torch.empty_like(a)
+        # dpre is the gradient of the residual; with the identity it is da as well
+        dres = torch.empty_like(a) if residual is not None and phi != _capi.LPM_CLASS_ROWS_IDENTITY else None
+        dbias = _empty((C,), a) if bias is not None else None
+        dgamma, dbeta = (_empty((C,), a), _empty((C,), a)) if gamma is not None else (None, None)
+        lib.check(lib._lpm_class_rows_bwd(ptr(dy), ptr(a), ptr(bias), ptr(residual), ptr(y), B, C, phi, norm, ptr(gamma), ptr(stats), ptr(da),
+                                          ptr(dres), ptr(dbias), ptr(dgamma), ptr(dbeta), stream_ptr()), "lpm_class_rows_bwd")
+        if residual is not None and dres is None:
+            dres = da
+        return da, dbias, dres, dgamma, dbeta, None, None, None
+
+
+def _class_rows_problem(a, bias, residual, phi, norm, ln, eps):
+    """Why ops.class_rows would refuse these arguments, or None.  Nothing is launched."""
+    if not isinstance(a, torch.Tensor) or a.dim() != 2 or a.numel() == 0:
+        return "a must be a non-empty [B, C] tensor"
+    B, C = a.shape
+    if not isinstance(phi, str) or phi not in CLASS_ROWS_PHIS:
+        return f"unknown phi {phi!r}; the gates are {sorted(CLASS_ROWS_PHIS)}"
+    if not isinstance(norm, str) or norm not in CLASS_ROWS_NORMS:
+        return f"unknown norm {norm!r}; the norms are {sorted(CLASS_ROWS_NORMS)}"
+    tensors = {"a": a, "bias": bias, "residual": residual}
+    if norm == "layer_norm":
+        if ln is None or len(ln) != 2:
+            return "norm 'layer_norm' needs ln = (gamma, beta)"
+        tensors.update(zip(("gamma", "beta"), ln))
+    elif ln is not None:
+        return f"ln = (gamma, beta) goes with norm 'layer_norm' only, got norm {norm!r}"
+    for n, t in tensors.items():
+        if t is None and n in ("bias", "residual"):
+            continue
+        if not isinstance(t, torch.Tensor):
+            return f"{n} must be a tensor"
+        if not t.is_cuda:
+            return f"{n} is a CPU tensor (the op needs tensors on an MI355X; layers.class_rows carries the torch formulation)"
+        if t.device != a.device:
+            return f"{n} is on {t.device}, a on {a.device}"
+        if not t.is_contiguous():
+            return f"{n} must be contiguous"
+        if t.dtype != torch.float32:
+            return f"{n}: expected float32, got {t.dtype}"
+        want = (B, C) if n in ("a", "residual") else (C,)
+        if tuple(t.shape) != want:
+            return f"{n} must be {list(want)} for a {[B, C]}, got {list(t.shape)}"
+    if B > CLASS_FILTER_MAX_ROWS:
+        return f"B = {B} rows: at most {CLASS_FILTER_MAX_ROWS} (ops.class_filter's limit: the two ops serve the same batches)"
+    if C > CLASS_ROWS_MAX_COLS:
+        return f"C = {C} columns: a workgroup holds a row of at most {CLASS_ROWS_MAX_COLS}"
+    if not eps > 0.0:
+        return f"eps must be positive, got {eps}"
+    return None
+
+
+def class_rows_ok(a, bias=None, residual=None, phi="identity", norm="none", ln=None, eps=LN_EPS):
+    """Whether ops.class_rows takes these arguments (fp32 contiguous [B, C] on the GPU, B <= 1024, C <= 16384, ...)."""
+    return _class_rows_problem(a, bias, residual, phi, norm, ln, eps) is None
+
+
+def class_rows(a, bias=None, residual=None, phi="identity", norm="none", ln=None, eps=LN_EPS):
+    """The row-wise glue over class scores behind a GEMM ``a`` [B, C], on the GPU (FishMoeModel3: video_level_models.py:431-436; the
+    class-gating modules: attention_modules.py:157-273): y = norm(phi(a + bias) + residual) with phi "identity" | "relu6" |
+    "neg_relu6" (-relu6(-t)) and norm "none" | "softmax" (over the row) | "layer_norm" (tf.contrib.layers.layer_norm at rank 2:
+    ln = (gamma, beta), the biased variance of the row, ``eps``).  Differentiable (once) in a, bias, residual, gamma and beta; the same
+    inputs give the same bits both ways.  Everything is checked before any launch."""
+    why = _class_rows_problem(a, bias, residual, phi, norm, ln, eps)
+    if why is not None:
+        raise LpmError("class_rows: " + why)
+    gamma, beta = ln if ln is not None else (None, None)
+    return _ClassRows.apply(a, bias, residual, gamma, beta, CLASS_ROWS_PHIS[phi], CLASS_ROWS_NORMS[norm], float(eps))
+
+
 class ComputeCopy:
     """The bf16 compute copy of a weight beside its fp32 master (SURVEY section 7 hard part 2: "keep master fp32 + bf16 compute copy";
     BASELINE configs[4]).  The owner (train.Trainer) attaches it to the variable as ``W._lpm_w16``; FactoredGradient.clip_adam keeps it

@@ -1,6 +1,7 @@
-"""MoeModel (reference: video_level_models.py:48-158), MoeModel2 (:441-541), JuhanMoeModel (:544-622), FourLayerBatchNeuralModel
-(:625-684), ClassLearningThreeNnModel (:687-714) and ClassLearningFourNnModel (:717-749) --
-host-side PyTorch per the north-star; the glue of the class filter behind MoeModel2 / JuhanMoeModel is ops.class_filter on the GPU."""
+"""MoeModel (reference: video_level_models.py:48-158), FishMoeModel3 (:367-438), MoeModel2 (:441-541), JuhanMoeModel (:544-622),
+FourLayerBatchNeuralModel (:625-684), ClassLearningThreeNnModel (:687-714) and ClassLearningFourNnModel (:717-749) --
+host-side PyTorch per the north-star; the glue of the class filter behind MoeModel2 / JuhanMoeModel is ops.class_filter on the GPU,
+the row-wise glue of FishMoeModel3 (LayerNorm, softmax) ops.class_rows."""
 from __future__ import annotations
 
 import math
@@ -203,6 +204,47 @@ class JuhanMoeModel(models.BaseModel):
             keep = _keep_mask(masks, "probabilities", tuple(probabilities.shape), probabilities.device)
             probabilities = probabilities * keep.to(probabilities.dtype) / CLASS_FILTER_KEEP_PROB
         return {"predictions": _class_filter(probabilities, vocab_size, is_training, "leaky_relu", masks)}
+
+
+def _batch_normalization(x, is_training):
+    """tf.layers.batch_normalization(x, training=is_training) over [B, V] with the next automatic name.  FLAGS.class_filter_fused on the
+    GPU: ops.class_filter with act "leaky_relu" and alpha = 1.0 -- t > 0 ? t : 1.0 t, exactly the identity both ways (SURVEY App. C56);
+    otherwise layers.tf_layers_bn_apply (the CPU path; same variables, same results)."""
+    from . import layers
+    bn = layers.tf_layers_bn_variables(x.shape[1], x.device)
+    if FLAGS.class_filter_fused and x.is_cuda:
+        from . import ops
+        if ops.class_filter_ok(x, None, None, "leaky_relu", bn, is_training):
+            return ops.class_filter(x, act="leaky_relu", bn=bn, is_training=is_training, decay=layers.TF_LAYERS_BN_MOMENTUM, alpha=1.0)
+    return layers.tf_layers_bn_apply(x, is_training, *bn)
+
+
+class FishMoeModel3(models.BaseModel):
+    """The MoE mixture, then a residual block over the vocabulary and a softmax (video_level_models.py:367-438): batch norm, dense
+    (V -> V filter_size, bias) + relu + batch norm, dense_1 (-> V, bias), p0 + r1 -> LayerNorm -> batch norm, dense_2 (V -> V, bias) +
+    softmax.  num_mixtures is the argument or FLAGS.moe_num_mixtures (:396), the penalty is FLAGS.moe_l2 (:397; the argument is
+    ignored), there is no low-rank gating.  tf.layers.dropout(r_activation0, 0.9) (:430) is given no ``training=``, so it is the
+    identity in TF1, also in training: no mask is drawn (a ``dropout_masks`` argument is accepted and read nowhere).
+    The variables carry tf.layers' and slim's automatic names.  ``labels`` / ``fused_cross_entropy`` (the trainer's) are ignored: the
+    loss is taken of the softmax output.  On the GPU the two row stages are one ops.class_rows each with FLAGS.class_rows_fused (off
+    by default: flags.py says what was measured), the three batch norms one ops.class_filter each (FLAGS.class_filter_fused)."""
+
+    def create_model(self, model_input, vocab_size, is_training=True, num_mixtures=None, l2_penalty=1e-6, filter_size=2,
+                     labels=None, fused_cross_entropy=False, **unused_params):
+        from . import layers
+        dev = model_input.device
+        store = vs.default_store()
+        num_mixtures = num_mixtures or FLAGS.moe_num_mixtures                                                # :396
+        probabilities0 = _mixture_of_experts(model_input, vocab_size, num_mixtures, FLAGS.moe_l2)            # :397-424
+        probabilities0 = _batch_normalization(probabilities0, is_training)                                   # :425
+        w0, b0 = layers.dense_variables(store.unique_layer_name("dense"), vocab_size, vocab_size * filter_size, True, dev)
+        r_activation0 = _filter_stage(_linear(probabilities0, w0), b0, None, "relu", True, is_training, None)   # :427-428 (:430: a no-op)
+        w1, b1 = layers.dense_variables(store.unique_layer_name("dense"), vocab_size * filter_size, vocab_size, True, dev)
+        ln = layers.layer_norm_variables("LayerNorm", vocab_size, dev)
+        probabilities1 = layers.class_rows(_linear(r_activation0, w1), b1, probabilities0, norm="layer_norm", ln=ln)   # :431-434
+        probabilities1 = _batch_normalization(probabilities1, is_training)                                   # :435
+        w2, b2 = layers.dense_variables(store.unique_layer_name("dense"), vocab_size, vocab_size, True, dev)
+        return {"predictions": layers.class_rows(_linear(probabilities1, w2), b2, norm="softmax")}           # :436-438
 
 
 class FourLayerBatchNeuralModel(models.BaseModel):
