@@ -856,6 +856,18 @@ int lpm_mha_bn_dk_correct_image(const float* q, const float* k, int64_t ld, int 
  * lpm_mha_bn_dk_correct (`moments`, of the UNSCALED q; q may then be NULL) the backward does not form them again.  d in {8, 16}. */
 int lpm_mha_logit_stats_moments(const float* q, const float* k, int64_t ld, int B, int L, int h, int d, float* partial, float* moments,
                                 lpm_stream_t stream);
+/* The statistics ops.mha_core_bn takes: lpm_mha_logit_stats_moments' raw sums (bit for bit) and, beside them, the same two sums about a
+ * per-(batch, head) pivot p_j = q_0 . k_j (q_0: the group's first query row) -- var = sumsq/n - mean^2 from raw fp32 sums loses
+ * eps32 (mean/std)^2 of the variance, and a biased q/k/v projection offsets every logit of a column.  partial [B*h][5][L] = (sum s, sum s^2,
+ * sum (s - p), sum (s - p)^2, p), lpm_mha_logit_stats_partial_bytes(B, L, h) bytes; partial_bytes is the size of the caller's buffer, and a
+ * buffer of the [B*h][2][L] the two entries above fill is refused before any launch.  lpm_mha_bn_fold has lpm_bn_fold's parameters (nblk = B*h,
+ * rows = B*h*L) and results: the raw sums' moments where mean^2 <= var -- bit for bit lpm_bn_fold's of the raw partials -- and the pivoted
+ * sums' elsewhere, the groups put together in fp64. */
+size_t lpm_mha_logit_stats_partial_bytes(int B, int L, int h);
+int lpm_mha_logit_stats_shifted(const float* q, const float* k, int64_t ld, int B, int L, int h, int d, float* partial, size_t partial_bytes,
+                                float* moments, lpm_stream_t stream);
+int lpm_mha_bn_fold(const float* partial, int nblk, int L, int64_t rows, const float* gamma, const float* beta, float eps, float decay,
+                    float* mean, float* var, float* scale, float* shift, float* moving_mean, float* moving_var, lpm_stream_t stream);
 /* The same backward (no logits_bn) writing the q/k/v gradients ONLY as the split-bf16 gradient image the projection GEMMs read:
  * dqkv3 [B*L, 9*h*d] bf16, row = [hi | hi | lo] planes of the concatenated columns [dq | dk | dv] (what lpm_split_rows with
  * order = 1 would produce from the fp32 gradients) -- the fp32 dq/dk/dv and the split pass over them never exist. */

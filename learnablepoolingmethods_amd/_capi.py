@@ -178,6 +178,9 @@ SIGNATURES = {
     "lpm_mha_bwd": (_i, [_f, _f, _f, _l, _f, _f, _l, _f, _i, _i, _i, _i, _fl, _f, _f, _f, _f, _f, _l, _f, _f, _f, _f]),
     "lpm_mha_bn_dk_correct": (_i, [_f, _f, _l, _i, _i, _i, _i, _fl, _f, _f, _f, _l, _f, _f]),
     "lpm_mha_logit_stats_moments": (_i, [_f, _f, _l, _i, _i, _i, _i, _f, _f, _f]),
+    "lpm_mha_logit_stats_partial_bytes": (_s, [_i, _i, _i]),
+    "lpm_mha_logit_stats_shifted": (_i, [_f, _f, _l, _i, _i, _i, _i, _f, _s, _f, _f]),
+    "lpm_mha_bn_fold": (_i, [_f, _i, _i, _l, _f, _f, _fl, _fl, _f, _f, _f, _f, _f, _f, _f]),
     "lpm_mha_bwd_x3": (_i, [_f, _f, _f, _l, _f, _f, _l, _f, _i, _i, _i, _i, _fl, _f, _f, _f, _f, _f, _l, _f, _f, _f, _f]),
     "lpm_mha_bwd_x3_image": (_i, [_f, _f, _f, _l, _f, _i, _f, _l, _f, _i, _i, _i, _i, _fl, _f, _f]),
     "lpm_mha_fwd_x3_image": (_i, [_f, _f, _f, _l, _i, _i, _i, _i, _fl, _f, _f, _f]),

@@ -14,7 +14,8 @@ namespace lpm {
 // 3 eps32 at any offset -- and more than the raw sums where the mean is small against the spread.  Both forms are evaluated; the shifted one decides: where mean^2 <= var the raw sums
 // are taken (there the results are bit for bit what they were before the shifted sums existed), elsewhere the shifted ones (as ln_moments,
 // layer_norm.hip).  lpm_frame_bn_fold (frame_prep.hip's frame_stats_kernel) passes its own shifted sums, the pivot the mean of eight gathered
-// rows spread over the batch.  shifted == NULL (lpm_bn_fold: K1's epilogue, the attention's logit statistics): the raw sums alone.
+// rows spread over the batch.  shifted == NULL (lpm_bn_fold: K1's epilogue): the raw sums alone.  The attention's logit statistics have a
+// fold of their own, mha_bn_fold_kernel below: their shifted sums have one pivot per (batch, head) group, not one per column.
 template <int CW>
 __global__ __launch_bounds__(1024) void bn_fold_kernel(const float* __restrict__ partial, int nblk, int C,
                                                        double inv_rows, double unbias,
@@ -64,6 +65,98 @@ __global__ __launch_bounds__(1024) void bn_fold_kernel(const float* __restrict__
             if (centre) centre[c] = 0.f;
             shift[c] = b - (float)mu * sc;
         }
+        if (moving_mean) {
+            moving_mean[c] = moving_mean[c] * decay + (float)mu * (1.f - decay);
+            moving_var[c] = moving_var[c] * decay + (float)(vr * unbias) * (1.f - decay);
+        }
+    }
+}
+
+// The fold of the attention's logit statistics (lpm_mha_bn_fold).  partial [nblk][5][L] from lpm_mha_logit_stats_shifted: per (batch, head)
+// group the raw column sums (sum s, sum s^2) over its nq queries, the same two sums about the group's own pivot (a = sum (s - p),
+// b = sum (s - p)^2) and the pivot p.  Every group has another pivot, so the groups meet in fp64 as sum s = a + nq p and
+// sum s^2 = b + 2 p a + nq p^2 (products of two fp32 numbers: exact in fp64; the fp64 fold of var = q/n - mu^2 loses 1e-16 (mean/std)^2).
+// The raw sums go through partial_colsums as in bn_fold_kernel and are taken where take mean^2 <= var (the raw moments decide: their
+// variance is off by eps32 mean^2, nothing beside var at the threshold): there every result is bit for bit lpm_bn_fold's, and the other
+// three rows of the group are not read -- a workgroup none of whose columns is offset ends like bn_fold_kernel.  Elsewhere the pivoted
+// sums give the moments, and the shift is rounded once, from fp64.
+template <int CW>
+__global__ __launch_bounds__(1024) void mha_bn_fold_kernel(const float* __restrict__ partial, int nblk, int L, int nq, double inv_rows,
+                                                           double unbias, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           float eps, float decay, float* mean, float* var, float* scale, float* shift,
+                                                           float* moving_mean, float* moving_var, double take) {
+    constexpr int RG = 1024 / CW;
+    __shared__ double piv_sh[2][16][CW];
+    __shared__ int off_sh[CW];
+    double s, q;
+    int c;
+    partial_colsums<CW>(partial, nblk, 5 * (int64_t)L, L, L, s, q, c);
+    const int cl = threadIdx.x & (CW - 1), rg = threadIdx.x / CW;
+    double mu = 0.0, vr = 0.0;
+    if (threadIdx.x < CW) {
+        mu = s * inv_rows;
+        vr = q * inv_rows - mu * mu;
+        if (vr < 0.0) vr = 0.0;
+        off_sh[cl] = (c < L && take * (mu * mu) > vr) ? 1 : 0;
+    }
+    __syncthreads();
+    const bool taken = off_sh[cl] != 0;
+    int any = 0;
+#pragma unroll
+    for (int i = 0; i < CW; ++i) any |= off_sh[i];
+    if (any) {                                      // (the same for every thread of the workgroup)
+        double ss = 0.0, sq = 0.0;
+        if (taken) {
+            const double n = (double)nq;
+            for (int b = rg; b < nblk; b += RG * 4) {
+                float pa[4], pb[4], pp[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int bb = b + RG * u;
+                    const float* p = partial + (int64_t)min(bb, nblk - 1) * 5 * L + c;
+                    pa[u] = (bb < nblk) ? p[2 * (int64_t)L] : 0.f;
+                    pb[u] = (bb < nblk) ? p[3 * (int64_t)L] : 0.f;
+                    pp[u] = (bb < nblk) ? p[4 * (int64_t)L] : 0.f;
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (b + RG * u < nblk) {
+                        const double a = (double)pa[u], pv = (double)pp[u];
+                        ss += a + n * pv;
+                        sq += (double)pb[u] + 2.0 * pv * a + n * pv * pv;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int o = CW; o < 64; o <<= 1) {
+            ss += __shfl_xor(ss, o, 64);
+            sq += __shfl_xor(sq, o, 64);
+        }
+        const int wave = threadIdx.x >> 6;
+        if ((threadIdx.x & 63) < CW) {
+            piv_sh[0][wave][cl] = ss;
+            piv_sh[1][wave][cl] = sq;
+        }
+        __syncthreads();
+        if (threadIdx.x < CW && taken) {
+            ss = piv_sh[0][0][cl]; sq = piv_sh[1][0][cl];
+            for (int i = 1; i < 16; ++i) {
+                ss += piv_sh[0][i][cl];
+                sq += piv_sh[1][i][cl];
+            }
+            mu = ss * inv_rows;
+            vr = sq * inv_rows - mu * mu;
+            if (vr < 0.0) vr = 0.0;
+        }
+    }
+    if (threadIdx.x < CW && c < L) {
+        const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
+        const float sc = g * (float)(1.0 / sqrt(vr + (double)eps));
+        if (mean) mean[c] = (float)mu;
+        if (var) var[c] = (float)vr;
+        scale[c] = sc;
+        shift[c] = taken ? (float)((double)b - mu * (double)sc) : b - (float)mu * sc;
         if (moving_mean) {
             moving_mean[c] = moving_mean[c] * decay + (float)mu * (1.f - decay);
             moving_var[c] = moving_var[c] * decay + (float)(vr * unbias) * (1.f - decay);
@@ -692,6 +785,27 @@ extern "C" int lpm_frame_bn_fold(const float* partial, int nblk, int C, int64_t 
     const float* pivot = partial ? shifted + (size_t)(nblk > 0 ? nblk : 0) * 2 * (size_t)(C > 0 ? C : 0) : nullptr;
     return bn_fold_launch(partial, nblk, C, rows, gamma, beta, eps, decay, mean, var, scale, shift, moving_mean, moving_var, shifted, pivot,
                           centre, 4.0, stream, "lpm_frame_bn_fold");
+}
+
+// The fold of lpm_mha_logit_stats_shifted's `partial` [nblk = B*h][5][L] (mha_bn_fold_kernel): lpm_bn_fold's arithmetic and results wherever
+// mean^2 <= var, the moments of the sums about the groups' pivots elsewhere.  rows = nblk * (queries per group).
+extern "C" int lpm_mha_bn_fold(const float* partial, int nblk, int L, int64_t rows, const float* gamma, const float* beta, float eps,
+                               float decay, float* mean, float* var, float* scale, float* shift, float* moving_mean, float* moving_var,
+                               lpm_stream_t stream) {
+    using namespace lpm;
+    LPM_REQUIRE(partial && scale && shift, LPM_ERR_BADARG, "lpm_mha_bn_fold: null pointer");
+    LPM_REQUIRE(nblk > 0 && L > 0 && rows > 0 && rows % nblk == 0, LPM_ERR_BADARG, "lpm_mha_bn_fold: bad sizes (rows must be nblk x queries)");
+    LPM_REQUIRE((moving_mean == nullptr) == (moving_var == nullptr), LPM_ERR_BADARG,
+                "lpm_mha_bn_fold: moving_mean and moving_var must be given together");
+    const double unbias = rows > 1 ? (double)rows / (double)(rows - 1) : 1.0;
+    const int nq = (int)(rows / nblk);
+    if (partial_colsums_cw(nblk) == 4)
+        hipLaunchKernelGGL(mha_bn_fold_kernel<4>, dim3((L + 3) / 4), dim3(1024), 0, (hipStream_t)stream, partial, nblk, L, nq, 1.0 / (double)rows,
+                           unbias, gamma, beta, eps, decay, mean, var, scale, shift, moving_mean, moving_var, 1.0);
+    else
+        hipLaunchKernelGGL(mha_bn_fold_kernel<16>, dim3((L + 15) / 16), dim3(1024), 0, (hipStream_t)stream, partial, nblk, L, nq,
+                           1.0 / (double)rows, unbias, gamma, beta, eps, decay, mean, var, scale, shift, moving_mean, moving_var, 1.0);
+    return check_launch("lpm_mha_bn_fold");
 }
 
 extern "C" size_t lpm_bn_bwd_workspace_bytes(int M, int K) {

@@ -32,6 +32,10 @@ inline int check_launch(const char* what) {
     return LPM_OK;
 }
 
+// mha.hip: the attention backward of a sequence of ONE key (dq = dk = 0, dv = dout, zero logits_bn sums), for lpm_mha_bwd and lpm_mha_bwd_x3
+int mha_bwd_one_key(const float* dout, int64_t ldo, int B, int h, int d, float* dq, float* dk, float* dv, int64_t ldd, float* dz_partial,
+                    lpm_stream_t stream, const char* what);
+
 #define LPM_REQUIRE(cond, code, ...)  \
     do {                              \
         if (!(cond)) {                \

@@ -1,7 +1,9 @@
 // K4 -- multi-head attention core, forward + backward, never materialising [B,h,L,L].
 //   o = softmax(scale * q k^T) v                          transformer_utils.py:564-581
 //   MultiHeadAttentionBN variant: z = (q k^T) * key_scale[j] + key_shift[j] (folded logits_bn over the
-//   key-position channel, :652-659); lpm_mha_logit_stats reduces the column statistics it needs.
+//   key-position channel, :652-659).  Its column statistics: per (batch, head) the raw sums of s = q.k_j and s^2 over the queries
+//   (lpm_mha_logit_stats, lpm_mha_logit_stats_moments) and, in the form ops.mha_core_bn takes (lpm_mha_logit_stats_shifted), beside them
+//   the same two sums about the pivot q_0 . k_j; lpm_mha_bn_fold (bn.hip) takes the raw pair where mean^2 <= var and the pivoted one elsewhere.
 //
 // gfx950 mapping.  One 256-thread workgroup per (batch, head); K and V (L x d, d in {8,16}) are staged
 // once into LDS (row stride 20 floats: both the "row-chunk" and the "column" MFMA operand walks are
@@ -460,6 +462,15 @@ static int reserve_lds(KernT kern, size_t bytes, const char* what) {
 // queries staged in LDS, fixed order) and one over k (a thread per key: G k_j, then the two dot products), all fp32 FMAs:
 // 2 L d^2 multiply-adds per head instead of L^2 d and the column reductions -- at cfg-3's video stream (80 x 64 heads, L = 300,
 // d = 16) 470 us -> the time to read q and k once.
+//
+// SHIFTED (lpm_mha_logit_stats_shifted): var = sum s^2 / n - mean^2 from these raw fp32 sums loses eps32 (mean / std)^2 of the variance, and a
+// q/k/v projection with a bias gives every logit of a column the same offset (measured: tests/test_gpu_attention_bounds.py, DESIGN.md
+// section 38).  So beside the raw sums -- formed exactly as without SHIFTED, bit for bit -- the same two sums are taken about a pivot: with
+// u = q - q_0, q_0 the (batch, head)'s first query row, already in registers, sum_q u.k_j = k_j . S' and sum_q (u.k_j)^2 = k_j^T G' k_j are the
+// sums of s - p_j and (s - p_j)^2 about p_j = q_0 . k_j.  partial [B*h][5][L] = (raw sum, raw sum of squares, shifted sum, shifted sum of
+// squares, pivot); lpm_mha_bn_fold puts the groups together in fp64 and decides which pair gives the moments.  The moments handed to the
+// backward stay the raw ones.
+template <bool SHIFTED>
 __global__ __launch_bounds__(256) void mha_logit_stats_quad_kernel(const float* __restrict__ q, const float* __restrict__ k, int64_t ld, int L,
                                                                    int h, int d, int nheads, float* __restrict__ partial,
                                                                    float* __restrict__ moments) {
@@ -467,6 +478,7 @@ __global__ __launch_bounds__(256) void mha_logit_stats_quad_kernel(const float* 
     // queries lane (l15, g) holds Q[4 s + g][l15], which is its element of BOTH operands of v_mfma_f32_16x16x4_f32 (A = Q^T, B = Q);
     // acc[r] = G[4 g + r][l15].  No staging: a wave-load touches four 64-byte rows.
     __shared__ __attribute__((aligned(16))) float Gs[4][16 * 16 + 16];
+    __shared__ __attribute__((aligned(16))) float Gp[SHIFTED ? 4 : 1][SHIFTED ? 16 * 16 + 32 : 4];     // G', S', q_0
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, g = lane >> 4;
     const int head = xcd_remap(blockIdx.x, gridDim.x) * 4 + wave;
@@ -475,27 +487,42 @@ __global__ __launch_bounds__(256) void mha_logit_stats_quad_kernel(const float* 
     const float* qp = q + (int64_t)b * L * ld + hh * d + l15;
     const bool col = l15 < d;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    float sacc = 0.f;
+    f32x4 accp = {0.f, 0.f, 0.f, 0.f};
+    float sacc = 0.f, saccp = 0.f;
+    const float q0 = (SHIFTED && col) ? qp[0] : 0.f;            // the pivot row's element of this lane's column
     const int ns = (L + 3) >> 2;
     int s = 0;
     for (; s + 4 < ns; s += 5) {                                 // five groups' loads together
         float a[5];
+        bool in[5];
 #pragma unroll
         for (int u = 0; u < 5; ++u) {
             const int row = 4 * (s + u) + g;
-            a[u] = (col && row < L) ? qp[(int64_t)row * ld] : 0.f;
+            in[u] = col && row < L;
+            a[u] = in[u] ? qp[(int64_t)row * ld] : 0.f;
         }
 #pragma unroll
         for (int u = 0; u < 5; ++u) {
             acc = mfma16(a[u], a[u], acc);
             sacc += a[u];
+            if (SHIFTED) {
+                const float ap = in[u] ? a[u] - q0 : 0.f;
+                accp = mfma16(ap, ap, accp);
+                saccp += ap;
+            }
         }
     }
     for (; s < ns; ++s) {
         const int row = 4 * s + g;
-        const float a = (col && row < L) ? qp[(int64_t)row * ld] : 0.f;
+        const bool in = col && row < L;
+        const float a = in ? qp[(int64_t)row * ld] : 0.f;
         acc = mfma16(a, a, acc);
         sacc += a;
+        if (SHIFTED) {
+            const float ap = in ? a - q0 : 0.f;
+            accp = mfma16(ap, ap, accp);
+            saccp += ap;
+        }
     }
     sacc += __shfl_xor(sacc, 16, 64);
     sacc += __shfl_xor(sacc, 32, 64);                            // sum_q Q[q][l15] on every lane
@@ -504,6 +531,19 @@ __global__ __launch_bounds__(256) void mha_logit_stats_quad_kernel(const float* 
 #pragma unroll
     for (int r = 0; r < 4; ++r) G[(4 * g + r) * 16 + l15] = acc[r];
     if (g == 0) sv[l15] = sacc;
+    float* Gq = Gp[SHIFTED ? wave : 0];
+    float* svq = Gq + 256;
+    float* pvq = Gq + 272;
+    if (SHIFTED) {
+        saccp += __shfl_xor(saccp, 16, 64);
+        saccp += __shfl_xor(saccp, 32, 64);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Gq[(4 * g + r) * 16 + l15] = accp[r];
+        if (g == 0) {
+            svq[l15] = saccp;
+            pvq[l15] = q0;
+        }
+    }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     if (moments) {                                               // [d * d + d] per head: G, then s (lpm_mha_bn_dk_correct reads them in the backward)
@@ -511,7 +551,7 @@ __global__ __launch_bounds__(256) void mha_logit_stats_quad_kernel(const float* 
         for (int i = lane; i < d * d; i += 64) mo[i] = G[(i / d) * 16 + i % d];
         if (lane < d) mo[d * d + lane] = sv[lane];
     }
-    float* out = partial + (int64_t)head * 2 * L;
+    float* out = partial + (int64_t)head * (SHIFTED ? 5 : 2) * L;
     for (int key = lane; key < L; key += 64) {
         float kv[16];
 #pragma unroll
@@ -534,7 +574,52 @@ __global__ __launch_bounds__(256) void mha_logit_stats_quad_kernel(const float* 
         }
         out[key] = sum;
         out[L + key] = sq;
+        if (SHIFTED) {
+            float sump = 0.f, sqp = 0.f, piv = 0.f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                float t = 0.f;
+#pragma unroll
+                for (int j = 0; j < 16; j += 4) {
+                    const float4 gr = *reinterpret_cast<const float4*>(Gq + i * 16 + j);
+                    t = fmaf(gr.x, kv[j], t); t = fmaf(gr.y, kv[j + 1], t); t = fmaf(gr.z, kv[j + 2], t); t = fmaf(gr.w, kv[j + 3], t);
+                }
+                sqp = fmaf(kv[i], t, sqp);
+                sump = fmaf(kv[i], svq[i], sump);
+                piv = fmaf(kv[i], pvq[i], piv);
+            }
+            out[2 * L + key] = sump;
+            out[3 * L + key] = sqp;
+            out[4 * L + key] = piv;
+        }
     }
+}
+
+// One key: the softmax of one entry is 1 whatever the logit, so out = v and nothing but dv = dout has a gradient -- dq, dk and the
+// logits_bn column sums (sum dz, sum dz s) are zero.  The two sweeps form ds = p (dp - D) from D = <dO, O> and dp = dO . v, the same
+// number summed in two orders, and leave rounding noise where the value is exactly zero; lpm_mha_bwd and lpm_mha_bwd_x3
+// write the known result instead.
+__global__ __launch_bounds__(256) void mha_bwd_one_key_kernel(const float* __restrict__ dout, int64_t ldo, int B, int h, int d, float* dq,
+                                                              float* dk, float* dv, int64_t ldd, float* dz_partial) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= B * h * d) return;
+    const int b = i / (h * d), c = i % (h * d);
+    if (dq) dq[(int64_t)b * ldd + c] = 0.f;
+    if (dk) {
+        dk[(int64_t)b * ldd + c] = 0.f;
+        dv[(int64_t)b * ldd + c] = dout[(int64_t)b * ldo + c];
+    }
+    if (dz_partial && c % d == 0) {
+        dz_partial[((int64_t)b * h + c / d) * 2] = 0.f;
+        dz_partial[((int64_t)b * h + c / d) * 2 + 1] = 0.f;
+    }
+}
+
+int mha_bwd_one_key(const float* dout, int64_t ldo, int B, int h, int d, float* dq, float* dk, float* dv, int64_t ldd, float* dz_partial,
+                    lpm_stream_t stream, const char* what) {
+    hipLaunchKernelGGL(mha_bwd_one_key_kernel, dim3((B * h * d + 255) / 256), dim3(256), 0, (hipStream_t)stream, dout, ldo, B, h, d, dq, dk, dv,
+                       ldd, dz_partial);
+    return check_launch(what);
 }
 
 }  // namespace lpm
@@ -585,7 +670,7 @@ extern "C" int lpm_mha_logit_stats(const float* q, const float* k, int64_t ld, i
     hipStream_t s = (hipStream_t)stream;
     // the quadratic form where q and k are aligned vectors; through the logits otherwise
     if ((((uintptr_t)q | (uintptr_t)k) & 15) == 0 && d % 4 == 0) {
-        hipLaunchKernelGGL(mha_logit_stats_quad_kernel, dim3((B * h + 3) / 4), dim3(256), 0, s, q, k, ld, L, h, d, B * h, partial,
+        hipLaunchKernelGGL(mha_logit_stats_quad_kernel<false>, dim3((B * h + 3) / 4), dim3(256), 0, s, q, k, ld, L, h, d, B * h, partial,
                            (float*)nullptr);
         return check_launch("lpm_mha_logit_stats");
     }
@@ -614,9 +699,28 @@ extern "C" int lpm_mha_logit_stats_moments(const float* q, const float* k, int64
     LPM_MHA_CHECK("lpm_mha_logit_stats_moments");
     LPM_REQUIRE((((uintptr_t)q | (uintptr_t)k) & 15) == 0 && d % 4 == 0, LPM_ERR_BADARG,
                 "lpm_mha_logit_stats_moments: q, k must be 16-byte aligned and d a multiple of 4");
-    hipLaunchKernelGGL(mha_logit_stats_quad_kernel, dim3((B * h + 3) / 4), dim3(256), 0, (hipStream_t)stream, q, k, ld, L, h, d, B * h, partial,
+    hipLaunchKernelGGL(mha_logit_stats_quad_kernel<false>, dim3((B * h + 3) / 4), dim3(256), 0, (hipStream_t)stream, q, k, ld, L, h, d, B * h, partial,
                        moments);
     return check_launch("lpm_mha_logit_stats_moments");
+}
+
+extern "C" size_t lpm_mha_logit_stats_partial_bytes(int B, int L, int h) {
+    return (B > 0 && L > 0 && h > 0) ? (size_t)B * (size_t)h * 5 * (size_t)L * sizeof(float) : 0;
+}
+
+extern "C" int lpm_mha_logit_stats_shifted(const float* q, const float* k, int64_t ld, int B, int L, int h, int d, float* partial,
+                                           size_t partial_bytes, float* moments, lpm_stream_t stream) {
+    using namespace lpm;
+    LPM_REQUIRE(q && k && partial, LPM_ERR_BADARG, "lpm_mha_logit_stats_shifted: null pointer");
+    LPM_MHA_CHECK("lpm_mha_logit_stats_shifted");
+    LPM_REQUIRE(partial_bytes >= lpm_mha_logit_stats_partial_bytes(B, L, h), LPM_ERR_BADARG,
+                "lpm_mha_logit_stats_shifted: partial too small (%zu bytes, need lpm_mha_logit_stats_partial_bytes = %zu: raw sums, shifted sums "
+                "and pivots, [B*h][5][L])", partial_bytes, lpm_mha_logit_stats_partial_bytes(B, L, h));
+    LPM_REQUIRE((((uintptr_t)q | (uintptr_t)k) & 15) == 0 && d % 4 == 0, LPM_ERR_BADARG,
+                "lpm_mha_logit_stats_shifted: q, k must be 16-byte aligned and d a multiple of 4");
+    hipLaunchKernelGGL(mha_logit_stats_quad_kernel<true>, dim3((B * h + 3) / 4), dim3(256), 0, (hipStream_t)stream, q, k, ld, L, h, d, B * h,
+                       partial, moments);
+    return check_launch("lpm_mha_logit_stats_shifted");
 }
 
 extern "C" int lpm_mha_bwd(const float* q, const float* k, const float* v, int64_t ld, const float* o, const float* dout,
@@ -631,6 +735,7 @@ extern "C" int lpm_mha_bwd(const float* q, const float* k, const float* v, int64
     LPM_MHA_CHECK("lpm_mha_bwd");
     LPM_REQUIRE((key_scale == nullptr) == (key_shift == nullptr), LPM_ERR_BADARG, "lpm_mha_bwd: key_scale/key_shift go together");
     LPM_REQUIRE(ldo >= (int64_t)h * d && ldo % 4 == 0 && ldd >= (int64_t)h * d && ldd % 4 == 0, LPM_ERR_BADARG, "lpm_mha_bwd: bad ldo/ldd");
+    if (L == 1) return mha_bwd_one_key(dout, ldo, B, h, d, dq, dk, dv, ldd, dz_partial, stream, "lpm_mha_bwd");
     const size_t lds = mha_bwd_lds(L);
     hipStream_t s = (hipStream_t)stream;
 #define LPM_MHA_BWD(AFF)                                                                                                  \

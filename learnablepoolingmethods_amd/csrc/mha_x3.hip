@@ -1357,6 +1357,7 @@ extern "C" int lpm_mha_bwd_x3(const float* q, const float* k, const float* v, in
     LPM_REQUIRE(ldo >= (int64_t)h * d && ldo % 4 == 0 && ldd >= (int64_t)h * d && ldd % 4 == 0, LPM_ERR_BADARG, "lpm_mha_bwd_x3: bad ldo/ldd");
     LPM_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) & 15) == 0,
                 LPM_ERR_BADARG, "lpm_mha_bwd_x3: pointers must be 16-byte aligned");
+    if (L == 1) return mha_bwd_one_key(dout, ldo, B, h, d, dq, dk, dv, ldd, dz_partial, stream, "lpm_mha_bwd_x3");   // (csrc/mha.hip)
     return mx_bwd_launch(q, k, v, ld, o, dout, ldo, lse, B, L, h, d, scale, key_scale, key_shift, dq, dk, dv, ldd, corr_a, corr_b,
                          dz_partial, 0, 0, stream, "lpm_mha_bwd_x3");
 }

@@ -3349,20 +3349,21 @@ def _bn_pass_precision(which, L=None):
 
 
 def _mha_fwd_fn(lib, bn=False, which="fwd", L=None):
+    """-> (entry, its name for lib.check): the arithmetic of a pass is visible in the name that passes through the check"""
     prec = _bn_pass_precision(which, L) if bn else MHA_PRECISION
     if prec == "bf16x3":
-        return lib._lpm_mha_fwd_x3
+        return lib._lpm_mha_fwd_x3, "lpm_mha_fwd_x3"
     if prec == "f32":
-        return lib._lpm_mha_fwd
+        return lib._lpm_mha_fwd, "lpm_mha_fwd"
     raise LpmError(f"unknown attention precision {prec!r} (bf16x3 | f32)")
 
 
 def _mha_bwd_fn(lib, bn=False, which="main", L=None):
     prec = _bn_pass_precision(which, L) if bn else MHA_PRECISION
     if prec == "bf16x3":
-        return lib._lpm_mha_bwd_x3
+        return lib._lpm_mha_bwd_x3, "lpm_mha_bwd_x3"
     if prec == "f32":
-        return lib._lpm_mha_bwd
+        return lib._lpm_mha_bwd, "lpm_mha_bwd"
     raise LpmError(f"unknown attention precision {prec!r} (bf16x3 | f32)")
 
 
@@ -3407,8 +3408,9 @@ class _MHACore(torch.autograd.Function):
         else:
             o = torch.empty(q.shape, dtype=torch.float32, device=q.device)
             with _timed("mha_fwd", (B, L, num_heads, d)):
-                lib.check(_mha_fwd_fn(lib)(ptr(q), ptr(k), ptr(v), q.stride(1), B, L, num_heads, d, scale, None, None, ptr(o),
-                                           o.stride(1), ptr(lse), stream_ptr()), "lpm_mha_fwd")
+                fwd, name = _mha_fwd_fn(lib)
+                lib.check(fwd(ptr(q), ptr(k), ptr(v), q.stride(1), B, L, num_heads, d, scale, None, None, ptr(o), o.stride(1), ptr(lse),
+                              stream_ptr()), name)
         ctx.save_for_backward(q, k, v, o, lse)
         return o
 
@@ -3439,9 +3441,9 @@ class _MHACore(torch.autograd.Function):
         if o_image:
             raise LpmError("mha backward: an image-form attention output needs the image-form backward")
         dq, dk, dv = _dqkv_buffers(q)
-        lib.check(_mha_bwd_fn(lib)(ptr(q), ptr(k), ptr(v), q.stride(1), ptr(o), ptr(do), o.stride(1), ptr(lse), B, L, h, d,
-                                   scale, None, None, ptr(dq), ptr(dk), ptr(dv), dq.stride(1), None, None, None, stream_ptr()),
-                  "lpm_mha_bwd")
+        bwd, name = _mha_bwd_fn(lib)
+        lib.check(bwd(ptr(q), ptr(k), ptr(v), q.stride(1), ptr(o), ptr(do), o.stride(1), ptr(lse), B, L, h, d,
+                      scale, None, None, ptr(dq), ptr(dk), ptr(dv), dq.stride(1), None, None, None, stream_ptr()), name)
         return dq, dk, dv, None, None, None
 
 
@@ -3666,25 +3668,27 @@ class _MHACoreBN(torch.autograd.Function):
         h = num_heads
         moments = None
         if is_training:
-            partial = _empty((B * h, 2, L), q)
-            # (lpm_mha_logit_stats_moments reads q and k as float4: 16-byte aligned views only; anything else takes the general kernel)
-            if d in (8, 16) and q.data_ptr() % 16 == 0 and k.data_ptr() % 16 == 0 and (q.stride(1) * 4) % 16 == 0:
-                # the statistics from the d x d moments of q, which the backward's repair of dk needs again (kept: 272 floats per head)
-                moments = _empty((B * h, d * d + d), q)
-                lib.check(lib._lpm_mha_logit_stats_moments(ptr(q), ptr(k), q.stride(1), B, L, h, d, ptr(partial), ptr(moments), stream_ptr()),
-                          "lpm_mha_logit_stats_moments")
-            else:
-                lib.check(lib._lpm_mha_logit_stats(ptr(q), ptr(k), q.stride(1), B, L, h, d, ptr(partial), stream_ptr()),
-                          "lpm_mha_logit_stats")
-            mean, var, kscale, kshift = bn_fold(partial, B * h, L, B * h * L, gamma, beta, moving_mean, moving_var)
+            # (lpm_mha_logit_stats_shifted reads q and k as float4: 16-byte aligned views only; anything else is copied to an aligned buffer)
+            if q.data_ptr() % 16 or k.data_ptr() % 16 or v.data_ptr() % 16:
+                q, k, v = q.clone(), k.clone(), v.clone()
+            # the statistics from the d x d moments of q, which the backward's repair of dk needs again (kept: 272 floats per head); raw
+            # sums, sums about a per-(batch, head) pivot and the pivots: lpm_mha_bn_fold decides which pair gives the moments
+            partial = _empty((lib._lpm_mha_logit_stats_partial_bytes(B, L, h) // 4,), q)
+            moments = _empty((B * h, d * d + d), q)
+            lib.check(lib._lpm_mha_logit_stats_shifted(ptr(q), ptr(k), q.stride(1), B, L, h, d, ptr(partial), partial.numel() * 4, ptr(moments),
+                                                       stream_ptr()), "lpm_mha_logit_stats_shifted")
+            mean, var, kscale, kshift = (_empty((L,), q) for _ in range(4))
+            lib.check(lib._lpm_mha_bn_fold(ptr(partial), B * h, L, B * h * L, ptr(gamma), ptr(beta), BN_EPS, BN_DECAY, ptr(mean), ptr(var),
+                                           ptr(kscale), ptr(kshift), ptr(moving_mean), ptr(moving_var), stream_ptr()), "lpm_mha_bn_fold")
         else:
             kscale, kshift = folded_eval_affine(gamma, beta, moving_mean, moving_var)
             kscale, kshift = kscale.contiguous(), kshift.contiguous()
             mean, var = moving_mean.detach().clone(), moving_var.detach().clone()
         o = torch.empty(q.shape, dtype=torch.float32, device=q.device)
         lse = _empty((B, h, L), q)
-        lib.check(_mha_fwd_fn(lib, bn=True, L=L)(ptr(q), ptr(k), ptr(v), q.stride(1), B, L, h, d, 1.0, ptr(kscale), ptr(kshift), ptr(o),
-                                   o.stride(1), ptr(lse), stream_ptr()), "lpm_mha_fwd")
+        fwd, name = _mha_fwd_fn(lib, bn=True, L=L)
+        lib.check(fwd(ptr(q), ptr(k), ptr(v), q.stride(1), B, L, h, d, 1.0, ptr(kscale), ptr(kshift), ptr(o), o.stride(1), ptr(lse),
+                      stream_ptr()), name)
         ctx.dims = (B, L, h, d, is_training)
         ctx.moments = moments
         ctx.save_for_backward(q, k, v, o, lse, kscale, kshift, mean, var, gamma)
@@ -3742,18 +3746,18 @@ class _MHACoreBN(torch.autograd.Function):
             return dq, dk, dv, dgamma, dbeta, None, None, None, None
         # pass 1: column sums of dz and dz*s over (B, h, query)
         partial = _empty((B * h, 2, L), q)
-        lib.check(_mha_bwd_fn(lib, bn=True, which="stats")(ptr(q), ptr(k), ptr(v), q.stride(1), ptr(o), ptr(do), o.stride(1), ptr(lse), B, L,
-                                                           h, d, 1.0, ptr(kscale), ptr(kshift), None, None, None, q.stride(1), None, None,
-                                                           ptr(partial), st), "lpm_mha_bwd(stats)")
+        bwd, name = _mha_bwd_fn(lib, bn=True, which="stats")
+        lib.check(bwd(ptr(q), ptr(k), ptr(v), q.stride(1), ptr(o), ptr(do), o.stride(1), ptr(lse), B, L, h, d, 1.0, ptr(kscale), ptr(kshift),
+                      None, None, None, q.stride(1), None, None, ptr(partial), st), name + "(stats)")
         # dbeta = sum dz, dgamma = sum dz * s_hat and (training) the two correction vectors of the main pass, fp64, in one launch
         dgamma, dbeta = _empty((L,), q), _empty((L,), q)
         corr_a, corr_b = (_empty((L,), q), _empty((L,), q)) if is_training else (None, None)
         lib.check(lib._lpm_mha_bn_corrections(ptr(partial), B * h, L, ptr(mean.contiguous()), ptr(var.contiguous()), ptr(kscale), BN_EPS,
                                               B * h * L, ptr(dgamma), ptr(dbeta), ptr(corr_a), ptr(corr_b), st), "lpm_mha_bn_corrections")
         dq, dk, dv = _dqkv_buffers(q)
-        lib.check(_mha_bwd_fn(lib, bn=True)(ptr(q), ptr(k), ptr(v), q.stride(1), ptr(o), ptr(do), o.stride(1), ptr(lse), B, L, h, d, 1.0,
-                                   ptr(kscale), ptr(kshift), ptr(dq), ptr(dk), ptr(dv), dq.stride(1), ptr(corr_a), ptr(corr_b),
-                                   None, st), "lpm_mha_bwd")
+        bwd, name = _mha_bwd_fn(lib, bn=True)
+        lib.check(bwd(ptr(q), ptr(k), ptr(v), q.stride(1), ptr(o), ptr(do), o.stride(1), ptr(lse), B, L, h, d, 1.0, ptr(kscale), ptr(kshift),
+                      ptr(dq), ptr(dk), ptr(dv), dq.stride(1), ptr(corr_a), ptr(corr_b), None, st), name)
         return dq, dk, dv, dgamma, dbeta, None, None, None, None
 
 

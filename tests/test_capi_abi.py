@@ -83,6 +83,25 @@ def test_frame_stats_refuse_a_partial_of_the_old_size():
             assert call(n) != 0 and name in lib.last_error() and "partial too small" in lib.last_error(), (name, n, lib.last_error())
 
 
+def test_mha_logit_stats_shifted_refuses_a_partial_of_the_old_size():
+    """lpm_mha_logit_stats_shifted fills partial [B*h][5][L] -- raw sums, sums about the pivots, pivots -- takes the size of the caller's
+    buffer and refuses, before any launch, the [B*h][2][L] that lpm_mha_logit_stats(_moments) fill; lpm_mha_bn_fold has lpm_bn_fold's
+    parameters.  (The pointers are never dereferenced: the check fails.)"""
+    from learnablepoolingmethods_amd import _capi
+    lib = _capi.load()
+    assert _capi.SIGNATURES["lpm_mha_bn_fold"] == _capi.SIGNATURES["lpm_bn_fold"]
+    moments = _capi.SIGNATURES["lpm_mha_logit_stats_moments"][1]
+    assert _capi.SIGNATURES["lpm_mha_logit_stats_shifted"][1] == moments[:8] + [ctypes.c_size_t] + moments[8:]
+    p = ctypes.c_void_p(4096)
+    for B, L, h, d in ((2, 16, 1, 8), (3, 48, 2, 16), (80, 300, 64, 16)):
+        new, old = lib._lpm_mha_logit_stats_partial_bytes(B, L, h), B * h * 2 * L * 4
+        assert new == B * h * 5 * L * 4
+        for n in (old, new - 1):
+            assert lib._lpm_mha_logit_stats_shifted(p, p, h * d, B, L, h, d, p, n, p, None) != 0
+            assert "lpm_mha_logit_stats_shifted" in lib.last_error() and "partial too small" in lib.last_error(), lib.last_error()
+    assert lib._lpm_mha_logit_stats_partial_bytes(0, 16, 1) == 0
+
+
 def test_version_and_error_string():
     from learnablepoolingmethods_amd import _capi
     lib = _capi.load()
